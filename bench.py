@@ -1,13 +1,24 @@
 """Headline benchmark: denoising-steps/sec of the point-cloud diffusion sampler hot path.
 
     python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--backbone pointnet|attention]
+                    [--full] [--dump-outputs DIR]
 
 Default (`--config cfg2`, BASELINE.json configs[1]): one "step" = one ancestral denoising step (`sample2`
 loop body, reference diffusion.py:241-257) of a whole batch: denoiser forward (HIP kernels) + on-device Philox
 noise + fused DDPM update; 2048 points, batch 64 per GPU, fp16 operands / fp32 accumulation, 1000-step
-schedule (the K timed steps are the first steps of that schedule).  Inputs are resident in HBM before the timed
-region.  With N > 1 every rank runs the same per-GPU batch (weak scaling, no data-path collective: shapes are
-independent).
+schedule (the W warm-up and K timed steps are the first steps of that schedule; past its end it starts over).
+Inputs are resident in HBM before the timed region.  With N > 1 every rank runs the same per-GPU batch (weak
+scaling, no data-path collective: shapes are independent).
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` / `ms_per_step` and, for the
+pointnet backbone launched eagerly, `roofline` from the HIP events the timed steps themselves record.  Everything
+else (the other launch mode, `roofline_attention`, `config.other_configs`, the CPU baselines; cfg3's eager GEMM
+profile, cfg5's latent / VAE legs) runs only under `--full`, where the `--no-*` options still leave parts out.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as float32
+`DIR/<name>.npy` (rank 0): cfg2 `x` = the sampler state (B, 2048, 3); cfg3 `clouds` (global batch, 2048, 3);
+cfg4 `latents` (32, 256) and `points` / `counts` (the voxel->points clouds, concatenated); cfg5 `points` / `counts`
+of the gathered clouds.  Inputs are seeded: the same arguments give the same inputs in every run.
 
 Launching: with N > 1 and no WORLD_SIZE in the environment this process never touches the GPU: it starts N
 child processes (one rank per GPU, RCCL rendezvous on 127.0.0.1; `shapegen_amd/launcher.py`), polls all of them,
@@ -74,6 +85,11 @@ def parse_args():
                          "other launch mode's number is reported beside it either way).  With N > 1 graph replay -- what "
                          "sample2() itself drives -- is the default: a rank's step then costs its host one launch, not 29")
     ap.add_argument("--eager", action="store_true", help="N > 1: time eager launches in the headline region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (other launch mode, attention roofline, other "
+                         "configs, CPU baselines, profiling runs); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
@@ -94,6 +110,31 @@ def synth_weights(backbone="pointnet"):
             else specs.unet_attention_spec(prefix="model."))
     gain = 1.3 if backbone == "pointnet" else 1.0
     return {k: torch.from_numpy(np.asarray(v)) for k, v in specs.synth_state_dict(spec, seed=0, gain=gain).items()}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def ragged(clouds):
+    """A list of (n_i, 3) clouds as one (sum n_i, 3) array of points and the (len,) array of n_i."""
+    import torch
+    counts = torch.tensor([int(c.shape[0]) for c in clouds], dtype=torch.float32)
+    points = torch.cat([c.detach().float().cpu().reshape(-1, 3) for c in clouds]) if clouds else torch.zeros(0, 3)
+    return {"points": points, "counts": counts}
+
+
+def dump_outputs(path, arrays):
+    """`arrays` (name -> tensor) as float32 `path/<name>.npy`.  An array over its share of DUMP_MAX_BYTES keeps a fixed,
+    seeded, sorted sample of its rows (first axis), so that two runs write the same rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def usable_cores() -> int:
@@ -465,7 +506,7 @@ def latent_legs(m, device, B=32, T=SCHEDULE_STEPS):
         raise SystemExit("non-finite latents after the latent loop")
     return {"batch": B, "steps": T, "encode_ms": enc_ms, "loop_ms": loop_wall_ms, "latent_us_per_step": loop_wall_ms * 1e3 / T,
             "decode_ms": dec_ms, "decode_and_voxel_to_points_ms": fin_wall_ms, "cfg4_ms": whole_wall_ms,
-            "clouds": [int(c.shape[0]) for c in clouds[:4]]}
+            "clouds": [int(c.shape[0]) for c in clouds[:4]], "latents": z0, "all_clouds": clouds}
 
 
 # dependent exchanges of one latent step in csrc/latent_persist.hip's plan and the idle hand-off latencies (profiles/r03_d)
@@ -546,8 +587,8 @@ def run_cfg2(args, R: Ranks):
     model.load_state_dict(sd, strict=True)
     model = model.to(R.device).eval()
     total = args.warmup + args.steps
-    if total + 1 > SCHEDULE_STEPS:
-        raise SystemExit("warmup+steps must be < 1000")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     tab = model.ddpm_table(SCHEDULE_STEPS, B_PER_GPU)
     bias = model.model.time_bias(tab.t)
     lib = _lib.load()
@@ -564,6 +605,8 @@ def run_cfg2(args, R: Ranks):
     def leg(use_graph, seed):
         x, stp = new_stepper(seed)
         for k in range(args.warmup):
+            if k and k % SCHEDULE_STEPS == 0:
+                stp.counter.zero_()          # the device-side step counter stops at the last step: start the schedule over
             stp.step(k, True)
         if use_graph:
             stp.capture()
@@ -572,6 +615,8 @@ def run_cfg2(args, R: Ranks):
         R.sync_all()
         t0 = time.perf_counter()
         for k in range(args.warmup, total):
+            if k and k % SCHEDULE_STEPS == 0:
+                stp.counter.zero_()
             if use_graph:
                 stp.replay()
             else:
@@ -584,20 +629,22 @@ def run_cfg2(args, R: Ranks):
             _lib.check(lib.pcd_unet_profile(handle, 0))
         if not torch.isfinite(x).all():
             raise SystemExit("non-finite state after the timed steps")
-        return R.max_over_ranks(elapsed), tot_ms.value, launches.value, elapsed
+        return R.max_over_ranks(elapsed), tot_ms.value, launches.value, elapsed, x
 
-    # the set-attention kernel's own roofline first, on an idle chip (100 launches = 27 ms; after the ~1 s of the two legs below
-    # the chip is power-throttled, which is a statement about the GEMM run that heated it, not about this kernel)
-    att = attention_roofline(R.device) if (R.world == 1 and not args.no_attention) else None
+    # (--full) the set-attention kernel's own roofline first, on an idle chip (100 launches = 27 ms; after the ~1 s of the two legs
+    # below the chip is power-throttled, which is a statement about the GEMM run that heated it, not about this kernel)
+    att = attention_roofline(R.device) if (args.full and R.world == 1 and not args.no_attention) else None
     head_graph = args.graph or (R.world > 1 and not args.eager)
-    elapsed, tot_ms, launches, own = leg(head_graph, 24 + R.rank)
-    other_elapsed, o_ms, o_launches, _ = leg(not head_graph, 24 + R.rank)      # the other launch mode, same K steps
+    elapsed, tot_ms, launches, own, x_head = leg(head_graph, 24 + R.rank)
+    outputs = {"x": x_head.float().cpu()} if args.dump_outputs else None        # the sampler state after the last timed step
+    if args.full:
+        other_elapsed, o_ms, o_launches, _, _ = leg(not head_graph, 24 + R.rank)      # the other launch mode, same K steps
+        if head_graph:       # HIP events cannot be recorded inside a captured step: the eager leg carries them
+            tot_ms, launches = o_ms, o_launches
     per_rank = R.gather_seconds(own)
-    if head_graph:           # HIP events cannot be recorded inside a captured step: the eager leg carries them
-        tot_ms, launches = o_ms, o_launches
     rccl_ranks = R.collective_ranks()
     if R.rank != 0:
-        return None
+        return None, None
     world = R.world
     name = "UNetPointNetLarge" if pointnet else "UNetAttentionPointExperimental"
     out = {
@@ -613,7 +660,6 @@ def run_cfg2(args, R: Ranks):
                                f"denoiser {name}",
                    "batch_per_gpu": B_PER_GPU, "points": N_POINTS, "sampler": "ddpm/sample2", "backbone": args.backbone,
                    "launch": "hipGraph replay" if head_graph else "eager",
-                   ("eager" if head_graph else "graph_replay") + "_steps_per_sec": world * args.steps / other_elapsed,
                    "point_steps_per_sec": world * args.steps * B_PER_GPU * N_POINTS / elapsed,
                    "rccl_ranks": rccl_ranks, "collective_backend": R.backend,
                    # every rank's own clock over the same K steps: an efficiency loss at N > 1 is attributable to a rank
@@ -621,14 +667,16 @@ def run_cfg2(args, R: Ranks):
                                               "slowest_rank": per_rank.index(max(per_rank))},
                    "rank_cpus": os.environ.get("PCD_RANK_CPUS"), "rank_host_threads": os.environ.get("OMP_NUM_THREADS")},
     }
-    if pointnet:
-        out["roofline"] = gf3_roofline(tot_ms / max(launches, 1), launches)
+    if args.full:
+        out["config"][("eager" if head_graph else "graph_replay") + "_steps_per_sec"] = world * args.steps / other_elapsed
+    if pointnet and launches:      # an eager leg ran: its HIP events timed the dominant GEMM
+        out["roofline"] = gf3_roofline(tot_ms / launches, launches)
     if att is not None:
         att["measured"] = "before the timed region, after 200 warm-up launches"
         out["roofline_attention"] = att
         if not pointnet:
             out["roofline"] = att
-    if world == 1 and pointnet and not args.no_other_configs:
+    if args.full and world == 1 and pointnet and not args.no_other_configs:
         oc = other_configs(model, R.device)
         # the headline region is short (K steps of ~3.6 ms); the chip is power limited, so a SUSTAINED figure stands beside it: 200
         # consecutive steps of the same loop through graph replay (25 replays of the 8-step graph sample2() itself uses) after a ramp
@@ -665,10 +713,10 @@ def run_cfg2(args, R: Ranks):
             raise SystemExit("non-finite state in the attention-backbone leg")
         del am, astp, ax
         out["config"]["other_configs"] = oc
-    if world == 1 and not args.no_cpu_baseline and pointnet:
+    if args.full and world == 1 and not args.no_cpu_baseline and pointnet:
         out["cpu_baseline"] = cpu_baseline(sd)
         out["cpu_baseline_cfg1"] = cpu_baseline_cfg1(sd)
-    return out
+    return out, outputs
 
 
 def other_configs(model, device):
@@ -719,20 +767,24 @@ def run_cfg3(args, R: Ranks):
     elapsed = R.max_over_ranks(time.perf_counter() - t0)
     ranks = R.collective_ranks()
     assert tuple(clouds.shape) == (gb, N_POINTS, 3) and torch.isfinite(clouds).all()
-    # dominant kernel, timed live after the timed region: one more sampler call with graph replay off (HIP events
+    # (--full) dominant kernel, timed live after the timed region: one more sampler call with graph replay off (HIP events
     # cannot be recorded inside a captured step), same 50 steps, same shapes
-    gf3_ms, gf3_launches = eager_gf3_profile(model, lambda: D.sample_sharded(model, gb, N_POINTS, T, gather=False))
+    if args.full:
+        gf3_ms, gf3_launches = eager_gf3_profile(model, lambda: D.sample_sharded(model, gb, N_POINTS, T, gather=False))
     if R.rank != 0:
-        return None
+        return None, None
+    outputs = {"clouds": clouds.float().cpu()} if args.dump_outputs else None
     steps = runs * T
-    return {"metric": "denoising-steps/sec (whole node), 2048-pt DDIM 50 steps, batch 64 per GPU", "value": R.world * steps / elapsed,
-            "roofline": gf3_roofline(gf3_ms, gf3_launches, "eager run of the same 50 steps after the timed region (rank 0)"),
-            "unit": "denoising-steps/sec", "n_gpus": R.world, "steps": steps, "warmup": max(1, args.warmup // T) * T,
-            "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: point-cloud DDIM (sample), 2048 points, 50 steps, batch 64 per GPU "
-                                   "batch-sharded, output clouds all-gathered; whole sampler calls timed (tables, graph capture, gather included)",
-                       "global_batch": gb, "runs": runs, "rccl_ranks": ranks, "collective_backend": R.backend}}
+    out = {"metric": "denoising-steps/sec (whole node), 2048-pt DDIM 50 steps, batch 64 per GPU", "value": R.world * steps / elapsed,
+           "unit": "denoising-steps/sec", "n_gpus": R.world, "steps": steps, "warmup": max(1, args.warmup // T) * T,
+           "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f16", "data": "synthetic",
+           "config": {"workload": "BASELINE configs[2]: point-cloud DDIM (sample), 2048 points, 50 steps, batch 64 per GPU "
+                                  "batch-sharded, output clouds all-gathered; whole sampler calls timed (tables, graph capture, gather included)",
+                      "global_batch": gb, "runs": runs, "rccl_ranks": ranks, "collective_backend": R.backend}}
+    if args.full:
+        out["roofline"] = gf3_roofline(gf3_ms, gf3_launches, "eager run of the same 50 steps after the timed region (rank 0)")
+    return out, outputs
 
 
 # ------------------------------------------------------------------------------------------ cfg5
@@ -769,18 +821,20 @@ def run_cfg5(args, R: Ranks):
     loop_s, eval_s = R.max_over_ranks(loop_s), R.max_over_ranks(eval_s)
     ranks = R.collective_ranks()
     assert len(allc) == gb and rows.shape == (gb, 3)
-    legs = latent_legs(m, R.device) if R.rank == 0 else None       # after the timed region: the latent step / decode on their own
     if R.rank != 0:
-        return None
-    lat, dec, _ = latent_rooflines(legs)
-    return {"metric": "denoising-steps/sec (whole node), latent diffusion 1000 steps, batch 32 per GPU", "value": R.world * T / loop_s,
-            "roofline": lat, "roofline_vae_decode": dec,
-            "unit": "denoising-steps/sec", "n_gpus": R.world, "steps": T, "warmup": T, "ms_per_step": loop_s / T * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[4]: latent diffusion, 1000 DDIM steps over (32, 256) latents per GPU + VAE3DLarge decode "
-                                   "+ voxel->points (timed as the loop), then all-gather of ragged clouds + per-sample Chamfer/Sinkhorn-EMD/voxel-BCE",
-                       "global_batch": gb, "eval_seconds": eval_s, "mean_metrics": [float(v) for v in rows.nanmean(dim=0)],
-                       "rccl_ranks": ranks, "collective_backend": R.backend}}
+        return None, None
+    outputs = ragged(allc) if args.dump_outputs else None
+    out = {"metric": "denoising-steps/sec (whole node), latent diffusion 1000 steps, batch 32 per GPU", "value": R.world * T / loop_s,
+           "unit": "denoising-steps/sec", "n_gpus": R.world, "steps": T, "warmup": T, "ms_per_step": loop_s / T * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+           "config": {"workload": "BASELINE configs[4]: latent diffusion, 1000 DDIM steps over (32, 256) latents per GPU + VAE3DLarge decode "
+                                  "+ voxel->points (timed as the loop), then all-gather of ragged clouds + per-sample Chamfer/Sinkhorn-EMD/voxel-BCE",
+                      "global_batch": gb, "eval_seconds": eval_s, "mean_metrics": [float(v) for v in rows.nanmean(dim=0)],
+                      "rccl_ranks": ranks, "collective_backend": R.backend}}
+    if args.full:        # after the timed region: the latent step / decode on their own (rank 0)
+        lat, dec, _ = latent_rooflines(latent_legs(m, R.device))
+        out["roofline"], out["roofline_vae_decode"] = lat, dec
+    return out, outputs
 
 
 # ------------------------------------------------------------------------------------------ cfg4
@@ -794,7 +848,8 @@ def run_cfg4(args, R: Ranks):
     loop_s = R.max_over_ranks(legs["loop_ms"] * 1e-3)
     ranks = R.collective_ranks()
     if R.rank != 0:
-        return None
+        return None, None
+    outputs = dict(latents=legs["latents"].float().cpu(), **ragged(legs["all_clouds"])) if args.dump_outputs else None
     lat, dec, enc = latent_rooflines(legs)
     T = legs["steps"]
     out = {"metric": "denoising-steps/sec (whole node), latent diffusion 1000 steps, batch 32 per GPU", "value": R.world * T / loop_s,
@@ -807,9 +862,9 @@ def run_cfg4(args, R: Ranks):
                       "latent_us_per_step": legs["latent_us_per_step"], "clouds_first4": legs["clouds"],
                       "rccl_ranks": ranks, "collective_backend": R.backend},
            "roofline": lat, "roofline_vae_decode": dec, "roofline_vae_encode": enc}
-    if R.world == 1 and not args.no_cpu_baseline:
+    if args.full and R.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_latent(sd)
-    return out
+    return out, outputs
 
 
 def main():
@@ -828,8 +883,10 @@ def main():
     import shapegen_amd  # noqa: F401
     torch.set_grad_enabled(False)
     R = Ranks(args)
-    out = {"cfg2": run_cfg2, "cfg3": run_cfg3, "cfg4": run_cfg4, "cfg5": run_cfg5}[args.config](args, R)
+    out, outputs = {"cfg2": run_cfg2, "cfg3": run_cfg3, "cfg4": run_cfg4, "cfg5": run_cfg5}[args.config](args, R)
     if R.rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     R.finish()
 

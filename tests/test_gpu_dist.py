@@ -48,7 +48,7 @@ def test_bench_launches_its_own_ranks(config):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(PCD_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     steps = ["--steps", "6", "--warmup", "2"] if config == "cfg2" else ["--steps", "50", "--warmup", "50"]   # cfg5 ignores both (T = 1000)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", config,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", config, "--full",
                         "--no-cpu-baseline", "--no-attention"] + steps, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

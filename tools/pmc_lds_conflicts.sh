@@ -6,10 +6,10 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/pmc_lds
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/bench -o r --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $OUT/bench.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/bench -o r --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > $OUT/bench.log 2>&1
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/latent -o r --output-format csv -- python3 $ROOT/tools/one_latent_steps.py > $OUT/latent.log 2>&1
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/eval -o r --output-format csv -- python3 $ROOT/tools/one_eval.py > $OUT/eval.log 2>&1
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/attn -o r --output-format csv -- python3 $ROOT/bench.py --backbone attention --steps 2 --warmup 1 --no-cpu-baseline > $OUT/attn.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/attn -o r --output-format csv -- python3 $ROOT/bench.py --backbone attention --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/attn.log 2>&1
 cd $ROOT
 python3 - <<PY > $OUT/summary.txt
 import csv, glob, collections

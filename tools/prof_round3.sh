@@ -7,7 +7,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/bench -o b --output-format csv -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/bench -o b --output-format csv -- python3 $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/cfg4 -o c --output-format csv -- python3 $ROOT/bench.py --config cfg4 --no-cpu-baseline > $OUT/cfg4_under_rocprof.json 2> $OUT/cfg4.err
 cd $ROOT
 GIT_HEAD=${GIT_HEAD:-unknown} bash tools/pmc_gf3.sh > $OUT/pmc_gf3.log 2>&1
