@@ -224,6 +224,12 @@ _SIGS = {
     "pcd_set_attention_f16": (i32, [vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "pcd_set_attention_config": (i32, [i32]),
     "pcd_set_attention_last_kernel": (C.c_char_p, []),
+    "pcd_set_attention_lse_f16": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+    "pcd_set_attention_backward_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "pcd_set_attention_backward_f16": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "pcd_layernorm_train_f16": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "pcd_layernorm_backward_workspace_bytes": (sz, [i64, i32]),
+    "pcd_layernorm_backward_f16": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "pcd_add_shape_bias_f16": (i32, [vp, i64, i32, i32, vp, vp, vp]),
     "pcd_add_shape_bias_strided_f16": (i32, [vp, i64, i32, i32, vp, i64, vp, vp]),
     "pcd_tail3": (i32, [vp, i32, vp, i32, i64, vp, vp, vp, vp, vp, vp]),

@@ -382,11 +382,10 @@ class PointCloudDiffusion(_DiffusionBase):
     def configure_optimizers(self):
         """AdamW(lr, weight_decay=1e-5) + ReduceLROnPlateau(min, factor 0.5, patience 5) on `val_loss`
         (diffusion.py:60-68); the optimizer object is the HIP trainer, which also owns forward/backward."""
-        from .training import PointTrainer, ReduceLROnPlateau
-        if self.backbone != "pointnet":
-            raise RuntimeError("training is implemented for the reference's wired denoiser (backbone='pointnet') only")
+        from .training import AttentionTrainer, PointTrainer, ReduceLROnPlateau
         if getattr(self, "_trainer", None) is None:
-            self._trainer = PointTrainer(self.model, lr=self.lr, weight_decay=1e-5)
+            cls = AttentionTrainer if self.backbone == "attention" else PointTrainer
+            self._trainer = cls(self.model, lr=self.lr, weight_decay=1e-5)
         return {"optimizer": self._trainer,
                 "lr_scheduler": {"scheduler": ReduceLROnPlateau(self._trainer, factor=0.5, patience=5), "monitor": "val_loss"}}
 

@@ -677,6 +677,348 @@ class LatentTrainer:
         return loss
 
 
+class _Sab:
+    """One SetAttentionBlock (networks.py:51-83) in the training step: its four Linear layers and its saved tensors."""
+
+    def __init__(self, name: str, c: int):
+        self.name, self.c = name, c
+        self.inp = _Conv(f"{name}.attention.in_proj", None, c, 3 * c)
+        self.outp = _Conv(f"{name}.attention.out_proj", None, c, c)
+        self.ff0 = _Conv(f"{name}.ff.0", None, c, 4 * c)
+        self.ff2 = _Conv(f"{name}.ff.2", None, 4 * c, c)
+
+
+ATTN_SABS = (("att1", 64), ("att2", 128), ("att3", 256), ("bottleneck", 256), ("att_dec3", 256), ("att_dec2", 128), ("att_dec1", 64))
+ATTN_EMBS = (("emb1", 3), ("emb2", 64), ("emb3", 128), ("emb_dec3", 256), ("emb_dec2", 128), ("emb_dec1", 64))
+DEC1_PAD = 64          # dec1 = PointNetLayer(128, 3) runs as 64-channel layers with zero rows (GEMM and BatchNorm widths)
+
+
+class AttentionTrainer(PointTrainer):
+    """Forward + backward + AdamW for `UNetAttentionPointExperimental` (networks.py:597-722) in train() mode: the
+    counterpart of `PointTrainer` (whose convolution / BatchNorm helpers, optimizer step and surface it shares).
+    Each SetAttentionBlock runs unfused and keeps what its backward needs: LN1 -> in_proj -> attention (+ log-sum-exp)
+    -> out_proj + residual -> LN2 -> Linear + ReLU -> Linear + residual; the attention backward is the flash-style
+    kernel pair of csrc/attn_bwd.hip.  `x.T + emb1(t)` in front of enc1.conv1 (K = 3) is a per-shape bias; dec1's
+    3-channel layers run zero-padded to 64 channels in private buffers, their gradients and running statistics are
+    copied to the real 3-channel tensors."""
+
+    def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8,
+                 loss_scale: float = 1024.0):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.model = model
+        self.lr, self.wd, self.betas, self.eps, self.loss_scale = lr, weight_decay, betas, eps, float(loss_scale)
+        self.dev = model.device
+        if self.dev.type != "cuda":
+            raise RuntimeError("AttentionTrainer needs the model on an MI355X (model.to('cuda'))")
+        if model.dim != 256 or model.time_dim != 256:
+            raise RuntimeError("AttentionTrainer implements the reference's configuration dim = time_dim = 256")
+        self.heads = model.num_heads
+        self.step_count = 0
+        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
+        self.names = list(self.p.keys())
+        self.buf = dict(model.named_buffers())
+        self.freqs = timestep_freqs(256)
+        self.enc = [[_Conv(f"{n}.conv{i}", f"{n}.bn{i}", a, b) for i, (a, b) in enumerate([(cin, c), (c, c), (c, c)], start=1)]
+                    for n, cin, c in (("enc1", 3, 64), ("enc2", 64, 128), ("enc3", 128, 256))]
+        self.dec = [[_Conv(f"{n}.conv{i}", f"{n}.bn{i}", a, b) for i, (a, b) in enumerate([(cin, c), (c, c), (c, c)], start=1)]
+                    for n, cin, c in (("dec3", 512, 128), ("dec2", 256, 64), ("dec1p", 128, DEC1_PAD))]
+        self.sab = {n: _Sab(n, c) for n, c in ATTN_SABS}
+        for s in self.sab.values():              # in_proj's parameters are named in_proj_weight / in_proj_bias
+            for d in (self.p, self.g):
+                d[s.inp.conv + ".weight"] = d[f"{s.name}.attention.in_proj_weight"]
+                d[s.inp.conv + ".bias"] = d[f"{s.name}.attention.in_proj_bias"]
+        # dec1 padded: parameters, gradients and running statistics in private 64-channel buffers
+        for i, k in ((1, 128), (2, DEC1_PAD), (3, DEC1_PAD)):
+            for d in (self.p, self.g):
+                d[f"dec1p.conv{i}.weight"] = torch.zeros(DEC1_PAD, k, 1, dtype=torch.float32, device=self.dev)
+                d[f"dec1p.conv{i}.bias"] = torch.zeros(DEC1_PAD, dtype=torch.float32, device=self.dev)
+                d[f"dec1p.bn{i}.weight"] = torch.zeros(DEC1_PAD, dtype=torch.float32, device=self.dev)
+                d[f"dec1p.bn{i}.bias"] = torch.zeros(DEC1_PAD, dtype=torch.float32, device=self.dev)
+            self.buf[f"dec1p.bn{i}.running_mean"] = torch.zeros(DEC1_PAD, dtype=torch.float32, device=self.dev)
+            self.buf[f"dec1p.bn{i}.running_var"] = torch.ones(DEC1_PAD, dtype=torch.float32, device=self.dev)
+            self.buf[f"dec1p.bn{i}.num_batches_tracked"] = self.buf[f"dec1.bn{i}.num_batches_tracked"]
+        self.w_head = torch.zeros(3, DEC1_PAD, dtype=torch.float32, device=self.dev)
+        self.w16: Dict[str, torch.Tensor] = {}
+        self.w16t: Dict[str, torch.Tensor] = {}
+        self._ws: Dict[str, torch.Tensor] = {}
+        self.debug: Optional[Dict[str, torch.Tensor]] = None
+        self.refresh_weights()
+        model.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh_weights())
+
+    def _all_convs(self):
+        for blk in self.enc:
+            yield from blk[1:] if blk is self.enc[0] else blk
+        for blk in self.dec:
+            yield from blk
+        for s in self.sab.values():
+            yield from (s.inp, s.outp, s.ff0, s.ff2)
+
+    def refresh_weights(self):
+        """fp16 W / W^T operand copies of the fp32 master weights (dec1 through its zero-padded images); enc1.conv1's
+        K = 3 weights stay fp32."""
+        lib, st = self.lib, self._st()
+        with torch.no_grad():
+            for i in (1, 2, 3):
+                w = self.p[f"dec1.conv{i}.weight"]
+                self.p[f"dec1p.conv{i}.weight"][:3, :w.shape[1]].copy_(w)
+                self.p[f"dec1p.conv{i}.bias"][:3].copy_(self.p[f"dec1.conv{i}.bias"])
+                for s in ("weight", "bias"):
+                    self.p[f"dec1p.bn{i}.{s}"][:3].copy_(self.p[f"dec1.bn{i}.{s}"])
+            self.w_head[:, :3].copy_(self.p["output.weight"][:, :, 0])
+        self.w_xyz = self.p["enc1.conv1.weight"][:, :, 0].contiguous()
+        for L in self._all_convs():
+            w = self.p[L.conv + ".weight"]
+            w2 = w.view(w.shape[0], w.shape[1])
+            c, k = w2.shape
+            a = self.w16.get(L.conv)
+            if a is None:
+                a = self.w16[L.conv] = torch.empty(c, k, dtype=torch.float16, device=self.dev)
+                self.w16t[L.conv] = torch.empty(k, c, dtype=torch.float16, device=self.dev)
+            self._chk(lib.pcd_f32_to_f16(w2.data_ptr(), a.data_ptr(), a.numel(), st), "f32_to_f16")
+            self._chk(lib.pcd_transpose_f16(a.data_ptr(), c, k, self.w16t[L.conv].data_ptr(), st), "transpose")
+        self.model.invalidate()        # the sampler's packed (BN-folded) weights are stale now
+
+    # ------------------------------------------------------------------ set-attention block
+    def _linear(self, L: _Conv, a: torch.Tensor, out: torch.Tensor, relu: int = 0, resid: Optional[torch.Tensor] = None):
+        m = a.shape[0]
+        L.inputs = [(a, L.cin)]
+        g = _gemm_desc(a.data_ptr(), L.cin, L.cin, None, 0, 0, self.w16[L.conv].data_ptr(), L.cin,
+                       self.p[L.conv + ".bias"].data_ptr(), None, 0, m, L.cout)
+        g.relu = relu
+        if resid is None:
+            self._chk(self.lib.pcd_gemm_f16(C.byref(g), out.data_ptr(), L.cout, self._st()), "gemm_f16")
+        else:
+            self._chk(self.lib.pcd_gemm_f16_residual(C.byref(g), resid.data_ptr(), L.cout, out.data_ptr(), L.cout, self._st()),
+                      "gemm_resid")
+        return out
+
+    def sab_forward(self, name: str, x: torch.Tensor, b: int, n: int) -> torch.Tensor:
+        """SetAttentionBlock `name` on x fp16 [b*n][C] (train-time, unfused); returns y fp16 [b*n][C] and keeps the
+        block's saved tensors."""
+        lib, st, S = self.lib, self._st(), self.sab[name]
+        c, m = S.c, b * n
+        f16 = torch.float16
+        B = lambda key, shape, dt=f16: self._buf(f"{name}.{key}", shape, dt)
+        S.b, S.n, S.x = b, n, x
+        S.mu1, S.rs1, S.mu2, S.rs2 = (B(k, (m,), torch.float32) for k in ("mu1", "rs1", "mu2", "rs2"))
+        S.h1 = B("h1", (m, c))
+        self._chk(lib.pcd_layernorm_train_f16(x.data_ptr(), m, c, self.p[name + ".ln1.weight"].data_ptr(),
+                                              self.p[name + ".ln1.bias"].data_ptr(), S.h1.data_ptr(), S.mu1.data_ptr(),
+                                              S.rs1.data_ptr(), st), "layernorm_train")
+        S.qkv = self._linear(S.inp, S.h1, B("qkv", (m, 3 * c)))
+        S.att = B("att", (m, c))
+        S.lse = B("lse", (b * self.heads * n,), torch.float32)
+        self._chk(lib.pcd_set_attention_lse_f16(S.qkv.data_ptr(), b, n, c, self.heads, S.att.data_ptr(), S.lse.data_ptr(), st),
+                  "set_attention_lse")
+        S.y1 = self._linear(S.outp, S.att, B("y1", (m, c)), resid=x)
+        S.h2 = B("h2", (m, c))
+        self._chk(lib.pcd_layernorm_train_f16(S.y1.data_ptr(), m, c, self.p[name + ".ln2.weight"].data_ptr(),
+                                              self.p[name + ".ln2.bias"].data_ptr(), S.h2.data_ptr(), S.mu2.data_ptr(),
+                                              S.rs2.data_ptr(), st), "layernorm_train")
+        S.f1 = self._linear(S.ff0, S.h2, B("f1", (m, 4 * c)), relu=1)
+        return self._linear(S.ff2, S.f1, B("y", (m, c)), resid=S.y1)
+
+    def _ln_backward(self, ln: str, dh: torch.Tensor, x: torch.Tensor, mu, rs, dx: torch.Tensor):
+        m, c = x.shape
+        ws = self._buf("bwd.ln_ws", (self.lib.pcd_layernorm_backward_workspace_bytes(m, c) // 4,), torch.float32)
+        self._chk(self.lib.pcd_layernorm_backward_f16(dh.data_ptr(), x.data_ptr(), m, c, mu.data_ptr(), rs.data_ptr(),
+                                                      self.p[ln + ".weight"].data_ptr(), 1, dx.data_ptr(),
+                                                      self.g[ln + ".weight"].data_ptr(), self.g[ln + ".bias"].data_ptr(),
+                                                      ws.data_ptr(), ws.numel() * 4, self._st()), "layernorm_backward")
+
+    def sab_backward(self, name: str, dy: torch.Tensor) -> torch.Tensor:
+        """Backward of the last `sab_forward(name, ...)`: dy fp16 [m][C] becomes dx in place; the block's twelve
+        parameter gradients go to the gradient buffer."""
+        lib, st, S = self.lib, self._st(), self.sab[name]
+        c, b, n = S.c, S.b, S.n
+        m = b * n
+        B = lambda key, shape, dt=torch.float16: self._buf(f"bwd.sab.{key}", shape, dt)
+        df1 = B(f"df1.{c}", (m, 4 * c))
+        self._conv_backward(S.ff2, dy, m, [("set", df1)])
+        self._chk(lib.pcd_relu_mask_f16(df1.data_ptr(), S.f1.data_ptr(), df1.numel(), df1.data_ptr(), st), "relu_mask")
+        dh = B(f"dh.{c}", (m, c))
+        self._conv_backward(S.ff0, df1, m, [("set", dh)])
+        self._ln_backward(name + ".ln2", dh, S.y1, S.mu2, S.rs2, dy)               # dy += LN2^T dh: the first residual's gradient
+        datt = B(f"datt.{c}", (m, c))
+        self._conv_backward(S.outp, dy, m, [("set", datt)])
+        dqkv = B(f"dqkv.{c}", (m, 3 * c))
+        ws = B("attn_ws", (lib.pcd_set_attention_backward_workspace_bytes(b, n, c, self.heads) // 4,), torch.float32)
+        self._chk(lib.pcd_set_attention_backward_f16(S.qkv.data_ptr(), S.att.data_ptr(), datt.data_ptr(), S.lse.data_ptr(), b, n, c,
+                                                     self.heads, dqkv.data_ptr(), ws.data_ptr(), ws.numel() * 4, st), "attention_backward")
+        self._conv_backward(S.inp, dqkv, m, [("set", dh)])
+        self._ln_backward(name + ".ln1", dh, S.x, S.mu1, S.rs1, dy)
+        return dy
+
+    # ------------------------------------------------------------------ forward
+    def _layer(self, blk, inputs, m: int, update_stats: bool) -> torch.Tensor:
+        a = self._conv(blk[0], inputs, m, True, update_stats)
+        a = self._conv(blk[1], [(a, blk[1].cin)], m, True, update_stats)
+        return self._conv(blk[2], [(a, blk[2].cin)], m, True, update_stats)
+
+    def _plus_emb(self, key: str, a: torch.Tensor, e: str) -> torch.Tensor:
+        out = self._buf(key, tuple(a.shape), torch.float16)
+        self._chk(self.lib.pcd_add_shape_bias_f16(a.data_ptr(), self.m, a.shape[1], self.n, self.E[e].data_ptr(), out.data_ptr(),
+                                                  self._st()), "add_shape_bias")
+        return out
+
+    def forward(self, x_t: torch.Tensor, t: torch.Tensor, update_stats: bool = True) -> torch.Tensor:
+        """eps_hat (B, N, 3) fp32 with the network in train() mode; keeps what backward needs."""
+        lib, st, p = self.lib, self._st(), self.p
+        b, n, _ = x_t.shape
+        m = b * n
+        if n % 64 != 0:
+            raise ValueError("the attention backbone trains on point counts N that are multiples of 64")
+        self.b, self.n, self.m = b, n, m
+        self.x = x_t.to(torch.float32).contiguous()
+        tt = t.detach().to("cpu", torch.float32)
+        e = tt[:, None] * self.freqs[None, :]
+        self.emb = torch.cat((torch.sin(e), torch.cos(e)), dim=-1).to(self.dev)
+        self.h1 = self._buf("t.h1", (b, 256), torch.float32)
+        self.s1 = self._buf("t.s1", (b, 256), torch.float32)
+        self.temb = self._buf("t.temb", (b, 256), torch.float32)
+        self._mm(self.emb.data_ptr(), 256, 0, p["time_mlp.0.weight"].data_ptr(), 256, 1, b, 256, 256,
+                 p["time_mlp.0.bias"].data_ptr(), 0, self.h1.data_ptr(), 256)
+        self._chk(lib.pcd_silu_f32(self.h1.data_ptr(), self.h1.numel(), self.s1.data_ptr(), st), "silu")
+        self._mm(self.s1.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 1, b, 256, 256,
+                 p["time_mlp.2.bias"].data_ptr(), 0, self.temb.data_ptr(), 256)
+        self.E = {}
+        for name, c in ATTN_EMBS:
+            self.E[name] = self._buf(f"t.{name}", (b, c), torch.float32)
+            self._mm(self.temb.data_ptr(), 256, 0, p[name + ".weight"].data_ptr(), 256, 1, b, c, 256, p[name + ".bias"].data_ptr(), 0,
+                     self.E[name].data_ptr(), c)
+        for i in (1, 2, 3):                      # dec1's padded running statistics start from the real ones
+            for s in ("running_mean", "running_var"):
+                self.buf[f"dec1p.bn{i}.{s}"][:3].copy_(self.buf[f"dec1.bn{i}.{s}"])
+        # enc1.conv1 on x + emb1(t): W (x + e) + b = W x + (W e + b), a per-shape bias
+        self.tbias = self._buf("t.tbias", (b, 64), torch.float32)
+        self._mm(self.E["emb1"].data_ptr(), 3, 0, self.w_xyz.data_ptr(), 3, 1, b, 64, 3, p["enc1.conv1.bias"].data_ptr(), 0,
+                 self.tbias.data_ptr(), 64)
+        z0 = self._buf("enc1.conv1.z", (m, 64), torch.float32)
+        self._chk(lib.pcd_enc1_linear(self.x.data_ptr(), m, n, self.w_xyz.data_ptr(), 64, self.tbias.data_ptr(), z0.data_ptr(), st),
+                  "enc1_linear")
+        e1 = self.enc[0]
+        a = self._bn_relu(e1[0], z0, m, update_stats)
+        a = self._conv(e1[1], [(a, 64)], m, True, update_stats)
+        a = self._conv(e1[2], [(a, 64)], m, True, update_stats)
+        self.x1 = self._plus_emb("x1", self.sab_forward("att1", a, b, n), "emb2")
+        a = self._layer(self.enc[1], [(self.x1, 64)], m, update_stats)
+        self.x2 = self._plus_emb("x2", self.sab_forward("att2", a, b, n), "emb3")
+        a = self._layer(self.enc[2], [(self.x2, 128)], m, update_stats)
+        self.x3 = self.sab_forward("att3", a, b, n)
+        h = self._plus_emb("xb", self.sab_forward("bottleneck", self.x3, b, n), "emb_dec3")
+        h = self.sab_forward("att_dec3", h, b, n)
+        a = self._layer(self.dec[0], [(h, 256), (self.x3, 256)], m, update_stats)
+        h = self.sab_forward("att_dec2", self._plus_emb("h2", a, "emb_dec2"), b, n)
+        a = self._layer(self.dec[1], [(h, 128), (self.x2, 128)], m, update_stats)
+        h = self.sab_forward("att_dec1", self._plus_emb("h1", a, "emb_dec1"), b, n)
+        self.a_out = self._layer(self.dec[2], [(h, 64), (self.x1, 64)], m, update_stats)
+        if update_stats:
+            for i in (1, 2, 3):
+                for s in ("running_mean", "running_var"):
+                    self.buf[f"dec1.bn{i}.{s}"].copy_(self.buf[f"dec1p.bn{i}.{s}"][:3])
+        self.pred = self._buf("pred", (b, n, 3), torch.float32)
+        self._chk(lib.pcd_head3(self.a_out.data_ptr(), m, DEC1_PAD, self.w_head.data_ptr(), p["output.bias"].data_ptr(),
+                                self.pred.data_ptr(), st), "head3")
+        return self.pred
+
+    # ------------------------------------------------------------------ backward
+    def _colsum_shape(self, key: str, d: torch.Tensor) -> torch.Tensor:
+        out = self._buf(key, (self.b, d.shape[1]), torch.float32)
+        self._chk(self.lib.pcd_colsum_f16(d.data_ptr(), self.n, self.b, d.shape[1], out.data_ptr(), self._st()), "colsum_shape")
+        return out
+
+    def _layer_backward(self, blk, da: torch.Tensor, targets) -> None:
+        m = self.m
+        for L in (blk[2], blk[1]):
+            dz = self._bn_backward(L, da, m)
+            da = self._buf(f"bwd.{L.conv}", (m, L.cin), torch.float16)
+            self._conv_backward(L, dz, m, [("set", da)])
+        self._conv_backward(blk[0], self._bn_backward(blk[0], da, m), m, targets)
+
+    def backward(self, target: torch.Tensor) -> torch.Tensor:
+        """L1 loss against `target` (the noise) and all parameter gradients (scaled by loss_scale) into self.G.
+        Returns the loss as a 0-d device tensor."""
+        lib, st = self.lib, self._st()
+        b, n, m, p, g = self.b, self.n, self.m, self.p, self.g
+        self._chk(lib.pcd_fill_zero(self.G.data_ptr(), self.G.numel() * 4, st), "fill_zero")
+        loss_sum = self._buf("loss", (1,), torch.float32)
+        dpred = self._buf("dpred", (m, 3), torch.float32)
+        target = target.to(torch.float32).contiguous()
+        self._chk(lib.pcd_l1_loss(self.pred.data_ptr(), target.data_ptr(), m * 3, self.loss_scale, loss_sum.data_ptr(),
+                                  dpred.data_ptr(), st), "l1_loss")
+        # output Conv1d(3, 3) on dec1's (padded) activation
+        gwh = self._buf("bwd.gw_head", (3, DEC1_PAD), torch.float32)
+        self._chk(lib.pcd_vec3_outer(self.a_out.data_ptr(), dpred.data_ptr(), m, DEC1_PAD, gwh.data_ptr(), g["output.bias"].data_ptr(), st),
+                  "vec3_outer")
+        g["output.weight"][:, :, 0].copy_(gwh[:, :3])
+        da = self._buf("bwd.da_out", (m, DEC1_PAD), torch.float16)
+        self._chk(lib.pcd_vec3_expand_f16(dpred.data_ptr(), self.w_head.data_ptr(), m, DEC1_PAD, da.data_ptr(), st), "vec3_expand")
+        fresh = lambda key, c: self._buf(key, (m, c), torch.float16)
+        dE = {}
+        # decoder: dec1 <- att_dec1 <- dec2 <- att_dec2 <- dec3 <- att_dec3 <- bottleneck
+        dh, dx1 = fresh("bwd.dh64", 64), fresh("bwd.dx1", 64)
+        self._layer_backward(self.dec[2], da, [("set", dh), ("set", dx1)])
+        for i, k in ((1, 128), (2, 3), (3, 3)):
+            g[f"dec1.conv{i}.weight"].copy_(g[f"dec1p.conv{i}.weight"][:3, :k])
+            g[f"dec1.bn{i}.weight"].copy_(g[f"dec1p.bn{i}.weight"][:3])
+            g[f"dec1.bn{i}.bias"].copy_(g[f"dec1p.bn{i}.bias"][:3])
+        dh = self.sab_backward("att_dec1", dh)
+        dE["emb_dec1"] = self._colsum_shape("bwd.e_dec1", dh)
+        dh2, dx2 = fresh("bwd.dh128", 128), fresh("bwd.dx2", 128)
+        self._layer_backward(self.dec[1], dh, [("set", dh2), ("set", dx2)])
+        dh2 = self.sab_backward("att_dec2", dh2)
+        dE["emb_dec2"] = self._colsum_shape("bwd.e_dec2", dh2)
+        dh3, dx3 = fresh("bwd.dh256", 256), fresh("bwd.dx3", 256)
+        self._layer_backward(self.dec[0], dh2, [("set", dh3), ("set", dx3)])
+        dh3 = self.sab_backward("att_dec3", dh3)
+        dE["emb_dec3"] = self._colsum_shape("bwd.e_dec3", dh3)
+        dh3 = self.sab_backward("bottleneck", dh3)
+        self._chk(lib.pcd_add_relu_f16(dx3.data_ptr(), dh3.data_ptr(), dx3.numel(), 0, dx3.data_ptr(), st), "add")
+        # encoder: x3 = att3(enc3(x2)), x2 = att2(enc2(x1)) + emb3, x1 = att1(enc1(x + emb1)) + emb2
+        self._layer_backward(self.enc[2], self.sab_backward("att3", dx3), [("add", dx2)])
+        dE["emb3"] = self._colsum_shape("bwd.e3", dx2)
+        self._layer_backward(self.enc[1], self.sab_backward("att2", dx2), [("add", dx1)])
+        dE["emb2"] = self._colsum_shape("bwd.e2", dx1)
+        da = self.sab_backward("att1", dx1)
+        e1 = self.enc[0]
+        for L in (e1[2], e1[1]):
+            dz = self._bn_backward(L, da, m)
+            da = self._buf(f"bwd.{L.conv}", (m, L.cin), torch.float16)
+            self._conv_backward(L, dz, m, [("set", da)])
+        dz0 = self._bn_backward(e1[0], da, m)
+        gw = g["enc1.conv1.weight"]
+        tmp = self._buf("bwd.wxyzT", (3, 64), torch.float32)
+        self._chk(lib.pcd_vec3_outer(dz0.data_ptr(), self.x.data_ptr(), m, 64, tmp.data_ptr(), None, st), "vec3_outer")
+        gw[:, :, 0].copy_(tmp.t())
+        dtb = self._colsum_shape("bwd.dtbias", dz0)
+        self._mm(dtb.data_ptr(), 64, 1, self.E["emb1"].data_ptr(), 3, 0, 64, 3, b, None, 1, gw.data_ptr(), 3)
+        dE["emb1"] = self._buf("bwd.e1", (b, 3), torch.float32)
+        self._mm(dtb.data_ptr(), 64, 0, self.w_xyz.data_ptr(), 3, 0, b, 3, 64, None, 0, dE["emb1"].data_ptr(), 3)
+        # the six embedding Linears and time_mlp
+        ones = self._buf("ones", (1, b), torch.float32)
+        ones.fill_(1.0)
+        dtemb = self._buf("bwd.dtemb", (b, 256), torch.float32)
+        for i, (name, c) in enumerate(ATTN_EMBS):
+            d = dE[name]
+            self._mm(d.data_ptr(), c, 1, self.temb.data_ptr(), 256, 0, c, 256, b, None, 0, g[name + ".weight"].data_ptr(), 256)
+            self._mm(ones.data_ptr(), b, 0, d.data_ptr(), c, 0, 1, c, b, None, 0, g[name + ".bias"].data_ptr(), c)
+            self._mm(d.data_ptr(), c, 0, p[name + ".weight"].data_ptr(), 256, 0, b, 256, c, None, int(i > 0), dtemb.data_ptr(), 256)
+        self._mm(dtemb.data_ptr(), 256, 1, self.s1.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.2.weight"].data_ptr(), 256)
+        self._mm(ones.data_ptr(), b, 0, dtemb.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.2.bias"].data_ptr(), 256)
+        ds = self._buf("bwd.ds", (b, 256), torch.float32)
+        self._mm(dtemb.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 0, b, 256, 256, None, 0, ds.data_ptr(), 256)
+        dh1 = self._buf("bwd.dh", (b, 256), torch.float32)
+        self._chk(lib.pcd_silu_backward_f32(self.h1.data_ptr(), ds.data_ptr(), ds.numel(), dh1.data_ptr(), st), "silu_bwd")
+        self._mm(dh1.data_ptr(), 256, 1, self.emb.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.0.weight"].data_ptr(), 256)
+        self._mm(ones.data_ptr(), b, 0, dh1.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.0.bias"].data_ptr(), 256)
+        return loss_sum[0] / float(m * 3)
+
+    def grads(self) -> Dict[str, torch.Tensor]:
+        """Unscaled parameter gradients (copies), keyed like `named_parameters()`."""
+        return {k: self.g[k].clone() / self.loss_scale for k in self.names}
+
+
 class CosineAnnealingLR:
     """torch.optim.lr_scheduler.CosineAnnealingLR(T_max, eta_min) in closed form (diffusion.py:415-419)."""
 

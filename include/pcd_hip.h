@@ -567,6 +567,28 @@ int pcd_set_attention_f16(const void* qkv, int batch, int n_points, int c, int h
 int pcd_set_attention_config(int force_generic);
 /* name of the kernel the last pcd_set_attention_f16 call of this process launched (measurement reports quote it) */
 const char* pcd_set_attention_last_kernel(void);
+/* ---- training of the set-attention block (csrc/attn_bwd.hip; networks.py:51-83 under autograd).  n_points % 64 == 0.
+ * Forward for training: pcd_set_attention_f16's output (the same kernels, the same bits) and lse fp32 [B][heads][N] =
+ * ln sum_k exp(q . k / sqrt d) per query row (an exact second pass over the keys). */
+int pcd_set_attention_lse_f16(const void* qkv, int batch, int n_points, int c, int heads, void* out, float* lse,
+                              void* stream);
+/* Backward of softmax(Q K^T / sqrt d) V, flash style (P recomputed from lse, the N x N matrix is never written):
+ * qkv fp16 [B*N][3C] (the forward's input), out / dout fp16 [B*N][C], lse from pcd_set_attention_lse_f16 ->
+ * dqkv fp16 [B*N][3C] = [dq | dk | dv] in qkv's layout, 1/sqrt(d) applied.  Deterministic: a key-block kernel (dK, dV)
+ * and a query-block kernel (dQ) each own their output rows; no atomics.  workspace: fp32 delta = rowsum(dO o O). */
+size_t pcd_set_attention_backward_workspace_bytes(int batch, int n_points, int c, int heads);
+int pcd_set_attention_backward_f16(const void* qkv, const void* out, const void* dout, const float* lse, int batch,
+                                   int n_points, int c, int heads, void* dqkv, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+/* LayerNorm for training, C = 64 / 128 / 256: the values of pcd_layernorm_f16, plus mean[rows] and rstd[rows] fp32 */
+int pcd_layernorm_train_f16(const void* x, int64_t rows, int c, const float* gamma, const float* beta, void* out,
+                            float* mean, float* rstd, void* stream);
+/* its backward: dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) (added onto dx if accumulate; dx != dy), and
+ * dgamma / dbeta [c] summed over all rows in a fixed order (per-workgroup slabs in the workspace, then one ordered sum) */
+size_t pcd_layernorm_backward_workspace_bytes(int64_t rows, int c);
+int pcd_layernorm_backward_f16(const void* dy, const void* x, int64_t rows, int c, const float* mean, const float* rstd,
+                               const float* gamma, int accumulate, void* dx, float* dgamma, float* dbeta, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* x[m][c] + e[m / rows_per_shape][c] -> out (fp16 in/out, e fp32): the additive per-level time
  * embeddings of UNetAttentionPointExperimental (networks.py:669-698). */

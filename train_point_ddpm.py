@@ -5,6 +5,10 @@ BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoint
 `.ckpt` layout.
 
     python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt resume.ckpt] [--max-steps N]
+                               [--backbone {pointnet,attention}]
+
+`--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
+import); `--ckpt` resumes with the backbone stored in the checkpoint's hyper-parameters.
 
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
@@ -54,6 +58,8 @@ def main():
     ap.add_argument("--synthetic-shapes", type=int, default=160)
     ap.add_argument("--sample-steps", type=int, default=1000)
     ap.add_argument("--out", default=os.path.join("samples", "point_cloud_diffusion"))
+    ap.add_argument("--backbone", choices=("pointnet", "attention"), default="pointnet",
+                    help="denoiser of a new model (a resumed checkpoint keeps its own)")
     args = ap.parse_args()
     torch.manual_seed(24)
     timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -69,8 +75,10 @@ def main():
         logger.info(f"Loading Diffusion model from checkpoint: {args.ckpt}")
         model = PointCloudDiffusion.load_from_checkpoint(args.ckpt)
         assert model.num_points == args.num_points
+        if model.backbone != args.backbone:
+            logger.info(f"checkpoint backbone {model.backbone!r} is used (--backbone {args.backbone} ignored)")
     else:
-        model = PointCloudDiffusion(num_points=args.num_points)
+        model = PointCloudDiffusion(num_points=args.num_points, backbone=args.backbone)
     model = model.to("cuda")
     logger.info("Starting Diffusion Training")
     fit(model, dm, max_epochs=args.epochs, ckpt_dir=os.path.join("checkpoints", "point_ddpm", timestamp), log=logger.info,
