@@ -32,14 +32,16 @@ BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 
 
-def _gemm_desc(a1, k1, lda1, a2, k2, lda2, w, ldw, bias, shape_bias, rps, m, c):
+def _gemm_desc(a1, k1, w, ldw, m, c, a2=None, k2=0, bias=None, shape_bias=None, rps=0, relu=0):
+    """Descriptor of the fp16 MFMA GEMM z [m][c] = [a1 | a2] W^T (+ bias) for device pointers; each A block is packed
+    (row stride = its width k), W has row stride ldw."""
     g = _lib.GemmDesc()
-    g.a1, g.lda1, g.k1 = a1, lda1, k1
-    g.a2, g.lda2, g.k2 = a2, lda2, k2
+    g.a1, g.lda1, g.k1 = a1, k1, k1
+    g.a2, g.lda2, g.k2 = a2, k2, k2
     g.w, g.ldw = w, ldw
     g.bias = bias
     g.shape_bias, g.rows_per_shape = shape_bias, rps
-    g.relu, g.m, g.c = 0, m, c
+    g.relu, g.m, g.c = relu, m, c
     return g
 
 
@@ -92,6 +94,183 @@ def _collective_inplace(fn, t: torch.Tensor, *args) -> None:
         t.copy_(h)
 
 
+class _Trainer:
+    """What every trainer shares: the module's own `nn.Parameter`s re-pointed into one flat fp32 buffer (so `state_dict()`
+    always shows the trained weights and checkpoints keep the reference's keys), the workspace, the GEMM and few-row fp32
+    product helpers, the time embedding of the denoisers and the AdamW step behind a torch.optim-like surface.
+    Gradients are kept multiplied by `loss_scale`.  A subclass builds its layer tables after this constructor and ends
+    with `refresh_weights()`, which derives whatever the kernels read from the fp32 master weights."""
+
+    def __init__(self, model, lr: float, weight_decay: float, betas, eps: float, loss_scale: float):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.model = model
+        self.lr, self.wd, self.betas, self.eps, self.loss_scale = lr, weight_decay, betas, eps, float(loss_scale)
+        self.dev = model.device
+        if self.dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} needs the model on an MI355X (model.to('cuda'))")
+        self.step_count = 0
+        # ---- one flat fp32 buffer for parameters, one for gradients, two for the AdamW moments
+        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
+        self.names = list(self.p)                  # the trained parameters (subclasses may add aliases to p and g)
+        self.buf = dict(model.named_buffers())
+        self.freqs = timestep_freqs(256)
+        self._ws: Dict[str, torch.Tensor] = {}
+        self.saved: Dict[str, tuple] = {}          # inputs of the few-row products, for their backward
+        # load_state_dict copies into the flat buffer in place: what refresh_weights derives must follow
+        model.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh_weights())
+
+    def refresh_weights(self):
+        self.model.invalidate()        # the sampler's packed weights are stale now
+
+    # ------------------------------------------------------------------ workspace
+    def _st(self):
+        return _lib.stream_ptr()
+
+    def _chk(self, rc, what):
+        _lib.check(rc, what)
+
+    def _buf(self, key: str, shape, dtype=torch.float32, zero: bool = False) -> torch.Tensor:
+        """The workspace tensor `key`, (re)allocated when the shape or dtype changes (zero-filled then if `zero`)."""
+        t = self._ws.get(key)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.dev)
+            self._ws[key] = t
+        return t
+
+    def _scratch(self, key: str, numel: int, dtype=torch.float16) -> torch.Tensor:
+        """A flat scratch buffer that only ever grows (shared by the layers: transposes, slabs, ...)."""
+        t = self._ws.get(key)
+        if t is None or t.numel() < numel or t.dtype != dtype:
+            t = torch.empty(numel, dtype=dtype, device=self.dev)
+            self._ws[key] = t
+        return t
+
+    def _ones(self, n: int) -> torch.Tensor:
+        """A row of n fp32 ones (the bias gradient 1^T dy of a few-row product); nothing writes it after allocation."""
+        t = self._ws.get("ones")
+        if t is None or t.numel() != n:
+            t = self._ws["ones"] = torch.ones(1, n, dtype=torch.float32, device=self.dev)
+        return t
+
+    # ------------------------------------------------------------------ products
+    def _mm(self, a, lda, ta, b, ldb, tb, m, n, k, bias, acc, c, ldc):
+        self._chk(self.lib.pcd_matmul_f32(a, lda, ta, b, ldb, tb, m, n, k, bias, acc, c, ldc, self._st()), "matmul_f32")
+
+    def _gemm(self, g, out: torch.Tensor, resid: Optional[torch.Tensor] = None):
+        """out [m][c] = the product of descriptor g: fp32 for an fp32 `out`, else fp16 (+ resid, fp16 [m][c], if given)."""
+        if out.dtype == torch.float32:
+            self._chk(self.lib.pcd_gemm_f16_out32(C.byref(g), out.data_ptr(), g.c, self._st()), "gemm_f16_out32")
+        elif resid is None:
+            self._chk(self.lib.pcd_gemm_f16(C.byref(g), out.data_ptr(), g.c, self._st()), "gemm_f16")
+        else:
+            self._chk(self.lib.pcd_gemm_f16_residual(C.byref(g), resid.data_ptr(), g.c, out.data_ptr(), g.c, self._st()), "gemm_resid")
+
+    def _weight_grad(self, dz: torch.Tensor, m: int, c: int, inputs, out: int, ldo: int) -> None:
+        """Backward-weight product dW = dz^T [a_1 | a_2 | ...] for row-major fp16 dz [m][c] and inputs (a_i [m][k_i], k_i):
+        fp32 into the device pointer `out` (row stride ldo), block i from column k_1 + ... + k_(i-1) on."""
+        lib, st = self.lib, self._st()
+        dzT = self._scratch("bwd.dzT", c * m)
+        self._chk(lib.pcd_transpose_f16(dz.data_ptr(), m, c, dzT.data_ptr(), st), "transpose")
+        for a, k in inputs:
+            aT = self._scratch("bwd.aT", k * m)
+            self._chk(lib.pcd_transpose_f16(a.data_ptr(), m, k, aT.data_ptr(), st), "transpose")
+            g = _gemm_desc(dzT.data_ptr(), m, aT.data_ptr(), m, c, k)
+            # a C x k output is a handful of tiles with an m-deep reduction: split the reduction so that one launch
+            # carries >= ~512 tiles, then add the fp32 slabs in a fixed order
+            tiles = -(-c // 128) * -(-k // 128)
+            splits = 1
+            while splits * tiles < 512 and (m // 64) % (splits * 2) == 0 and m // (splits * 2) >= 256:
+                splits *= 2
+            if splits == 1:
+                self._chk(lib.pcd_gemm_f16_out32(C.byref(g), out, ldo, st), "gemm_dW")
+            else:
+                slabs = self._scratch("bwd.slabs", splits * c * k, torch.float32)
+                self._chk(lib.pcd_gemm_f16_splitk(C.byref(g), splits, slabs.data_ptr(), st), "gemm_dW_splitk")
+                self._chk(lib.pcd_sum_slabs_f32(slabs.data_ptr(), splits, c, k, out, ldo, st), "sum_slabs")
+            out += k * 4
+
+    def _lin(self, name: str, inputs, col0: int = 0) -> torch.Tensor:
+        """y = [inputs] W^T + b as few-row fp32 products (`pcd_matmul_f32`: weights read once): an nn.Linear, whose
+        torch.cat input (networks.py:1062,1074-1077) is a split product, or the per-shape part of a Conv1d(k=1), whose
+        weight columns start at col0.  Returns the workspace buffer `name.y` [rows][C]."""
+        w, b = self.p[name + ".weight"], self.p[name + ".bias"]
+        c, ldw = w.shape[0], w.shape[1]
+        rows = inputs[0][0].shape[0]
+        y = self._buf(name + ".y", (rows, c), torch.float32)
+        off = col0
+        for i, (a, k) in enumerate(inputs):
+            self._mm(a.data_ptr(), k, 0, w.data_ptr() + off * 4, ldw, 1, rows, c, k, b.data_ptr() if i == 0 else None, 1 if i else 0,
+                     y.data_ptr(), c)
+            off += k
+        self.saved[name] = (tuple(inputs), col0)
+        return y
+
+    def _lin_backward(self, name: str, dy: torch.Tensor, targets, bias: bool = True, acc: int = 0) -> None:
+        """Backward of the last `_lin(name, ...)` from dy [rows][C]: db = 1^T dy (not with `bias` False: a bias in front of
+        a BatchNorm keeps its analytic zero), then per input dW = dy^T a into its column block of the weight gradient
+        (added to it with `acc`) and the input gradient dy W into targets[i] = None | ('set'|'add', tensor)."""
+        inputs, col0 = self.saved[name]
+        w, gw = self.p[name + ".weight"], self.g[name + ".weight"]
+        c, ldw = w.shape[0], w.shape[1]
+        rows = dy.shape[0]
+        if bias:
+            self._mm(self._ones(rows).data_ptr(), rows, 0, dy.data_ptr(), c, 0, 1, c, rows, None, 0, self.g[name + ".bias"].data_ptr(), c)
+        off = col0
+        for (a, k), tgt in zip(inputs, targets):
+            self._mm(dy.data_ptr(), c, 1, a.data_ptr(), k, 0, c, k, rows, None, acc, gw.data_ptr() + off * 4, ldw)
+            if tgt is not None:
+                mode, dst = tgt
+                self._mm(dy.data_ptr(), c, 0, w.data_ptr() + off * 4, ldw, 0, rows, k, c, None, 1 if mode == "add" else 0,
+                         dst.data_ptr(), k)
+            off += k
+
+    # ------------------------------------------------------------------ time embedding
+    def _time_embedding(self, t: torch.Tensor) -> torch.Tensor:
+        """time_mlp(sinusoid(t)) [B][256]: the sinusoid on the host with the reference's ops (networks.py:820-838),
+        Linear -> SiLU -> Linear on the device."""
+        tt = t.detach().to("cpu", torch.float32)
+        e = tt[:, None] * self.freqs[None, :]
+        emb = torch.cat((torch.sin(e), torch.cos(e)), dim=-1).to(self.dev)
+        self.h1 = self._lin("time_mlp.0", [(emb, 256)])
+        s1 = self._buf("t.s1", tuple(self.h1.shape))
+        self._chk(self.lib.pcd_silu_f32(self.h1.data_ptr(), self.h1.numel(), s1.data_ptr(), self._st()), "silu")
+        self.temb = self._lin("time_mlp.2", [(s1, 256)])
+        return self.temb
+
+    def _time_mlp_backward(self, dtemb: torch.Tensor) -> None:
+        """time_mlp's parameter gradients from dtemb, the gradient of `_time_embedding`'s output."""
+        ds = self._buf("bwd.ds", tuple(dtemb.shape))
+        self._lin_backward("time_mlp.2", dtemb, [("set", ds)])
+        dh = self._buf("bwd.dh", tuple(dtemb.shape))
+        self._chk(self.lib.pcd_silu_backward_f32(self.h1.data_ptr(), ds.data_ptr(), ds.numel(), dh.data_ptr(), self._st()), "silu_bwd")
+        self._lin_backward("time_mlp.0", dh, [None])
+
+    # ------------------------------------------------------------------ optimizer
+    def grads(self) -> Dict[str, torch.Tensor]:
+        """Unscaled parameter gradients (copies), keyed like `named_parameters()`."""
+        return {k: self.g[k].clone() / self.loss_scale for k in self.names}
+
+    def optimizer_step(self):
+        self.step_count += 1
+        b1, b2 = self.betas
+        world = _allreduce_gradients(self.G)           # data parallel: mean gradient over the ranks (BatchNorm stays per rank)
+        self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+                                          self.P.numel(), self.lr, b1, b2, self.eps, self.wd, self.step_count,
+                                          self.loss_scale * world, self._st()), "adamw")
+        self.refresh_weights()
+
+    # torch.optim-like aliases so the object can stand where the reference's optimizer does
+    def step(self):
+        self.optimizer_step()
+
+    def zero_grad(self):
+        pass                                # every backward overwrites the whole gradient buffer
+
+    def state_dict(self):
+        return {"step": self.step_count, "lr": self.lr, "exp_avg": self.M1, "exp_avg_sq": self.M2}
+
+
 class _Conv:
     """One Conv1d(k=1) [+ BatchNorm1d + ReLU]: names of its parameters and its saved tensors."""
 
@@ -101,26 +280,20 @@ class _Conv:
         self.inputs: List[Tuple[torch.Tensor, int]] = []
 
 
-class PointTrainer:
-    """Forward + backward + AdamW for `UNetPointNetLarge` (networks.py:725-818).  Parameters stay the
-    module's own `nn.Parameter`s (re-pointed into one flat fp32 buffer), so `state_dict()` always shows the
-    trained weights and checkpoints keep the reference's keys."""
+class PointTrainer(_Trainer):
+    """Forward + backward + AdamW for `UNetPointNetLarge` (networks.py:725-818)."""
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  loss_scale: float = 1024.0):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.model = model
-        self.lr, self.wd, self.betas, self.eps, self.loss_scale = lr, weight_decay, betas, eps, float(loss_scale)
-        self.dev = model.device
-        if self.dev.type != "cuda":
-            raise RuntimeError("PointTrainer needs the model on an MI355X (model.to('cuda'))")
-        self.step_count = 0
-        # ---- one flat fp32 buffer for parameters, one for gradients, two for the AdamW moments
-        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
-        self.buf = dict(model.named_buffers())
-        self.freqs = timestep_freqs(256)
-        # ---- layer table in execution order
+        super().__init__(model, lr, weight_decay, betas, eps, loss_scale)
+        self.w16: Dict[str, torch.Tensor] = {}
+        self.w16t: Dict[str, torch.Tensor] = {}
+        self.debug: Optional[Dict[str, torch.Tensor]] = None    # tests set a dict: per-layer da / dz copies are kept
+        self._build_layers()
+        self.refresh_weights()
+
+    def _build_layers(self):
+        """The layer table in execution order."""
         self.enc = [[_Conv(f"{n}.conv{i}", f"{n}.bn{i}", a, b) for i, (a, b) in
                      enumerate([(259 if cin is None else cin, mid), (mid, mid), (mid, cout)], start=1)]
                     for n, cin, mid, cout in POINT_ENC]
@@ -129,27 +302,6 @@ class PointTrainer:
                      enumerate([(cin, mid), (mid, mid), (mid, cout)], start=1)] for n, cin, mid, cout in POINT_DEC]
         self.out0 = _Conv("output.0", "output.1", 64, 64)
         self.refine = {c: _Conv(n, None, c, c) for n, c in POINT_REFINE}
-        self.w16: Dict[str, torch.Tensor] = {}
-        self.w16t: Dict[str, torch.Tensor] = {}
-        self._ws: Dict[str, torch.Tensor] = {}
-        self.debug: Optional[Dict[str, torch.Tensor]] = None    # tests set a dict: per-layer da / dz copies are kept
-        self.refresh_weights()
-        # load_state_dict copies into the flat buffer in place: the fp16 operand copies must follow
-        model.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh_weights())
-
-    # ------------------------------------------------------------------ helpers
-    def _st(self):
-        return _lib.stream_ptr()
-
-    def _chk(self, rc, what):
-        _lib.check(rc, what)
-
-    def _buf(self, key: str, shape, dtype) -> torch.Tensor:
-        t = self._ws.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.dev)
-            self._ws[key] = t
-        return t
 
     def _all_convs(self):
         for blk in self.enc:
@@ -160,10 +312,19 @@ class PointTrainer:
         yield self.out0
         yield from self.refine.values()
 
+    def _f16_operands(self, key: str, w2: torch.Tensor) -> None:
+        """fp16 copies of the fp32 weight matrix w2 [C][K]: W for the forward product, W^T [K][C] for backward-data."""
+        c, k = w2.shape
+        a = self.w16.get(key)
+        if a is None:
+            a = self.w16[key] = torch.empty(c, k, dtype=torch.float16, device=self.dev)
+            self.w16t[key] = torch.empty(k, c, dtype=torch.float16, device=self.dev)
+        self._chk(self.lib.pcd_f32_to_f16(w2.data_ptr(), a.data_ptr(), a.numel(), self._st()), "f32_to_f16")
+        self._chk(self.lib.pcd_transpose_f16(a.data_ptr(), c, k, self.w16t[key].data_ptr(), self._st()), "transpose")
+
     def refresh_weights(self):
-        """fp16 operand copies of the fp32 master weights: W [C][K] for the forward product and W^T [K][C] for
-        backward-data.  enc1.conv1 (K = 3 + 256) and the global half of dec4.conv1 stay fp32."""
-        lib, st = self.lib, self._st()
+        """fp16 operand copies of the fp32 master weights.  enc1.conv1 (K = 3 + 256) and the global half of dec4.conv1
+        stay fp32."""
         for L in self._all_convs():
             w = self.p[L.conv + ".weight"]
             if L.conv == "enc1.conv1":
@@ -173,27 +334,8 @@ class PointTrainer:
                 w2 = w[:, 4096:, 0].contiguous()               # the refine4(x4) half; the 4096 global columns stay fp32
             else:
                 w2 = w.view(w.shape[0], w.shape[1])
-            c, k = w2.shape
-            a = self.w16.get(L.conv)
-            if a is None:
-                a = self.w16[L.conv] = torch.empty(c, k, dtype=torch.float16, device=self.dev)
-                self.w16t[L.conv] = torch.empty(k, c, dtype=torch.float16, device=self.dev)
-            self._chk(lib.pcd_f32_to_f16(w2.data_ptr(), a.data_ptr(), a.numel(), st), "f32_to_f16")
-            self._chk(lib.pcd_transpose_f16(a.data_ptr(), c, k, self.w16t[L.conv].data_ptr(), st), "transpose")
+            self._f16_operands(L.conv, w2)
         self.model.invalidate()        # the sampler's packed (BN-folded) weights are stale now
-
-    def _mm(self, a, lda, ta, b, ldb, tb, m, n, k, bias, acc, c, ldc):
-        self._chk(self.lib.pcd_matmul_f32(a, lda, ta, b, ldb, tb, m, n, k, bias, acc, c, ldc, self._st()), "matmul_f32")
-
-    def _gemm(self, a1, k1, a2, k2, w, ldw, bias, shape_bias, rps, m, c, out, resid=None):
-        g = _gemm_desc(a1.data_ptr(), k1, k1, a2.data_ptr() if a2 is not None else None, k2, k2, w, ldw,
-                       bias, shape_bias, rps, m, c)
-        if out.dtype == torch.float32:
-            self._chk(self.lib.pcd_gemm_f16_out32(C.byref(g), out.data_ptr(), c, self._st()), "gemm_f16_out32")
-        elif resid is None:
-            self._chk(self.lib.pcd_gemm_f16(C.byref(g), out.data_ptr(), c, self._st()), "gemm_f16")
-        else:
-            self._chk(self.lib.pcd_gemm_f16_residual(C.byref(g), resid.data_ptr(), c, out.data_ptr(), c, self._st()), "gemm_resid")
 
     # ------------------------------------------------------------------ forward
     def _bn_relu(self, L: _Conv, z: torch.Tensor, m: int, train_stats: bool):
@@ -216,7 +358,7 @@ class PointTrainer:
                                        L.a.data_ptr(), st), "bn_apply")
         return L.a
 
-    def _conv(self, L: _Conv, inputs, m: int, bn: bool, update_stats: bool, shape_bias=None, rps=0, w=None, ldw=None):
+    def _conv(self, L: _Conv, inputs, m: int, bn: bool, update_stats: bool, shape_bias=None, rps=0):
         """z = [inputs] W^T + b, then BatchNorm(batch statistics) + ReLU if the layer has one."""
         L.inputs = inputs
         (a1, k1) = inputs[0]
@@ -225,12 +367,19 @@ class PointTrainer:
         z = self._buf(L.conv + ".z", (m, L.cout), torch.float32 if bn else torch.float16)
         wt = self.w16[L.conv]
         bias = None if shape_bias is not None else self.p[L.conv + ".bias"].data_ptr()
-        self._gemm(a1, k1, a2, k2, wt.data_ptr() if w is None else w, wt.shape[1] if ldw is None else ldw, bias,
-                   shape_bias, rps, m, L.cout, z)
+        self._gemm(_gemm_desc(a1.data_ptr(), k1, wt.data_ptr(), wt.shape[1], m, L.cout, a2=a2.data_ptr() if a2 is not None else None,
+                              k2=k2, bias=bias, shape_bias=shape_bias, rps=rps), z)
         if not bn:
             L.z = L.a = z
             return z
         return self._bn_relu(L, z, m, update_stats)
+
+    def _enc1(self, tbias: torch.Tensor, update_stats: bool) -> torch.Tensor:
+        """enc1.conv1 on the xyz columns (K = 3, fp32) plus the per-shape bias tbias [B][64], then BatchNorm + ReLU."""
+        z0 = self._buf("enc1.conv1.z", (self.m, 64), torch.float32)
+        self._chk(self.lib.pcd_enc1_linear(self.x.data_ptr(), self.m, self.n, self.w_xyz.data_ptr(), 64, tbias.data_ptr(),
+                                           z0.data_ptr(), self._st()), "enc1_linear")
+        return self._bn_relu(self.enc[0][0], z0, self.m, update_stats)
 
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, update_stats: bool = True) -> torch.Tensor:
         """eps_hat (B, N, 3) fp32 with the network in train() mode; keeps what backward needs."""
@@ -241,29 +390,10 @@ class PointTrainer:
             raise ValueError("B*N must be a multiple of 64 (reduction length of the backward-weight GEMM)")
         self.b, self.n, self.m = b, n, m
         self.x = x_t.to(torch.float32).contiguous()
-        # time embedding: sinusoid on the host with the reference's ops (networks.py:820-838), MLP on the device
-        tt = t.detach().to("cpu", torch.float32)
-        e = tt[:, None] * self.freqs[None, :]
-        self.emb = torch.cat((torch.sin(e), torch.cos(e)), dim=-1).to(self.dev)
         p = self.p
-        self.h1 = self._buf("t.h1", (b, 256), torch.float32)
-        self.s1 = self._buf("t.s1", (b, 256), torch.float32)
-        self.temb = self._buf("t.temb", (b, 256), torch.float32)
-        self._mm(self.emb.data_ptr(), 256, 0, p["time_mlp.0.weight"].data_ptr(), 256, 1, b, 256, 256,
-                 p["time_mlp.0.bias"].data_ptr(), 0, self.h1.data_ptr(), 256)
-        self._chk(lib.pcd_silu_f32(self.h1.data_ptr(), self.h1.numel(), self.s1.data_ptr(), st), "silu")
-        self._mm(self.s1.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 1, b, 256, 256,
-                 p["time_mlp.2.bias"].data_ptr(), 0, self.temb.data_ptr(), 256)
+        temb = self._time_embedding(t)
         # enc1.conv1: [xyz | temb] -> 64; the time columns give a per-shape bias
-        e1 = self.enc[0][0]
-        w1 = p["enc1.conv1.weight"]
-        self.tbias = self._buf("t.tbias", (b, 64), torch.float32)
-        self._mm(self.temb.data_ptr(), 256, 0, w1.data_ptr() + 3 * 4, 259, 1, b, 64, 256, p["enc1.conv1.bias"].data_ptr(), 0,
-                 self.tbias.data_ptr(), 64)
-        z0 = self._buf("enc1.conv1.z", (m, 64), torch.float32)
-        self._chk(lib.pcd_enc1_linear(self.x.data_ptr(), m, n, self.w_xyz.data_ptr(), 64, self.tbias.data_ptr(), z0.data_ptr(), st),
-                  "enc1_linear")
-        a = self._bn_relu(e1, z0, m, update_stats)
+        a = self._enc1(self._lin("enc1.conv1", [(temb, 256)], col0=3), update_stats)
         skips = []
         for bi, blk in enumerate(self.enc):
             for li, L in enumerate(blk):
@@ -279,10 +409,7 @@ class PointTrainer:
         self.garg = self._buf("g.arg", (b, 4096), torch.int32)
         self._chk(lib.pcd_colmax_argmax_f16(a.data_ptr(), b, n, 4096, self.gmax.data_ptr(), self.garg.data_ptr(), st), "colmax")
         # dec4.conv1 = [global (4096, constant over N) | refine4(x4) (1024)]: the global half is a per-shape bias
-        w4 = p["dec4.conv1.weight"]
-        self.gbias = self._buf("g.bias", (b, 1024), torch.float32)
-        self._mm(self.gmax.data_ptr(), 4096, 0, w4.data_ptr(), 5120, 1, b, 1024, 4096, p["dec4.conv1.bias"].data_ptr(), 0,
-                 self.gbias.data_ptr(), 1024)
+        self.gbias = self._lin("dec4.conv1", [(self.gmax, 4096)])
         prev = None
         for blk, xs in zip(self.dec, (x4, x3, x2, x1)):
             c = xs.shape[1]
@@ -304,50 +431,26 @@ class PointTrainer:
     def _conv_backward(self, L: _Conv, dz: torch.Tensor, m: int, targets, w_cols0: int = 0):
         """Given dz (M, C): dW, db into the gradient views, and the input gradients.
         targets: per input either None (not needed), ('set', tensor) or ('add', tensor)."""
-        lib, st = self.lib, self._st()
         c = L.cout
         gw = self.g[L.conv + ".weight"]
-        ktot = gw.shape[1]
         if self.debug is not None:
             self.debug[L.conv + ".dz"] = dz.clone()
         if not L.bn:
-            self._chk(lib.pcd_colsum_f16(dz.data_ptr(), m, 1, c, self.g[L.conv + ".bias"].data_ptr(), st), "colsum")
+            self._chk(self.lib.pcd_colsum_f16(dz.data_ptr(), m, 1, c, self.g[L.conv + ".bias"].data_ptr(), self._st()), "colsum")
         # (a conv bias in front of a BatchNorm: dz is mean-free per channel by construction, its column sum is exactly the
         #  analytic zero - the gradient view keeps the 0 it was allocated with; autograd leaves ~1e-9 rounding noise there)
-        dzT = self._buf("bwd.dzT", (4096 * m,), torch.float16)
-        self._chk(lib.pcd_transpose_f16(dz.data_ptr(), m, c, dzT.data_ptr(), st), "transpose")
-        aT = self._buf("bwd.aT", (4096 * m,), torch.float16)
-        col = w_cols0
+        self._weight_grad(dz, m, c, L.inputs, gw.data_ptr() + w_cols0 * 4, gw.shape[1])
         wt = self.w16t[L.conv]
         row = 0
         for (a_in, k), tgt in zip(L.inputs, targets):
-            # dW[:, col:col+k] = dz^T a_in : rows = C, reduction = M, columns = k
-            self._chk(lib.pcd_transpose_f16(a_in.data_ptr(), m, k, aT.data_ptr(), st), "transpose")
-            g = _gemm_desc(dzT.data_ptr(), m, m, None, 0, 0, aT.data_ptr(), m, None, None, 0, c, k)
-            # a C x k output is a handful of tiles with an M-deep reduction: split the reduction so that one launch
-            # carries >= ~512 tiles, then add the fp32 slabs in a fixed order
-            tiles = -(-c // 128) * -(-k // 128)
-            splits = 1
-            while splits * tiles < 512 and (m // 64) % (splits * 2) == 0 and m // (splits * 2) >= 256:
-                splits *= 2
-            if splits == 1:
-                self._chk(lib.pcd_gemm_f16_out32(C.byref(g), gw.data_ptr() + col * 4, ktot, st), "gemm_dW")
-            else:
-                slabs = self._buf("bwd.slabs", (16 * 1024 * 1024,), torch.float32)
-                if splits * c * k > slabs.numel():
-                    slabs = self._buf("bwd.slabs", (splits * c * k,), torch.float32)
-                self._chk(lib.pcd_gemm_f16_splitk(C.byref(g), splits, slabs.data_ptr(), st), "gemm_dW_splitk")
-                self._chk(lib.pcd_sum_slabs_f32(slabs.data_ptr(), splits, c, k, gw.data_ptr() + col * 4, ktot, st), "sum_slabs")
             if tgt is not None:
                 mode, dst = tgt
                 # da_in = dz W[:, col:col+k] : the rows [row, row+k) of W^T
                 if self.debug is not None and mode == "add":
                     self.debug[f"{L.conv}.in{len(self.debug)}.before_add"] = dst.clone()
-                self._gemm(dz, c, None, 0, wt.data_ptr() + row * c * 2, c, None, None, 0, m, k, dst,
-                           resid=dst if mode == "add" else None)
+                self._gemm(_gemm_desc(dz.data_ptr(), c, wt.data_ptr() + row * c * 2, c, m, k), dst, resid=dst if mode == "add" else None)
                 if self.debug is not None:
-                    self.debug[f"{L.conv}.din{col - w_cols0}"] = dst.clone()
-            col += k
+                    self.debug[f"{L.conv}.din{row}"] = dst.clone()
             row += k
 
     def _bn_backward(self, L: _Conv, da: torch.Tensor, m: int) -> torch.Tensor:
@@ -360,11 +463,38 @@ class PointTrainer:
                                                da.data_ptr(), self._st()), "bn_backward")
         return da
 
+    def _chain_backward(self, layers, da: torch.Tensor, m: int, targets=None) -> torch.Tensor:
+        """Backward through conv + BatchNorm + ReLU layers, given last first, from da = the gradient of the last one's
+        output.  Each layer's input gradient goes to a fresh buffer that feeds the next one; the final layer's go to
+        `targets` instead when given.  Returns the last fresh buffer."""
+        for i, L in enumerate(layers):
+            dz = self._bn_backward(L, da, m)
+            if targets is not None and i == len(layers) - 1:
+                self._conv_backward(L, dz, m, targets)
+            else:
+                da = self._buf(f"bwd.{L.conv}", (m, L.cin), torch.float16)
+                self._conv_backward(L, dz, m, [("set", da)])
+        return da
+
+    def _colsum_shape(self, key: str, d: torch.Tensor) -> torch.Tensor:
+        """Per-shape column sums [B][C] of d [B*N][C]: the gradient of a per-shape bias."""
+        out = self._buf(key, (self.b, d.shape[1]), torch.float32)
+        self._chk(self.lib.pcd_colsum_f16(d.data_ptr(), self.n, self.b, d.shape[1], out.data_ptr(), self._st()), "colsum_shape")
+        return out
+
+    def _enc1_backward(self, da: torch.Tensor) -> torch.Tensor:
+        """Backward of `_enc1` from da: the xyz columns of enc1.conv1's weight gradient; returns the gradient of tbias."""
+        dz0 = self._bn_backward(self.enc[0][0], da, self.m)
+        tmp = self._buf("bwd.wxyzT", (3, 64), torch.float32)
+        self._chk(self.lib.pcd_vec3_outer(dz0.data_ptr(), self.x.data_ptr(), self.m, 64, tmp.data_ptr(), None, self._st()), "vec3_outer")
+        self.g["enc1.conv1.weight"][:, :3, 0].copy_(tmp.t())
+        return self._colsum_shape("bwd.dtbias", dz0)
+
     def backward(self, target: torch.Tensor) -> torch.Tensor:
         """L1 loss against `target` (the noise) and all parameter gradients (scaled by loss_scale) into self.G.
         Returns the loss as a 0-d device tensor."""
         lib, st = self.lib, self._st()
-        b, n, m, p, g = self.b, self.n, self.m, self.p, self.g
+        b, n, m, g = self.b, self.n, self.m, self.g
         loss_sum = self._buf("loss", (1,), torch.float32)
         dpred = self._buf("dpred", (m, 3), torch.float32)
         target = target.to(torch.float32).contiguous()
@@ -377,41 +507,27 @@ class PointTrainer:
         da = self._buf("bwd.da0", (m, 64), torch.float16)
         self._chk(lib.pcd_vec3_expand_f16(dpred.data_ptr(), self.w_head.data_ptr(), m, 64, da.data_ptr(), st), "vec3_expand")
 
-        def chain(L: _Conv, da_out, targets):
-            dz = self._bn_backward(L, da_out, m) if L.bn else da_out
-            self._conv_backward(L, dz, m, targets)
-
         def fresh(key, c):
             return self._buf(key, (m, c), torch.float16)
 
-        d_in = fresh("bwd.d_out0", 64)
-        chain(self.out0, da, [("set", d_in)])
-        da = d_in
+        da = self._chain_backward([self.out0], da, m)
         dskip: Dict[int, torch.Tensor] = {}
         # decoder, last block first
         for bi in (3, 2, 1, 0):
             blk = self.dec[bi]
             c_skip = (1024, 512, 256, 128)[bi]
-            d2 = fresh(f"bwd.{blk[2].conv}", blk[2].cin)
-            chain(blk[2], da, [("set", d2)])
-            d1 = fresh(f"bwd.{blk[1].conv}", blk[1].cin)
-            chain(blk[1], d2, [("set", d1)])
+            d1 = self._chain_backward(blk[:0:-1], da, m)
             dr = fresh(f"bwd.r{c_skip}", c_skip)
             if bi == 0:
                 dz = self._bn_backward(blk[0], d1, m)
                 # global half: per-shape sums of dz drive dW[:, :4096] and the max-pool gradient
-                S = self._buf("bwd.S", (b, 1024), torch.float32)
-                self._chk(lib.pcd_colsum_f16(dz.data_ptr(), n, b, 1024, S.data_ptr(), st), "colsum_shape")
-                gw = g["dec4.conv1.weight"]
-                self._mm(S.data_ptr(), 1024, 1, self.gmax.data_ptr(), 4096, 0, 1024, 4096, b, None, 0, gw.data_ptr(), 5120)
+                S = self._colsum_shape("bwd.S", dz)
                 dG = self._buf("bwd.dG", (b, 4096), torch.float32)
-                self._mm(S.data_ptr(), 1024, 0, p["dec4.conv1.weight"].data_ptr(), 5120, 0, b, 4096, 1024, None, 0, dG.data_ptr(), 4096)
+                self._lin_backward("dec4.conv1", S, [("set", dG)], bias=False)
                 self._conv_backward(blk[0], dz, m, [("set", dr)], w_cols0=4096)
-                da = None
             else:
-                dprev = fresh(f"bwd.prev{bi}", blk[0].inputs[0][1])
-                chain(blk[0], d1, [("set", dprev), ("set", dr)])
-                da = dprev
+                da = fresh(f"bwd.prev{bi}", blk[0].inputs[0][1])
+                self._chain_backward(blk[:1], d1, m, [("set", da), ("set", dr)])
             # refine_k: bare conv on the skip tensor
             dx = fresh(f"bwd.x{c_skip}", c_skip)
             self._conv_backward(self.refine[c_skip], dr, m, [("set", dx)])
@@ -419,59 +535,17 @@ class PointTrainer:
         # global_feat: scatter dG through the argmax, then two conv+BN+ReLU stages into dx4
         dgf = self._buf("bwd.dgf", (m, 4096), torch.float16)
         self._chk(lib.pcd_maxpool_backward_f16(dG.data_ptr(), self.garg.data_ptr(), b, n, 4096, dgf.data_ptr(), st), "maxpool_bwd")
-        d_g0 = fresh("bwd.g0", 2048)
-        chain(self.gf[1], dgf, [("set", d_g0)])
-        chain(self.gf[0], d_g0, [("add", dskip[1024])])
+        self._chain_backward(self.gf[::-1], dgf, m, [("add", dskip[1024])])
         # encoder: each block ends in a skip tensor whose gradient is already seeded by the decoder side
-        for bi in (3, 2, 1, 0):
+        for bi in (3, 2, 1):
             blk = self.enc[bi]
-            c_out = (128, 256, 512, 1024)[bi]
-            da = dskip[c_out]
-            d2 = fresh(f"bwd.{blk[2].conv}", blk[2].cin)
-            chain(blk[2], da, [("set", d2)])
-            d1 = fresh(f"bwd.{blk[1].conv}", blk[1].cin)
-            chain(blk[1], d2, [("set", d1)])
-            if bi > 0:
-                chain(blk[0], d1, [("add", dskip[blk[0].cin])])
-        # enc1.conv1: K = 3 + 256, all fp32 side products
-        e1 = self.enc[0][0]
-        dz0 = self._bn_backward(e1, d1, m)
-        gw = g["enc1.conv1.weight"]
-        tmp = self._buf("bwd.wxyzT", (3, 64), torch.float32)
-        self._chk(lib.pcd_vec3_outer(dz0.data_ptr(), self.x.data_ptr(), m, 64, tmp.data_ptr(), None, st), "vec3_outer")
-        gw[:, :3, 0].copy_(tmp.t())
-        dtb = self._buf("bwd.dtbias", (b, 64), torch.float32)
-        self._chk(lib.pcd_colsum_f16(dz0.data_ptr(), n, b, 64, dtb.data_ptr(), st), "colsum_shape")
-        ones = self._buf("ones", (1, b), torch.float32)
-        ones.fill_(1.0)
-        self._mm(dtb.data_ptr(), 64, 1, self.temb.data_ptr(), 256, 0, 64, 256, b, None, 0, gw.data_ptr() + 3 * 4, 259)
-        self._mm(ones.data_ptr(), b, 0, dtb.data_ptr(), 64, 0, 1, 64, b, None, 0, g["enc1.conv1.bias"].data_ptr(), 64)
+            self._chain_backward(blk[::-1], dskip[blk[2].cout], m, [("add", dskip[blk[0].cin])])
+        # enc1: K = 3 + 256, all fp32 side products
+        dtb = self._enc1_backward(self._chain_backward(self.enc[0][:0:-1], dskip[128], m))
         dtemb = self._buf("bwd.dtemb", (b, 256), torch.float32)
-        self._mm(dtb.data_ptr(), 64, 0, p["enc1.conv1.weight"].data_ptr() + 3 * 4, 259, 0, b, 256, 64, None, 0, dtemb.data_ptr(), 256)
-        # time_mlp: Linear -> SiLU -> Linear
-        self._mm(dtemb.data_ptr(), 256, 1, self.s1.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.2.weight"].data_ptr(), 256)
-        self._mm(ones.data_ptr(), b, 0, dtemb.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.2.bias"].data_ptr(), 256)
-        ds = self._buf("bwd.ds", (b, 256), torch.float32)
-        self._mm(dtemb.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 0, b, 256, 256, None, 0, ds.data_ptr(), 256)
-        dh = self._buf("bwd.dh", (b, 256), torch.float32)
-        self._chk(lib.pcd_silu_backward_f32(self.h1.data_ptr(), ds.data_ptr(), ds.numel(), dh.data_ptr(), st), "silu_bwd")
-        self._mm(dh.data_ptr(), 256, 1, self.emb.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.0.weight"].data_ptr(), 256)
-        self._mm(ones.data_ptr(), b, 0, dh.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.0.bias"].data_ptr(), 256)
+        self._lin_backward("enc1.conv1", dtb, [("set", dtemb)])
+        self._time_mlp_backward(dtemb)
         return loss_sum[0] / float(m * 3)
-
-    # ------------------------------------------------------------------ optimizer
-    def grads(self) -> Dict[str, torch.Tensor]:
-        """Unscaled parameter gradients (copies), keyed like `named_parameters()`."""
-        return {k: v.clone() / self.loss_scale for k, v in self.g.items()}
-
-    def optimizer_step(self):
-        self.step_count += 1
-        b1, b2 = self.betas
-        world = _allreduce_gradients(self.G)           # data parallel: mean gradient over the ranks (BatchNorm stays per rank)
-        self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
-                                          self.P.numel(), self.lr, b1, b2, self.eps, self.wd, self.step_count,
-                                          self.loss_scale * world, self._st()), "adamw")
-        self.refresh_weights()
 
     def train_step(self, x_t: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
         self.forward(x_t, t, update_stats=True)
@@ -480,78 +554,20 @@ class PointTrainer:
         return loss
 
 
-    # torch.optim-like aliases so the object can stand where the reference's optimizer does
-    def step(self):
-        self.optimizer_step()
-
-    def zero_grad(self):
-        pass                                # every backward overwrites the whole gradient buffer
-
-    def state_dict(self):
-        return {"step": self.step_count, "lr": self.lr, "exp_avg": self.M1, "exp_avg_sq": self.M2}
-
-
-class LatentTrainer:
+class LatentTrainer(_Trainer):
     """Forward + backward + AdamW for `SimpleLatentUNetPointNet` (networks.py:963-1086) in train() mode, as used by
     `LatentDiffusion.training_step` (diffusion.py:424-443; the VAE stays frozen).  The batch is 16-32 latent vectors,
-    so every product is a few-row fp32 product (`pcd_matmul_f32`: weights read once) and everything stays fp32 -
-    GroupNorm is per sample, so unlike the point denoiser nothing here couples the batch.  Dropout(0.1) after `dec1`
-    (networks.py:1035) takes its keep mask from torch's generator, or from the caller (parity tests)."""
+    so every product is a few-row fp32 product (`pcd_matmul_f32`: weights read once) and everything stays fp32 (no loss
+    scale) - GroupNorm is per sample, so unlike the point denoiser nothing here couples the batch.  Dropout(0.1) after
+    `dec1` (networks.py:1035) takes its keep mask from torch's generator, or from the caller (parity tests)."""
 
     GROUPS = 8
     DROPOUT = 0.1
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.model = model
-        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
-        self.dev = model.device
-        if self.dev.type != "cuda":
-            raise RuntimeError("LatentTrainer needs the model on an MI355X (model.to('cuda'))")
-        self.step_count = 0
-        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
-        self.freqs = timestep_freqs(256)
-        self._ws: Dict[str, torch.Tensor] = {}
-        self.saved: Dict[str, tuple] = {}
-
-    _st = PointTrainer._st
-    _chk = PointTrainer._chk
-    _buf = PointTrainer._buf
-    _mm = PointTrainer._mm
+        super().__init__(model, lr, weight_decay, betas, eps, loss_scale=1.0)
 
     # ------------------------------------------------------------------ layer helpers
-    def _lin(self, name: str, inputs) -> torch.Tensor:
-        """y = [inputs] W^T + b  (nn.Linear; the torch.cat of networks.py:1062,1074-1077 is a split product)."""
-        w, b = self.p[name + ".weight"], self.p[name + ".bias"]
-        c, ktot = w.shape
-        rows = inputs[0][0].shape[0]
-        y = self._buf(name + ".y", (rows, c), torch.float32)
-        off = 0
-        for i, (a, k) in enumerate(inputs):
-            self._mm(a.data_ptr(), k, 0, w.data_ptr() + off * 4, ktot, 1, rows, c, k, b.data_ptr() if i == 0 else None, 1 if i else 0,
-                     y.data_ptr(), c)
-            off += k
-        self.saved[name] = tuple(inputs)
-        return y
-
-    def _lin_backward(self, name: str, dy: torch.Tensor, targets) -> None:
-        """dW, db into the gradient views; input gradients into targets[i] = None | ('set'|'add', tensor)."""
-        w, gw, gb = self.p[name + ".weight"], self.g[name + ".weight"], self.g[name + ".bias"]
-        c, ktot = w.shape
-        rows = dy.shape[0]
-        ones = self._buf("ones", (1, rows), torch.float32)
-        ones.fill_(1.0)
-        self._mm(ones.data_ptr(), rows, 0, dy.data_ptr(), c, 0, 1, c, rows, None, 0, gb.data_ptr(), c)
-        off = 0
-        for (a, k), tgt in zip(self.saved[name], targets):
-            self._mm(dy.data_ptr(), c, 1, a.data_ptr(), k, 0, c, k, rows, None, 0, gw.data_ptr() + off * 4, ktot)      # dW = dy^T a
-            if tgt is not None:
-                mode, dst = tgt
-                self._mm(dy.data_ptr(), c, 0, w.data_ptr() + off * 4, ktot, 0, rows, k, c, None, 1 if mode == "add" else 0,
-                         dst.data_ptr(), k)                                                                          # da = dy W
-            off += k
-
     def _gn(self, name: str, x: torch.Tensor) -> torch.Tensor:
         rows, c = x.shape
         y = self._buf(name + ".y", (rows, c), torch.float32)
@@ -578,13 +594,7 @@ class LatentTrainer:
         lib, st = self.lib, self._st()
         b = z_t.shape[0]
         self.z = z_t.to(torch.float32).contiguous()
-        tt = t.detach().to("cpu", torch.float32)
-        e = tt[:, None] * self.freqs[None, :]
-        self.emb = torch.cat((torch.sin(e), torch.cos(e)), dim=-1).to(self.dev)
-        h1 = self._lin("time_mlp.0", [(self.emb, 256)])
-        s1 = self._buf("t.s1", (b, 256), torch.float32)
-        self._chk(lib.pcd_silu_f32(h1.data_ptr(), h1.numel(), s1.data_ptr(), st), "silu")
-        te = self._lin("time_mlp.2", [(s1, 256)])
+        te = self._time_embedding(t)
         z1 = self._gn("enc1.1", self._lin("enc1.0", [(self.z, 256), (te, 256)]))
         z2 = self._gn("enc2.1", self._lin("enc2.0", [(z1, 128)]))
         z3 = self._gn("enc3.1", self._lin("enc3.0", [(z2, 256)]))
@@ -613,7 +623,8 @@ class LatentTrainer:
         loss_sum = self._buf("loss", (1,), torch.float32)
         d = self._buf("d.pred", (b, 256), torch.float32)
         target = target.to(self.dev, torch.float32).contiguous()
-        self._chk(lib.pcd_l1_loss(self.pred.data_ptr(), target.data_ptr(), n, 1.0, loss_sum.data_ptr(), d.data_ptr(), st), "l1_loss")
+        self._chk(lib.pcd_l1_loss(self.pred.data_ptr(), target.data_ptr(), n, self.loss_scale, loss_sum.data_ptr(), d.data_ptr(), st),
+                  "l1_loss")
 
         def new(key, c):
             return self._buf("d." + key, (b, c), torch.float32)
@@ -646,29 +657,8 @@ class LatentTrainer:
         dx = self._gn_backward("enc1.1", dz[128])
         d_te = new("te", 256)
         self._lin_backward("enc1.0", dx, [None, ("set", d_te)])
-        d_s1 = new("s1", 256)
-        self._lin_backward("time_mlp.2", d_te, [("set", d_s1)])
-        d_h1 = new("th1", 256)
-        h1 = self._ws["time_mlp.0.y"]
-        self._chk(lib.pcd_silu_backward_f32(h1.data_ptr(), d_s1.data_ptr(), d_s1.numel(), d_h1.data_ptr(), st), "silu_bwd")
-        self._lin_backward("time_mlp.0", d_h1, [None])
+        self._time_mlp_backward(d_te)
         return loss_sum[0] / float(n)
-
-    def grads(self) -> Dict[str, torch.Tensor]:
-        return {k: v.clone() for k, v in self.g.items()}
-
-    def optimizer_step(self):
-        self.step_count += 1
-        b1, b2 = self.betas
-        world = _allreduce_gradients(self.G)
-        self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(), self.P.numel(),
-                                          self.lr, b1, b2, self.eps, self.wd, self.step_count, float(world), self._st()), "adamw")
-        self.model.invalidate()        # the sampler's packed fp16 weights are stale now
-
-    step = optimizer_step
-
-    def zero_grad(self):
-        pass
 
     def train_step(self, z_t, t, noise, dropout_mask=None) -> torch.Tensor:
         self.forward(z_t, t, dropout_mask)
@@ -702,23 +692,11 @@ class AttentionTrainer(PointTrainer):
     3-channel layers run zero-padded to 64 channels in private buffers, their gradients and running statistics are
     copied to the real 3-channel tensors."""
 
-    def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8,
-                 loss_scale: float = 1024.0):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.model = model
-        self.lr, self.wd, self.betas, self.eps, self.loss_scale = lr, weight_decay, betas, eps, float(loss_scale)
-        self.dev = model.device
-        if self.dev.type != "cuda":
-            raise RuntimeError("AttentionTrainer needs the model on an MI355X (model.to('cuda'))")
+    def _build_layers(self):
+        model = self.model
         if model.dim != 256 or model.time_dim != 256:
             raise RuntimeError("AttentionTrainer implements the reference's configuration dim = time_dim = 256")
         self.heads = model.num_heads
-        self.step_count = 0
-        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
-        self.names = list(self.p.keys())
-        self.buf = dict(model.named_buffers())
-        self.freqs = timestep_freqs(256)
         self.enc = [[_Conv(f"{n}.conv{i}", f"{n}.bn{i}", a, b) for i, (a, b) in enumerate([(cin, c), (c, c), (c, c)], start=1)]
                     for n, cin, c in (("enc1", 3, 64), ("enc2", 64, 128), ("enc3", 128, 256))]
         self.dec = [[_Conv(f"{n}.conv{i}", f"{n}.bn{i}", a, b) for i, (a, b) in enumerate([(cin, c), (c, c), (c, c)], start=1)]
@@ -739,12 +717,6 @@ class AttentionTrainer(PointTrainer):
             self.buf[f"dec1p.bn{i}.running_var"] = torch.ones(DEC1_PAD, dtype=torch.float32, device=self.dev)
             self.buf[f"dec1p.bn{i}.num_batches_tracked"] = self.buf[f"dec1.bn{i}.num_batches_tracked"]
         self.w_head = torch.zeros(3, DEC1_PAD, dtype=torch.float32, device=self.dev)
-        self.w16: Dict[str, torch.Tensor] = {}
-        self.w16t: Dict[str, torch.Tensor] = {}
-        self._ws: Dict[str, torch.Tensor] = {}
-        self.debug: Optional[Dict[str, torch.Tensor]] = None
-        self.refresh_weights()
-        model.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh_weights())
 
     def _all_convs(self):
         for blk in self.enc:
@@ -757,7 +729,6 @@ class AttentionTrainer(PointTrainer):
     def refresh_weights(self):
         """fp16 W / W^T operand copies of the fp32 master weights (dec1 through its zero-padded images); enc1.conv1's
         K = 3 weights stay fp32."""
-        lib, st = self.lib, self._st()
         with torch.no_grad():
             for i in (1, 2, 3):
                 w = self.p[f"dec1.conv{i}.weight"]
@@ -769,28 +740,14 @@ class AttentionTrainer(PointTrainer):
         self.w_xyz = self.p["enc1.conv1.weight"][:, :, 0].contiguous()
         for L in self._all_convs():
             w = self.p[L.conv + ".weight"]
-            w2 = w.view(w.shape[0], w.shape[1])
-            c, k = w2.shape
-            a = self.w16.get(L.conv)
-            if a is None:
-                a = self.w16[L.conv] = torch.empty(c, k, dtype=torch.float16, device=self.dev)
-                self.w16t[L.conv] = torch.empty(k, c, dtype=torch.float16, device=self.dev)
-            self._chk(lib.pcd_f32_to_f16(w2.data_ptr(), a.data_ptr(), a.numel(), st), "f32_to_f16")
-            self._chk(lib.pcd_transpose_f16(a.data_ptr(), c, k, self.w16t[L.conv].data_ptr(), st), "transpose")
+            self._f16_operands(L.conv, w.view(w.shape[0], w.shape[1]))
         self.model.invalidate()        # the sampler's packed (BN-folded) weights are stale now
 
     # ------------------------------------------------------------------ set-attention block
     def _linear(self, L: _Conv, a: torch.Tensor, out: torch.Tensor, relu: int = 0, resid: Optional[torch.Tensor] = None):
-        m = a.shape[0]
         L.inputs = [(a, L.cin)]
-        g = _gemm_desc(a.data_ptr(), L.cin, L.cin, None, 0, 0, self.w16[L.conv].data_ptr(), L.cin,
-                       self.p[L.conv + ".bias"].data_ptr(), None, 0, m, L.cout)
-        g.relu = relu
-        if resid is None:
-            self._chk(self.lib.pcd_gemm_f16(C.byref(g), out.data_ptr(), L.cout, self._st()), "gemm_f16")
-        else:
-            self._chk(self.lib.pcd_gemm_f16_residual(C.byref(g), resid.data_ptr(), L.cout, out.data_ptr(), L.cout, self._st()),
-                      "gemm_resid")
+        self._gemm(_gemm_desc(a.data_ptr(), L.cin, self.w16[L.conv].data_ptr(), L.cin, a.shape[0], L.cout,
+                              bias=self.p[L.conv + ".bias"].data_ptr(), relu=relu), out, resid)
         return out
 
     def sab_forward(self, name: str, x: torch.Tensor, b: int, n: int) -> torch.Tensor:
@@ -871,34 +828,14 @@ class AttentionTrainer(PointTrainer):
             raise ValueError("the attention backbone trains on point counts N that are multiples of 64")
         self.b, self.n, self.m = b, n, m
         self.x = x_t.to(torch.float32).contiguous()
-        tt = t.detach().to("cpu", torch.float32)
-        e = tt[:, None] * self.freqs[None, :]
-        self.emb = torch.cat((torch.sin(e), torch.cos(e)), dim=-1).to(self.dev)
-        self.h1 = self._buf("t.h1", (b, 256), torch.float32)
-        self.s1 = self._buf("t.s1", (b, 256), torch.float32)
-        self.temb = self._buf("t.temb", (b, 256), torch.float32)
-        self._mm(self.emb.data_ptr(), 256, 0, p["time_mlp.0.weight"].data_ptr(), 256, 1, b, 256, 256,
-                 p["time_mlp.0.bias"].data_ptr(), 0, self.h1.data_ptr(), 256)
-        self._chk(lib.pcd_silu_f32(self.h1.data_ptr(), self.h1.numel(), self.s1.data_ptr(), st), "silu")
-        self._mm(self.s1.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 1, b, 256, 256,
-                 p["time_mlp.2.bias"].data_ptr(), 0, self.temb.data_ptr(), 256)
-        self.E = {}
-        for name, c in ATTN_EMBS:
-            self.E[name] = self._buf(f"t.{name}", (b, c), torch.float32)
-            self._mm(self.temb.data_ptr(), 256, 0, p[name + ".weight"].data_ptr(), 256, 1, b, c, 256, p[name + ".bias"].data_ptr(), 0,
-                     self.E[name].data_ptr(), c)
+        temb = self._time_embedding(t)
+        self.E = {name: self._lin(name, [(temb, 256)]) for name, _ in ATTN_EMBS}
         for i in (1, 2, 3):                      # dec1's padded running statistics start from the real ones
             for s in ("running_mean", "running_var"):
                 self.buf[f"dec1p.bn{i}.{s}"][:3].copy_(self.buf[f"dec1.bn{i}.{s}"])
         # enc1.conv1 on x + emb1(t): W (x + e) + b = W x + (W e + b), a per-shape bias
-        self.tbias = self._buf("t.tbias", (b, 64), torch.float32)
-        self._mm(self.E["emb1"].data_ptr(), 3, 0, self.w_xyz.data_ptr(), 3, 1, b, 64, 3, p["enc1.conv1.bias"].data_ptr(), 0,
-                 self.tbias.data_ptr(), 64)
-        z0 = self._buf("enc1.conv1.z", (m, 64), torch.float32)
-        self._chk(lib.pcd_enc1_linear(self.x.data_ptr(), m, n, self.w_xyz.data_ptr(), 64, self.tbias.data_ptr(), z0.data_ptr(), st),
-                  "enc1_linear")
         e1 = self.enc[0]
-        a = self._bn_relu(e1[0], z0, m, update_stats)
+        a = self._enc1(self._lin("enc1.conv1", [(self.E["emb1"], 3)]), update_stats)
         a = self._conv(e1[1], [(a, 64)], m, True, update_stats)
         a = self._conv(e1[2], [(a, 64)], m, True, update_stats)
         self.x1 = self._plus_emb("x1", self.sab_forward("att1", a, b, n), "emb2")
@@ -923,24 +860,11 @@ class AttentionTrainer(PointTrainer):
         return self.pred
 
     # ------------------------------------------------------------------ backward
-    def _colsum_shape(self, key: str, d: torch.Tensor) -> torch.Tensor:
-        out = self._buf(key, (self.b, d.shape[1]), torch.float32)
-        self._chk(self.lib.pcd_colsum_f16(d.data_ptr(), self.n, self.b, d.shape[1], out.data_ptr(), self._st()), "colsum_shape")
-        return out
-
-    def _layer_backward(self, blk, da: torch.Tensor, targets) -> None:
-        m = self.m
-        for L in (blk[2], blk[1]):
-            dz = self._bn_backward(L, da, m)
-            da = self._buf(f"bwd.{L.conv}", (m, L.cin), torch.float16)
-            self._conv_backward(L, dz, m, [("set", da)])
-        self._conv_backward(blk[0], self._bn_backward(blk[0], da, m), m, targets)
-
     def backward(self, target: torch.Tensor) -> torch.Tensor:
         """L1 loss against `target` (the noise) and all parameter gradients (scaled by loss_scale) into self.G.
         Returns the loss as a 0-d device tensor."""
         lib, st = self.lib, self._st()
-        b, n, m, p, g = self.b, self.n, self.m, self.p, self.g
+        b, m, g = self.b, self.m, self.g
         self._chk(lib.pcd_fill_zero(self.G.data_ptr(), self.G.numel() * 4, st), "fill_zero")
         loss_sum = self._buf("loss", (1,), torch.float32)
         dpred = self._buf("dpred", (m, 3), torch.float32)
@@ -958,7 +882,7 @@ class AttentionTrainer(PointTrainer):
         dE = {}
         # decoder: dec1 <- att_dec1 <- dec2 <- att_dec2 <- dec3 <- att_dec3 <- bottleneck
         dh, dx1 = fresh("bwd.dh64", 64), fresh("bwd.dx1", 64)
-        self._layer_backward(self.dec[2], da, [("set", dh), ("set", dx1)])
+        self._chain_backward(self.dec[2][::-1], da, m, [("set", dh), ("set", dx1)])
         for i, k in ((1, 128), (2, 3), (3, 3)):
             g[f"dec1.conv{i}.weight"].copy_(g[f"dec1p.conv{i}.weight"][:3, :k])
             g[f"dec1.bn{i}.weight"].copy_(g[f"dec1p.bn{i}.weight"][:3])
@@ -966,57 +890,29 @@ class AttentionTrainer(PointTrainer):
         dh = self.sab_backward("att_dec1", dh)
         dE["emb_dec1"] = self._colsum_shape("bwd.e_dec1", dh)
         dh2, dx2 = fresh("bwd.dh128", 128), fresh("bwd.dx2", 128)
-        self._layer_backward(self.dec[1], dh, [("set", dh2), ("set", dx2)])
+        self._chain_backward(self.dec[1][::-1], dh, m, [("set", dh2), ("set", dx2)])
         dh2 = self.sab_backward("att_dec2", dh2)
         dE["emb_dec2"] = self._colsum_shape("bwd.e_dec2", dh2)
         dh3, dx3 = fresh("bwd.dh256", 256), fresh("bwd.dx3", 256)
-        self._layer_backward(self.dec[0], dh2, [("set", dh3), ("set", dx3)])
+        self._chain_backward(self.dec[0][::-1], dh2, m, [("set", dh3), ("set", dx3)])
         dh3 = self.sab_backward("att_dec3", dh3)
         dE["emb_dec3"] = self._colsum_shape("bwd.e_dec3", dh3)
         dh3 = self.sab_backward("bottleneck", dh3)
         self._chk(lib.pcd_add_relu_f16(dx3.data_ptr(), dh3.data_ptr(), dx3.numel(), 0, dx3.data_ptr(), st), "add")
         # encoder: x3 = att3(enc3(x2)), x2 = att2(enc2(x1)) + emb3, x1 = att1(enc1(x + emb1)) + emb2
-        self._layer_backward(self.enc[2], self.sab_backward("att3", dx3), [("add", dx2)])
+        self._chain_backward(self.enc[2][::-1], self.sab_backward("att3", dx3), m, [("add", dx2)])
         dE["emb3"] = self._colsum_shape("bwd.e3", dx2)
-        self._layer_backward(self.enc[1], self.sab_backward("att2", dx2), [("add", dx1)])
+        self._chain_backward(self.enc[1][::-1], self.sab_backward("att2", dx2), m, [("add", dx1)])
         dE["emb2"] = self._colsum_shape("bwd.e2", dx1)
-        da = self.sab_backward("att1", dx1)
-        e1 = self.enc[0]
-        for L in (e1[2], e1[1]):
-            dz = self._bn_backward(L, da, m)
-            da = self._buf(f"bwd.{L.conv}", (m, L.cin), torch.float16)
-            self._conv_backward(L, dz, m, [("set", da)])
-        dz0 = self._bn_backward(e1[0], da, m)
-        gw = g["enc1.conv1.weight"]
-        tmp = self._buf("bwd.wxyzT", (3, 64), torch.float32)
-        self._chk(lib.pcd_vec3_outer(dz0.data_ptr(), self.x.data_ptr(), m, 64, tmp.data_ptr(), None, st), "vec3_outer")
-        gw[:, :, 0].copy_(tmp.t())
-        dtb = self._colsum_shape("bwd.dtbias", dz0)
-        self._mm(dtb.data_ptr(), 64, 1, self.E["emb1"].data_ptr(), 3, 0, 64, 3, b, None, 1, gw.data_ptr(), 3)
+        dtb = self._enc1_backward(self._chain_backward(self.enc[0][:0:-1], self.sab_backward("att1", dx1), m))
         dE["emb1"] = self._buf("bwd.e1", (b, 3), torch.float32)
-        self._mm(dtb.data_ptr(), 64, 0, self.w_xyz.data_ptr(), 3, 0, b, 3, 64, None, 0, dE["emb1"].data_ptr(), 3)
+        self._lin_backward("enc1.conv1", dtb, [("set", dE["emb1"])], bias=False, acc=1)
         # the six embedding Linears and time_mlp
-        ones = self._buf("ones", (1, b), torch.float32)
-        ones.fill_(1.0)
         dtemb = self._buf("bwd.dtemb", (b, 256), torch.float32)
-        for i, (name, c) in enumerate(ATTN_EMBS):
-            d = dE[name]
-            self._mm(d.data_ptr(), c, 1, self.temb.data_ptr(), 256, 0, c, 256, b, None, 0, g[name + ".weight"].data_ptr(), 256)
-            self._mm(ones.data_ptr(), b, 0, d.data_ptr(), c, 0, 1, c, b, None, 0, g[name + ".bias"].data_ptr(), c)
-            self._mm(d.data_ptr(), c, 0, p[name + ".weight"].data_ptr(), 256, 0, b, 256, c, None, int(i > 0), dtemb.data_ptr(), 256)
-        self._mm(dtemb.data_ptr(), 256, 1, self.s1.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.2.weight"].data_ptr(), 256)
-        self._mm(ones.data_ptr(), b, 0, dtemb.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.2.bias"].data_ptr(), 256)
-        ds = self._buf("bwd.ds", (b, 256), torch.float32)
-        self._mm(dtemb.data_ptr(), 256, 0, p["time_mlp.2.weight"].data_ptr(), 256, 0, b, 256, 256, None, 0, ds.data_ptr(), 256)
-        dh1 = self._buf("bwd.dh", (b, 256), torch.float32)
-        self._chk(lib.pcd_silu_backward_f32(self.h1.data_ptr(), ds.data_ptr(), ds.numel(), dh1.data_ptr(), st), "silu_bwd")
-        self._mm(dh1.data_ptr(), 256, 1, self.emb.data_ptr(), 256, 0, 256, 256, b, None, 0, g["time_mlp.0.weight"].data_ptr(), 256)
-        self._mm(ones.data_ptr(), b, 0, dh1.data_ptr(), 256, 0, 1, 256, b, None, 0, g["time_mlp.0.bias"].data_ptr(), 256)
+        for i, (name, _) in enumerate(ATTN_EMBS):
+            self._lin_backward(name, dE[name], [("add" if i else "set", dtemb)])
+        self._time_mlp_backward(dtemb)
         return loss_sum[0] / float(m * 3)
-
-    def grads(self) -> Dict[str, torch.Tensor]:
-        """Unscaled parameter gradients (copies), keyed like `named_parameters()`."""
-        return {k: self.g[k].clone() / self.loss_scale for k in self.names}
 
 
 class CosineAnnealingLR:

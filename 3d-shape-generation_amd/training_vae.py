@@ -16,14 +16,12 @@ run end to end on an MI355X; the sampler's implicit-GEMM convolutions (`csrc/con
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
-from . import _lib
 from .specs import VAE_DEC, VAE_ENC
-from .training import BN_EPS, BN_MOMENTUM, PointTrainer, _allreduce_gradients, _flatten_parameters
+from .training import BN_EPS, BN_MOMENTUM, _Trainer, _gemm_desc
 
 
 def _up(v: int, a: int) -> int:
@@ -45,47 +43,18 @@ class _VConv:
         self.col = self.z = self.a = self.mean = self.var = None
 
 
-class VAETrainer:
-    """Forward + backward + Adam for `VAE3DLarge`; parameters are the module's own, re-pointed into one flat buffer."""
+class VAETrainer(_Trainer):
+    """Forward + backward + Adam for `VAE3DLarge`: torch.optim.Adam(lr) (networks.py:2290) is the AdamW step with zero
+    weight decay."""
 
     def __init__(self, vae, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, loss_scale: float = 32768.0):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.vae = vae
-        self.lr, self.betas, self.eps, self.loss_scale = lr, betas, eps, float(loss_scale)
-        self.dev = vae.device
-        if self.dev.type != "cuda":
-            raise RuntimeError("VAETrainer needs the model on an MI355X (vae.to('cuda'))")
-        self.step_count = 0
-        self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(vae, self.dev)
-        self.buf = dict(vae.named_buffers())
-        self._ws: Dict[str, torch.Tensor] = {}
+        super().__init__(vae, lr, 0.0, betas, eps, loss_scale)
         self.enc = self._program("encoder", VAE_ENC, 32)
         self.dec = self._program("decoder", VAE_DEC, 4)
         self.wm: Dict[str, torch.Tensor] = {}
         self.wmt: Dict[str, torch.Tensor] = {}
         self.bias: Dict[str, torch.Tensor] = {}
         self.refresh_weights()
-        vae.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh_weights())
-
-    _st = PointTrainer._st
-    _chk = PointTrainer._chk
-    _mm = PointTrainer._mm
-
-    def _buf(self, key, shape, dtype, zero=False):
-        t = self._ws.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.dev)
-            self._ws[key] = t
-        return t
-
-    def _scratch(self, key: str, numel: int, dtype=torch.float16) -> torch.Tensor:
-        """A flat scratch buffer that only ever grows (shared by the layers: transposes, dcol, P, slabs)."""
-        t = self._ws.get(key)
-        if t is None or t.numel() < numel or t.dtype != dtype:
-            t = torch.empty(numel, dtype=dtype, device=self.dev)
-            self._ws[key] = t
-        return t
 
     # ------------------------------------------------------------------ structure
     def _program(self, prefix: str, prog, d0: int):
@@ -140,7 +109,7 @@ class VAETrainer:
                 ga.fill_(1.0)
                 ga[:L.cout] = self.p[L.bn + ".weight"]
                 be[:L.cout] = self.p[L.bn + ".bias"]
-        self.vae.invalidate()
+        self.model.invalidate()
 
     # ------------------------------------------------------------------ one layer
     def _convT_fwd(self, L: _VConv, a_in: torch.Tensor, b: int) -> torch.Tensor:
@@ -150,11 +119,7 @@ class VAETrainer:
         m_in, m = b * L.din ** 3, b * L.dout ** 3
         L.m, L.mp, L.m_in, L.mp_in, L.a_in = m, _up(m, 64), m_in, _up(m_in, 64), a_in
         P = self._scratch("convT.P", L.mp_in * L.np_)
-        g = _lib.GemmDesc()
-        g.a1, g.lda1, g.k1 = a_in.data_ptr(), L.cin, L.cin
-        g.w, g.ldw = self.wm[L.key].data_ptr(), L.cin
-        g.m, g.c = m_in, L.np_
-        self._chk(lib.pcd_gemm_f16(C.byref(g), P.data_ptr(), L.np_, st), "gemm_convT")
+        self._gemm(_gemm_desc(a_in.data_ptr(), L.cin, self.wm[L.key].data_ptr(), L.cin, m_in, L.np_), P)
         y = self._buf(L.key + ".y", (L.mp, L.cout), torch.float16, zero=True)
         self._chk(lib.pcd_col2im_f16(P.data_ptr(), b, L.cout, L.dout, L.dout, L.dout, L.din, L.din, L.din, L.k, L.s, L.p, 0, L.np_, y.data_ptr(), st),
                   "col2im_convT")
@@ -169,39 +134,16 @@ class VAETrainer:
         db = self._buf("bwd.db", (512,), torch.float32)
         self._chk(lib.pcd_colsum_f16(dz.data_ptr(), L.m, 1, L.cout, db.data_ptr(), st), "colsum")
         self.g[L.key + ".bias"].copy_(db[:L.cout])
-        n = L.mp_in * L.np_
         dP = self._buf(L.key + ".dP", (L.mp_in, L.np_), torch.float16, zero=True)          # rows >= M_in stay zero
         self._chk(lib.pcd_im2col_f16(dz.data_ptr(), b, L.cout, L.dout, L.dout, L.dout, L.din, L.din, L.din, L.k, L.s, L.p, 0, L.np_,
                                      dP.data_ptr(), st), "im2col_convT")
         # dWg [k^3*Cout][Cin] = dP^T x
-        dPT = self._scratch("bwd.dzT", n)
-        nx = L.cin * L.mp_in
-        xT = self._scratch("bwd.colT", nx)
-        self._chk(lib.pcd_transpose_f16(dP.data_ptr(), L.mp_in, L.np_, dPT.data_ptr(), st), "transpose")
-        self._chk(lib.pcd_transpose_f16(L.a_in.data_ptr(), L.mp_in, L.cin, xT.data_ptr(), st), "transpose")
         dwg = self._buf(L.key + ".dwg", (L.np_, L.cin), torch.float32)
-        g = _lib.GemmDesc()
-        g.a1, g.lda1, g.k1 = dPT.data_ptr(), L.mp_in, L.mp_in
-        g.w, g.ldw = xT.data_ptr(), L.mp_in
-        g.m, g.c = L.np_, L.cin
-        tiles = -(-L.np_ // 128) * -(-L.cin // 128)
-        splits = 1
-        while splits * tiles < 512 and (L.mp_in // 64) % (splits * 2) == 0 and L.mp_in // (splits * 2) >= 256:
-            splits *= 2
-        if splits == 1:
-            self._chk(lib.pcd_gemm_f16_out32(C.byref(g), dwg.data_ptr(), L.cin, st), "gemm_dWg")
-        else:
-            slabs = self._scratch("bwd.slabs", splits * L.np_ * L.cin, torch.float32)
-            self._chk(lib.pcd_gemm_f16_splitk(C.byref(g), splits, slabs.data_ptr(), st), "gemm_dWg_splitk")
-            self._chk(lib.pcd_sum_slabs_f32(slabs.data_ptr(), splits, L.np_, L.cin, dwg.data_ptr(), L.cin, st), "sum_slabs")
+        self._weight_grad(dP, L.mp_in, L.np_, [(L.a_in, L.cin)], dwg.data_ptr(), L.cin)
         self.g[L.key + ".weight"].copy_(dwg[:L.k ** 3 * L.cout].reshape(L.k, L.k, L.k, L.cout, L.cin).permute(4, 3, 0, 1, 2))
         # dx = dP Wg
         dx = self._buf(L.key + ".dx", (L.mp_in, L.cin), torch.float16, zero=True)
-        g2 = _lib.GemmDesc()
-        g2.a1, g2.lda1, g2.k1 = dP.data_ptr(), L.np_, L.np_
-        g2.w, g2.ldw = self.wmt[L.key].data_ptr(), L.np_
-        g2.m, g2.c = L.m_in, L.cin
-        self._chk(lib.pcd_gemm_f16(C.byref(g2), dx.data_ptr(), L.cin, st), "gemm_dx_convT")
+        self._gemm(_gemm_desc(dP.data_ptr(), L.np_, self.wmt[L.key].data_ptr(), L.np_, L.m_in, L.cin), dx)
         return dx
 
     def _conv_fwd(self, L: _VConv, a_in: torch.Tensor, b: int, update_stats: bool) -> torch.Tensor:
@@ -215,12 +157,9 @@ class VAETrainer:
         self._chk(lib.pcd_im2col_f16(a_in.data_ptr(), b, L.cin, L.din, L.din, L.din, L.dout, L.dout, L.dout, L.k, L.s, L.p, L.transposed,
                                      L.kp, L.col.data_ptr(), st), "im2col")
         L.z = self._buf(L.key + ".z", (mp, L.cp), torch.float32 if L.bn else torch.float16, zero=True)
-        g = _lib.GemmDesc()
-        g.a1, g.lda1, g.k1 = L.col.data_ptr(), L.kp, L.kp
-        g.w, g.ldw, g.bias = self.wm[L.key].data_ptr(), L.kp, self.bias[L.key].data_ptr()
-        g.relu, g.m, g.c = int(L.relu and not L.bn), m, L.cp
+        self._gemm(_gemm_desc(L.col.data_ptr(), L.kp, self.wm[L.key].data_ptr(), L.kp, m, L.cp, bias=self.bias[L.key].data_ptr(),
+                              relu=int(L.relu and not L.bn)), L.z)        # fp32 z in front of a BatchNorm
         if L.bn:
-            self._chk(lib.pcd_gemm_f16_out32(C.byref(g), L.z.data_ptr(), L.cp, st), "gemm_out32")
             L.mean = self._buf(L.key + ".mean", (L.cp,), torch.float32)
             L.var = self._buf(L.key + ".var", (L.cp,), torch.float32)
             scratch = self._buf("bn.scratch", (2 * 512,), torch.float32)
@@ -243,7 +182,6 @@ class VAETrainer:
                                            self._ws[L.bn + ".gamma_p"].data_ptr(), self._ws[L.bn + ".beta_p"].data_ptr(), BN_EPS,
                                            int(L.relu), L.a.data_ptr(), st), "bn_apply")
         else:
-            self._chk(lib.pcd_gemm_f16(C.byref(g), L.z.data_ptr(), L.cp, st), "gemm_f16")
             L.a = L.z
         return L.a
 
@@ -272,36 +210,15 @@ class VAETrainer:
             self._chk(lib.pcd_colsum_f16(dz.data_ptr(), m, 1, L.cp, db.data_ptr(), st), "colsum")
             self.g[L.key + ".bias"].copy_(db[:L.cout])
         # dWm = dz^T col  (rows Cp, reduction Mp, columns Kp)
-        dzT = self._scratch("bwd.dzT", L.cp * mp)
-        colT = self._scratch("bwd.colT", L.kp * mp)
-        self._chk(lib.pcd_transpose_f16(dz.data_ptr(), mp, L.cp, dzT.data_ptr(), st), "transpose")
-        self._chk(lib.pcd_transpose_f16(L.col.data_ptr(), mp, L.kp, colT.data_ptr(), st), "transpose")
         dwm = self._buf(L.key + ".dwm", (L.cp, L.kp), torch.float32)
-        g = _lib.GemmDesc()
-        g.a1, g.lda1, g.k1 = dzT.data_ptr(), mp, mp
-        g.w, g.ldw = colT.data_ptr(), mp
-        g.m, g.c = L.cp, L.kp
-        tiles = -(-L.cp // 128) * -(-L.kp // 128)
-        splits = 1
-        while splits * tiles < 512 and (mp // 64) % (splits * 2) == 0 and mp // (splits * 2) >= 256:
-            splits *= 2
-        if splits == 1:
-            self._chk(lib.pcd_gemm_f16_out32(C.byref(g), dwm.data_ptr(), L.kp, st), "gemm_dW")
-        else:
-            slabs = self._scratch("bwd.slabs", splits * L.cp * L.kp, torch.float32)
-            self._chk(lib.pcd_gemm_f16_splitk(C.byref(g), splits, slabs.data_ptr(), st), "gemm_dW_splitk")
-            self._chk(lib.pcd_sum_slabs_f32(slabs.data_ptr(), splits, L.cp, L.kp, dwm.data_ptr(), L.kp, st), "sum_slabs")
+        self._weight_grad(dz, mp, L.cp, [(L.col, L.kp)], dwm.data_ptr(), L.kp)
         gw = dwm[:L.cout, :L.kk].reshape(L.cout, L.k, L.k, L.k, L.cin)
         self.g[L.key + ".weight"].copy_(gw.permute(4, 0, 1, 2, 3) if L.transposed else gw.permute(0, 4, 1, 2, 3))
         if not need_dx:
             return None
         # dcol = dz Wm, then the adjoint of the gather
         dcol = self._scratch("bwd.dcol", mp * L.kp)
-        g2 = _lib.GemmDesc()
-        g2.a1, g2.lda1, g2.k1 = dz.data_ptr(), L.cp, L.cp
-        g2.w, g2.ldw = self.wmt[L.key].data_ptr(), L.cp
-        g2.m, g2.c = mp, L.kp
-        self._chk(lib.pcd_gemm_f16(C.byref(g2), dcol.data_ptr(), L.kp, st), "gemm_dcol")
+        self._gemm(_gemm_desc(dz.data_ptr(), L.cp, self.wmt[L.key].data_ptr(), L.cp, mp, L.kp), dcol)
         m_in = b * L.din ** 3
         dx = self._buf(L.key + ".dx", (_up(m_in, 64), L.cin), torch.float16, zero=True)
         self._chk(lib.pcd_col2im_f16(dcol.data_ptr(), b, L.cin, L.din, L.din, L.din, L.dout, L.dout, L.dout, L.k, L.s, L.p, L.transposed,
@@ -378,12 +295,8 @@ class VAETrainer:
         h = self._run_fwd(self.enc, a0, b, update_stats)                         # [64 (B rows valid)][512]
         self.h32 = self._buf("h32", (b, 512), torch.float32)
         self._chk(lib.pcd_f16_to_f32(h.data_ptr(), self.h32.data_ptr(), b * 512, st), "f16_to_f32")
-        p = self.p
-        self.mu = self._buf("mu", (b, 256), torch.float32)
-        self.logvar = self._buf("logvar", (b, 256), torch.float32)
-        self._mm(self.h32.data_ptr(), 512, 0, p["fc_mu.weight"].data_ptr(), 512, 1, b, 256, 512, p["fc_mu.bias"].data_ptr(), 0, self.mu.data_ptr(), 256)
-        self._mm(self.h32.data_ptr(), 512, 0, p["fc_logvar.weight"].data_ptr(), 512, 1, b, 256, 512, p["fc_logvar.bias"].data_ptr(), 0,
-                 self.logvar.data_ptr(), 256)
+        self.mu = self._lin("fc_mu", [(self.h32, 512)])
+        self.logvar = self._lin("fc_logvar", [(self.h32, 512)])
         if eps is None:
             eps = torch.empty(b, 256, device=self.dev)
             self._eps_offset = getattr(self, "_eps_offset", 0)       # running Philox position: every draw (training or validation) is fresh
@@ -394,9 +307,7 @@ class VAETrainer:
         self.zlat = self._buf("z", (b, 256), torch.float32)
         self._chk(lib.pcd_reparameterize(self.mu.data_ptr(), self.logvar.data_ptr(), self.eps_draw.data_ptr(), self.zlat.data_ptr(), b * 256, st),
                   "reparameterize")
-        di = self._buf("dec_in", (b, 32768), torch.float32)
-        self._mm(self.zlat.data_ptr(), 256, 0, p["decoder_input.weight"].data_ptr(), 256, 1, b, 32768, 256, p["decoder_input.bias"].data_ptr(), 0,
-                 di.data_ptr(), 32768)
+        di = self._lin("decoder_input", [(self.zlat, 256)])
         a = di.view(b, 512, 64).transpose(1, 2).reshape(b * 64, 512).to(torch.float16)       # (B,512,4,4,4) -> channels-last rows
         logits = self._run_fwd(self.dec, a, b, update_stats)                     # last conv: [Mp][64], column 0 = the logit
         self.logits = self.dec[-1][1].a
@@ -405,7 +316,7 @@ class VAETrainer:
     def backward(self, kl_weight: float):
         """BCE + kl_weight * KL and all parameter gradients (scaled by loss_scale).  Returns (loss, recon_loss, kl) tensors."""
         lib, st = self.lib, self._st()
-        b, p, g = self.b, self.p, self.g
+        b = self.b
         last = self.dec[-1][1]
         n = b * 32768
         loss_sum = self._buf("loss", (1,), torch.float32)
@@ -417,44 +328,21 @@ class VAETrainer:
         d = self._conv_bwd(last, dl, b, True)
         d = self._run_bwd(self.dec[:-1], d, b, True)                             # [B*64][512] wrt the reshaped decoder input
         ddi = d[:b * 64].float().view(b, 64, 512).transpose(1, 2).reshape(b, 32768).contiguous()
-        ones = self._buf("ones", (1, b), torch.float32)
-        ones.fill_(1.0)
-        self._mm(ddi.data_ptr(), 32768, 1, self.zlat.data_ptr(), 256, 0, 32768, 256, b, None, 0, g["decoder_input.weight"].data_ptr(), 256)
-        self._mm(ones.data_ptr(), b, 0, ddi.data_ptr(), 32768, 0, 1, 32768, b, None, 0, g["decoder_input.bias"].data_ptr(), 32768)
         dz = self._buf("dz", (b, 256), torch.float32)
-        self._mm(ddi.data_ptr(), 32768, 0, p["decoder_input.weight"].data_ptr(), 256, 0, b, 256, 32768, None, 0, dz.data_ptr(), 256)
+        self._lin_backward("decoder_input", ddi, [("set", dz)])
         dmu, dlv = self._buf("dmu", (b, 256), torch.float32), self._buf("dlv", (b, 256), torch.float32)
         kl_sum = self._buf("kl", (1,), torch.float32)
         self._chk(lib.pcd_vae_latent_backward(self.mu.data_ptr(), self.logvar.data_ptr(), self.eps_draw.data_ptr(), dz.data_ptr(), b * 256,
                                               float(kl_weight) * self.loss_scale, dmu.data_ptr(), dlv.data_ptr(), kl_sum.data_ptr(), st),
                   "latent_backward")
         dh = self._buf("dh", (b, 512), torch.float32)
-        for name, dd, acc in (("fc_mu", dmu, 0), ("fc_logvar", dlv, 1)):
-            self._mm(dd.data_ptr(), 256, 1, self.h32.data_ptr(), 512, 0, 256, 512, b, None, 0, g[name + ".weight"].data_ptr(), 512)
-            self._mm(ones.data_ptr(), b, 0, dd.data_ptr(), 256, 0, 1, 256, b, None, 0, g[name + ".bias"].data_ptr(), 256)
-            self._mm(dd.data_ptr(), 256, 0, p[name + ".weight"].data_ptr(), 512, 0, b, 512, 256, None, acc, dh.data_ptr(), 512)
+        self._lin_backward("fc_mu", dmu, [("set", dh)])
+        self._lin_backward("fc_logvar", dlv, [("add", dh)])
         d = dh.to(torch.float16)
         self._run_bwd(self.enc, d, b, False)
         recon_loss = loss_sum[0] / float(n)
         kl = -0.5 * kl_sum[0] / float(b * 256)
         return recon_loss + float(kl_weight) * kl, recon_loss, kl
-
-    def grads(self) -> Dict[str, torch.Tensor]:
-        return {k: v.clone() / self.loss_scale for k, v in self.g.items()}
-
-    def optimizer_step(self):
-        """torch.optim.Adam(lr) (networks.py:2290) = the AdamW kernel with zero weight decay."""
-        self.step_count += 1
-        b1, b2 = self.betas
-        world = _allreduce_gradients(self.G)
-        self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(), self.P.numel(),
-                                          self.lr, b1, b2, self.eps, 0.0, self.step_count, self.loss_scale * world, self._st()), "adam")
-        self.refresh_weights()
-
-    step = optimizer_step
-
-    def zero_grad(self):
-        pass
 
     def train_step(self, x, kl_weight: float, eps=None):
         self.forward(x, eps)
