@@ -58,11 +58,13 @@ class ParamTree(nn.Module):
 
 
 class _HipModule(ParamTree):
-    """Common machinery: packed-weight cache invalidation and device checks."""
+    """Common machinery: packed-weight cache invalidation, the C handles made from the packed weights, and device checks."""
 
     def __init__(self):
         super().__init__()
         self._packed = None
+        self._handle = None                 # the module's C handle, while packed
+        self._owned = []                    # (destroy, handle) of every C handle made from the packed weights, in creation order
         self._ws: Dict[tuple, torch.Tensor] = {}
         # a parent's load_state_dict recurses through _load_from_state_dict and never calls a child's
         # load_state_dict override: the post hook fires for every module that received keys
@@ -74,8 +76,23 @@ class _HipModule(ParamTree):
         self._packed = None
         self._ws = {}
 
+    def _create(self, create, destroy, desc) -> C.c_void_p:
+        """The handle `create(&desc, &handle)` makes; `invalidate` and garbage collection pass it to `destroy`."""
+        handle = C.c_void_p()
+        _lib.check(create(C.byref(desc), C.byref(handle)), create.__name__)
+        self._owned.append((destroy, handle))
+        return handle
+
     def _release(self) -> None:
-        pass
+        owned, self._owned, self._handle = self._owned, [], None
+        for destroy, handle in owned:
+            destroy(handle)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
 
     def _apply(self, fn, *a, **k):
         self.invalidate()
@@ -115,43 +132,91 @@ def _dev32(a: np.ndarray, dev) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(torch.float32).to(dev).contiguous()
 
 
-PRECISIONS = ("fp16", "fp32")
+class _Denoiser(_HipModule):
+    """`precision`: "fp16" (default; fp16 operands on the matrix cores, fp32 accumulation) or "fp32" (SURVEY 8(c)'s parity
+    mode: fp32 weights, activations and products -- the reference's own arithmetic type, held to eps rel-L2 <= 1e-4).  Chosen
+    per module with `set_precision`, or for every module created afterwards with the environment variable PCD_PARITY=fp32."""
+
+    PRECISIONS = ("fp16", "fp32")
+
+    def __init__(self):
+        super().__init__()
+        self.precision = os.environ.get("PCD_PARITY", "fp16")
+        if self.precision not in self.PRECISIONS:
+            raise ValueError(f"PCD_PARITY must be one of {self.PRECISIONS}, got {self.precision!r}")
+
+    def set_precision(self, precision: str):
+        """Switch to "fp16" or "fp32"; a change drops the packed weights."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {self.PRECISIONS}, got {precision!r}")
+        if precision != self.precision:
+            self.invalidate()
+            self.precision = precision
+        return self
+
+    @property
+    def _dtype(self) -> torch.dtype:
+        """The activation type of the active precision."""
+        return torch.float32 if self.precision == "fp32" else torch.float16
 
 
-def _check_precision(precision: str) -> None:
-    if precision not in PRECISIONS:
-        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+class _HandleDenoiser(_Denoiser):
+    """A denoiser behind a C handle: eps = forward_with_bias(x, time_bias(t), 1), one C call once the time bias is known.
+    `_ensure_packed` creates the handle of the active precision and binds the entry points that run on it (`_bind`)."""
+
+    def _bind(self, desc, create, destroy, workspace_bytes, forward, tap=None) -> C.c_void_p:
+        """Make the handle of `desc`; `forward_with_bias` and `_tap` call `forward` / `tap` on it from now on."""
+        handle = self._create(create, destroy, desc)
+        self._entry = (handle, workspace_bytes, forward, tap)
+        return handle
+
+    def forward_with_bias(self, x: torch.Tensor, tbias: torch.Tensor, shape_stride: int,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """eps for x (B,N,3) -- z (B,latent) for the latent denoiser -- given a precomputed time bias row (stride 0) or one
+        row per shape (1)."""
+        self._ensure_packed()
+        handle, workspace_bytes, forward, _ = self._entry
+        dims = x.shape[:-1]
+        if out is None:
+            out = torch.empty_like(x)
+        ws = self._workspace(dims, workspace_bytes(*dims))
+        _lib.check(forward(handle, x.data_ptr(), *dims, tbias.data_ptr(), shape_stride, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                           _lib.stream_ptr()), forward.__name__)
+        return out
+
+    def _tap(self, name: str, batch: int, n_points: int, ws: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+        handle, _, _, tap = self._entry
+        _lib.check(tap(handle, name.encode(), batch, n_points, ws.data_ptr(), dst.data_ptr(), dst.numel() * dst.element_size(),
+                       _lib.stream_ptr()), tap.__name__)
+        return dst
 
 
-def _env_precision() -> str:
-    """PCD_PARITY=fp32 puts every denoiser created afterwards into its fp32 parity mode."""
-    p = os.environ.get("PCD_PARITY", "fp16")
-    if p not in PRECISIONS:
-        raise ValueError(f"PCD_PARITY must be one of {PRECISIONS}, got {p!r}")
-    return p
+def _time_embed(m: _HandleDenoiser, t: torch.Tensor, mlp_dim: int, c1: int = 0) -> torch.Tensor:
+    """pcd_time_embed on m's packed time MLP: time_mlp(get_timestep_embedding(t)) as (len(t), mlp_dim) fp32, or with c1 > 0
+    the hoisted time half of enc1 as (len(t), c1) fp32."""
+    pk = m._ensure_packed()
+    t = t.to(m.device, torch.float32).contiguous()
+    out = torch.empty(t.numel(), c1 or mlp_dim, dtype=torch.float32, device=m.device)
+    if c1:
+        temb, e1w_t, e1b, tbias = 0, pk["e1w_t"].data_ptr(), pk["e1b"].data_ptr(), out.data_ptr()
+    else:
+        temb, e1w_t, e1b, tbias = out.data_ptr(), 0, 0, 0
+    _lib.check(_lib.load().pcd_time_embed(
+        t.data_ptr(), t.numel(), pk["freqs"].data_ptr(), m.time_dim, mlp_dim,
+        pk["tw0"].data_ptr(), pk["tb0"].data_ptr(), pk["tw2"].data_ptr(), pk["tb2"].data_ptr(),
+        temb, e1w_t, e1b, c1, tbias, _lib.stream_ptr()), "time_embed")
+    return out
 
 
 # ------------------------------------------------------------------ UNetPointNetLarge
-class UNetPointNetLarge(_HipModule):
-    """Drop-in for reference networks.py:724-838: eps = model(x (B,N,3), t (B,)).
-
-    `precision`: "fp16" (default; fp16 operands on the fp16 matrix cores, fp32 accumulation: csrc/unet.hip) or "fp32"
-    (SURVEY 8(c)'s parity mode: fp32 weights, activations and products, csrc/unet_f32.hip -- the reference's own
-    arithmetic type, held to eps rel-L2 <= 1e-4).  Chosen per module with `set_precision`, or for every module created
-    afterwards with the environment variable PCD_PARITY=fp32.  The constructor signature stays the reference's."""
-
-    PRECISIONS = ("fp16", "fp32")
+class UNetPointNetLarge(_HandleDenoiser):
+    """Drop-in for reference networks.py:724-838: eps = model(x (B,N,3), t (B,)).  fp16 mode: csrc/unet.hip, fp32 mode:
+    csrc/unet_f32.hip (see `_Denoiser`).  The constructor signature stays the reference's."""
 
     def __init__(self, dim: int = 512, time_dim: int = 256):
         super().__init__()
         self.dim, self.time_dim = dim, time_dim
         self._build_from_spec(specs.unet_pointnet_large_spec(dim, time_dim))
-        self._handle = None
-        self._handle_f32 = False
-        self._capture = None
-        self.precision = os.environ.get("PCD_PARITY", "fp16")
-        if self.precision not in self.PRECISIONS:
-            raise ValueError(f"PCD_PARITY must be one of {self.PRECISIONS}, got {self.precision!r}")
         # fp16 mode: the narrow layers at the two ends of the U-net (enc1.conv2/3, enc2.conv3, dec1.*, output.0: the direct route from
         # the coordinates to the predicted noise) carry hi / lo weights -- the fp16 weights and the fp16 of their rounding residuals,
         # two MFMA passes, < 2 % of the FLOPs -- because the fp16 rounding of THESE weights is what the 1000-step DDPM trajectory
@@ -166,28 +231,7 @@ class UNetPointNetLarge(_HipModule):
             self.hilo_mask = mask
         return self
 
-    def set_precision(self, precision: str) -> "UNetPointNetLarge":
-        if precision not in self.PRECISIONS:
-            raise ValueError(f"precision must be one of {self.PRECISIONS}, got {precision!r}")
-        if precision != self.precision:
-            self.invalidate()
-            self.precision = precision
-        return self
-
     # -- packing -----------------------------------------------------------------
-    def _release(self):
-        if getattr(self, "_handle", None):
-            lib = _lib.load()
-            (lib.pcd_unet_f32_destroy if self._handle_f32 else lib.pcd_unet_destroy)(self._handle)
-        self._handle = None
-        self._capture = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
     def _ensure_packed(self):
         if self._packed is not None:
             return self._packed
@@ -215,55 +259,23 @@ class UNetPointNetLarge(_HipModule):
             keep[f"b{i}"] = _dev32(b, dev)
             desc.lin[i].w, desc.lin[i].b = keep[f"w{i}"].data_ptr(), keep[f"b{i}"].data_ptr()
             desc.lin[i].c, desc.lin[i].k = w.shape
-        handle = C.c_void_p()
         if f32:
-            _lib.check(lib.pcd_unet_f32_create(C.byref(desc), C.byref(handle)), "unet_f32_create")
+            self._handle = self._bind(desc, lib.pcd_unet_f32_create, lib.pcd_unet_f32_destroy, lib.pcd_unet_f32_workspace_bytes,
+                                      lib.pcd_unet_f32_forward, lib.pcd_unet_f32_tap)
         else:
-            _lib.check(lib.pcd_unet_create(C.byref(desc), C.byref(handle)), "unet_create")
-        self._handle, self._handle_f32 = handle, f32
+            self._handle = self._bind(desc, lib.pcd_unet_create, lib.pcd_unet_destroy, lib.pcd_unet_workspace_bytes,
+                                      lib.pcd_unet_forward, lib.pcd_unet_tap)
         self._packed = keep
         return keep
 
     # -- pieces used by the samplers ---------------------------------------------------
     def time_bias(self, t: torch.Tensor) -> torch.Tensor:
         """Hoisted time half of enc1.conv1 for each value of t: (len(t), 64) fp32 (K3)."""
-        pk = self._ensure_packed()
-        t = t.to(self.device, torch.float32).contiguous()
-        out = torch.empty(t.numel(), 64, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().pcd_time_embed(
-            t.data_ptr(), t.numel(), pk["freqs"].data_ptr(), self.time_dim, self.dim,
-            pk["tw0"].data_ptr(), pk["tb0"].data_ptr(), pk["tw2"].data_ptr(), pk["tb2"].data_ptr(),
-            0, pk["e1w_t"].data_ptr(), pk["e1b"].data_ptr(), 64, out.data_ptr(), _lib.stream_ptr()), "time_embed")
-        return out
+        return _time_embed(self, t, self.dim, 64)
 
     def time_mlp_out(self, t: torch.Tensor) -> torch.Tensor:
         """time_mlp(get_timestep_embedding(t)) (networks.py:791-792), for parity tests."""
-        pk = self._ensure_packed()
-        t = t.to(self.device, torch.float32).contiguous()
-        out = torch.empty(t.numel(), self.dim, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().pcd_time_embed(
-            t.data_ptr(), t.numel(), pk["freqs"].data_ptr(), self.time_dim, self.dim,
-            pk["tw0"].data_ptr(), pk["tb0"].data_ptr(), pk["tw2"].data_ptr(), pk["tb2"].data_ptr(),
-            out.data_ptr(), 0, 0, 0, 0, _lib.stream_ptr()), "time_embed")
-        return out
-
-    def forward_with_bias(self, x: torch.Tensor, tbias: torch.Tensor, shape_stride: int,
-                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """eps for x (B,N,3) given a precomputed time bias row (stride 0) or one row per shape (1)."""
-        self._ensure_packed()
-        b, n, _ = x.shape
-        lib = _lib.load()
-        if out is None:
-            out = torch.empty_like(x)
-        if self._handle_f32:
-            ws = self._workspace((b, n), lib.pcd_unet_f32_workspace_bytes(b, n))
-            _lib.check(lib.pcd_unet_f32_forward(self._handle, x.data_ptr(), b, n, tbias.data_ptr(), shape_stride,
-                                                out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "unet_f32_forward")
-            return out
-        ws = self._workspace((b, n), lib.pcd_unet_workspace_bytes(b, n))
-        _lib.check(lib.pcd_unet_forward(self._handle, x.data_ptr(), b, n, tbias.data_ptr(), shape_stride,
-                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "unet_forward")
-        return out
+        return _time_embed(self, t, self.dim)
 
     def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         self._need_cuda(x, t)
@@ -280,35 +292,31 @@ class UNetPointNetLarge(_HipModule):
         """fp16 path, parity tests: make the following forwards of this shape keep the decoder blocks' outputs
         (dec4..dec1, networks.py:811-814) for `tap("d4".."d1")`; they otherwise live in ping-pong buffers and inside
         the chained tail.  The fp32 path always keeps them."""
-        self._ensure_packed()
-        if self._handle_f32:
+        pk = self._ensure_packed()
+        if self.precision == "fp32":
             return
         if on:
-            self._capture = {k: torch.empty(batch, n_points, self._TAP_WIDTHS[k], dtype=torch.float16, device=self.device)
+            pk["capture"] = {k: torch.empty(batch, n_points, self._TAP_WIDTHS[k], dtype=torch.float16, device=self.device)
                              for k in ("d4", "d3", "d2", "d1")}
-            ptrs = [self._capture[k].data_ptr() for k in ("d4", "d3", "d2", "d1")]
+            ptrs = [pk["capture"][k].data_ptr() for k in ("d4", "d3", "d2", "d1")]
         else:
-            self._capture, ptrs = None, [0, 0, 0, 0]
+            pk["capture"], ptrs = None, [0, 0, 0, 0]
         _lib.check(_lib.load().pcd_unet_capture(self._handle, *ptrs), "unet_capture")
 
     def tap(self, name: str, batch: int, n_points: int) -> torch.Tensor:
         """Intermediate of the last forward (parity tests): x1..x4 / d4..d1 as (B,N,C) (fp16, or fp32 in the fp32 mode),
         pooled / gbias fp32."""
         ws = self._ws[(batch, n_points)]
-        lib = _lib.load()
         if name in self._TAP_WIDTHS:
-            if not self._handle_f32 and name.startswith("d"):
-                if self._capture is None or tuple(self._capture[name].shape[:2]) != (batch, n_points):
+            if self.precision == "fp16" and name.startswith("d"):     # the fp16 library keeps them only in capture_decoder's buffers
+                capture = self._packed.get("capture")
+                if capture is None or tuple(capture[name].shape[:2]) != (batch, n_points):
                     raise RuntimeError("decoder taps of the fp16 path need capture_decoder(batch, n_points) before the forward")
-                return self._capture[name].clone()
-            dst = torch.empty(batch, n_points, self._TAP_WIDTHS[name], device=self.device,
-                              dtype=torch.float32 if self._handle_f32 else torch.float16)
+                return capture[name].clone()
+            dst = torch.empty(batch, n_points, self._TAP_WIDTHS[name], dtype=self._dtype, device=self.device)
         else:
             dst = torch.empty(batch, {"pooled": 4096, "gbias": 1024}[name], dtype=torch.float32, device=self.device)
-        fn = lib.pcd_unet_f32_tap if self._handle_f32 else lib.pcd_unet_tap
-        _lib.check(fn(self._handle, name.encode(), batch, n_points, ws.data_ptr(),
-                      dst.data_ptr(), dst.numel() * dst.element_size(), _lib.stream_ptr()), "tap")
-        return dst
+        return self._tap(name, batch, n_points, ws, dst)
 
 
 # ------------------------------------------------------------------ set attention
@@ -372,29 +380,24 @@ class _PackedSAB:
         return d
 
 
-class SetAttentionBlock(_HipModule):
-    """Drop-in for reference networks.py:51-83: (B, N, C) -> (B, N, C), pre-LN MHA + FFN, one pcd_sab_forward call."""
+class SetAttentionBlock(_Denoiser):
+    """Drop-in for reference networks.py:51-83: (B, N, C) -> (B, N, C), pre-LN MHA + FFN, one pcd_sab_forward call
+    (fp16: flash-style kernel on the matrix cores; fp32: csrc/attn_f32.hip)."""
 
     def __init__(self, dim: int, num_heads: int):
         super().__init__()
         self.dim, self.num_heads = dim, num_heads
         self._build_from_spec(specs.set_attention_spec(dim))
-        self.precision = _env_precision()
-
-    def set_precision(self, precision: str) -> "SetAttentionBlock":
-        """"fp16" (default: fp16 operands, flash-style kernel on the matrix cores) or "fp32" (the reference's arithmetic type, csrc/attn_f32.hip)."""
-        _check_precision(precision)
-        if precision != self.precision:
-            self.invalidate()
-            self.precision = precision
-        return self
 
     def _ensure_packed(self):
         if self._packed is None:
             dev = self._need_cuda()
             _lib.require_gpu()
-            pk = _PackedSAB(self.state_dict(), "", self.dim, dev, f32=self.precision == "fp32")
-            self._packed = (pk, pk.fill(_lib.SabDesc()))
+            lib = _lib.load()
+            f32 = self.precision == "fp32"
+            pk = _PackedSAB(self.state_dict(), "", self.dim, dev, f32=f32)
+            entry = (lib.pcd_sab_f32_workspace_bytes, lib.pcd_sab_f32_forward) if f32 else (lib.pcd_sab_workspace_bytes, lib.pcd_sab_forward)
+            self._packed = (pk, pk.fill(_lib.SabDesc()), *entry)
         return self._packed
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -402,27 +405,20 @@ class SetAttentionBlock(_HipModule):
         b, n, c = x.shape
         if c != self.dim:
             raise ValueError(f"expected {self.dim} channels, got {c}")
-        _, desc = self._ensure_packed()
-        lib = _lib.load()
-        if self.precision == "fp32":
-            x32 = x.to(torch.float32).contiguous().reshape(b * n, c)
-            y32 = torch.empty_like(x32)
-            ws = self._workspace((b, n), lib.pcd_sab_f32_workspace_bytes(b * n, c))
-            _lib.check(lib.pcd_sab_f32_forward(C.byref(desc), x32.data_ptr(), b, n, self.num_heads, y32.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _lib.stream_ptr()), "sab_f32_forward")
-            return y32.reshape(b, n, c).to(x.dtype)
-        x16 = x.to(torch.float16).contiguous().reshape(b * n, c)
-        y16 = torch.empty_like(x16)
-        ws = self._workspace((b, n), lib.pcd_sab_workspace_bytes(b * n, c))
-        _lib.check(lib.pcd_sab_forward(C.byref(desc), x16.data_ptr(), b, n, self.num_heads, y16.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), _lib.stream_ptr()), "sab_forward")
-        return y16.reshape(b, n, c).to(x.dtype)
+        _, desc, workspace_bytes, forward = self._ensure_packed()
+        xa = x.to(self._dtype).contiguous().reshape(b * n, c)
+        y = torch.empty_like(xa)
+        ws = self._workspace((b, n), workspace_bytes(b * n, c))
+        _lib.check(forward(C.byref(desc), xa.data_ptr(), b, n, self.num_heads, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                           _lib.stream_ptr()), forward.__name__)
+        return y.reshape(b, n, c).to(x.dtype)
 
 
-class UNetAttentionPointExperimental(_HipModule):
+class UNetAttentionPointExperimental(_HandleDenoiser):
     """Drop-in for reference networks.py:597-722 (the carrier of the set-attention blocks): eps = model(x (B,N,3), t (B,)).
     One pcd_attn_unet_forward call per forward; `time_bias` / `forward_with_bias` give the samplers the same two-stage
-    surface as UNetPointNetLarge (the whole time path once per sampler call, one 704-float row per timestep)."""
+    surface as UNetPointNetLarge (the whole time path once per sampler call, one 704-float row per timestep).  fp32 mode:
+    fp32 weights / activations / arithmetic, csrc/attn_f32.hip."""
 
     TB = _lib.PCD_ATTN_UNET_TB
 
@@ -430,31 +426,6 @@ class UNetAttentionPointExperimental(_HipModule):
         super().__init__()
         self.num_points, self.dim, self.num_heads, self.time_dim = num_points, dim, num_heads, time_dim
         self._build_from_spec(specs.unet_attention_spec(dim, time_dim))
-        self._handle = None
-        self._handle32 = None
-        self.precision = _env_precision()
-
-    def set_precision(self, precision: str) -> "UNetAttentionPointExperimental":
-        """"fp16" (default) or "fp32" (fp32 weights / activations / arithmetic, csrc/attn_f32.hip: the reference's arithmetic type, 1e-4)."""
-        _check_precision(precision)
-        if precision != self.precision:
-            self.invalidate()
-            self.precision = precision
-        return self
-
-    def _release(self):
-        if getattr(self, "_handle", None):
-            _lib.load().pcd_attn_unet_destroy(self._handle)
-        if getattr(self, "_handle32", None):
-            _lib.load().pcd_attn_unet_f32_destroy(self._handle32)
-        self._handle = None
-        self._handle32 = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def _ensure_packed(self):
         if self._packed is not None:
@@ -501,12 +472,12 @@ class UNetAttentionPointExperimental(_HipModule):
         keep["t_b234"] = _dev32(np.stack([b2, b3, b4]), dev)
         for k in ("t_w1", "t_b1", "t_w234", "t_b234"):
             setattr(desc, k, keep[k].data_ptr())
-        handle = C.c_void_p()
-        _lib.check(_lib.load().pcd_attn_unet_create(C.byref(desc), C.byref(handle)), "attn_unet_create")
-        self._handle, self._packed = handle, keep
+        lib = _lib.load()
+        # the time path is fp32 in both modes and runs on this handle (pcd_attn_unet_time_bias)
+        self._handle = self._bind(desc, lib.pcd_attn_unet_create, lib.pcd_attn_unet_destroy, lib.pcd_attn_unet_workspace_bytes,
+                                  lib.pcd_attn_unet_forward, lib.pcd_attn_unet_tap)
         if self.precision == "fp32":
-            # the fp32 parity mode: a second descriptor whose layer / attention weights are fp32 (the time path above is fp32 in both modes
-            # and stays with the first handle: pcd_attn_unet_time_bias)
+            # the fp32 parity mode: a second descriptor whose layer / attention weights are fp32
             d32 = _lib.AttnUnetDesc()
             C.memmove(C.byref(d32), C.byref(desc), C.sizeof(desc))
             for j, (name, i) in enumerate(stages):
@@ -517,9 +488,9 @@ class UNetAttentionPointExperimental(_HipModule):
                                            ("att_dec2", 128), ("att_dec1", 64))):
                 keep[name + "_32"] = _PackedSAB(sd, name + ".", c, dev, f32=True)
                 keep[name + "_32"].fill(d32.sab[j])
-            h32 = C.c_void_p()
-            _lib.check(_lib.load().pcd_attn_unet_f32_create(C.byref(d32), C.byref(h32)), "attn_unet_f32_create")
-            self._handle32 = h32
+            self._bind(d32, lib.pcd_attn_unet_f32_create, lib.pcd_attn_unet_f32_destroy, lib.pcd_attn_unet_f32_workspace_bytes,
+                       lib.pcd_attn_unet_f32_forward, lib.pcd_attn_unet_f32_tap)
+        self._packed = keep
         return keep
 
     def time_bias(self, t: torch.Tensor) -> torch.Tensor:
@@ -533,87 +504,25 @@ class UNetAttentionPointExperimental(_HipModule):
                                                        out.data_ptr(), _lib.stream_ptr()), "attn_unet_time_bias")
         return out
 
-    def forward_with_bias(self, x: torch.Tensor, tbias: torch.Tensor, shape_stride: int,
-                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        self._ensure_packed()
-        b, n, _ = x.shape
-        lib = _lib.load()
-        if out is None:
-            out = torch.empty_like(x)
-        if self._handle32 is not None:
-            ws = self._workspace((b, n), lib.pcd_attn_unet_f32_workspace_bytes(b, n))
-            _lib.check(lib.pcd_attn_unet_f32_forward(self._handle32, x.data_ptr(), b, n, tbias.data_ptr(), shape_stride,
-                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "attn_unet_f32_forward")
-            return out
-        ws = self._workspace((b, n), lib.pcd_attn_unet_workspace_bytes(b, n))
-        _lib.check(lib.pcd_attn_unet_forward(self._handle, x.data_ptr(), b, n, tbias.data_ptr(), shape_stride,
-                                             out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "attn_unet_forward")
-        return out
-
-    def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-        self._need_cuda(x, t)
-        if x.dim() != 3 or x.shape[2] != 3:
-            raise ValueError(f"x must be (B, N, 3), got {tuple(x.shape)}")
-        if t.dim() != 1 or t.shape[0] != x.shape[0]:
-            raise ValueError(f"t must be (B,), got {tuple(t.shape)} for batch {x.shape[0]}")
-        x = x.to(torch.float32).contiguous()
-        return self.forward_with_bias(x, self.time_bias(t), 1)
+    forward = UNetPointNetLarge.forward
 
     def tap(self, name: str, batch: int, n_points: int) -> torch.Tensor:
         """Skip tensor of the last forward (parity tests): x1 / x2 / x3 as (B, N, 64 / 128 / 256) fp16 (fp32 in the fp32 parity mode)."""
         ws = self._ws[(batch, n_points)]
-        if self._handle32 is not None:
-            dst = torch.empty(batch, n_points, {"x1": 64, "x2": 128, "x3": 256}[name], dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().pcd_attn_unet_f32_tap(self._handle32, name.encode(), batch, n_points, ws.data_ptr(), dst.data_ptr(),
-                                                         dst.numel() * 4, _lib.stream_ptr()), "attn_unet_f32_tap")
-            return dst
-        dst = torch.empty(batch, n_points, {"x1": 64, "x2": 128, "x3": 256}[name], dtype=torch.float16, device=self.device)
-        _lib.check(_lib.load().pcd_attn_unet_tap(self._handle, name.encode(), batch, n_points, ws.data_ptr(), dst.data_ptr(),
-                                                 dst.numel() * 2, _lib.stream_ptr()), "attn_unet_tap")
-        return dst
+        dst = torch.empty(batch, n_points, {"x1": 64, "x2": 128, "x3": 256}[name], dtype=self._dtype, device=self.device)
+        return self._tap(name, batch, n_points, ws, dst)
 
 
 # ------------------------------------------------------------------ latent denoiser
-class SimpleLatentUNetPointNet(_HipModule):
+class SimpleLatentUNetPointNet(_HandleDenoiser):
     """Drop-in for reference networks.py:962-1106: eps = model(z (B, latent), t (B,)).
-    Eval-mode only (Dropout(0.1) in dec1 is the identity, as in every sampler)."""
+    Eval-mode only (Dropout(0.1) in dec1 is the identity, as in every sampler).  fp16 mode: the per-layer launches or the
+    persistent kernel; fp32 mode: one launch per layer, csrc/latent_f32.hip (see `_Denoiser`)."""
 
     def __init__(self, latent_dim, dim=512, time_dim=256, dropout_rate=0.1):
         super().__init__()
         self.latent_dim, self.dim, self.time_dim = latent_dim, dim, time_dim
         self._build_from_spec(specs.latent_unet_spec(latent_dim, dim, time_dim))
-        self._handle = None
-        self._handle_f32 = False
-        self._persist = None
-        self.precision = os.environ.get("PCD_PARITY", "fp16")     # "fp32": the parity mode of csrc/latent_f32.hip (see UNetPointNetLarge)
-        if self.precision not in UNetPointNetLarge.PRECISIONS:
-            raise ValueError(f"PCD_PARITY must be one of {UNetPointNetLarge.PRECISIONS}, got {self.precision!r}")
-
-    def set_precision(self, precision: str) -> "SimpleLatentUNetPointNet":
-        """"fp16" (default: fp16 operands, the per-layer launches / the persistent kernel) or "fp32" (fp32 weights, activations
-        and products, one launch per layer: the reference's arithmetic type, eps rel-L2 <= 1e-4)."""
-        if precision not in UNetPointNetLarge.PRECISIONS:
-            raise ValueError(f"precision must be one of {UNetPointNetLarge.PRECISIONS}, got {precision!r}")
-        if precision != self.precision:
-            self.invalidate()
-            self.precision = precision
-        return self
-
-    def _release(self):
-        if getattr(self, "_handle", None):
-            lib = _lib.load()
-            (lib.pcd_latent_f32_destroy if self._handle_f32 else lib.pcd_latent_destroy)(self._handle)
-        if getattr(self, "_persist", None):
-            _lib.load().pcd_latent_persist_destroy(self._persist)
-        self._handle = None
-        self._persist = None
-        self._persist_ws = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ the whole step as one persistent launch
     def persist_supported(self, batch: int) -> bool:
@@ -624,15 +533,13 @@ class SimpleLatentUNetPointNet(_HipModule):
         return bool(_lib.load().pcd_latent_persist_supported(int(batch)))
 
     def _persist_handle(self):
-        self._ensure_packed()
-        if getattr(self, "_persist", None) is None:
-            handle = C.c_void_p()
-            _lib.check(_lib.load().pcd_latent_persist_create(C.byref(self._desc), C.byref(handle)), "latent_persist_create")
-            self._persist = handle
-        if getattr(self, "_persist_ws", None) is None:                   # its own buffer: the per-layer path keeps `_ws`
-            self._persist_ws = torch.empty(_lib.load().pcd_latent_persist_workspace_bytes(self._persist), dtype=torch.uint8,
-                                           device=self.device)
-        return self._persist, self._persist_ws
+        pk = self._ensure_packed()
+        if "persist" not in pk:
+            lib = _lib.load()
+            pk["persist"] = self._create(lib.pcd_latent_persist_create, lib.pcd_latent_persist_destroy, pk["desc"])
+            # its own buffer: the per-layer path keeps `_ws`
+            pk["persist_ws"] = torch.empty(lib.pcd_latent_persist_workspace_bytes(pk["persist"]), dtype=torch.uint8, device=self.device)
+        return pk["persist"], pk["persist_ws"]
 
     def persist_status(self) -> int:
         """Waits for the current stream (the one the launch was enqueued on) and returns the status word of the last persistent launch: 0 = every wait was met, else
@@ -680,11 +587,12 @@ class SimpleLatentUNetPointNet(_HipModule):
                                "(the configuration diffusion.py:362,380 instantiates)")
         dev = self._need_cuda()
         _lib.require_gpu()
+        lib = _lib.load()
         lin, gn, ex = packing.pack_latent_unet(self.state_dict(), "")
         keep = {"freqs": packing.timestep_freqs(self.time_dim).to(dev)}
         for k, v in ex.items():
             keep[k] = _dev32(v, dev)
-        desc = _lib.LatentDesc()
+        desc = keep["desc"] = _lib.LatentDesc()
         f32 = self.precision == "fp32"
         for i, (w, b) in enumerate(lin):
             keep[f"w{i}"], keep[f"b{i}"] = (_dev32 if f32 else _dev16)(w, dev), _dev32(b, dev)
@@ -693,40 +601,18 @@ class SimpleLatentUNetPointNet(_HipModule):
         for i, (gm, bt) in enumerate(gn):
             keep[f"g{i}"], keep[f"be{i}"] = _dev32(gm, dev), _dev32(bt, dev)
             desc.gn_gamma[i], desc.gn_beta[i] = keep[f"g{i}"].data_ptr(), keep[f"be{i}"].data_ptr()
-        handle = C.c_void_p()
         if f32:
-            _lib.check(_lib.load().pcd_latent_f32_create(C.byref(desc), C.byref(handle)), "latent_f32_create")
+            self._handle = self._bind(desc, lib.pcd_latent_f32_create, lib.pcd_latent_f32_destroy, lib.pcd_latent_f32_workspace_bytes,
+                                      lib.pcd_latent_f32_forward)
         else:
-            _lib.check(_lib.load().pcd_latent_create(C.byref(desc), C.byref(handle)), "latent_create")
-        self._handle, self._handle_f32, self._packed, self._desc = handle, f32, keep, desc
+            self._handle = self._bind(desc, lib.pcd_latent_create, lib.pcd_latent_destroy, lib.pcd_latent_workspace_bytes,
+                                      lib.pcd_latent_forward)
+        self._packed = keep
         return keep
 
     def time_bias(self, t: torch.Tensor) -> torch.Tensor:
         """Hoisted time half of enc1 for each value of t: (len(t), 128) fp32."""
-        pk = self._ensure_packed()
-        t = t.to(self.device, torch.float32).contiguous()
-        out = torch.empty(t.numel(), 128, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().pcd_time_embed(
-            t.data_ptr(), t.numel(), pk["freqs"].data_ptr(), self.time_dim, self.time_dim,
-            pk["tw0"].data_ptr(), pk["tb0"].data_ptr(), pk["tw2"].data_ptr(), pk["tb2"].data_ptr(),
-            0, pk["e1w_t"].data_ptr(), pk["e1b"].data_ptr(), 128, out.data_ptr(), _lib.stream_ptr()), "time_embed")
-        return out
-
-    def forward_with_bias(self, z, tbias, shape_stride, out=None):
-        self._ensure_packed()
-        lib = _lib.load()
-        b = z.shape[0]
-        if out is None:
-            out = torch.empty_like(z)
-        if self._handle_f32:
-            ws = self._workspace((b,), lib.pcd_latent_f32_workspace_bytes(b))
-            _lib.check(lib.pcd_latent_f32_forward(self._handle, z.data_ptr(), b, tbias.data_ptr(), shape_stride,
-                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "latent_f32_forward")
-            return out
-        ws = self._workspace((b,), lib.pcd_latent_workspace_bytes(b))
-        _lib.check(lib.pcd_latent_forward(self._handle, z.data_ptr(), b, tbias.data_ptr(), shape_stride,
-                                          out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "latent_forward")
-        return out
+        return _time_embed(self, t, self.time_dim, 128)
 
     def forward(self, z: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         self._need_cuda(z, t)

@@ -7,7 +7,6 @@ The training surface (`calculate_loss`, `training_step`, `configure_optimizers`)
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, List, Tuple
 
@@ -87,7 +86,6 @@ class VAE3DLarge(_HipModule):
             raise ValueError("VAE3DLarge's encoder reduces 32^3 to 1^3; other input shapes fail in the reference too")
         self.latent_dim = latent_dim
         self._build_from_spec(specs.vae3d_large_spec(latent_dim))
-        self._handle = None
         # the residual blocks' 1x1x1 projection shortcuts inside their conv2 launches (csrc/conv3d.hip, second source);
         # PCD_VAE_FUSE_SHORTCUT=0 / set_fuse_shortcut(False): a pointwise launch + a residual read per block, as before round 4
         self.fuse_shortcut = os.environ.get("PCD_VAE_FUSE_SHORTCUT", "1") != "0"
@@ -270,22 +268,10 @@ class VAE3DLarge(_HipModule):
         d.last_w, d.last_b = pk["last_w"].data_ptr(), pk["last_b"]
         d.taps3, d.taps4s2, d.taps4p0, d.taps1 = (pk[k].data_ptr() for k in ("taps3", "taps4s2", "taps4p0", "taps1"))
         d.zero_page = pk["zero"].data_ptr()
-        handle = C.c_void_p()
-        _lib.check(_lib.load().pcd_vae_create(C.byref(d), C.byref(handle)), "vae_create")
-        self._handle = handle
+        lib = _lib.load()
+        self._handle = self._create(lib.pcd_vae_create, lib.pcd_vae_destroy, d)
         self._packed = pk
         return pk
-
-    def _release(self):
-        if getattr(self, "_handle", None):
-            _lib.load().pcd_vae_destroy(self._handle)
-        self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     # ---------------------------------------------------------------- reference API
     def encode(self, x: torch.Tensor):
