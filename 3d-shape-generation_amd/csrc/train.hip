@@ -38,6 +38,44 @@ __device__ __forceinline__ void cr_finish(float (&acc)[NV][8], float* const (&ou
     }
 }
 
+// The same, reproducibly: the block's partial goes to ws[v][group * chunks + chunk][col] and cr_reduce_kernel adds the chunks
+// of a column in their fixed order (an atomicAdd per block makes the last bit depend on which block arrives first).
+template <int NV>
+__device__ __forceinline__ void cr_finish_ws(float (&acc)[NV][8], float* __restrict__ ws, int64_t stride_v, int col0, int c) {
+    __shared__ float red[NV][CR_LANES][CR_COLS + 1];
+    const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[v][rl][cg * 8 + e] = acc[v][e];
+    __syncthreads();
+    if (threadIdx.x < CR_COLS) {
+        const int col = col0 + threadIdx.x;
+        if (col < c) {
+            const int64_t slot = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * c + col;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                float s = 0.f;
+                for (int r = 0; r < CR_LANES; ++r) s += red[v][r][threadIdx.x];
+                ws[v * stride_v + slot] = s;
+            }
+        }
+    }
+}
+// out_v[group][col] = sum over the chunks, in order, of ws[v][group * chunks + chunk][col]   (v < 2)
+__global__ void cr_reduce_kernel(const float* __restrict__ ws, int64_t stride_v, int nv, int groups, int chunks, int c,
+                                 float* __restrict__ out0, float* __restrict__ out1) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)nv * groups * c) return;
+    const int v = (int)(i / ((int64_t)groups * c));
+    const int64_t gc = i % ((int64_t)groups * c);
+    const int64_t g = gc / c, col = gc % c;
+    const float* p = ws + v * stride_v + g * chunks * c + col;
+    float s = 0.f;
+    for (int y = 0; y < chunks; ++y) s += p[(int64_t)y * c];
+    (v == 0 ? out0 : out1)[gc] = s;
+}
+
 // rows [row0, row1) of this block; returns false if the block has nothing to do
 __device__ __forceinline__ bool cr_range(int64_t rows_per_group, int rows_per_block, int64_t& row0, int64_t& row1) {
     const int64_t g0 = (int64_t)blockIdx.z * rows_per_group;
@@ -83,7 +121,7 @@ __device__ __forceinline__ void st8(half_t* p, int col, int c, const half8& v) {
 // out[g][col] += sum over the rows of group g of x[row][col]
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, int64_t rows_per_group, int c,
-                                                      float* __restrict__ out, int rpb) {
+                                                      float* __restrict__ ws, int rpb) {
     int64_t row0, row1;
     if (!cr_range(rows_per_group, rpb, row0, row1)) return;
     const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
@@ -95,15 +133,14 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[0][e] += v.v[e];
         }
-    float* const outs[1] = {out + (int64_t)blockIdx.z * c};
-    cr_finish<1>(acc, outs, col0, c);
+    cr_finish_ws<1>(acc, ws, 0, col0, c);
 }
 
 // One pass over z for the batch statistics: sums of (z - shift) and (z - shift)^2 with shift[col] = z[0][col].  The
 // shift keeps E[d^2] - E[d]^2 free of cancellation (|mean - shift| is a few sigma at most), so a second read of z
 // for sum (z - mean)^2 is not needed.
-__global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ x, int64_t m, int c, float* __restrict__ s1,
-                                                        float* __restrict__ s2, int rpb) {
+__global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ x, int64_t m, int c, float* __restrict__ ws,
+                                                        int64_t stride_v, int rpb) {
     int64_t row0, row1;
     if (!cr_range(m, rpb, row0, row1)) return;
     const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
@@ -117,8 +154,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
             for (int e = 0; e < 8; ++e) { const float d = v.v[e] - sh.v[e]; acc[0][e] += d; acc[1][e] += d * d; }
         }
     }
-    float* const outs[2] = {s1, s2};
-    cr_finish<2>(acc, outs, col0, c);
+    cr_finish_ws<2>(acc, ws, stride_v, col0, c);
 }
 
 __global__ void bn_finalize_kernel(const float* x, const float* s1, const float* s2, int64_t m, int c, float momentum,
@@ -172,7 +208,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const half_t* __rest
                                                              int64_t m, int c, const float* __restrict__ mean,
                                                              const float* __restrict__ var, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps, int relu,
-                                                             float* __restrict__ dbeta, float* __restrict__ dgamma, int rpb) {
+                                                             float* __restrict__ ws, int64_t stride_v, int rpb) {
     int64_t row0, row1;
     if (!cr_range(m, rpb, row0, row1)) return;
     const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
@@ -197,8 +233,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const half_t* __rest
             }
         }
     }
-    float* const outs[2] = {dbeta, dgamma};
-    cr_finish<2>(acc, outs, col0, c);
+    cr_finish_ws<2>(acc, ws, stride_v, col0, c);          // v = 0: dbeta, v = 1: dgamma
 }
 
 // dz = gamma * rstd * (g - dbeta/m - xhat * dgamma/m), column strips like bn_apply_kernel
@@ -406,11 +441,12 @@ __global__ void matmul_f32_kernel(const float* __restrict__ a, int64_t lda, int 
 // re-reads B once per output row and, for B stored [n][k], walks it uncoalesced (697 us for the 16 x 1024 x 4096
 // per-shape bias of dec4.conv1); here B is read once.
 // B stored [k][n]: a thread owns output column j and the k range of its block row (64 deep), keeps all m partial sums
-// and adds them atomically (c zeroed by the host side when not accumulating): n/256 x k/64 blocks instead of n/256.
+// and writes them to part[k block][i][j]; matmul_f32_fewrows_sum_kernel adds the k blocks in order (reproducible, unlike an
+// atomicAdd per block): n/256 x k/64 blocks instead of n/256.
 __global__ __launch_bounds__(256) void matmul_f32_fewrows_nn_kernel(const float* __restrict__ a, int64_t lda,
                                                                      const float* __restrict__ b, int64_t ldb, int mm, int nn,
                                                                      int kk, const float* __restrict__ bias,
-                                                                     float* __restrict__ c, int64_t ldc) {
+                                                                     float* __restrict__ part) {
     __shared__ float as[32][64];
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int k0 = blockIdx.y * 64, k1 = min(kk, k0 + 64);
@@ -430,7 +466,16 @@ __global__ __launch_bounds__(256) void matmul_f32_fewrows_nn_kernel(const float*
     }
 #pragma unroll
     for (int i = 0; i < 32; ++i)
-        if (i < mm) atomicAdd(c + (int64_t)i * ldc + j, acc[i] + ((bias != nullptr && blockIdx.y == 0) ? bias[j] : 0.f));
+        if (i < mm) part[((int64_t)blockIdx.y * mm + i) * nn + j] = acc[i] + ((bias != nullptr && blockIdx.y == 0) ? bias[j] : 0.f);
+}
+__global__ void matmul_f32_fewrows_sum_kernel(const float* __restrict__ part, int kblocks, int mm, int nn, int accumulate,
+                                              float* __restrict__ c, int64_t ldc) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)mm * nn) return;
+    const int i = (int)(idx / nn), j = (int)(idx % nn);
+    float s = accumulate ? c[(int64_t)i * ldc + j] : 0.f;
+    for (int y = 0; y < kblocks; ++y) s += part[(int64_t)y * mm * nn + idx];
+    c[(int64_t)i * ldc + j] = s;
 }
 // B stored [n][k]: one wave per output column j; lanes stride over k (both operands read contiguously)
 __global__ __launch_bounds__(256) void matmul_f32_fewrows_nt_kernel(const float* __restrict__ a, int64_t lda,
@@ -736,6 +781,21 @@ static inline ColGrid cr_grid(int c, int64_t rows_per_group, int groups) {
 }
 static inline unsigned nblk256(int64_t n) { return (unsigned)ceil_div(n, 256); }
 
+// Device scratch for the per-block partial sums of the two-stage reductions: grown on demand, reused by every call.  The
+// calls of one process are issued from one thread into one stream (the trainers' contract), which orders its users.
+static float* reduce_workspace(size_t floats) {
+    static float* ws = nullptr;
+    static size_t cap = 0;
+    if (floats > cap) {
+        if (ws != nullptr && hipFree(ws) != hipSuccess) return nullptr;          // hipFree waits for the kernels in flight
+        ws = nullptr; cap = 0;
+        const size_t want = floats < ((size_t)1 << 20) ? ((size_t)1 << 20) : floats;
+        if (hipMalloc((void**)&ws, want * sizeof(float)) != hipSuccess) { ws = nullptr; return nullptr; }
+        cap = want;
+    }
+    return ws;
+}
+
 }  // namespace pcd
 
 using namespace pcd;
@@ -743,9 +803,12 @@ using namespace pcd;
 extern "C" int pcd_colsum_f16(const void* x, int64_t rows_per_group, int groups, int c, float* out, void* stream) {
     PCD_CHECK_ARG(x && out && rows_per_group > 0 && groups > 0 && groups <= 65535 && c > 0);
     hipStream_t s = (hipStream_t)stream;
-    PCD_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)groups * c, s));
     const ColGrid g = cr_grid(c, rows_per_group, groups);
-    hipLaunchKernelGGL(colsum_kernel<half_t>, g.grid, dim3(256), 0, s, (const half_t*)x, rows_per_group, c, out, g.rpb);
+    const int64_t slots = (int64_t)groups * g.grid.y * c;
+    float* ws = reduce_workspace((size_t)slots);
+    PCD_CHECK_ARG(ws != nullptr);
+    hipLaunchKernelGGL(colsum_kernel<half_t>, g.grid, dim3(256), 0, s, (const half_t*)x, rows_per_group, c, ws, g.rpb);
+    hipLaunchKernelGGL(cr_reduce_kernel, dim3(nblk256((int64_t)groups * c)), dim3(256), 0, s, ws, slots, 1, groups, (int)g.grid.y, c, out, out);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
@@ -756,9 +819,12 @@ extern "C" int pcd_bn_batch_stats(const float* z, int64_t m, int c, float moment
     PCD_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
     hipStream_t s = (hipStream_t)stream;
     float *s1 = scratch, *s2 = scratch + c;
-    PCD_CHECK_HIP(hipMemsetAsync(scratch, 0, sizeof(float) * 2 * (size_t)c, s));
     const ColGrid g = cr_grid(c, m, 1);
-    hipLaunchKernelGGL(colstats_kernel, g.grid, dim3(256), 0, s, z, m, c, s1, s2, g.rpb);
+    const int64_t slots = (int64_t)g.grid.y * c;
+    float* ws = reduce_workspace((size_t)(2 * slots));
+    PCD_CHECK_ARG(ws != nullptr);
+    hipLaunchKernelGGL(colstats_kernel, g.grid, dim3(256), 0, s, z, m, c, ws, slots, g.rpb);
+    hipLaunchKernelGGL(cr_reduce_kernel, dim3(nblk256(2 * (int64_t)c)), dim3(256), 0, s, ws, slots, 2, 1, (int)g.grid.y, c, s1, s2);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(nblk256(c)), dim3(256), 0, s, z, s1, s2, m, c, momentum, mean, var, running_mean,
                        running_var);
     PCD_CHECK_LAUNCH();
@@ -780,11 +846,13 @@ extern "C" int pcd_bn_backward_f16(const void* da, const float* z, int64_t m, in
                                    void* dz, void* stream) {
     PCD_CHECK_ARG(da && z && mean && var && gamma && beta && dgamma && dbeta && dz && m > 0 && c > 0);
     hipStream_t s = (hipStream_t)stream;
-    PCD_CHECK_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * (size_t)c, s));
-    PCD_CHECK_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * (size_t)c, s));
     const ColGrid g = cr_grid(c, m, 1);
+    const int64_t slots = (int64_t)g.grid.y * c;
+    float* ws = reduce_workspace((size_t)(2 * slots));
+    PCD_CHECK_ARG(ws != nullptr);
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, g.grid, dim3(256), 0, s, (const half_t*)da, z, m, c, mean, var, gamma, beta, eps, relu,
-                       dbeta, dgamma, g.rpb);
+                       ws, slots, g.rpb);
+    hipLaunchKernelGGL(cr_reduce_kernel, dim3(nblk256(2 * (int64_t)c)), dim3(256), 0, s, ws, slots, 2, 1, (int)g.grid.y, c, dbeta, dgamma);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, g.grid, dim3(256), 0, s, (const half_t*)da, z, m, c, mean, var, gamma, beta, eps, relu,
                        dbeta, dgamma, (half_t*)dz, g.rpb);
     PCD_CHECK_LAUNCH();
@@ -857,9 +925,13 @@ extern "C" int pcd_matmul_f32(const float* a, int64_t lda, int trans_a, const fl
                               int k, const float* bias, int accumulate, float* c, int64_t ldc, void* stream) {
     PCD_CHECK_ARG(a && b && c && m > 0 && n > 0 && k > 0);
     if (!trans_a && m <= 32 && !trans_b) {
-        if (!accumulate) PCD_CHECK_HIP(hipMemset2DAsync(c, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)n, (size_t)m, (hipStream_t)stream));
-        hipLaunchKernelGGL(matmul_f32_fewrows_nn_kernel, dim3(nblk256(n), (unsigned)ceil_div(k, 64)), dim3(256), 0, (hipStream_t)stream, a,
-                           lda, b, ldb, m, n, k, bias, c, ldc);
+        const int kblocks = (int)ceil_div(k, 64);
+        float* part = reduce_workspace((size_t)kblocks * m * n);
+        PCD_CHECK_ARG(part != nullptr);
+        hipLaunchKernelGGL(matmul_f32_fewrows_nn_kernel, dim3(nblk256(n), (unsigned)kblocks), dim3(256), 0, (hipStream_t)stream, a,
+                           lda, b, ldb, m, n, k, bias, part);
+        hipLaunchKernelGGL(matmul_f32_fewrows_sum_kernel, dim3(nblk256((int64_t)m * n)), dim3(256), 0, (hipStream_t)stream, part, kblocks,
+                           m, n, accumulate, c, ldc);
     }
     else if (!trans_a && m <= 32 && trans_b)
         hipLaunchKernelGGL(matmul_f32_fewrows_nt_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb,

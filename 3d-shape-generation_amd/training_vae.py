@@ -54,6 +54,7 @@ class VAETrainer(_Trainer):
         self.wm: Dict[str, torch.Tensor] = {}
         self.wmt: Dict[str, torch.Tensor] = {}
         self.bias: Dict[str, torch.Tensor] = {}
+        self._rows: Dict[str, tuple] = {}        # (tensor, rows last written) of the row-padded workspace tensors (`_rows_buf`)
         self.refresh_weights()
 
     # ------------------------------------------------------------------ structure
@@ -111,6 +112,19 @@ class VAETrainer(_Trainer):
                 be[:L.cout] = self.p[L.bn + ".bias"]
         self.model.invalidate()
 
+    def _rows_buf(self, key: str, rows: int, shape, dtype) -> torch.Tensor:
+        """The zero-initialised workspace tensor `key` [Mp][..] of which the caller writes the first `rows` rows and whose
+        rows up to Mp are read as zeros (the backward-weight product reduces over all Mp rows).  A batch-size change
+        that keeps Mp (only where M = B < 64: encoder.12) keeps the tensor, so what a larger batch wrote past `rows`
+        is cleared here.  (Nothing reads the tail of `.z`; clearing it keeps the activation's padding rows zero as
+        documented.)"""
+        t = self._buf(key, shape, dtype, zero=True)
+        same, written = self._rows.get(key, (None, 0))
+        if same is t and written > rows:
+            t[rows:].zero_()
+        self._rows[key] = (t, rows)              # a reallocated tensor is fresh zeros: its record starts over
+        return t
+
     # ------------------------------------------------------------------ one layer
     def _convT_fwd(self, L: _VConv, a_in: torch.Tensor, b: int) -> torch.Tensor:
         """ConvTranspose3d(k, s, p) = adjoint of Conv3d(k, s, p) from the output grid to the input grid:
@@ -153,10 +167,10 @@ class VAETrainer(_Trainer):
         m = b * L.dout ** 3
         mp = _up(m, 64)
         L.m, L.mp, L.a_in = m, mp, a_in
-        L.col = self._buf(L.key + ".col", (mp, L.kp), torch.float16, zero=True)
+        L.col = self._rows_buf(L.key + ".col", m, (mp, L.kp), torch.float16)
         self._chk(lib.pcd_im2col_f16(a_in.data_ptr(), b, L.cin, L.din, L.din, L.din, L.dout, L.dout, L.dout, L.k, L.s, L.p, L.transposed,
                                      L.kp, L.col.data_ptr(), st), "im2col")
-        L.z = self._buf(L.key + ".z", (mp, L.cp), torch.float32 if L.bn else torch.float16, zero=True)
+        L.z = self._rows_buf(L.key + ".z", m, (mp, L.cp), torch.float32 if L.bn else torch.float16)
         self._gemm(_gemm_desc(L.col.data_ptr(), L.kp, self.wm[L.key].data_ptr(), L.kp, m, L.cp, bias=self.bias[L.key].data_ptr(),
                               relu=int(L.relu and not L.bn)), L.z)        # fp32 z in front of a BatchNorm
         if L.bn:
@@ -201,7 +215,7 @@ class VAETrainer(_Trainer):
             self.g[L.bn + ".bias"].copy_(dbe[:L.cout])
             dz = d_out
         elif L.relu:
-            dz = self._buf(L.key + ".dz", (mp, L.cp), torch.float16, zero=True)
+            dz = self._rows_buf(L.key + ".dz", m, (mp, L.cp), torch.float16)
             self._chk(lib.pcd_relu_mask_f16(d_out.data_ptr(), L.a.data_ptr(), m * L.cp, dz.data_ptr(), st), "relu_mask")
         else:
             dz = d_out
@@ -237,7 +251,7 @@ class VAETrainer(_Trainer):
         """gradient wrt the narrowed output [.., Cout] -> [Mp][Cp] with zero padding channels."""
         if L.cp == L.cout and d.shape[0] == L.mp:
             return d
-        out = self._buf(key, (L.mp, L.cp), torch.float16, zero=True)
+        out = self._rows_buf(key, d.shape[0], (L.mp, L.cp), torch.float16)
         out[:d.shape[0], :L.cout] = d[:, :L.cout]
         return out
 

@@ -399,3 +399,197 @@ def test_im2col_col2im_against_torch_convs():
     loss.backward()
     assert abs(ls.item() / 777 - loss.item()) < 1e-5 and torch.allclose(rec, r.detach(), atol=1e-6)
     assert rel_l2(dl[:, 0].float() / 64.0, z.grad) < 2e-3
+
+
+# ------------------------------------------------------------------ the VAE step's small kernels, each against CPU torch
+def test_bias_act_f16_kernel():
+    """out = half_sat(float(x) + bias[col]) [ReLU]: one fp32 add and one rounding, so the result is exact."""
+    L, lib, st = _lib()
+    g = torch.Generator().manual_seed(11)
+    rows = 37                                            # 37 * c is no multiple of the 256-thread block for any c below
+    for c in (1, 32, 64, 200):
+        for relu in (0, 1):
+            x = (torch.randn(rows, c, generator=g) * 3).half()
+            bias = torch.randn(c, generator=g) + torch.arange(c) * 0.25          # distinct per column: bias[i % c]
+            x[0, 0], x[rows - 1, c - 1] = 65504.0, -65504.0                         # the sum leaves fp16's range: saturates
+            if c > 1:
+                bias[c - 1] = -100.0 - bias[c - 1].abs()
+            bias[0] = 100.0 + bias[0].abs()
+            out = torch.full((rows, c), float("nan"), dtype=torch.float16, device="cuda")
+            xd, bd = x.cuda(), bias.cuda()
+            L.check(lib.pcd_bias_act_f16(xd.data_ptr(), bd.data_ptr(), rows, c, relu, out.data_ptr(), st))
+            want = x.float() + bias                                                 # fp32, as the kernel adds
+            assert want[0, 0] > 65504.0
+            if relu:
+                want = want.clamp_min(0)
+            want = want.clamp(-65504.0, 65504.0).half()
+            assert torch.equal(out.cpu(), want), (c, relu)
+            assert out[0, 0].item() == 65504.0 and (relu or c == 1 or out[rows - 1, c - 1].item() == -65504.0)
+            # and the fp32 add loses nothing that matters: within half an fp16 ulp of the float64 sum
+            w64 = x.double() + bias.double()
+            w64 = (w64.clamp_min(0) if relu else w64).clamp(-65504.0, 65504.0)
+            assert ((out.cpu().double() - w64).abs() <= w64.abs().clamp_min(2.0 ** -14) * 2.0 ** -11 * 1.001).all()
+
+
+def _latent_inputs(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    mu = torch.randn(n, generator=g) * 2
+    lv = torch.linspace(-20, 10, n)[torch.randperm(n, generator=g)].float()
+    eps, dz = torch.randn(n, generator=g), torch.randn(n, generator=g) * 0.3
+    return mu, lv, eps, dz
+
+
+def test_reparameterize_and_latent_backward_kernels():
+    """z = mu + eps exp(logvar / 2); the gradients of <z, dz> + kl_scale * KL by float64 autograd; the KL sum.  The
+    vectors are fp32 results of a few operations and one expf (a few ulp): 2e-6 rel-L2; kl_sum is an fp32 atomic sum
+    of n terms: 1e-5 relative.  MI355X: z 4.3e-8, dmu 4.4e-8, dlogvar 5.6e-8, kl_sum 1.1e-8 (the worse of the two n);
+    the element-wise rtol 1e-5 / atol 1e-6 (terms of order 1, a few fp32 roundings each) is an allclose and has no figure."""
+    L, lib, st = _lib()
+    for n, seed in ((2 * 256, 5), (777, 6)):
+        mu, lv, eps, dz = _latent_inputs(n, seed)
+        d = [t.cuda() for t in (mu, lv, eps, dz)]
+        z = torch.full((n,), float("nan"), device="cuda")
+        L.check(lib.pcd_reparameterize(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), z.data_ptr(), n, st))
+        mu64, lv64 = mu.double().requires_grad_(True), lv.double().requires_grad_(True)
+        z64 = mu64 + eps.double() * torch.exp(lv64 / 2)
+        print(f"n {n}: z {rel_l2(z.cpu(), z64.detach()):.2e}")
+        assert rel_l2(z.cpu(), z64.detach()) < 2e-6
+        kl_scale = 0.37 * 1024.0
+        kl_terms = 1 + lv64 - mu64 ** 2 - torch.exp(lv64)
+        ((z64 * dz.double()).sum() + kl_scale * (-0.5 * kl_terms.mean())).backward()
+        dmu, dlv = torch.full((n,), float("nan"), device="cuda"), torch.full((n,), float("nan"), device="cuda")
+        kl_sum = torch.full((1,), float("nan"), device="cuda")
+        L.check(lib.pcd_vae_latent_backward(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), n, kl_scale,
+                                            dmu.data_ptr(), dlv.data_ptr(), kl_sum.data_ptr(), st))
+        print(f"n {n}: dmu {rel_l2(dmu.cpu(), mu64.grad):.2e} dlogvar {rel_l2(dlv.cpu(), lv64.grad):.2e} "
+              f"kl_sum {abs(kl_sum.item() - kl_terms.sum().item()) / abs(kl_terms.sum().item()):.2e}")
+        assert rel_l2(dmu.cpu(), mu64.grad) < 2e-6, rel_l2(dmu.cpu(), mu64.grad)
+        assert rel_l2(dlv.cpu(), lv64.grad) < 2e-6, rel_l2(dlv.cpu(), lv64.grad)
+        # element-wise too: the large exp(logvar) terms must not hide the small ones
+        assert torch.allclose(dlv.cpu().double(), lv64.grad, rtol=1e-5, atol=1e-6)
+        assert torch.allclose(dmu.cpu().double(), mu64.grad, rtol=1e-5, atol=1e-6)
+        want = kl_terms.sum().item()
+        assert abs(kl_sum.item() - want) < 1e-5 * abs(want), (kl_sum.item(), want)
+        # the call VAE3DLarge.calculate_loss makes in eval mode: zero eps / dz (one tensor), scale 0, both outputs aliased
+        zero, scratch = torch.zeros(n, device="cuda"), torch.empty(n, device="cuda")
+        out = torch.full((2,), float("nan"), device="cuda")
+        L.check(lib.pcd_vae_latent_backward(d[0].data_ptr(), d[1].data_ptr(), zero.data_ptr(), zero.data_ptr(), n, 0.0,
+                                            scratch.data_ptr(), scratch.data_ptr(), out[1:].data_ptr(), st))
+        assert abs(out[1].item() - want) < 1e-5 * abs(want) and torch.isnan(out[0])
+        assert torch.equal(d[0].cpu(), mu) and torch.equal(d[1].cpu(), lv) and not zero.any()
+
+
+def test_f16_to_f32_kernel_is_exact():
+    """Every fp16 bit pattern that is not a NaN (subnormals, +-0, +-65504, +-inf): 63490 elements, 2 past a block."""
+    L, lib, st = _lib()
+    bits = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16)
+    h = bits.view(torch.float16)
+    h = h[~torch.isnan(h)]
+    n = h.numel()
+    assert n == 63490 and n % 256 == 2 and (h == 65504).any() and (h == -65504).any() and (h.abs() == 2.0 ** -24).sum() == 2
+    src = h.cuda()
+    dst = torch.full((n + 8,), 7.0, device="cuda")
+    L.check(lib.pcd_f16_to_f32(src.data_ptr(), dst.data_ptr(), n, st))
+    got = dst.cpu()
+    assert torch.equal(got[:n].view(torch.int32), h.float().view(torch.int32))          # bitwise: the sign of zero too
+    assert bool((got[n:] == 7.0).all())
+    for m in (1, 255, 257):
+        dst.fill_(7.0)
+        L.check(lib.pcd_f16_to_f32(src.data_ptr(), dst.data_ptr(), m, st))
+        assert torch.equal(dst.cpu()[:m], h.float()[:m]) and bool((dst[m:] == 7.0).all())
+
+
+def test_sigmoid_bce_kernel_strided_grid_stride():
+    """The trainer's call shape: logits in column 0 of an [n][64] fp16 matrix, n = 600000 > 2048 blocks * 256 threads,
+    so the grid-stride loop runs.  The loss reference is float32 on the CPU (the reference project's arithmetic):
+    for a logit z > 16.64 float32 gives 1 + exp(-z) == 1, sigmoid == 1 and log(1 - sigmoid) = -inf, clamped to -100 by
+    torch's BCE, so a target 0 there costs exactly 100 (float64 would say z).  Those elements (z >= 18, target 0) are
+    also run on their own, where the sum is exact.  On the negative side nothing saturates (sigmoid(-30) = 9.4e-14)."""
+    L, lib, st = _lib()
+    g = torch.Generator().manual_seed(13)
+    n, ld, scale = 600000, 64, 32768.0
+    z = torch.randn(n, generator=g) * 4
+    z[:4000] = torch.linspace(18, 30, 4000)
+    z[4000:8000] = torch.linspace(-30, -18, 4000)
+    z[(z > 16.0) & (z < 18.0)] = 16.0          # keep the full run off the band where 1 + exp(-z) rounds to 1 (z ~ 16.64): one
+    #                                            logit judged differently by expf and the CPU would move a term from ~17 to 100
+    z = z[torch.randperm(n, generator=g)].half()
+    x = (torch.rand(n, generator=g) > 0.7).float()
+    logit = (torch.randn(n, ld, generator=g) * 4).half()              # columns 1.. hold other numbers: must not be read
+    logit[:, 0] = z
+    dl0 = torch.randn(n, ld, generator=g).half()
+    sat = (z.float() >= 18) & (x == 0)
+    assert z.float().max() == 30 and z.float().min() == -30 and 500 < int(sat.sum()) < 160000
+
+    def run(zm, xt, dl):
+        ls, rec = torch.full((1,), float("nan"), device="cuda"), torch.full((xt.numel(),), float("nan"), device="cuda")
+        L.check(lib.pcd_sigmoid_bce(zm.data_ptr(), ld, xt.data_ptr(), xt.numel(), scale, ls.data_ptr(), rec.data_ptr(), dl.data_ptr(), st))
+        return ls.item(), rec.cpu()
+
+    dl = dl0.cuda()
+    ls, rec = run(logit.cuda(), x.cuda(), dl)
+    assert torch.allclose(rec.double(), torch.sigmoid(z.double()), rtol=0, atol=1e-6)
+    r32 = torch.sigmoid(z.float())
+    per = F.binary_cross_entropy(r32, x, reduction="none")
+    assert bool((per[sat] == 100.0).all())                                 # the regime the docstring describes
+    want = per.double().sum().item()
+    assert abs(ls - want) < 1e-5 * want, (ls, want)
+    dl = dl.cpu()
+    assert torch.equal(dl[:, 1:], dl0[:, 1:])                              # only column 0 is written
+    want_d = scale * (torch.sigmoid(z.double()) - x.double()) / n
+    assert rel_l2(dl[:, 0], want_d) < 2e-3
+    # the clamp regime alone: every term is exactly 100, and sums of those are exact in fp32
+    ns = int(sat.sum())
+    ls_sat, rec_sat = run(logit[sat].contiguous().cuda(), x[sat].contiguous().cuda(), torch.zeros(ns, ld, dtype=torch.float16, device="cuda"))
+    assert ls_sat == 100.0 * ns and bool((rec_sat == 1.0).all())
+    # and the rest against float64, where float32's sigmoid is accurate
+    rest = z.float().abs() < 8
+    nr = int(rest.sum())
+    ls_r, _ = run(logit[rest].contiguous().cuda(), x[rest].contiguous().cuda(), torch.zeros(nr, ld, dtype=torch.float16, device="cuda"))
+    want_r = F.binary_cross_entropy(torch.sigmoid(z[rest].double()), x[rest].double(), reduction="sum").item()
+    assert abs(ls_r - want_r) < 1e-5 * want_r, (ls_r, want_r)
+
+
+
+def test_point_and_latent_trainers_across_a_batch_size_change(golden):
+    """One trainer stepped at the golden batch and then at half of it, and one stepped twice at the half, against a
+    fresh trainer at the half: nothing an earlier step left in the workspace may reach a later one.  Gradients bitwise,
+    except the three that `pcd_vec3_outer` still adds atomically per block (1e-6 rel-L2, their norms are ~1e2); the
+    atomically summed loss at 1e-6 relative.  (The VAE trainer's version is in test_gpu_train_vae.py.)"""
+    from helpers import latent_sd
+    from shapegen_amd.diffusion import LatentDiffusion
+    from shapegen_amd.training import LatentTrainer, PointTrainer
+    from shapegen_amd.vae import VAE3DLarge
+    atomic = ("output.3.weight", "output.3.bias", "enc1.conv1.weight")
+
+    def point(sizes):
+        model, sd, x_t, t, noise, g = _setup(golden)
+        tr = PointTrainer(model.model)
+        for b in sizes:
+            tr.forward(x_t[:b].cuda(), t[:b].cuda(), update_stats=False)
+            loss = tr.backward(noise[:b].cuda())
+        return loss.item(), {k: v.clone() for k, v in tr.g.items()}
+
+    def latent(sizes):
+        g = golden("train_latent.npz")
+        m = LatentDiffusion(VAE3DLarge())
+        m.load_state_dict(latent_sd(), strict=True)
+        m = m.to("cuda")
+        z_t, t, noise, mask = (torch.from_numpy(g[k]) for k in ("z_t", "t", "noise", "mask"))
+        tr = LatentTrainer(m.model)
+        for b in sizes:
+            tr.forward(z_t[:b].cuda(), t[:b].cuda(), mask[:b].cuda())
+            loss = tr.backward(noise[:b].cuda())
+        return loss.item(), {k: v.clone() for k, v in tr.g.items()}
+
+    for step, full, half in ((point, 2, 1), (latent, 4, 2)):
+        loss_ref, grads_ref = step((half,))
+        for sizes in ((full, half), (half, half)):
+            loss, grads = step(sizes)
+            assert abs(loss - loss_ref) <= 1e-6 * abs(loss_ref), (step.__name__, sizes, loss, loss_ref)
+            assert sorted(grads) == sorted(grads_ref)
+            for k, v in grads_ref.items():
+                if step is point and k in atomic:
+                    assert v.norm() > 1 and rel_l2(grads[k], v) < 1e-6, (sizes, k, rel_l2(grads[k], v))
+                else:
+                    assert torch.equal(grads[k], v), (step.__name__, sizes, k, rel_l2(grads[k], v))
