@@ -305,6 +305,7 @@ _SIGS = {
     "pcd_sigmoid_bce": (i32, [vp, i64, vp, i64, f32, vp, vp, vp, vp]),
     "pcd_vae_latent_backward": (i32, [vp, vp, vp, vp, i64, f32, vp, vp, vp, vp]),
     "pcd_adamw_step": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "pcd_adamw_ema_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

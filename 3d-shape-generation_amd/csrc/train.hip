@@ -361,9 +361,11 @@ __global__ void enc1_linear_kernel(const float* __restrict__ x, int64_t m, int n
     out[i] = xr[0] * w[col * 3] + xr[1] * w[col * 3 + 1] + xr[2] * w[col * 3 + 2] + tbias[(row / n_points) * c + col];
 }
 
-// out[j][k] += sum_m vec[m][j] * mat[m][k]  (j < 3)  and  vsum[j] += sum_m vec[m][j]
+// out[j][k] = sum_m vec[m][j] * mat[m][k]  (j < 3)  and  vsum[j] = sum_m vec[m][j], reproducibly: each row chunk's partials go
+// to ws[j][chunk][col] (and vws[chunk][j]) and vec3_outer_reduce_kernel adds the chunks in their fixed order
 __global__ __launch_bounds__(256) void vec3_outer_kernel(const half_t* __restrict__ mat, const float* __restrict__ vec,
-                                                          int64_t m, int k, float* __restrict__ out, float* __restrict__ vsum, int rpb) {
+                                                          int64_t m, int k, float* __restrict__ ws, int64_t stride_v,
+                                                          float* __restrict__ vws, int rpb) {
     int64_t row0, row1;
     if (!cr_range(m, rpb, row0, row1)) return;
     const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
@@ -382,11 +384,27 @@ __global__ __launch_bounds__(256) void vec3_outer_kernel(const half_t* __restric
             }
         }
     }
-    float* const outs[3] = {out, out + k, out + 2 * k};
-    cr_finish<3>(acc, outs, col0, k);
-    if (vsum != nullptr && blockIdx.x == 0 && cg == 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) atomicAdd(vsum + j, vs[j]);
+    __shared__ float vred[3][CR_LANES];
+    if (cg == 0) { vred[0][rl] = vs[0]; vred[1][rl] = vs[1]; vred[2][rl] = vs[2]; }
+    cr_finish_ws<3>(acc, ws, stride_v, col0, k);          // its barrier also orders vred
+    if (vws != nullptr && blockIdx.x == 0 && threadIdx.x < 3) {
+        float t = 0.f;
+        for (int r = 0; r < CR_LANES; ++r) t += vred[threadIdx.x][r];
+        vws[(int64_t)blockIdx.y * 3 + threadIdx.x] = t;
+    }
+}
+__global__ void vec3_outer_reduce_kernel(const float* __restrict__ ws, int64_t stride_v, const float* __restrict__ vws, int chunks,
+                                         int k, float* __restrict__ out, float* __restrict__ vsum) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 3 * k) {
+        const float* p = ws + (int64_t)(i / k) * stride_v + i % k;
+        float t = 0.f;
+        for (int y = 0; y < chunks; ++y) t += p[(int64_t)y * k];
+        out[i] = t;
+    } else if (i < 3 * k + 3 && vsum != nullptr) {
+        float t = 0.f;
+        for (int y = 0; y < chunks; ++y) t += vws[y * 3 + (i - 3 * k)];
+        vsum[i - 3 * k] = t;
     }
 }
 
@@ -753,20 +771,64 @@ __global__ void vae_latent_bwd_kernel(const float* mu, const float* lv, const fl
     atomicAdd(kl_sum, 1.f + lv[i] - mu[i] * mu[i] - e);
 }
 
-// torch.optim.AdamW (decoupled weight decay), one flat buffer
+// torch.optim.AdamW (decoupled weight decay) on one flat buffer, optionally with the exponential moving average of the
+// weights kept in the same launch: ema = decay * ema + (1 - decay) * w_new, from the register that holds w_new.  One
+// element update, written once: the plain and the EMA entry points and the vector and scalar forms all inline this same
+// expression tree, so the parameters and moments they produce are bitwise equal.
+struct AdamwArgs { float lr, b1, b2, eps, wd, bc1, bc2, inv_scale, decay; };
+
+template <bool EMA>
+__device__ __forceinline__ void adamw_element(float& w, const float g, float& m1, float& m2, float& e, const AdamwArgs& a) {
+    // The arithmetic pcd_adamw_step has always had, pinned: the decay term is one fused multiply-add, both moments are two
+    // rounded products and a rounded sum.  Contraction is off because, left to the compiler, the vector and the scalar
+    // instantiation fused these sums differently (and differently from the one-element kernel this replaces).
+#pragma clang fp contract(off)
+    const float gr = g * a.inv_scale;
+    w = __builtin_fmaf(-(a.lr * a.wd), w, w);
+    const float m = a.b1 * m1 + (1.f - a.b1) * gr;
+    const float v = a.b2 * m2 + (1.f - a.b2) * gr * gr;
+    m1 = m; m2 = v;
+    w -= (a.lr / a.bc1) * m / (sqrtf(v) / sqrtf(a.bc2) + a.eps);
+    if (EMA) e = __builtin_fmaf(a.decay, e, (1.f - a.decay) * w);
+}
+
+// VEC: lane i owns the four consecutive floats [4 i, 4 i + 4) (16-byte loads and stores; the buffers are 16-byte aligned),
+// lane n / 4 the n % 4 tail elements one by one.  Not VEC: one element per lane (buffers of any alignment).
+template <bool EMA, bool VEC>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2,
-                             int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2,
-                             float inv_scale) {
+                             float* __restrict__ ema, int64_t n, AdamwArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gr = g[i] * inv_scale;
-    float w = p[i];
-    w -= lr * wd * w;
-    const float m = b1 * m1[i] + (1.f - b1) * gr;
-    const float v = b2 * m2[i] + (1.f - b2) * gr * gr;
-    m1[i] = m; m2[i] = v;
-    w -= (lr / bc1) * m / (sqrtf(v) / sqrtf(bc2) + eps);
-    p[i] = w;
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        if (i < n4) {
+            float4 w = reinterpret_cast<float4*>(p)[i];
+            const float4 gr = reinterpret_cast<const float4*>(g)[i];
+            float4 m = reinterpret_cast<float4*>(m1)[i], v = reinterpret_cast<float4*>(m2)[i];
+            float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (EMA) e = reinterpret_cast<float4*>(ema)[i];
+            adamw_element<EMA>(w.x, gr.x, m.x, v.x, e.x, a);
+            adamw_element<EMA>(w.y, gr.y, m.y, v.y, e.y, a);
+            adamw_element<EMA>(w.z, gr.z, m.z, v.z, e.z, a);
+            adamw_element<EMA>(w.w, gr.w, m.w, v.w, e.w, a);
+            reinterpret_cast<float4*>(p)[i] = w;
+            reinterpret_cast<float4*>(m1)[i] = m;
+            reinterpret_cast<float4*>(m2)[i] = v;
+            if (EMA) reinterpret_cast<float4*>(ema)[i] = e;
+        } else if (i == n4) {
+            for (int64_t j = n4 * 4; j < n; ++j) {
+                float w = p[j], m = m1[j], v = m2[j], e = EMA ? ema[j] : 0.f;
+                adamw_element<EMA>(w, g[j], m, v, e, a);
+                p[j] = w; m1[j] = m; m2[j] = v;
+                if (EMA) ema[j] = e;
+            }
+        }
+    } else {
+        if (i >= n) return;
+        float w = p[i], m = m1[i], v = m2[i], e = EMA ? ema[i] : 0.f;
+        adamw_element<EMA>(w, g[i], m, v, e, a);
+        p[i] = w; m1[i] = m; m2[i] = v;
+        if (EMA) ema[i] = e;
+    }
 }
 
 // column-strip launch geometry: enough row chunks for ~2048 blocks in total, chunks a multiple of the 32 row lanes
@@ -895,10 +957,15 @@ extern "C" int pcd_enc1_linear(const float* x, int64_t m, int n_points, const fl
 extern "C" int pcd_vec3_outer(const void* mat, const float* vec, int64_t m, int k, float* out, float* vsum, void* stream) {
     PCD_CHECK_ARG(mat && vec && out && m > 0 && k > 0);
     hipStream_t s = (hipStream_t)stream;
-    PCD_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float) * 3 * (size_t)k, s));
-    if (vsum != nullptr) PCD_CHECK_HIP(hipMemsetAsync(vsum, 0, sizeof(float) * 3, s));
     const ColGrid g = cr_grid(k, m, 1);
-    hipLaunchKernelGGL(vec3_outer_kernel, g.grid, dim3(256), 0, s, (const half_t*)mat, vec, m, k, out, vsum, g.rpb);
+    const int64_t slots = (int64_t)g.grid.y * k;
+    float* ws = reduce_workspace((size_t)(3 * slots + 3 * (int64_t)g.grid.y));
+    PCD_CHECK_ARG(ws != nullptr);
+    float* vws = ws + 3 * slots;
+    hipLaunchKernelGGL(vec3_outer_kernel, g.grid, dim3(256), 0, s, (const half_t*)mat, vec, m, k, ws, slots, vsum != nullptr ? vws : nullptr,
+                       g.rpb);
+    hipLaunchKernelGGL(vec3_outer_reduce_kernel, dim3(nblk256(3 * (int64_t)k + 3)), dim3(256), 0, s, ws, slots, vws, (int)g.grid.y, k, out,
+                       vsum);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
@@ -957,12 +1024,35 @@ extern "C" int pcd_silu_backward_f32(const float* x, const float* dy, int64_t n,
     return PCD_OK;
 }
 
+template <bool EMA>
+static void adamw_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_decay,
+                         void* stream) {
+    const AdamwArgs a = {lr, beta1, beta2, eps, weight_decay, 1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step),
+                         1.f / grad_scale, ema_decay};
+    const uintptr_t bits = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema;
+    if ((bits & 15) == 0)          // n / 4 vector lanes and one lane for the tail
+        hipLaunchKernelGGL((adamw_kernel<EMA, true>), dim3(nblk256(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                           exp_avg_sq, ema, n, a);
+    else
+        hipLaunchKernelGGL((adamw_kernel<EMA, false>), dim3(nblk256(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                           exp_avg_sq, ema, n, a);
+}
+
 extern "C" int pcd_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                               float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
     PCD_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && n > 0 && step >= 1 && grad_scale > 0.f);
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(nblk256(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2, 1.f / grad_scale);
+    adamw_launch<false>(params, grads, exp_avg, exp_avg_sq, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0.f, stream);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_adamw_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                  float ema_decay, void* stream) {
+    PCD_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && ema && n > 0 && step >= 1 && grad_scale > 0.f);
+    PCD_CHECK_ARG(ema_decay >= 0.f && ema_decay < 1.f);
+    adamw_launch<true>(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ema_decay, stream);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }

@@ -366,10 +366,11 @@ class PointCloudDiffusion(_DiffusionBase):
         self._init_schedule(noise_schedule)
 
     @classmethod
-    def load_from_checkpoint(cls, path, map_location="cpu", **kwargs):
-        """Lightning-free loader for the reference's `.ckpt` layout (test_point_ddpm.py:161)."""
+    def load_from_checkpoint(cls, path, map_location="cpu", weights="raw", **kwargs):
+        """Lightning-free loader for the reference's `.ckpt` layout (test_point_ddpm.py:161).  `weights="ema"` loads the
+        averaged weights of a run trained with an EMA decay (an error for a file without them)."""
         from .checkpoint import load_lightning_checkpoint
-        hp, sd = load_lightning_checkpoint(path, map_location)
+        hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
         obj = cls(**{k: hp[k] for k in ("num_points", "dim", "time_dim", "lr", "noise_schedule", "backbone") if k in hp})
         obj.load_state_dict(sd, strict=True)
@@ -492,12 +493,12 @@ class LatentDiffusion(_DiffusionBase):
             self.vae.invalidate()
 
     @classmethod
-    def load_from_checkpoint(cls, path, vae=None, map_location="cpu", **kwargs):
+    def load_from_checkpoint(cls, path, vae=None, map_location="cpu", weights="raw", **kwargs):
         """`vae=` is required: the reference saves hyper-parameters with ignore=['vae'] (diffusion.py:375)."""
         from .checkpoint import load_lightning_checkpoint
         if vae is None:
             raise TypeError("LatentDiffusion.load_from_checkpoint needs vae=")
-        hp, sd = load_lightning_checkpoint(path, map_location)
+        hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
         keys = ("latent_dim", "dim", "time_dim", "lr", "noise_schedule", "is_voxel_based")
         obj = cls(vae, **{k: hp[k] for k in keys if k in hp})

@@ -110,6 +110,8 @@ class _Trainer:
         if self.dev.type != "cuda":
             raise RuntimeError(f"{type(self).__name__} needs the model on an MI355X (model.to('cuda'))")
         self.step_count = 0
+        self.EMA: Optional[torch.Tensor] = None    # flat fp32 moving average of P, kept by the optimizer launch (`enable_ema`)
+        self.ema_decay: Optional[float] = None
         # ---- one flat fp32 buffer for parameters, one for gradients, two for the AdamW moments
         self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
         self.names = list(self.p)                  # the trained parameters (subclasses may add aliases to p and g)
@@ -251,13 +253,28 @@ class _Trainer:
         """Unscaled parameter gradients (copies), keyed like `named_parameters()`."""
         return {k: self.g[k].clone() / self.loss_scale for k in self.names}
 
+    def enable_ema(self, decay: float) -> None:
+        """Keep an exponential moving average of the trained weights: a flat fp32 buffer `EMA`, initialised to the current
+        parameters, which `optimizer_step` then updates in the AdamW launch itself (`pcd_adamw_ema_step`)."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"ema decay must be in [0, 1), got {decay}")
+        if self.EMA is None:
+            self.EMA = self.P.clone()
+        self.ema_decay = decay
+
     def optimizer_step(self):
         self.step_count += 1
         b1, b2 = self.betas
         world = _allreduce_gradients(self.G)           # data parallel: mean gradient over the ranks (BatchNorm stays per rank)
-        self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
-                                          self.P.numel(), self.lr, b1, b2, self.eps, self.wd, self.step_count,
-                                          self.loss_scale * world, self._st()), "adamw")
+        if self.EMA is None:
+            self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+                                              self.P.numel(), self.lr, b1, b2, self.eps, self.wd, self.step_count,
+                                              self.loss_scale * world, self._st()), "adamw")
+        else:
+            self._chk(self.lib.pcd_adamw_ema_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+                                                  self.EMA.data_ptr(), self.P.numel(), self.lr, b1, b2, self.eps, self.wd,
+                                                  self.step_count, self.loss_scale * world, self.ema_decay, self._st()), "adamw_ema")
         self.refresh_weights()
 
     # torch.optim-like aliases so the object can stand where the reference's optimizer does
@@ -267,8 +284,70 @@ class _Trainer:
     def zero_grad(self):
         pass                                # every backward overwrites the whole gradient buffer
 
+    def param_layout(self) -> List[Tuple[str, int]]:
+        """(name, element count) of the trained parameters in the order they lie in the flat buffers."""
+        return [(k, self.p[k].numel()) for k in self.names]
+
     def state_dict(self):
-        return {"step": self.step_count, "lr": self.lr, "exp_avg": self.M1, "exp_avg_sq": self.M2}
+        """Everything the optimizer carries from step to step besides the parameters themselves (those, and BatchNorm's
+        running statistics, travel in the module's `state_dict()`).  The tensors are the live device buffers."""
+        return {"step": self.step_count, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
+                "loss_scale": self.loss_scale, "exp_avg": self.M1, "exp_avg_sq": self.M2, "ema": self.EMA,
+                "ema_decay": self.ema_decay, "layout": self.param_layout()}
+
+    def load_state_dict(self, state) -> None:
+        """Inverse of `state_dict()`.  The parameter layout (names and sizes in flat order) must be this trainer's."""
+        layout = [(str(k), int(n)) for k, n in state["layout"]]
+        if layout != self.param_layout():
+            mine = self.param_layout()
+            bad = next((i for i, (a, b) in enumerate(zip(layout, mine)) if a != b), min(len(layout), len(mine)))
+            raise RuntimeError(f"optimizer state is for another parameter layout: {len(layout)} tensors against {len(mine)} here, first "
+                               f"difference at position {bad} ({layout[bad] if bad < len(layout) else None} / {mine[bad] if bad < len(mine) else None})")
+        for key, dst in (("exp_avg", self.M1), ("exp_avg_sq", self.M2)):
+            src = state[key]
+            if src.numel() != dst.numel():
+                raise RuntimeError(f"optimizer state {key} has {src.numel()} elements, the flat buffer {dst.numel()}")
+            dst.copy_(src.reshape(-1).to(self.dev, torch.float32))
+        self.step_count, self.lr = int(state["step"]), float(state["lr"])
+        self.betas = tuple(float(b) for b in state.get("betas", self.betas))
+        self.eps, self.wd = float(state.get("eps", self.eps)), float(state.get("weight_decay", self.wd))
+        self.loss_scale = float(state.get("loss_scale", self.loss_scale))
+        ema = state.get("ema")
+        if ema is None:
+            self.EMA = self.ema_decay = None
+        else:
+            if ema.numel() != self.P.numel():
+                raise RuntimeError(f"EMA buffer has {ema.numel()} elements, the flat parameter buffer {self.P.numel()}")
+            self.enable_ema(state["ema_decay"])
+            self.EMA.copy_(ema.reshape(-1).to(self.dev, torch.float32))
+        self.refresh_weights()
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The module's `state_dict()` with every trained parameter taken from the moving average (copies); buffers
+        (BatchNorm's running statistics are not averaged) as they are."""
+        if self.EMA is None:
+            raise RuntimeError("no EMA weights: call enable_ema(decay) before training")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        off = 0
+        for name, n in self.param_layout():
+            sd[name] = self.EMA[off:off + n].view(self.p[name].shape).clone()
+            off += n
+        return sd
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the module computes with the averaged weights (they are swapped into the flat parameter buffer and
+        everything the kernels read is rebuilt); the raw weights come back on exit, also after an exception."""
+        if self.EMA is None:
+            raise RuntimeError("no EMA weights: call enable_ema(decay) before training")
+        raw = self.P.clone()
+        self.P.copy_(self.EMA)
+        self.refresh_weights()
+        try:
+            yield self
+        finally:
+            self.P.copy_(raw)
+            self.refresh_weights()
 
 
 class _Conv:
@@ -926,6 +1005,18 @@ class CosineAnnealingLR:
         self.epoch += 1
         self.trainer.lr = self.eta_min + (self.base - self.eta_min) * (1 + math.cos(math.pi * self.epoch / self.T_max)) / 2
 
+    def state_dict(self) -> dict:
+        """torch's field names for what this object has."""
+        return {"last_epoch": self.epoch, "base_lrs": [self.base], "T_max": self.T_max, "eta_min": self.eta_min,
+                "_last_lr": [self.trainer.lr]}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.epoch = int(state.get("last_epoch", self.epoch))
+        self.base = float(state.get("base_lrs", [self.base])[0])
+        self.T_max, self.eta_min = state.get("T_max", self.T_max), state.get("eta_min", self.eta_min)
+        if state.get("_last_lr"):
+            self.trainer.lr = float(state["_last_lr"][0])
+
 
 class ReduceLROnPlateau:
     """torch.optim.lr_scheduler.ReduceLROnPlateau(mode='min', factor, patience) as configured at diffusion.py:61,
@@ -944,17 +1035,207 @@ class ReduceLROnPlateau:
             self.trainer.lr *= self.factor
             self.bad = 0
 
+    def state_dict(self) -> dict:
+        """torch's field names for what this object has."""
+        return {"best": self.best, "num_bad_epochs": self.bad, "factor": self.factor, "patience": self.patience,
+                "threshold": self.threshold, "_last_lr": [self.trainer.lr]}
 
-def save_checkpoint(model, path: str, epoch: int, extra: Optional[dict] = None) -> None:
+    def load_state_dict(self, state: dict) -> None:
+        self.best, self.bad = float(state.get("best", self.best)), int(state.get("num_bad_epochs", self.bad))
+        self.factor, self.patience = state.get("factor", self.factor), state.get("patience", self.patience)
+        self.threshold = state.get("threshold", self.threshold)
+        if state.get("_last_lr"):
+            self.trainer.lr = float(state["_last_lr"][0])
+
+
+CKPT_KEY = "shapegen_amd"      # the one private key of a checkpoint: what Lightning's layout has no place for
+CKPT_FORMAT = 1
+# where a module keeps its position in the on-device Philox streams: the diffusions' noise, the VAE's reparameterisation
+# and prior draws (the VAE trainer's own stream position travels in its state dict)
+_PHILOX_POSITIONS = ("_philox_offset", "_philox", "_philox_sample")
+
+
+def adamw_state_to_torch(exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int, layout, order, lr: float, betas, eps: float,
+                         weight_decay: float) -> dict:
+    """The flat AdamW moments as a `torch.optim.AdamW(...).state_dict()` (what Lightning stores under `optimizer_states`).
+    `layout` = (name, shape) of the trained parameters in flat order, `order` = the names of all the module's
+    `parameters()`: a parameter's index is its position there, a frozen one takes an index and carries no state.
+    A pure function of CPU tensors."""
+    index = {name: i for i, name in enumerate(order)}
+    state, off = {}, 0
+    for name, shape in layout:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        state[index[name]] = {"step": torch.tensor(float(step)),
+                              "exp_avg": exp_avg[off:off + n].detach().to("cpu", torch.float32).reshape(tuple(shape)).clone(),
+                              "exp_avg_sq": exp_avg_sq[off:off + n].detach().to("cpu", torch.float32).reshape(tuple(shape)).clone()}
+        off += n
+    if off != exp_avg.numel() or off != exp_avg_sq.numel():
+        raise ValueError(f"layout covers {off} elements, the moments have {exp_avg.numel()} / {exp_avg_sq.numel()}")
+    group = {"lr": float(lr), "betas": tuple(float(b) for b in betas), "eps": float(eps), "weight_decay": float(weight_decay),
+             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+             "params": list(range(len(order)))}
+    return {"state": state, "param_groups": [group]}
+
+
+def adamw_state_from_torch(opt_state: dict, layout, order):
+    """Inverse of `adamw_state_to_torch`: (exp_avg, exp_avg_sq, step, param group) with the moments flat in `layout`'s
+    order.  A trained parameter without state (it never received a gradient) reads as zeros."""
+    groups = opt_state["param_groups"]
+    if len(groups) != 1:
+        raise RuntimeError(f"expected one optimizer param group, the file has {len(groups)}")
+    ids = list(groups[0]["params"])
+    if len(ids) != len(order):
+        raise RuntimeError(f"optimizer state is for {len(ids)} parameters, the module has {len(order)}")
+    index = {name: ids[i] for i, name in enumerate(order)}
+    m1, m2, step = [], [], 0
+    for name, shape in layout:
+        st = opt_state["state"].get(index[name])
+        if st is None:
+            m1.append(torch.zeros(tuple(shape)).reshape(-1))
+            m2.append(torch.zeros(tuple(shape)).reshape(-1))
+            continue
+        if tuple(st["exp_avg"].shape) != tuple(shape):
+            raise RuntimeError(f"optimizer state of {name}: shape {tuple(st['exp_avg'].shape)}, the parameter is {tuple(shape)}")
+        m1.append(st["exp_avg"].detach().to("cpu", torch.float32).reshape(-1))
+        m2.append(st["exp_avg_sq"].detach().to("cpu", torch.float32).reshape(-1))
+        step = max(step, int(round(float(st["step"]))))
+    return torch.cat(m1), torch.cat(m2), step, dict(groups[0])
+
+
+def _trainer_prefix(model, trainer) -> str:
+    """The prefix of the trainer's module inside `model` ('model.' for the diffusions, '' for the VAE)."""
+    for name, mod in model.named_modules():
+        if mod is trainer.model:
+            return name + "." if name else ""
+    raise RuntimeError("the trainer's module is not part of the model being saved")
+
+
+def _trainer_layout(model, trainer):
+    pre = _trainer_prefix(model, trainer)
+    return pre, [(pre + k, tuple(trainer.p[k].shape)) for k in trainer.names], [n for n, _ in model.named_parameters()]
+
+
+def split_fingerprint(data_module) -> Optional[str]:
+    """A hash of the train / validation index lists of a data module that splits with `random_split` (None otherwise)."""
+    import hashlib
+    tr = getattr(getattr(data_module, "train_dataset", None), "indices", None)
+    va = getattr(getattr(data_module, "val_dataset", None), "indices", None)
+    if tr is None or va is None:
+        return None
+    h = hashlib.sha256()
+    for part in (tr, va):
+        h.update(torch.as_tensor(list(part), dtype=torch.int64).numpy().tobytes())
+        h.update(b"|")
+    return h.hexdigest()
+
+
+def _rng_get(device) -> dict:
+    import random
+    import numpy as np
+    device = torch.device(device)
+    return {"torch": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device) if device.type == "cuda" else None,
+            "python": random.getstate(), "numpy": np.random.get_state()}
+
+
+def _rng_set(state: dict, device) -> None:
+    import random
+    import numpy as np
+    device = torch.device(device)
+    torch.set_rng_state(state["torch"].cpu())
+    if state.get("device") is not None and device.type == "cuda":
+        torch.cuda.set_rng_state(state["device"].cpu(), device)
+    random.setstate(state["python"])
+    np.random.set_state(state["numpy"])
+
+
+def save_checkpoint(model, path: str, epoch: int, extra: Optional[dict] = None, optimizer=None, scheduler=None,
+                    loop: Optional[dict] = None) -> None:
     """A `.ckpt` in the layout the reference's Lightning checkpoints have (`state_dict` + `hyper_parameters`),
-    which `PointCloudDiffusion.load_from_checkpoint` of either code base reads back."""
+    which `PointCloudDiffusion.load_from_checkpoint` of either code base reads back.  With `optimizer` / `scheduler` /
+    `loop` it also carries what a run needs to continue: `global_step`, `optimizer_states` (torch.optim.AdamW's own
+    layout, indexed like the module's `parameters()`), `lr_schedulers`, `ema_state_dict` and, under the private key
+    `shapegen_amd`, the loss scale, EMA decay, loop state, Philox positions and RNG states.  `hyper_parameters` is never
+    extended: the reference's loader hands it to the constructor.  The file is written to a temporary name in the same
+    directory and renamed over `path`."""
     import os
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     payload = {"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                "hyper_parameters": dict(model.hparams), "epoch": epoch,
                "pytorch-lightning_version": "2.3.3"}       # the reference's pin; Lightning's loader looks for this key
+    private = {"format": CKPT_FORMAT}
+    if optimizer is not None and hasattr(optimizer, "state_dict") and hasattr(optimizer, "load_state_dict"):
+        st = optimizer.state_dict()
+        if isinstance(optimizer, _Trainer):
+            pre, layout, order = _trainer_layout(model, optimizer)
+            payload["global_step"] = int(st["step"])
+            payload["optimizer_states"] = [adamw_state_to_torch(st["exp_avg"].cpu(), st["exp_avg_sq"].cpu(), st["step"], layout, order,
+                                                                st["lr"], st["betas"], st["eps"], st["weight_decay"])]
+            private["trainer"] = {k: v for k, v in st.items() if k not in ("exp_avg", "exp_avg_sq", "ema")}
+            if st["ema"] is not None:
+                ema = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+                trained = set(optimizer.names)
+                ema.update({pre + k: v.cpu() for k, v in optimizer.ema_state_dict().items() if k in trained})
+                payload["ema_state_dict"] = ema
+        else:
+            payload["optimizer_states"] = [st]
+    if scheduler is not None and hasattr(scheduler, "state_dict") and hasattr(scheduler, "load_state_dict"):
+        payload["lr_schedulers"] = [scheduler.state_dict()]
+    if loop is not None:
+        private.update(loop)
+        payload.setdefault("global_step", int(loop.get("steps", 0)))
+    if len(private) > 1:
+        private["philox"] = {name: {a: int(getattr(mod, a)) for a in _PHILOX_POSITIONS if hasattr(mod, a)}
+                             for name, mod in model.named_modules() if any(hasattr(mod, a) for a in _PHILOX_POSITIONS)}
+        payload[CKPT_KEY] = private
     payload.update(extra or {})
-    torch.save(payload, path)
+    tmp = f"{path}.tmp.{os.getpid()}"
+    try:
+        torch.save(payload, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def restore_training_state(ckpt: dict, model, optimizer, scheduler, log=print) -> Optional[dict]:
+    """Put a checkpoint dict (`checkpoint.read_checkpoint`) back into the module, the optimizer and the scheduler.  Returns
+    the private part of the file, or None for a file without it (one written by Lightning): then weights, moments,
+    scheduler, epoch and step are restored and `log` is told what was not."""
+    model.load_state_dict(ckpt["state_dict"], strict=True)
+    private = ckpt.get(CKPT_KEY)
+    if private is not None and private.get("format") != CKPT_FORMAT:
+        raise RuntimeError(f"checkpoint training state has format {private.get('format')}, this code reads {CKPT_FORMAT}")
+    states = ckpt.get("optimizer_states") or []
+    if states and hasattr(optimizer, "load_state_dict"):
+        if isinstance(optimizer, _Trainer):
+            pre, layout, order = _trainer_layout(model, optimizer)
+            m1, m2, step, group = adamw_state_from_torch(states[0], layout, order)
+            st = {"layout": optimizer.param_layout(), "exp_avg": m1, "exp_avg_sq": m2, "step": ckpt.get("global_step", step),
+                  "lr": group.get("lr", optimizer.lr), "betas": group.get("betas", optimizer.betas), "eps": group.get("eps", optimizer.eps),
+                  "weight_decay": group.get("weight_decay", optimizer.wd), "ema": None, "ema_decay": None}
+            if private is not None and "trainer" in private:
+                st.update(private["trainer"])
+                if private["trainer"].get("ema_decay") is not None:
+                    src = ckpt["ema_state_dict"]
+                    st["ema"] = torch.cat([src[name].reshape(-1).to(torch.float32) for name, _ in layout])
+            optimizer.load_state_dict(st)
+        else:
+            optimizer.load_state_dict(states[0])
+    scheds = ckpt.get("lr_schedulers") or []
+    if scheds and hasattr(scheduler, "load_state_dict"):
+        scheduler.load_state_dict(scheds[0])
+    if private is None:
+        log("checkpoint has no 'shapegen_amd' training state (a Lightning-written file): weights, optimizer moments, scheduler, epoch "
+            "and step are restored; loss scale, EMA weights, top-k list, loss history, Philox positions and RNG states are not")
+        return None
+    mods = dict(model.named_modules())
+    for name, positions in private.get("philox", {}).items():
+        for attr, off in positions.items():
+            if name in mods and attr in _PHILOX_POSITIONS:
+                setattr(mods[name], attr, int(off))
+    return private
 
 
 class _RankRng:
@@ -987,12 +1268,21 @@ class _RankRng:
 
 
 def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = None, log=print, max_steps: Optional[int] = None,
-        save_top_k: int = 10, ckpt_name: str = "point_cloud_diffusion"):
-    """What `pl.Trainer(max_epochs=...).fit(model, data_module)` does for the reference's train_point_ddpm.py:78-87 and
-    train_point_ldm.py:100-108: epochs of training_step + optimizer step, then validation_step over the validation
-    loader in eval() mode, the model's scheduler (plateau on `val_loss` / cosine per epoch), and the `save_top_k` best
-    checkpoints by val_loss (train_point_ddpm.py:60-66)."""
+        save_top_k: int = 10, ckpt_name: str = "point_cloud_diffusion", ckpt_path: Optional[str] = None, save_last: bool = False,
+        ema_decay: Optional[float] = None):
+    """What `pl.Trainer(max_epochs=...).fit(model, data_module, ckpt_path=...)` does for the reference's
+    train_point_ddpm.py:78-87 and train_point_ldm.py:84-108,144: epochs of training_step + optimizer step, then
+    validation_step over the validation loader in eval() mode, the model's scheduler (plateau on `val_loss` / cosine per
+    epoch), and the `save_top_k` best checkpoints by val_loss (train_point_ddpm.py:60-66).
+
+    `ckpt_path` continues a run at the epoch after the one the file was written in: module, optimizer, scheduler, loop
+    state and RNG states come from the file (after `data_module.setup()` has drawn its split under the caller's seed,
+    which must therefore be the first run's; a different split raises).  `save_last` also writes `<ckpt_name>-last.ckpt`
+    after every epoch.  `ema_decay` turns on the trainer's moving average of the weights (a resumed run takes the decay
+    from the file).  With several ranks, rank 0 writes: its `ckpt_dir` / `save_last` decide, the other ranks may pass none
+    (they only take part in gathering the per-rank random streams and histories when rank 0 saves)."""
     import inspect
+    import os
     if "max_epochs" in inspect.signature(model.configure_optimizers).parameters:
         cfg = model.configure_optimizers(max_epochs=max_epochs)
     else:
@@ -1023,10 +1313,63 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
         _collective_inplace(dist.broadcast, seed, 0)
         torch.manual_seed(int(seed.item()))
     rank_rng = _RankRng(model.device, rank) if world > 1 else contextlib.nullcontext()
+    if ema_decay is not None and hasattr(opt, "enable_ema"):
+        opt.enable_ema(ema_decay)              # after the broadcast: the average starts from rank 0's weights on every rank
     kept: List[Tuple[float, str]] = []
     steps = 0
     history = []
-    for epoch in range(max_epochs):
+    first_epoch = 0
+    split = split_fingerprint(data_module)
+    if ckpt_path is not None:
+        from .checkpoint import read_checkpoint
+        ckpt = read_checkpoint(ckpt_path)
+        private = restore_training_state(ckpt, model, opt, sched, log)
+        first_epoch = int(ckpt.get("epoch", -1)) + 1
+        steps = int(ckpt.get("global_step", 0))
+        if ckpt_dir is None:
+            ckpt_dir = os.path.dirname(os.path.abspath(ckpt_path))
+        if private is not None:
+            if split is not None and private.get("split") is not None and private["split"] != split:
+                raise RuntimeError(f"{ckpt_path}: the train / validation split of this data module differs from the one the checkpoint "
+                                   "was trained on (seed the process as the first run did before fit()): validation samples would "
+                                   "move into the training set")
+            kept = [(float(v), os.path.join(ckpt_dir, name)) for v, name in private.get("kept", [])]
+            steps, history = int(private.get("steps", steps)), [tuple(h) for h in private.get("history", [])]
+            if private.get("rng") is not None:
+                _rng_set(private["rng"], model.device)                # after setup(): the split above came from the caller's seed
+            streams = private.get("rank_rng") or []
+            if world > 1:
+                if len(streams) == world:
+                    rank_rng.mine = (streams[rank][0].cpu(), None if streams[rank][1] is None else streams[rank][1].cpu())
+                    history = [tuple(h) for h in private["rank_history"][rank]]
+                else:
+                    rank_rng = _RankRng(model.device, rank)       # reseeded from the restored shared stream
+                    log(f"resuming on {world} ranks a run saved on {max(len(streams), 1)}: the per-rank random streams are reseeded, "
+                        "the continuation is not bitwise the uninterrupted run")
+            elif len(streams) > 1:
+                log(f"resuming on 1 rank a run saved on {len(streams)}: the continuation is not bitwise the uninterrupted run")
+        if ema_decay is not None and hasattr(opt, "enable_ema") and getattr(opt, "EMA", None) is None:
+            opt.enable_ema(ema_decay)
+            log(f"{ckpt_path} holds no EMA weights: the average starts from the restored weights with decay {ema_decay}")
+        log(f"resumed from {ckpt_path}: continuing at epoch {first_epoch}, step {steps}, lr {getattr(opt, 'lr', float('nan')):.2e}")
+
+    saving = ckpt_dir is not None
+    if world > 1:                              # rank 0 writes, so its settings decide on every rank whether the gather below runs
+        flags = torch.tensor([int(saving), int(save_last)], dtype=torch.int64, device=model.device if dist.get_backend() == "nccl" else "cpu")
+        _collective_inplace(dist.broadcast, flags, 0)
+        saving, save_last = bool(flags[0].item()), bool(flags[1].item())
+
+    def loop_state():
+        """What the private checkpoint key records about this loop (every rank calls it: the rank streams are gathered)."""
+        streams = histories = None
+        if world > 1:                          # per rank: its private random stream and its own train losses
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, (tuple(None if t is None else t.cpu() for t in rank_rng.mine), list(history)))
+            streams, histories = [r[0] for r in per_rank], [r[1] for r in per_rank]
+        return {"kept": [(v, os.path.basename(p)) for v, p in kept], "steps": steps, "history": list(history), "max_epochs": max_epochs,
+                "world": world, "rng": _rng_get(model.device), "rank_rng": streams, "rank_history": histories, "split": split}
+
+    for epoch in range(first_epoch, max_epochs):
         if hasattr(model, "current_epoch"):
             model.current_epoch, model._max_epochs = epoch, max_epochs      # VAE3DLarge.get_kl_weight reads these
         model.train()
@@ -1061,17 +1404,27 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
         sched.step(val_loss)
         history.append((epoch, train_loss, val_loss, opt.lr))
         log(f"epoch {epoch}: train_loss {train_loss:.4f} val_loss {val_loss:.4f} lr {opt.lr:.2e}")
-        if ckpt_dir is not None and rank == 0:
-            import os
-            path = os.path.join(ckpt_dir, f"{ckpt_name}-epoch={epoch:02d}-val_loss={val_loss:.2f}.ckpt")
-            if len(kept) < save_top_k or val_loss < max(kept)[0]:
-                save_checkpoint(model, path, epoch)
+        if saving:
+            # every rank keeps the top-k list (val_loss is the same everywhere) and takes part in gathering the rank streams; rank 0 writes
+            path = os.path.join(ckpt_dir or "", f"{ckpt_name}-epoch={epoch:02d}-val_loss={val_loss:.2f}.ckpt")
+            enters = len(kept) < save_top_k or val_loss < max(kept)[0]
+            dropped = []
+            if enters:
                 kept.append((val_loss, path))
                 kept.sort()
-                for _, old in kept[save_top_k:]:
-                    if os.path.exists(old) and old != path:
+                dropped, kept = [old for _, old in kept[save_top_k:] if old != path], kept[:save_top_k]
+            if enters or save_last:
+                state = loop_state()
+                if rank == 0:
+                    if enters:
+                        save_checkpoint(model, path, epoch, optimizer=opt, scheduler=sched, loop=state)
+                    if save_last:
+                        save_checkpoint(model, os.path.join(ckpt_dir, f"{ckpt_name}-last.ckpt"), epoch, optimizer=opt, scheduler=sched,
+                                        loop=state)
+            if rank == 0:
+                for old in dropped:
+                    if os.path.exists(old):
                         os.remove(old)
-                kept = kept[:save_top_k]
         if max_steps is not None and steps >= max_steps:
             break
     return history

@@ -57,6 +57,14 @@ class VAETrainer(_Trainer):
         self._rows: Dict[str, tuple] = {}        # (tensor, rows last written) of the row-padded workspace tensors (`_rows_buf`)
         self.refresh_weights()
 
+    def state_dict(self):
+        """The base trainer's state plus the position in the Philox stream the reparameterisation noise is drawn from."""
+        return {**super().state_dict(), "eps_offset": getattr(self, "_eps_offset", 0)}
+
+    def load_state_dict(self, state) -> None:
+        super().load_state_dict(state)
+        self._eps_offset = int(state.get("eps_offset", getattr(self, "_eps_offset", 0)))
+
     # ------------------------------------------------------------------ structure
     def _program(self, prefix: str, prog, d0: int):
         ops, d = [], d0

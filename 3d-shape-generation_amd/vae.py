@@ -102,10 +102,10 @@ class VAE3DLarge(_HipModule):
         return self
 
     @classmethod
-    def load_from_checkpoint(cls, path, map_location="cpu", **kwargs):
+    def load_from_checkpoint(cls, path, map_location="cpu", weights="raw", **kwargs):
         """Lightning-free loader for the reference's `.ckpt` layout (test_point_ldm.py:156, train_point_ldm.py:191)."""
         from .checkpoint import load_lightning_checkpoint
-        hp, sd = load_lightning_checkpoint(path, map_location)
+        hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
         keys = ("input_shape", "latent_dim", "lr", "kl_warmup_epochs", "kl_warmup_max_beta", "kl_annealing_epochs")
         obj = cls(**{k: hp[k] for k in keys if k in hp})
@@ -373,9 +373,9 @@ class VAE3D(_HipModule):
         self._build_from_spec(specs.vae3d_small_spec(latent_dim))
 
     @classmethod
-    def load_from_checkpoint(cls, path, map_location="cpu", **kwargs):
+    def load_from_checkpoint(cls, path, map_location="cpu", weights="raw", **kwargs):
         from .checkpoint import load_lightning_checkpoint
-        hp, sd = load_lightning_checkpoint(path, map_location)
+        hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
         obj = cls(**{k: hp[k] for k in ("input_shape", "latent_dim", "beta") if k in hp})
         obj.load_state_dict(sd, strict=True)

@@ -827,6 +827,11 @@ int pcd_vae_latent_backward(const float* mu, const float* logvar, const float* e
 /* torch.optim.AdamW step on one flat fp32 buffer (diffusion.py:60: lr, weight_decay 1e-5); grads are divided by grad_scale */
 int pcd_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
+/* The same step (params, exp_avg, exp_avg_sq come out bitwise equal) and, in the same launch, the exponential moving
+ * average of the weights: ema[i] = ema_decay * ema[i] + (1 - ema_decay) * params_new[i]; ema_decay in [0, 1) */
+int pcd_adamw_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                       float ema_decay, void* stream);
 
 #ifdef __cplusplus
 }

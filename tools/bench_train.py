@@ -1,5 +1,6 @@
 """Dev tool: time one training step (forward + backward + AdamW) of the point denoiser at the reference's training
-configuration (batch 16 x 2048 points, train_point_ddpm.py:43-46) on one MI355X."""
+configuration (batch 16 x 2048 points, train_point_ddpm.py:43-46) on one MI355X.  EMA=0.999 in the environment times
+the step with the moving average of the weights kept in the AdamW launch."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,6 +12,8 @@ B, N = int(os.environ.get("B", 16)), int(os.environ.get("N", 2048))
 torch.manual_seed(0)
 model = PointCloudDiffusion(num_points=N).to("cuda")
 tr = PointTrainer(model.model, lr=1e-4)
+if os.environ.get("EMA"):
+    tr.enable_ema(float(os.environ["EMA"]))
 x0 = torch.randn(B, N, 3, device="cuda") * 0.4
 steps = int(os.environ.get("STEPS", 10))
 def one():
@@ -26,4 +29,4 @@ for _ in range(steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 flop = 3 * 42_615_552 * B * N          # literal forward count x (forward + backward-data + backward-weight)
-print(f"B={B} N={N}: {dt*1e3:.2f} ms/step  {1/dt:.1f} steps/s  {B/dt:.0f} shapes/s  ~{flop/dt/1e12:.0f} TFLOP/s dense-equivalent  loss {loss.item():.4f}")
+print(f"B={B} N={N} ema={tr.ema_decay}: {dt*1e3:.2f} ms/step  {1/dt:.1f} steps/s  {B/dt:.0f} shapes/s  ~{flop/dt/1e12:.0f} TFLOP/s dense-equivalent  loss {loss.item():.4f}")

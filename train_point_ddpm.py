@@ -4,11 +4,15 @@ Training runs on the HIP trainer (`shapegen_amd.training`): fp16 MFMA GEMMs for 
 BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoints by val_loss in the reference's
 `.ckpt` layout.
 
-    python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt resume.ckpt] [--max-steps N]
-                               [--backbone {pointnet,attention}]
+    python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt weights.ckpt] [--max-steps N]
+                               [--backbone {pointnet,attention}] [--resume last.ckpt] [--save-last] [--ema-decay D]
 
 `--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
-import); `--ckpt` resumes with the backbone stored in the checkpoint's hyper-parameters.
+import); `--ckpt` starts a new run from a checkpoint's weights (with the backbone stored in its hyper-parameters).
+`--resume` continues an interrupted run exactly: weights, optimizer moments, scheduler, epoch, top-k list and random
+streams come from the file, and checkpoints keep going into the directory the file lies in.  `--save-last` writes
+`point_cloud_diffusion-last.ckpt` after every epoch (the file to resume from); `--ema-decay` keeps an exponential moving
+average of the weights, saved next to the raw ones (`PointCloudDiffusion.load_from_checkpoint(path, weights="ema")`).
 
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
@@ -48,7 +52,11 @@ def synthetic_clouds(count: int, num_points: int, seed: int = 24) -> np.ndarray:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ckpt", default=None, help="reference-layout .ckpt to resume from")
+    ap.add_argument("--ckpt", default=None, help="reference-layout .ckpt whose weights start a new run (weights only: see --resume)")
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="continue the run that wrote this checkpoint: optimizer, scheduler, epoch, top-k list and RNG are restored")
+    ap.add_argument("--save-last", action="store_true", help="also write <name>-last.ckpt after every epoch")
+    ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the weights")
     ap.add_argument("--data-dir", default=os.path.join("data", "shape_net_voxel_data_v1"))
     ap.add_argument("--category", default="chair")
     ap.add_argument("--num-points", type=int, default=2048)
@@ -71,9 +79,9 @@ def main():
     else:
         logger.info(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic clouds")
         dm = _Unwrap(PointCloudDataModule(synthetic_clouds(args.synthetic_shapes, args.num_points), batch_size=args.batch_size))
-    if args.ckpt:
-        logger.info(f"Loading Diffusion model from checkpoint: {args.ckpt}")
-        model = PointCloudDiffusion.load_from_checkpoint(args.ckpt)
+    if args.ckpt or args.resume:
+        logger.info(f"Loading Diffusion model from checkpoint: {args.resume or args.ckpt}")
+        model = PointCloudDiffusion.load_from_checkpoint(args.resume or args.ckpt)
         assert model.num_points == args.num_points
         if model.backbone != args.backbone:
             logger.info(f"checkpoint backbone {model.backbone!r} is used (--backbone {args.backbone} ignored)")
@@ -81,8 +89,10 @@ def main():
         model = PointCloudDiffusion(num_points=args.num_points, backbone=args.backbone)
     model = model.to("cuda")
     logger.info("Starting Diffusion Training")
-    fit(model, dm, max_epochs=args.epochs, ckpt_dir=os.path.join("checkpoints", "point_ddpm", timestamp), log=logger.info,
-        max_steps=args.max_steps)
+    # a resumed run keeps writing where the file it resumed from lies: the restored top-k list prunes the files it names
+    ckpt_dir = os.path.dirname(os.path.abspath(args.resume)) if args.resume else os.path.join("checkpoints", "point_ddpm", timestamp)
+    fit(model, dm, max_epochs=args.epochs, ckpt_dir=ckpt_dir, log=logger.info, max_steps=args.max_steps, ckpt_path=args.resume,
+        save_last=args.save_last, ema_decay=args.ema_decay)
     model.eval()
     samples = model.sample(num_samples=10, num_points=args.num_points, num_steps=args.sample_steps)   # train_point_ddpm.py:91-93
     os.makedirs(args.out, exist_ok=True)
@@ -98,6 +108,7 @@ class _Unwrap:
 
     def setup(self):
         self.dm.setup()
+        self.train_dataset, self.val_dataset = self.dm.train_dataset, self.dm.val_dataset     # their index lists identify the split
 
     def train_dataloader(self):
         return (b[0] for b in self.dm.train_dataloader())

@@ -5,6 +5,12 @@ latent trainer (frozen VAE encode -> L1 loss -> AdamW + cosine schedule).
 
     python train_point_ldm.py [--vae-ckpt vae.ckpt | --train-vae-epochs N] [--diffusion-ckpt ldm.ckpt | --train-diffusion-epochs N]
                               [--data-dir DIR] [--category table] [--steps 1000]
+                              [--resume-vae last.ckpt | --resume last.ckpt] [--save-last] [--ema-decay D]
+
+`--vae-ckpt` / `--diffusion-ckpt` load weights only.  `--resume` continues an interrupted latent-diffusion training exactly
+(`--resume-vae` the VAE's): optimizer moments, scheduler, epoch, top-k list and random streams come from the file, and
+checkpoints keep going into the directory the file lies in.  `--save-last` writes `<name>-last.ckpt` after every epoch;
+`--ema-decay` keeps an exponential moving average of the latent denoiser's weights next to the raw ones.
 """
 from __future__ import annotations
 
@@ -22,8 +28,12 @@ from shapegen_amd.vae import VAE3DLarge as VAE
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--vae-ckpt", default=None)
-    ap.add_argument("--diffusion-ckpt", default=None)
+    ap.add_argument("--vae-ckpt", default=None, help="VAE weights (weights only)")
+    ap.add_argument("--diffusion-ckpt", default=None, help="latent-diffusion weights (weights only)")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="continue the latent-diffusion run that wrote this checkpoint")
+    ap.add_argument("--resume-vae", default=None, metavar="PATH", help="continue the VAE run that wrote this checkpoint")
+    ap.add_argument("--save-last", action="store_true", help="also write <name>-last.ckpt after every epoch")
+    ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the denoiser's weights")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--train-vae-epochs", type=int, default=0, help="train the voxel VAE first (train_point_ldm.py:24-79, `train_vae`)")
     ap.add_argument("--train-diffusion-epochs", type=int, default=0, help="0 = the reference default (perform_diffusion_training = False)")
@@ -35,8 +45,8 @@ def main():
     args = ap.parse_args()
     torch.manual_seed(24)
     is_voxel_based = True                                     # train_point_ldm.py:160: VAE3DLarge path
-    if args.vae_ckpt:
-        vae = VAE.load_from_checkpoint(args.vae_ckpt)
+    if args.vae_ckpt or args.resume_vae:
+        vae = VAE.load_from_checkpoint(args.resume_vae or args.vae_ckpt)
     else:
         vae = VAE()
         sd = specs.synth_state_dict(specs.vae3d_large_spec(256), seed=2, gain=1.3)
@@ -45,15 +55,17 @@ def main():
     vae = vae.to("cuda")
     if args.train_vae_epochs > 0:                            # train_point_ldm.py:24-79 (`train_vae`)
         from shapegen_amd.training import fit
-        fit(vae, _data_module(args), max_epochs=args.train_vae_epochs, ckpt_dir=os.path.join("checkpoints", "point_ldm", "vae"), ckpt_name="vae")
+        vae_dir = os.path.dirname(os.path.abspath(args.resume_vae)) if args.resume_vae else os.path.join("checkpoints", "point_ldm", "vae")
+        fit(vae, _data_module(args), max_epochs=args.train_vae_epochs, ckpt_dir=vae_dir, ckpt_name="vae", ckpt_path=args.resume_vae,
+            save_last=args.save_last)
     vae = vae.eval()
     os.makedirs(args.out, exist_ok=True)
     num_samples = 10
     samples_vae = vae.sample(num_samples=num_samples)                       # train_point_ldm.py:197
     np.savez_compressed(os.path.join(args.out, "vae_samples.npz"), **{f"sample_{i}": c.cpu().numpy() for i, c in enumerate(samples_vae)})
     print(f"Generated {num_samples} VAE samples")
-    if args.diffusion_ckpt:
-        diffusion = LatentDiffusion.load_from_checkpoint(args.diffusion_ckpt, vae=vae, is_voxel_based=is_voxel_based)
+    if args.diffusion_ckpt or args.resume:
+        diffusion = LatentDiffusion.load_from_checkpoint(args.resume or args.diffusion_ckpt, vae=vae, is_voxel_based=is_voxel_based)
     else:
         diffusion = LatentDiffusion(vae, is_voxel_based=is_voxel_based)
         lsd = specs.synth_state_dict(specs.latent_unet_spec(prefix="model."), seed=1, gain=1.3)
@@ -63,8 +75,10 @@ def main():
     diffusion = diffusion.to("cuda")
     if args.train_diffusion_epochs > 0:                      # train_point_ldm.py:81-110 (`train_diffusion`)
         from shapegen_amd.training import fit
-        fit(diffusion, _data_module(args), max_epochs=args.train_diffusion_epochs,
-            ckpt_dir=os.path.join("checkpoints", "point_ldm", "latent_diffusion"), ckpt_name="latent_diffusion")
+        ldm_dir = (os.path.dirname(os.path.abspath(args.resume)) if args.resume
+                   else os.path.join("checkpoints", "point_ldm", "latent_diffusion"))
+        fit(diffusion, _data_module(args), max_epochs=args.train_diffusion_epochs, ckpt_dir=ldm_dir, ckpt_name="latent_diffusion",
+            ckpt_path=args.resume, save_last=args.save_last, ema_decay=args.ema_decay)
     diffusion = diffusion.eval()
     samples = diffusion.sample(num_samples=num_samples, num_steps=args.steps)  # train_point_ldm.py:222
     np.savez_compressed(os.path.join(args.out, "latent_diffusion_samples.npz"), **{f"sample_{i}": c.cpu().numpy() for i, c in enumerate(samples)})
