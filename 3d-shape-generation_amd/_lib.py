@@ -306,6 +306,9 @@ _SIGS = {
     "pcd_vae_latent_backward": (i32, [vp, vp, vp, vp, i64, f32, vp, vp, vp, vp]),
     "pcd_adamw_step": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "pcd_adamw_ema_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp]),
+    "pcd_grad_norm_f32": (i32, [vp, i64, f32, f32, i32, f32, f32, vp, vp]),
+    "pcd_adamw_guarded_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp]),
+    "pcd_grad_accumulate_f32": (i32, [vp, vp, i64, i32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -777,6 +777,18 @@ __global__ void vae_latent_bwd_kernel(const float* mu, const float* lv, const fl
 // expression tree, so the parameters and moments they produce are bitwise equal.
 struct AdamwArgs { float lr, b1, b2, eps, wd, bc1, bc2, inv_scale, decay; };
 
+// The gradient guard's device state block: 16 32-bit words, layout documented in include/pcd_hip.h (PCD_GUARD_*).
+struct GuardState {
+    float norm;        // 0: norm of the unscaled gradient of the last pcd_grad_norm_f32 call
+    int apply;         // 1: 1 = the step is taken, 0 = a non-finite gradient, the step is dropped
+    float coef;        // 2: clip coefficient min(1, max_norm / (norm + 1e-6))
+    float inv_scale;   // 3: (1 / grad_scale) * coef
+    float bc1, bc2;    // 4, 5: AdamW's bias corrections for this step
+    int applied, skipped, clipped;   // 6, 7, 8: running counters
+    int reserved[7];
+};
+static_assert(sizeof(GuardState) == 64, "the guard state block is 16 words");
+
 template <bool EMA>
 __device__ __forceinline__ void adamw_element(float& w, const float g, float& m1, float& m2, float& e, const AdamwArgs& a) {
     // The arithmetic pcd_adamw_step has always had, pinned: the decay term is one fused multiply-add, both moments are two
@@ -794,9 +806,16 @@ __device__ __forceinline__ void adamw_element(float& w, const float g, float& m1
 
 // VEC: lane i owns the four consecutive floats [4 i, 4 i + 4) (16-byte loads and stores; the buffers are 16-byte aligned),
 // lane n / 4 the n % 4 tail elements one by one.  Not VEC: one element per lane (buffers of any alignment).
-template <bool EMA, bool VEC>
+// GUARD: the launch obeys the device state block that pcd_grad_norm_f32 has just written (include/pcd_hip.h): with its apply
+// flag at 0 every block returns before it reads or writes a parameter, a moment or the average, otherwise inv_scale, bc1
+// and bc2 are taken from the block; the element update is the same expression tree.
+template <bool EMA, bool VEC, bool GUARD>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2,
-                             float* __restrict__ ema, int64_t n, AdamwArgs a) {
+                             float* __restrict__ ema, int64_t n, AdamwArgs a, const GuardState* __restrict__ guard) {
+    if (GUARD) {
+        if (guard->apply == 0) return;
+        a.inv_scale = guard->inv_scale; a.bc1 = guard->bc1; a.bc2 = guard->bc2;
+    }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (VEC) {
         const int64_t n4 = n / 4;
@@ -828,6 +847,126 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         adamw_element<EMA>(w, g[i], m, v, e, a);
         p[i] = w; m1[i] = m; m2[i] = v;
         if (EMA) ema[i] = e;
+    }
+}
+
+// Gradient norm + non-finite scan of a flat fp32 buffer, stage 1.  The grid is fixed by n alone (at most GN_BLOCKS blocks
+// of 256 lanes, grid-stride), every lane adds its squares in double in a fixed order, the wave and block sums are fixed
+// trees: partial[block] is a function of the data only.  bad[block] != 0 iff one of its elements has all exponent bits set
+// (tested on the bits: no floating-point flag can fold it away).  VEC as in adamw_kernel: 16-byte loads, lane n / 4 of the
+// conceptual lane sequence takes the n % 4 tail.
+constexpr int GN_BLOCKS = 1024;
+
+__device__ __forceinline__ void gn_take(const float x, double& s, unsigned& bad) {
+    bad |= (unsigned)((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u);
+    const double d = (double)x;
+    s = __builtin_fma(d, d, s);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partial,
+                                                                unsigned* __restrict__ bad_out) {
+    const int64_t lanes = (int64_t)gridDim.x * blockDim.x;
+    double s = 0.0;
+    unsigned bad = 0u;
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        for (; i + 3 * lanes < n4; i += 4 * lanes) {          // four independent loads in flight; the adds keep the lane's order
+            const float4* q = reinterpret_cast<const float4*>(g) + i;
+            const float4 v0 = q[0], v1 = q[lanes], v2 = q[2 * lanes], v3 = q[3 * lanes];
+            gn_take(v0.x, s, bad); gn_take(v0.y, s, bad); gn_take(v0.z, s, bad); gn_take(v0.w, s, bad);
+            gn_take(v1.x, s, bad); gn_take(v1.y, s, bad); gn_take(v1.z, s, bad); gn_take(v1.w, s, bad);
+            gn_take(v2.x, s, bad); gn_take(v2.y, s, bad); gn_take(v2.z, s, bad); gn_take(v2.w, s, bad);
+            gn_take(v3.x, s, bad); gn_take(v3.y, s, bad); gn_take(v3.z, s, bad); gn_take(v3.w, s, bad);
+        }
+        for (; i <= n4; i += lanes) {
+            if (i < n4) {
+                const float4 v = reinterpret_cast<const float4*>(g)[i];
+                gn_take(v.x, s, bad); gn_take(v.y, s, bad); gn_take(v.z, s, bad); gn_take(v.w, s, bad);
+            } else {
+                for (int64_t j = n4 * 4; j < n; ++j) gn_take(g[j], s, bad);
+            }
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += lanes) gn_take(g[i], s, bad);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_down(s, off, 64);
+        bad |= __shfl_down(bad, off, 64);
+    }
+    __shared__ double ws[4];
+    __shared__ unsigned wb[4];
+    if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = s; wb[threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+        bad_out[blockIdx.x] = wb[0] | wb[1] | wb[2] | wb[3];
+    }
+}
+
+// Stage 2, one block: the block partials are added in index order by one lane (no atomics: bitwise repeatable), then that
+// lane prepares the step: norm, apply flag, clip coefficient, effective inverse scale, counters and bias corrections.
+// bc1_host / bc2_host are the corrections the host forms for `step`; they are used as they are while no step has been
+// skipped (an armed guard that never fires leaves the run bitwise unchanged), afterwards AdamW's step is step - skipped.
+__global__ __launch_bounds__(256) void grad_prepare_kernel(const double* __restrict__ partial, const unsigned* __restrict__ bad_in,
+                                                           int blocks, double grad_scale, float inv_scale, float max_norm, int step,
+                                                           float b1, float b2, float bc1_host, float bc2_host,
+                                                           GuardState* __restrict__ st) {
+    __shared__ double sp[GN_BLOCKS];
+    unsigned bad = 0u;
+    for (int i = threadIdx.x; i < blocks; i += blockDim.x) { sp[i] = partial[i]; bad |= bad_in[i]; }
+    const int any_bad = __syncthreads_or((int)bad);
+    if (threadIdx.x != 0) return;
+    double sumsq = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < blocks; ++i) sumsq += sp[i];          // (unrolled: the LDS reads run ahead of the dependent adds)
+    const float norm = (float)(sqrt(sumsq) / grad_scale);
+    int applied = st->applied, skipped = st->skipped, clipped = st->clipped;
+    float coef = 0.f;
+    if (any_bad) {
+        ++skipped;
+    } else {
+        coef = 1.0f;
+        if (max_norm > 0.f) {
+            const float c = max_norm / (norm + 1e-6f);          // torch.nn.utils.clip_grad_norm_
+            if (c < 1.0f) { coef = c; ++clipped; }
+        }
+        ++applied;
+    }
+    float bc1 = bc1_host, bc2 = bc2_host;
+    if (skipped > 0) {                  // a skipped step does not advance AdamW's step
+        const float t = (float)(step - skipped);
+        bc1 = 1.f - powf(b1, t);
+        bc2 = 1.f - powf(b2, t);
+    }
+    st->norm = norm;
+    st->apply = any_bad ? 0 : 1;
+    st->coef = coef;
+    st->inv_scale = inv_scale * coef;
+    st->bc1 = bc1; st->bc2 = bc2;
+    st->applied = applied; st->skipped = skipped; st->clipped = clipped;
+}
+
+// acc = g (first) or acc += g: the gradient accumulation buffer of the trainers.  VEC as in adamw_kernel.
+template <bool VEC>
+__global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n, int first) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        if (i < n4) {
+            float4 v = reinterpret_cast<const float4*>(g)[i];
+            if (!first) {
+                const float4 a = reinterpret_cast<const float4*>(acc)[i];
+                v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w;
+            }
+            reinterpret_cast<float4*>(acc)[i] = v;
+        } else if (i == n4) {
+            for (int64_t j = n4 * 4; j < n; ++j) acc[j] = first ? g[j] : acc[j] + g[j];
+        }
+    } else {
+        if (i >= n) return;
+        acc[i] = first ? g[i] : acc[i] + g[i];
     }
 }
 
@@ -1024,19 +1163,25 @@ extern "C" int pcd_silu_backward_f32(const float* x, const float* dy, int64_t n,
     return PCD_OK;
 }
 
+template <bool EMA, bool GUARD>
+static void adamw_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, const AdamwArgs& a,
+                         const GuardState* guard, void* stream) {
+    const uintptr_t bits = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema;
+    if ((bits & 15) == 0)          // n / 4 vector lanes and one lane for the tail
+        hipLaunchKernelGGL((adamw_kernel<EMA, true, GUARD>), dim3(nblk256(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                           exp_avg, exp_avg_sq, ema, n, a, guard);
+    else
+        hipLaunchKernelGGL((adamw_kernel<EMA, false, GUARD>), dim3(nblk256(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                           exp_avg_sq, ema, n, a, guard);
+}
+
 template <bool EMA>
 static void adamw_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
                          float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_decay,
                          void* stream) {
     const AdamwArgs a = {lr, beta1, beta2, eps, weight_decay, 1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step),
                          1.f / grad_scale, ema_decay};
-    const uintptr_t bits = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema;
-    if ((bits & 15) == 0)          // n / 4 vector lanes and one lane for the tail
-        hipLaunchKernelGGL((adamw_kernel<EMA, true>), dim3(nblk256(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, ema, n, a);
-    else
-        hipLaunchKernelGGL((adamw_kernel<EMA, false>), dim3(nblk256(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, ema, n, a);
+    adamw_launch<EMA, false>(params, grads, exp_avg, exp_avg_sq, ema, n, a, nullptr, stream);
 }
 
 extern "C" int pcd_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -1053,6 +1198,56 @@ extern "C" int pcd_adamw_ema_step(float* params, const float* grads, float* exp_
     PCD_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && ema && n > 0 && step >= 1 && grad_scale > 0.f);
     PCD_CHECK_ARG(ema_decay >= 0.f && ema_decay < 1.f);
     adamw_launch<true>(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ema_decay, stream);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_grad_norm_f32(const float* grads, int64_t n, float grad_scale, float max_norm, int step, float beta1, float beta2,
+                                 void* state, void* stream) {
+    PCD_CHECK_ARG(grads && state && n > 0 && grad_scale > 0.f && step >= 1);
+    const bool vec = ((uintptr_t)grads & 15) == 0;
+    int64_t blocks = ceil_div(vec ? n / 4 + 1 : n, 256);
+    if (blocks > GN_BLOCKS) blocks = GN_BLOCKS;
+    // GN_BLOCKS doubles, then GN_BLOCKS flags
+    float* ws = reduce_workspace((size_t)GN_BLOCKS * 3);
+    if (ws == nullptr) {
+        set_error("%s:%d: no device memory for the reduction workspace", __FILE__, __LINE__);
+        return PCD_ERR_WORKSPACE;
+    }
+    double* partial = reinterpret_cast<double*>(ws);
+    unsigned* bad = reinterpret_cast<unsigned*>(ws + 2 * GN_BLOCKS);
+    hipStream_t s = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL((grad_norm_partial_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, grads, n, partial, bad);
+    else
+        hipLaunchKernelGGL((grad_norm_partial_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, grads, n, partial, bad);
+    hipLaunchKernelGGL(grad_prepare_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, (const unsigned*)bad, (int)blocks,
+                       (double)grad_scale, 1.f / grad_scale, max_norm, step, beta1, beta2, 1.f - powf(beta1, (float)step),
+                       1.f - powf(beta2, (float)step), (GuardState*)state);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_adamw_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                                      const void* state, void* stream) {
+    PCD_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && state && n > 0);
+    PCD_CHECK_ARG(ema == nullptr || (ema_decay >= 0.f && ema_decay < 1.f));
+    const AdamwArgs a = {lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, 0.f, ema_decay};      // bc1, bc2, inv_scale: from the state block
+    if (ema != nullptr)
+        adamw_launch<true, true>(params, grads, exp_avg, exp_avg_sq, ema, n, a, (const GuardState*)state, stream);
+    else
+        adamw_launch<false, true>(params, grads, exp_avg, exp_avg_sq, nullptr, n, a, (const GuardState*)state, stream);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_grad_accumulate_f32(float* acc, const float* grads, int64_t n, int first, void* stream) {
+    PCD_CHECK_ARG(acc && grads && n > 0);
+    if ((((uintptr_t)acc | (uintptr_t)grads) & 15) == 0)
+        hipLaunchKernelGGL((grad_accumulate_kernel<true>), dim3(nblk256(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, acc, grads, n, first);
+    else
+        hipLaunchKernelGGL((grad_accumulate_kernel<false>), dim3(nblk256(n)), dim3(256), 0, (hipStream_t)stream, acc, grads, n, first);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }

@@ -112,6 +112,12 @@ class _Trainer:
         self.step_count = 0
         self.EMA: Optional[torch.Tensor] = None    # flat fp32 moving average of P, kept by the optimizer launch (`enable_ema`)
         self.ema_decay: Optional[float] = None
+        self.guard = False                         # `set_gradient_guard`: norm + non-finite scan in front of a guarded AdamW
+        self.clip_norm: Optional[float] = None
+        self.guard_state: Optional[torch.Tensor] = None     # the device state block of include/pcd_hip.h (16 int32 words)
+        self.accum = 1                             # `set_accumulation`: micro-batches per optimizer step
+        self.A: Optional[torch.Tensor] = None      # flat fp32 sum of the micro-batches' G
+        self._micro = 0                            # micro-batches in A
         # ---- one flat fp32 buffer for parameters, one for gradients, two for the AdamW moments
         self.P, self.G, self.M1, self.M2, self.p, self.g = _flatten_parameters(model, self.dev)
         self.names = list(self.p)                  # the trained parameters (subclasses may add aliases to p and g)
@@ -263,18 +269,102 @@ class _Trainer:
             self.EMA = self.P.clone()
         self.ema_decay = decay
 
+    def set_gradient_guard(self, clip_norm: Optional[float] = None, skip_nonfinite: bool = False) -> None:
+        """Arm (or, with the defaults, disarm) the guard in front of the optimizer.  Armed, every `optimizer_step` takes
+        the norm of the gradient buffer on the device (`pcd_grad_norm_f32`: after the all-reduce, so it is the norm of the
+        mean gradient and the same on every rank) and the AdamW launch obeys what that found without a host round trip:
+        a step whose gradient holds a NaN or an infinity is dropped whole (parameters, moments and EMA untouched, AdamW's
+        step not advanced), and with `clip_norm` the gradient is scaled by min(1, clip_norm / (norm + 1e-6)) as
+        `torch.nn.utils.clip_grad_norm_` does.  Clipping implies skipping.  Unarmed, the step is the plain launch.
+        Arming allocates the device state block and writes its counters (not for use inside a step): every step so far
+        counts as applied.  Disarming folds the skipped steps out of `step_count` and drops the block, so the clipped /
+        skipped history does not survive a later re-arming; changing the settings of an armed guard keeps the counters."""
+        clip = None if clip_norm is None else float(clip_norm)
+        if clip is not None and not clip > 0.0:
+            raise ValueError(f"clip_norm must be positive, got {clip_norm}")
+        armed = clip is not None or bool(skip_nonfinite)
+        if armed and self.guard_state is None:
+            self.guard_state = torch.zeros(16, dtype=torch.int32, device=self.dev)
+            self._set_guard_counters(self.step_count, 0, 0)    # applied + skipped stays the number of steps so far
+        if not armed and self.guard_state is not None:
+            self.step_count -= self.guard_stats()["skipped"]   # the plain launch forms its bias corrections from step_count
+            self.guard_state = None
+        self.guard, self.clip_norm = armed, clip
+
+    def _set_guard_counters(self, applied: int, skipped: int, clipped: int, last_norm: float = 0.0) -> None:
+        words = torch.zeros(16, dtype=torch.int32)
+        words[:1].view(torch.float32)[0] = last_norm
+        words[6], words[7], words[8] = applied, skipped, clipped
+        self.guard_state.copy_(words)
+
+    def guard_stats(self) -> dict:
+        """{applied, skipped, clipped, last_norm} of the guard: the one place that reads the device state block (it waits
+        for the device).  Unarmed: every step so far counts as applied and last_norm is None."""
+        if self.guard_state is None:
+            return {"applied": self.step_count, "skipped": 0, "clipped": 0, "last_norm": None}
+        h = self.guard_state.cpu()
+        return {"applied": int(h[6]), "skipped": int(h[7]), "clipped": int(h[8]), "last_norm": float(h[:1].view(torch.float32)[0])}
+
+    def set_accumulation(self, k: int) -> None:
+        """Take one optimizer step per k micro-batches: `micro_step` adds each micro-batch's G into a second flat buffer A
+        and steps on A at the k-th (or at `flush`), with the gradient scale loss_scale * world * k (every micro-loss
+        counts 1/k, also in a partial flush)."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"accumulation needs k >= 1, got {k}")
+        if self._micro:
+            raise RuntimeError("set_accumulation with micro-batches pending: flush() first")
+        self.accum = k
+        if k > 1 and self.A is None:
+            self.A = torch.zeros_like(self.G)
+        if k == 1:
+            self.A = None
+
+    def micro_step(self) -> bool:
+        """What follows every backward: the optimizer step itself without accumulation, else one more micro-batch into A
+        and the optimizer step when it is the k-th.  Returns whether the optimizer stepped."""
+        if self.accum == 1:
+            self.optimizer_step()
+            return True
+        self._chk(self.lib.pcd_grad_accumulate_f32(self.A.data_ptr(), self.G.data_ptr(), self.G.numel(), int(self._micro == 0), self._st()),
+                  "grad_accumulate")
+        self._micro += 1
+        if self._micro < self.accum:
+            return False
+        self.optimizer_step()
+        return True
+
+    def flush(self) -> bool:
+        """The optimizer step on the micro-batches accumulated so far, if any (the end of an epoch)."""
+        if self._micro == 0:
+            return False
+        self.optimizer_step()
+        return True
+
     def optimizer_step(self):
-        self.step_count += 1
         b1, b2 = self.betas
-        world = _allreduce_gradients(self.G)           # data parallel: mean gradient over the ranks (BatchNorm stays per rank)
-        if self.EMA is None:
-            self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+        grad, scale = self.G, self.loss_scale
+        if self.accum > 1:
+            if self._micro == 0:
+                raise RuntimeError("optimizer_step under accumulation without a micro-batch: call micro_step() after each backward")
+            grad, scale, self._micro = self.A, scale * self.accum, 0
+        self.step_count += 1
+        scale *= _allreduce_gradients(grad)            # data parallel: mean gradient over the ranks (BatchNorm stays per rank)
+        if self.guard:
+            self._chk(self.lib.pcd_grad_norm_f32(grad.data_ptr(), grad.numel(), scale, self.clip_norm or 0.0, self.step_count, b1, b2,
+                                                 self.guard_state.data_ptr(), self._st()), "grad_norm")
+            self._chk(self.lib.pcd_adamw_guarded_step(self.P.data_ptr(), grad.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+                                                      None if self.EMA is None else self.EMA.data_ptr(), self.P.numel(), self.lr,
+                                                      b1, b2, self.eps, self.wd, self.ema_decay or 0.0, self.guard_state.data_ptr(),
+                                                      self._st()), "adamw_guarded")
+        elif self.EMA is None:
+            self._chk(self.lib.pcd_adamw_step(self.P.data_ptr(), grad.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
                                               self.P.numel(), self.lr, b1, b2, self.eps, self.wd, self.step_count,
-                                              self.loss_scale * world, self._st()), "adamw")
+                                              scale, self._st()), "adamw")
         else:
-            self._chk(self.lib.pcd_adamw_ema_step(self.P.data_ptr(), self.G.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
+            self._chk(self.lib.pcd_adamw_ema_step(self.P.data_ptr(), grad.data_ptr(), self.M1.data_ptr(), self.M2.data_ptr(),
                                                   self.EMA.data_ptr(), self.P.numel(), self.lr, b1, b2, self.eps, self.wd,
-                                                  self.step_count, self.loss_scale * world, self.ema_decay, self._st()), "adamw_ema")
+                                                  self.step_count, scale, self.ema_decay, self._st()), "adamw_ema")
         self.refresh_weights()
 
     # torch.optim-like aliases so the object can stand where the reference's optimizer does
@@ -290,10 +380,16 @@ class _Trainer:
 
     def state_dict(self):
         """Everything the optimizer carries from step to step besides the parameters themselves (those, and BatchNorm's
-        running statistics, travel in the module's `state_dict()`).  The tensors are the live device buffers."""
-        return {"step": self.step_count, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
-                "loss_scale": self.loss_scale, "exp_avg": self.M1, "exp_avg_sq": self.M2, "ema": self.EMA,
-                "ema_decay": self.ema_decay, "layout": self.param_layout()}
+        running statistics, travel in the module's `state_dict()`).  The tensors are the live device buffers.  The keys
+        `guard` (settings and counters of an armed gradient guard) and `accumulate` are there only when in use."""
+        st = {"step": self.step_count, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
+              "loss_scale": self.loss_scale, "exp_avg": self.M1, "exp_avg_sq": self.M2, "ema": self.EMA,
+              "ema_decay": self.ema_decay, "layout": self.param_layout()}
+        if self.guard:             # `step` counts every optimizer step, dropped ones too: AdamW's own step is guard["applied"]
+            st["guard"] = {"clip_norm": self.clip_norm, **self.guard_stats()}
+        if self.accum > 1:
+            st["accumulate"] = self.accum
+        return st
 
     def load_state_dict(self, state) -> None:
         """Inverse of `state_dict()`.  The parameter layout (names and sizes in flat order) must be this trainer's."""
@@ -320,6 +416,15 @@ class _Trainer:
                 raise RuntimeError(f"EMA buffer has {ema.numel()} elements, the flat parameter buffer {self.P.numel()}")
             self.enable_ema(state["ema_decay"])
             self.EMA.copy_(ema.reshape(-1).to(self.dev, torch.float32))
+        guard = state.get("guard")
+        if guard is not None:
+            self.set_gradient_guard(guard.get("clip_norm"), True)
+            self._set_guard_counters(int(guard["applied"]), int(guard["skipped"]), int(guard["clipped"]), float(guard.get("last_norm") or 0.0))
+        elif self.guard:           # a state without the key (an unarmed run, or a file from before the guard) into an armed trainer:
+            self._set_guard_counters(self.step_count, 0, 0)    # the settings stay, and every step of that run was applied
+        if state.get("accumulate") is not None:
+            self._micro = 0
+            self.set_accumulation(int(state["accumulate"]))
         self.refresh_weights()
 
     def ema_state_dict(self) -> Dict[str, torch.Tensor]:
@@ -629,7 +734,7 @@ class PointTrainer(_Trainer):
     def train_step(self, x_t: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
         self.forward(x_t, t, update_stats=True)
         loss = self.backward(noise)
-        self.optimizer_step()
+        self.micro_step()
         return loss
 
 
@@ -742,7 +847,7 @@ class LatentTrainer(_Trainer):
     def train_step(self, z_t, t, noise, dropout_mask=None) -> torch.Tensor:
         self.forward(z_t, t, dropout_mask)
         loss = self.backward(noise)
-        self.optimizer_step()
+        self.micro_step()
         return loss
 
 
@@ -1156,7 +1261,8 @@ def save_checkpoint(model, path: str, epoch: int, extra: Optional[dict] = None, 
     which `PointCloudDiffusion.load_from_checkpoint` of either code base reads back.  With `optimizer` / `scheduler` /
     `loop` it also carries what a run needs to continue: `global_step`, `optimizer_states` (torch.optim.AdamW's own
     layout, indexed like the module's `parameters()`), `lr_schedulers`, `ema_state_dict` and, under the private key
-    `shapegen_amd`, the loss scale, EMA decay, loop state, Philox positions and RNG states.  `hyper_parameters` is never
+    `shapegen_amd`, the loss scale, EMA decay, gradient-guard settings and counters, loop state, Philox positions and RNG
+    states.  `hyper_parameters` is never
     extended: the reference's loader hands it to the constructor.  The file is written to a temporary name in the same
     directory and renamed over `path`."""
     import os
@@ -1170,7 +1276,8 @@ def save_checkpoint(model, path: str, epoch: int, extra: Optional[dict] = None, 
         if isinstance(optimizer, _Trainer):
             pre, layout, order = _trainer_layout(model, optimizer)
             payload["global_step"] = int(st["step"])
-            payload["optimizer_states"] = [adamw_state_to_torch(st["exp_avg"].cpu(), st["exp_avg_sq"].cpu(), st["step"], layout, order,
+            adam_step = st["guard"]["applied"] if "guard" in st else st["step"]     # torch's step: dropped steps do not count
+            payload["optimizer_states"] = [adamw_state_to_torch(st["exp_avg"].cpu(), st["exp_avg_sq"].cpu(), adam_step, layout, order,
                                                                 st["lr"], st["betas"], st["eps"], st["weight_decay"])]
             private["trainer"] = {k: v for k, v in st.items() if k not in ("exp_avg", "exp_avg_sq", "ema")}
             if st["ema"] is not None:
@@ -1269,7 +1376,8 @@ class _RankRng:
 
 def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = None, log=print, max_steps: Optional[int] = None,
         save_top_k: int = 10, ckpt_name: str = "point_cloud_diffusion", ckpt_path: Optional[str] = None, save_last: bool = False,
-        ema_decay: Optional[float] = None):
+        ema_decay: Optional[float] = None, gradient_clip_val: Optional[float] = None, accumulate_grad_batches: int = 1,
+        skip_nonfinite: bool = False):
     """What `pl.Trainer(max_epochs=...).fit(model, data_module, ckpt_path=...)` does for the reference's
     train_point_ddpm.py:78-87 and train_point_ldm.py:84-108,144: epochs of training_step + optimizer step, then
     validation_step over the validation loader in eval() mode, the model's scheduler (plateau on `val_loss` / cosine per
@@ -1279,7 +1387,13 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
     state and RNG states come from the file (after `data_module.setup()` has drawn its split under the caller's seed,
     which must therefore be the first run's; a different split raises).  `save_last` also writes `<ckpt_name>-last.ckpt`
     after every epoch.  `ema_decay` turns on the trainer's moving average of the weights (a resumed run takes the decay
-    from the file).  With several ranks, rank 0 writes: its `ckpt_dir` / `save_last` decide, the other ranks may pass none
+    from the file).  `gradient_clip_val`, `accumulate_grad_batches` and `skip_nonfinite` are Lightning's
+    `pl.Trainer(gradient_clip_val=..., accumulate_grad_batches=...)` (norm clipping) and the trainer's non-finite step
+    guard (`set_gradient_guard`, `set_accumulation`): an optimizer step every k usable micro-batches and once more at the
+    epoch's last one, `max_steps` and `global_step` count optimizer steps.  On resume, a file that carries guard settings
+    or an accumulation count (it was written by a run that used them) decides them, like the EMA decay; for a file without
+    them the caller's arguments stay in force, and the guard starts with every step of the file counted as applied.
+    With several ranks, rank 0 writes: its `ckpt_dir` / `save_last` decide, the other ranks may pass none
     (they only take part in gathering the per-rank random streams and histories when rank 0 saves)."""
     import inspect
     import os
@@ -1315,6 +1429,13 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
     rank_rng = _RankRng(model.device, rank) if world > 1 else contextlib.nullcontext()
     if ema_decay is not None and hasattr(opt, "enable_ema"):
         opt.enable_ema(ema_decay)              # after the broadcast: the average starts from rank 0's weights on every rank
+    if gradient_clip_val is not None or skip_nonfinite or accumulate_grad_batches != 1:
+        if not isinstance(opt, _Trainer):
+            raise RuntimeError("gradient_clip_val / accumulate_grad_batches / skip_nonfinite need the model's optimizer to be a HIP trainer")
+        opt.set_gradient_guard(gradient_clip_val, skip_nonfinite)
+        opt.set_accumulation(accumulate_grad_batches)
+    micro_step = opt.micro_step if isinstance(opt, _Trainer) else (lambda: opt.step() or True)
+    flush = opt.flush if isinstance(opt, _Trainer) else (lambda: False)
     kept: List[Tuple[float, str]] = []
     steps = 0
     history = []
@@ -1385,11 +1506,14 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
             group = []
             with rank_rng:
                 loss = model.training_step(batch, i)
-            opt.step()
             tl.append(loss)
+            if not micro_step():
+                continue                       # accumulating: the optimizer steps at the k-th micro-batch
             steps += 1
             if max_steps is not None and steps >= max_steps:
                 break
+        if flush():                            # the epoch's last micro-batches, fewer than k; validation comes after it
+            steps += 1
         model.eval()
         vl = []
         for i, b in enumerate(data_module.val_dataloader()):
@@ -1403,7 +1527,11 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
             val_loss = float(v.item()) / world
         sched.step(val_loss)
         history.append((epoch, train_loss, val_loss, opt.lr))
-        log(f"epoch {epoch}: train_loss {train_loss:.4f} val_loss {val_loss:.4f} lr {opt.lr:.2e}")
+        line = f"epoch {epoch}: train_loss {train_loss:.4f} val_loss {val_loss:.4f} lr {opt.lr:.2e}"
+        if getattr(opt, "guard", False):
+            gs = opt.guard_stats()
+            line += f" grad_norm {gs['last_norm']:.3e} clipped {gs['clipped']} skipped {gs['skipped']}"
+        log(line)
         if saving:
             # every rank keeps the top-k list (val_loss is the same everywhere) and takes part in gathering the rank streams; rank 0 writes
             path = os.path.join(ckpt_dir or "", f"{ckpt_name}-epoch={epoch:02d}-val_loss={val_loss:.2f}.ckpt")

@@ -369,5 +369,5 @@ class VAETrainer(_Trainer):
     def train_step(self, x, kl_weight: float, eps=None):
         self.forward(x, eps)
         out = self.backward(kl_weight)
-        self.optimizer_step()
+        self.micro_step()
         return out

@@ -833,6 +833,38 @@ int pcd_adamw_ema_step(float* params, const float* grads, float* exp_avg, float*
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                        float ema_decay, void* stream);
 
+/* ------------------------------------------------ gradient guard: norm, non-finite scan, clipping, skipped steps, accumulation
+ * None of these synchronises the stream or copies to the host; what the guard decides stays on the device, in a state
+ * block of 16 32-bit words (64 bytes, 4-byte aligned, zero-filled by the caller before first use) that only
+ * these two entry points write and read:
+ *   word 0  float  norm       norm of the unscaled gradient seen by the last pcd_grad_norm_f32
+ *   word 1  int    apply      1: the step is taken; 0: a gradient element was non-finite, the step is dropped
+ *   word 2  float  coef       clip coefficient min(1, max_norm / (norm + 1e-6)); exactly 1.0f without clipping, 0 when dropped
+ *   word 3  float  inv_scale  (1.f / grad_scale) * coef: what the guarded AdamW multiplies the gradients by
+ *   word 4  float  bc1        AdamW's bias corrections 1 - beta^t for this step (see below)
+ *   word 5  float  bc2
+ *   word 6  int    applied    running count of steps taken
+ *   word 7  int    skipped    running count of steps dropped
+ *   word 8  int    clipped    running count of steps taken with coef < 1
+ *   words 9-15     reserved (left as they are)
+ * The caller may preset the counters (resuming a run); it keeps applied + skipped equal to `step` - 1 before a call. */
+/* One pass over grads[n] (16-byte loads when the pointer is 16-byte aligned, else one element per lane; launch geometry
+ * fixed by n): the squares are summed in double, block partials are added in index order by one block (no atomics: the
+ * result is bitwise repeatable), an element whose exponent bits are all ones makes the buffer non-finite.  The same
+ * block then writes the state block: norm = sqrt(sum) / grad_scale formed in double and rounded to fp32 once; apply;
+ * coef (max_norm <= 0: no clipping); inv_scale; the counters.  A dropped step does not advance AdamW's step: while
+ * skipped == 0 the bias corrections are the host's 1.f - powf(beta, (float)step), exactly those of pcd_adamw_step for
+ * that step, afterwards they are recomputed on the device for t = step - skipped. */
+int pcd_grad_norm_f32(const float* grads, int64_t n, float grad_scale, float max_norm, int step, float beta1, float beta2,
+                      void* state, void* stream);
+/* pcd_adamw_step / pcd_adamw_ema_step (ema may be NULL; the same element update, bitwise) taking inv_scale, bc1, bc2 and
+ * the apply flag from the state block: with apply == 0 nothing is read or written besides the block */
+int pcd_adamw_guarded_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                           const void* state, void* stream);
+/* acc[i] = grads[i] if first, else acc[i] + grads[i]  (gradient accumulation over micro-batches) */
+int pcd_grad_accumulate_f32(float* acc, const float* grads, int64_t n, int first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

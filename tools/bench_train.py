@@ -1,6 +1,7 @@
 """Dev tool: time one training step (forward + backward + AdamW) of the point denoiser at the reference's training
 configuration (batch 16 x 2048 points, train_point_ddpm.py:43-46) on one MI355X.  EMA=0.999 in the environment times
-the step with the moving average of the weights kept in the AdamW launch."""
+the step with the moving average of the weights kept in the AdamW launch; GUARD=1 arms the gradient guard (norm + non-finite
+scan in front of the guarded AdamW launch), CLIP=<norm> arms it with clipping to that norm."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,6 +15,8 @@ model = PointCloudDiffusion(num_points=N).to("cuda")
 tr = PointTrainer(model.model, lr=1e-4)
 if os.environ.get("EMA"):
     tr.enable_ema(float(os.environ["EMA"]))
+if os.environ.get("GUARD") or os.environ.get("CLIP"):
+    tr.set_gradient_guard(float(os.environ["CLIP"]) if os.environ.get("CLIP") else None, skip_nonfinite=True)
 x0 = torch.randn(B, N, 3, device="cuda") * 0.4
 steps = int(os.environ.get("STEPS", 10))
 def one():
@@ -29,4 +32,5 @@ for _ in range(steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 flop = 3 * 42_615_552 * B * N          # literal forward count x (forward + backward-data + backward-weight)
-print(f"B={B} N={N} ema={tr.ema_decay}: {dt*1e3:.2f} ms/step  {1/dt:.1f} steps/s  {B/dt:.0f} shapes/s  ~{flop/dt/1e12:.0f} TFLOP/s dense-equivalent  loss {loss.item():.4f}")
+guard = f" guard={tr.guard_stats()}" if tr.guard else ""
+print(f"B={B} N={N} ema={tr.ema_decay}{guard}: {dt*1e3:.2f} ms/step  {1/dt:.1f} steps/s  {B/dt:.0f} shapes/s  ~{flop/dt/1e12:.0f} TFLOP/s dense-equivalent  loss {loss.item():.4f}")

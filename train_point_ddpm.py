@@ -6,6 +6,7 @@ BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoint
 
     python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt weights.ckpt] [--max-steps N]
                                [--backbone {pointnet,attention}] [--resume last.ckpt] [--save-last] [--ema-decay D]
+                               [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
 
 `--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
 import); `--ckpt` starts a new run from a checkpoint's weights (with the backbone stored in its hyper-parameters).
@@ -13,6 +14,9 @@ import); `--ckpt` starts a new run from a checkpoint's weights (with the backbon
 streams come from the file, and checkpoints keep going into the directory the file lies in.  `--save-last` writes
 `point_cloud_diffusion-last.ckpt` after every epoch (the file to resume from); `--ema-decay` keeps an exponential moving
 average of the weights, saved next to the raw ones (`PointCloudDiffusion.load_from_checkpoint(path, weights="ema")`).
+`--grad-clip` and `--accumulate-grad-batches` are `pl.Trainer(gradient_clip_val=..., accumulate_grad_batches=...)`;
+`--skip-nonfinite` (implied by `--grad-clip`) drops an optimizer step whose gradient holds a NaN or an infinity.  The epoch
+log line then carries the last gradient norm and the clipped / skipped counts.
 
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
@@ -57,6 +61,9 @@ def main():
                     help="continue the run that wrote this checkpoint: optimizer, scheduler, epoch, top-k list and RNG are restored")
     ap.add_argument("--save-last", action="store_true", help="also write <name>-last.ckpt after every epoch")
     ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the weights")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="NORM", help="clip the gradient's L2 norm (pl.Trainer(gradient_clip_val=...))")
+    ap.add_argument("--accumulate-grad-batches", type=int, default=1, metavar="K", help="one optimizer step per K batches")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="drop an optimizer step whose gradient holds a NaN or an infinity")
     ap.add_argument("--data-dir", default=os.path.join("data", "shape_net_voxel_data_v1"))
     ap.add_argument("--category", default="chair")
     ap.add_argument("--num-points", type=int, default=2048)
@@ -92,7 +99,8 @@ def main():
     # a resumed run keeps writing where the file it resumed from lies: the restored top-k list prunes the files it names
     ckpt_dir = os.path.dirname(os.path.abspath(args.resume)) if args.resume else os.path.join("checkpoints", "point_ddpm", timestamp)
     fit(model, dm, max_epochs=args.epochs, ckpt_dir=ckpt_dir, log=logger.info, max_steps=args.max_steps, ckpt_path=args.resume,
-        save_last=args.save_last, ema_decay=args.ema_decay)
+        save_last=args.save_last, ema_decay=args.ema_decay, gradient_clip_val=args.grad_clip,
+        accumulate_grad_batches=args.accumulate_grad_batches, skip_nonfinite=args.skip_nonfinite)
     model.eval()
     samples = model.sample(num_samples=10, num_points=args.num_points, num_steps=args.sample_steps)   # train_point_ddpm.py:91-93
     os.makedirs(args.out, exist_ok=True)

@@ -6,11 +6,14 @@ latent trainer (frozen VAE encode -> L1 loss -> AdamW + cosine schedule).
     python train_point_ldm.py [--vae-ckpt vae.ckpt | --train-vae-epochs N] [--diffusion-ckpt ldm.ckpt | --train-diffusion-epochs N]
                               [--data-dir DIR] [--category table] [--steps 1000]
                               [--resume-vae last.ckpt | --resume last.ckpt] [--save-last] [--ema-decay D]
+                              [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
 
 `--vae-ckpt` / `--diffusion-ckpt` load weights only.  `--resume` continues an interrupted latent-diffusion training exactly
 (`--resume-vae` the VAE's): optimizer moments, scheduler, epoch, top-k list and random streams come from the file, and
 checkpoints keep going into the directory the file lies in.  `--save-last` writes `<name>-last.ckpt` after every epoch;
 `--ema-decay` keeps an exponential moving average of the latent denoiser's weights next to the raw ones.
+`--grad-clip`, `--accumulate-grad-batches` and `--skip-nonfinite` (gradient-norm clipping, one optimizer step per K batches,
+dropping a step with a non-finite gradient) apply to both trainings.
 """
 from __future__ import annotations
 
@@ -34,6 +37,9 @@ def main():
     ap.add_argument("--resume-vae", default=None, metavar="PATH", help="continue the VAE run that wrote this checkpoint")
     ap.add_argument("--save-last", action="store_true", help="also write <name>-last.ckpt after every epoch")
     ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the denoiser's weights")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="NORM", help="clip the gradient's L2 norm (pl.Trainer(gradient_clip_val=...))")
+    ap.add_argument("--accumulate-grad-batches", type=int, default=1, metavar="K", help="one optimizer step per K batches")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="drop an optimizer step whose gradient holds a NaN or an infinity")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--train-vae-epochs", type=int, default=0, help="train the voxel VAE first (train_point_ldm.py:24-79, `train_vae`)")
     ap.add_argument("--train-diffusion-epochs", type=int, default=0, help="0 = the reference default (perform_diffusion_training = False)")
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--synthetic-shapes", type=int, default=160)
     ap.add_argument("--out", default=os.path.join("samples", "point_ldm"))
     args = ap.parse_args()
+    guard = dict(gradient_clip_val=args.grad_clip, accumulate_grad_batches=args.accumulate_grad_batches, skip_nonfinite=args.skip_nonfinite)
     torch.manual_seed(24)
     is_voxel_based = True                                     # train_point_ldm.py:160: VAE3DLarge path
     if args.vae_ckpt or args.resume_vae:
@@ -57,7 +64,7 @@ def main():
         from shapegen_amd.training import fit
         vae_dir = os.path.dirname(os.path.abspath(args.resume_vae)) if args.resume_vae else os.path.join("checkpoints", "point_ldm", "vae")
         fit(vae, _data_module(args), max_epochs=args.train_vae_epochs, ckpt_dir=vae_dir, ckpt_name="vae", ckpt_path=args.resume_vae,
-            save_last=args.save_last)
+            save_last=args.save_last, **guard)
     vae = vae.eval()
     os.makedirs(args.out, exist_ok=True)
     num_samples = 10
@@ -78,7 +85,7 @@ def main():
         ldm_dir = (os.path.dirname(os.path.abspath(args.resume)) if args.resume
                    else os.path.join("checkpoints", "point_ldm", "latent_diffusion"))
         fit(diffusion, _data_module(args), max_epochs=args.train_diffusion_epochs, ckpt_dir=ldm_dir, ckpt_name="latent_diffusion",
-            ckpt_path=args.resume, save_last=args.save_last, ema_decay=args.ema_decay)
+            ckpt_path=args.resume, save_last=args.save_last, ema_decay=args.ema_decay, **guard)
     diffusion = diffusion.eval()
     samples = diffusion.sample(num_samples=num_samples, num_steps=args.steps)  # train_point_ldm.py:222
     np.savez_compressed(os.path.join(args.out, "latent_diffusion_samples.npz"), **{f"sample_{i}": c.cpu().numpy() for i, c in enumerate(samples)})
