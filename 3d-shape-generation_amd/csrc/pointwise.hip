@@ -1,7 +1,7 @@
 // Elementwise / small kernels of the sampler path (all HBM- or latency-bound):
 //   time embedding + time_mlp + hoisted enc1 time bias (K3), enc1 xyz half (K=3),
 //   output head (C=3), add/remove noise and DDIM/DDPM updates (K4), Philox normals (K5),
-//   fp32<->fp16 converts.
+//   fp32<->fp16 converts, the row update of shape completion.
 #include "common.h"
 
 namespace pcd {
@@ -212,10 +212,8 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
     c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
 
-__global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 outputs per thread
-    if (q * 4 >= n) return;
-    const uint64_t ctr = (uint64_t)q + offset;
+// Philox4x32-10 on counter `ctr` + Box-Muller: the 4 standard normals of one counter
+__device__ __forceinline__ void philox_normals4(uint64_t ctr, uint64_t seed, float (&v)[4]) {
     uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
@@ -223,7 +221,6 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
         philox_round(c, k0, k1);
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    float v[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
@@ -234,6 +231,14 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
         v[2 * h] = r * cs;
         v[2 * h + 1] = r * sn;
     }
+}
+
+__global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 outputs per thread
+    if (q * 4 >= n) return;
+    const uint64_t ctr = (uint64_t)q + offset;
+    float v[4];
+    philox_normals4(ctr, seed, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (q * 4 + e < n) out[q * 4 + e] = v[e];
@@ -326,17 +331,18 @@ __global__ __launch_bounds__(256) void reparam_kernel(const float* __restrict__ 
 #pragma clang fp contract(fast)
 
 // Device-side step selection so that ONE captured HIP graph can be replayed for every timestep:
-// k = counter[0]; copy row k of the time-bias table and column k of the four rate tables to fixed
-// buffers; counter[1] = k (for consumers later in the step); counter[0] = k + 1.
+// k = counter[0]; copy row k of the time-bias table and column k of the `cols` rate tables (four for the
+// samplers, seven for a completion row) to fixed buffers; counter[1] = k (for consumers later in the step);
+// counter[0] = k + 1.
 __global__ __launch_bounds__(256) void step_select_kernel(int* __restrict__ counter, int n_steps,
                                                            const float* __restrict__ tb_table, int tb_elems,
                                                            float* __restrict__ tb_cur,
-                                                           const float* __restrict__ rate_tables, int width,
+                                                           const float* __restrict__ rate_tables, int cols, int width,
                                                            float* __restrict__ rates_cur) {
     int k = counter[0];
     k = k < n_steps ? k : n_steps - 1;
     for (int i = threadIdx.x; i < tb_elems; i += blockDim.x) tb_cur[i] = tb_table[(int64_t)k * tb_elems + i];
-    for (int i = threadIdx.x; i < 4 * width; i += blockDim.x) {
+    for (int i = threadIdx.x; i < cols * width; i += blockDim.x) {
         const int tbl = i / width, j = i - tbl * width;
         rates_cur[i] = rate_tables[((int64_t)tbl * n_steps + k) * width + j];
     }
@@ -350,24 +356,8 @@ __global__ __launch_bounds__(256) void randn_step_kernel(float* __restrict__ out
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q * 4 >= n) return;
     const uint64_t ctr = (uint64_t)q + base + stride * (uint64_t)counter[1];
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
     float v[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float r = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.28318530717958647692f * u2, &sn, &cs);
-        v[2 * h] = r * cs;
-        v[2 * h + 1] = r * sn;
-    }
+    philox_normals4(ctr, seed, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (q * 4 + e < n) out[q * 4 + e] = v[e];
@@ -537,24 +527,8 @@ __global__ __launch_bounds__(256) void ddpm_update_philox_kernel(const float* __
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q * 4 >= total) return;
     const uint64_t ctr = (uint64_t)q + base + pstride * (uint64_t)counter[1];
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
     float v[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float r = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.28318530717958647692f * u2, &sn, &cs);
-        v[2 * h] = r * cs;
-        v[2 * h + 1] = r * sn;
-    }
+    philox_normals4(ctr, seed, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int64_t i = q * 4 + e;
@@ -569,9 +543,15 @@ __global__ __launch_bounds__(256) void ddpm_update_philox_kernel(const float* __
 
 extern "C" int pcd_step_select(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_cur,
                                const float* rate_tables, int width, float* rates_cur, void* stream) {
+    return pcd_step_select_cols(counter, n_steps, tb_table, tb_elems, tb_cur, rate_tables, 4, width, rates_cur, stream);
+}
+
+extern "C" int pcd_step_select_cols(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_cur,
+                                    const float* rate_tables, int cols, int width, float* rates_cur, void* stream) {
     PCD_CHECK_ARG(counter && tb_table && tb_cur && rate_tables && rates_cur && n_steps > 0 && tb_elems > 0 && width > 0);
+    PCD_CHECK_ARG(cols > 0 && cols <= 16);
     hipLaunchKernelGGL(step_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, counter, n_steps, tb_table,
-                       tb_elems, tb_cur, rate_tables, width, rates_cur);
+                       tb_elems, tb_cur, rate_tables, cols, width, rates_cur);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
@@ -592,6 +572,158 @@ extern "C" int pcd_randn_step(float* out, int64_t n, uint64_t seed, uint64_t bas
     PCD_CHECK_ARG(out && counter && n > 0);
     hipLaunchKernelGGL(randn_step_kernel, dim3(nblk(ceil_div(n, 4))), dim3(256), 0, (hipStream_t)stream, out, n, seed,
                        base_offset, per_step_stride, counter);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+// ------------------------------------------------------------ shape completion
+// One row of `PointCloudDiffusion.complete`: the DDPM step of sample2 on the rows a shape does not know, the known points noised
+// forward to the step's time on the rows it does, then (rows that carry one) the RePaint forward jump of the whole cloud.
+// rates = the row's seven per-shape scalars [7][width]: n, s, coef, s_prev, n_prev, ja, jb (ja = 0 marks a row without a jump).
+// A shape knows its first counts[shape] rows of `row_elems` floats.  Expression order follows tests/completion_statement.py.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void complete_elem(float xv, float ev, float zv, float pv, bool known, float nb, float sb, float cb,
+                                              float s2b, float n2b, bool next, float& x0, float& xn) {
+    ddpm_elem(xv, ev, zv, nb, sb, cb, s2b, next, x0, xn);      // unknown rows: bitwise pcd_ddpm_update
+    if (known) {
+        if (next) {
+            const float a = s2b * pv;
+            const float c = n2b * zv;
+            xn = a + c;
+        } else {
+            x0 = pv;                                           // last row: the known points as given
+        }
+    }
+}
+
+__device__ __forceinline__ float jump_elem(float xv, float z2v, float ja, float jb) {
+    const float a = ja * xv;
+    const float c = jb * z2v;
+    return a + c;
+}
+
+// start state: known rows of x (the start draw) become s * p + n * x
+__global__ __launch_bounds__(256) void complete_start_kernel(float* x, const float* __restrict__ p,
+                                                              const int* __restrict__ counts, const float* __restrict__ n,
+                                                              const float* __restrict__ s, int stride, int64_t total,
+                                                              int64_t per_shape, int row_elems) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t sh = i / per_shape;
+    if ((i - sh * per_shape) / row_elems >= counts[sh]) return;
+    const int64_t b = sh * stride;
+    const float a = s[b] * p[i];
+    const float c = n[b] * x[i];
+    x[i] = a + c;
+}
+
+// x and xn may be the same buffer (every element is read before it is written by the one thread that owns it)
+__global__ __launch_bounds__(256) void complete_update_kernel(const float* x, const float* __restrict__ eps,
+                                                               const float* __restrict__ z, const float* __restrict__ z2,
+                                                               const float* __restrict__ p, const int* __restrict__ counts,
+                                                               const float* __restrict__ rates, int width, int stride,
+                                                               int64_t total, int64_t per_shape, int row_elems,
+                                                               float* __restrict__ x0o, float* xn) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t sh = i / per_shape;
+    const int64_t b = sh * stride;
+    const bool known = (i - sh * per_shape) / row_elems < counts[sh];
+    const bool next = xn != nullptr;
+    float x0, xv;
+    complete_elem(x[i], eps[i], next ? z[i] : 0.f, known ? p[i] : 0.f, known, rates[b], rates[width + b], rates[2 * width + b],
+                  rates[3 * width + b], rates[4 * width + b], next, x0, xv);
+    if (x0o != nullptr) x0o[i] = x0;
+    if (next) {
+        if (z2 != nullptr) {
+            const float ja = rates[5 * width + b];
+            if (ja != 0.f) xv = jump_elem(xv, z2[i], ja, rates[6 * width + b]);
+        }
+        xn[i] = xv;
+    }
+}
+#pragma clang fp contract(fast)
+
+// The same row with its normal draws generated in place (thread = 4 consecutive elements = one Philox counter, as in
+// ddpm_update_philox_kernel): z from counter base + pstride * row + element / 4, and -- only in a run with jumps, and only on a row
+// that carries one -- z2 from that counter + z2_off.  Neither is stored.
+__global__ __launch_bounds__(256) void complete_update_philox_kernel(const float* x, const float* __restrict__ eps,
+                                                                      const float* __restrict__ p, const int* __restrict__ counts,
+                                                                      const float* __restrict__ rates, int width, int stride,
+                                                                      int64_t total, int64_t per_shape, int row_elems, int jumps,
+                                                                      float* __restrict__ x0o, float* xn, uint64_t seed,
+                                                                      uint64_t base, uint64_t pstride, uint64_t z2_off,
+                                                                      const int* __restrict__ counter) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q * 4 >= total) return;
+    const bool next = xn != nullptr;
+    const uint64_t ctr = (uint64_t)q + base + pstride * (uint64_t)counter[1];
+    float v[4] = {0.f, 0.f, 0.f, 0.f}, v2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (next) philox_normals4(ctr, seed, v);
+    // the 4 elements of a thread can straddle two shapes (per-shape rates): draw z2 when either end jumps
+    bool any_jump = false;
+    if (next && jumps) {
+        const int64_t last = q * 4 + 3 < total ? q * 4 + 3 : total - 1;
+        any_jump = rates[5 * width + (q * 4 / per_shape) * stride] != 0.f || rates[5 * width + (last / per_shape) * stride] != 0.f;
+        if (any_jump) philox_normals4(ctr + z2_off, seed, v2);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t i = q * 4 + e;
+        if (i >= total) break;
+        const int64_t sh = i / per_shape;
+        const int64_t b = sh * stride;
+        const bool known = (i - sh * per_shape) / row_elems < counts[sh];
+        float x0, xv;
+        complete_elem(x[i], eps[i], v[e], known ? p[i] : 0.f, known, rates[b], rates[width + b], rates[2 * width + b],
+                      rates[3 * width + b], rates[4 * width + b], next, x0, xv);
+        if (x0o != nullptr) x0o[i] = x0;
+        if (next) {
+            if (any_jump) {
+                const float ja = rates[5 * width + b];
+                if (ja != 0.f) xv = jump_elem(xv, v2[e], ja, rates[6 * width + b]);
+            }
+            xn[i] = xv;
+        }
+    }
+}
+
+extern "C" int pcd_complete_start(float* x, const float* p, const int* counts, const float* n, const float* s, int stride,
+                                  int64_t total, int64_t per_shape, int row_elems, void* stream) {
+    PCD_CHECK_ARG(x && p && counts && n && s && total > 0 && per_shape > 0 && row_elems > 0 && (stride == 0 || stride == 1));
+    PCD_CHECK_ARG(total % per_shape == 0 && per_shape % row_elems == 0);
+    hipLaunchKernelGGL(complete_start_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, p, counts, n, s, stride,
+                       total, per_shape, row_elems);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_complete_update(const float* x, const float* eps, const float* z, const float* z2, const float* p,
+                                   const int* counts, const float* rates, int width, int stride, int64_t total,
+                                   int64_t per_shape, int row_elems, float* x0, float* x_next, void* stream) {
+    PCD_CHECK_ARG(x && eps && p && counts && rates && width > 0 && total > 0 && per_shape > 0 && row_elems > 0);
+    PCD_CHECK_ARG(total % per_shape == 0 && per_shape % row_elems == 0);
+    PCD_CHECK_ARG(stride == 0 || (stride == 1 && width == total / per_shape));
+    PCD_CHECK_ARG(x0 != nullptr || x_next != nullptr);
+    PCD_CHECK_ARG(x_next == nullptr || z != nullptr);
+    hipLaunchKernelGGL(complete_update_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, eps, z, z2, p, counts,
+                       rates, width, stride, total, per_shape, row_elems, x0, x_next);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_complete_update_philox(const float* x, const float* eps, const float* p, const int* counts,
+                                          const float* rates, int width, int stride, int64_t total, int64_t per_shape,
+                                          int row_elems, int jumps, float* x0, float* x_next, uint64_t seed,
+                                          uint64_t base_offset, uint64_t per_step_stride, uint64_t z2_offset,
+                                          const int* counter, void* stream) {
+    PCD_CHECK_ARG(x && eps && p && counts && rates && counter && width > 0 && total > 0 && per_shape > 0 && row_elems > 0);
+    PCD_CHECK_ARG(total % per_shape == 0 && per_shape % row_elems == 0);
+    PCD_CHECK_ARG(stride == 0 || (stride == 1 && width == total / per_shape));
+    PCD_CHECK_ARG(x0 != nullptr || x_next != nullptr);
+    hipLaunchKernelGGL(complete_update_philox_kernel, dim3(nblk(ceil_div(total, 4))), dim3(256), 0, (hipStream_t)stream, x, eps,
+                       p, counts, rates, width, stride, total, per_shape, row_elems, jumps, x0, x_next, seed, base_offset,
+                       per_step_stride, z2_offset, counter);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }

@@ -45,11 +45,14 @@ class StepTable:
     shape shares the rates (cosine schedule), R = batch for the linear schedule whose
     batch-axis cumprod (diffusion.py:202) gives each shape its own rates."""
 
+    @staticmethod
+    def _col(rows, device):
+        if isinstance(rows, torch.Tensor):                         # already (T, R): the vectorised cosine tables
+            return rows.to(torch.float32).reshape(rows.shape[0], -1).contiguous().to(device)
+        return torch.stack([torch.as_tensor(x, dtype=torch.float32).reshape(-1) for x in rows]).contiguous().to(device)
+
     def __init__(self, t, n, s, a, b, device):
-        def f(rows):
-            if isinstance(rows, torch.Tensor):                     # already (T, R): the vectorised cosine tables
-                return rows.to(torch.float32).reshape(rows.shape[0], -1).contiguous().to(device)
-            return torch.stack([torch.as_tensor(x, dtype=torch.float32).reshape(-1) for x in rows]).contiguous().to(device)
+        f = lambda rows: self._col(rows, device)
         if isinstance(t, torch.Tensor):
             t = t.reshape(t.shape[0], -1)[:, :1]
         else:
@@ -62,6 +65,47 @@ class StepTable:
 
     def offset(self, k: int) -> int:
         return 4 * k * self.width
+
+    def columns(self) -> List[torch.Tensor]:
+        """The per-step rate tables in the order the update kernels read them."""
+        return [self.n, self.s, self.a, self.b]
+
+
+def completion_rows(num_steps: int, jump: int, resample: int) -> List[Tuple[int, Optional[int]]]:
+    """The walk of `complete` over time indices, one entry per network evaluation: (i, None) steps from i to i - 1;
+    (i, to) steps to i - 1 and is then thrown forward to index `to` = i - 1 + jump.  RePaint's schedule: every index in
+    range(0, T - jump, jump) is left `resample - 1` times by a jump before the walk passes it."""
+    left = {k: resample - 1 for k in range(0, num_steps - jump, jump)} if resample > 1 else {}
+    rows, i = [], num_steps - 1
+    while i > 0:
+        lands = i - 1
+        if left.get(lands, 0) > 0:
+            left[lands] -= 1
+            rows.append((i, lands + jump))
+            i = lands + jump
+        else:
+            rows.append((i, None))
+            i = lands
+    rows.append((0, None))
+    return rows
+
+
+class CompletionTable(StepTable):
+    """StepTable of `complete`: the DDPM columns plus n_prev (known rows) and the forward jump ja, jb (0, 0 on a row without
+    one).  `draws[k]` is the index of row k's first normal draw in consumption order; a jump row uses `draws[k] + 1` too."""
+
+    def __init__(self, rows, t, n, s, a, b, n2, ja, jb, device):
+        super().__init__(t, n, s, a, b, device)
+        self.n2, self.ja, self.jb = (self._col(c, device) for c in (n2, ja, jb))
+        self.rows = rows
+        self.jumps = any(to is not None for _, to in rows)
+        self.draws, j = [], 0
+        for _, to in rows:
+            self.draws.append(j)
+            j += 1 if to is None else 2
+
+    def columns(self) -> List[torch.Tensor]:
+        return [self.n, self.s, self.a, self.b, self.n2, self.ja, self.jb]
 
 
 class _DiffusionBase(nn.Module):
@@ -232,6 +276,47 @@ class _DiffusionBase(nn.Module):
                 n2.append(torch.zeros(())); s2.append(torch.zeros(()))
         return StepTable(ts, ns, ss, n2, s2, self.device)
 
+    def completion_table(self, num_steps: int, jump: int = 10, resample: int = 1, batch: int = 1) -> CompletionTable:
+        """`complete`: one row per network evaluation (`completion_rows`).  n, s, a, b are `ddpm_table`'s at the row's index i,
+        n_prev goes with s_prev, and a row that jumps to index `to` carries ja = s(to/T) / s_prev, jb = sqrt(1 - ja^2), formed in
+        float64 and rounded once (exact for the cosine schedule, s^2 + n^2 = 1); ja = jb = 0 marks a row without a jump."""
+        w = self._width(batch)
+        T = num_steps
+        rows = completion_rows(T, jump, resample)
+        L = len(rows)
+        if w == 1 and self.vectorized_tables:
+            i = torch.tensor([r[0] for r in rows], dtype=torch.float32)
+            t = torch.ones(L) * i / T
+            n, s = self._host_schedule(t)
+            npv, sp = self._host_schedule(torch.ones(L) * (i - 1) / T)
+            co = torch.sqrt(npv / n)
+            to = torch.tensor([r[0] if r[1] is None else r[1] for r in rows], dtype=torch.float32)
+            _, sb = self._host_schedule(torch.ones(L) * to / T)
+            ja = sb.double() / sp.double()
+            jb = torch.sqrt(1 - ja * ja)
+            has = torch.tensor([r[1] is not None for r in rows])
+            ja, jb = torch.where(has, ja.float(), torch.zeros(L)), torch.where(has, jb.float(), torch.zeros(L))
+            co[-1], sp[-1], npv[-1] = 0.0, 0.0, 0.0                 # i = 0: the result is x_0, no update
+            return CompletionTable(rows, t, n, s, co, sp, npv, ja, jb, self.device)
+        ts, ns, ss, co, s2, n2, jas, jbs = [], [], [], [], [], [], [], []
+        for i, to in rows:
+            t = torch.ones(w) * i / T
+            n, s = self._host_schedule(t)
+            ts.append(t); ns.append(n); ss.append(s)
+            ja, jb = torch.zeros(w), torch.zeros(w)
+            if i > 0:
+                npv, sp = self._host_schedule(torch.ones(w) * (i - 1) / T)
+                co.append(torch.sqrt(npv / n)); s2.append(sp); n2.append(npv)
+                if to is not None:
+                    _, sb = self._host_schedule(torch.ones(w) * to / T)
+                    ja = sb.double() / sp.double()
+                    jb = torch.sqrt(1 - ja * ja).float()
+                    ja = ja.float()
+            else:
+                co.append(torch.zeros(w)); s2.append(torch.zeros(w)); n2.append(torch.zeros(w))
+            jas.append(ja); jbs.append(jb)
+        return CompletionTable(rows, ts, ns, ss, co, s2, n2, jas, jbs, self.device)
+
     vectorized_tables = True     # False: per-step host loop (the literal transcription; kept for the equality test)
 
     # ------------------------------------------------------------------ stepping
@@ -240,11 +325,12 @@ class _DiffusionBase(nn.Module):
     use_graphs = True          # 100 us latent step was launch-bound at one step per graph)
 
     def _run(self, x, tab: "StepTable", bias_table: torch.Tensor, forward, kind: str, noises=None,
-             skip_last_update: bool = False):
-        """kind 'ddim' | 'ddpm'.  forward(x, tb_cur, eps_out) enqueues the denoiser for the current step."""
-        stp = Stepper(self, x, tab, bias_table, forward, kind, noises)
+             skip_last_update: bool = False, known=None):
+        """kind 'ddim' | 'ddpm' | 'complete' (`known` = (p, counts) on the device, `tab` a CompletionTable).
+        forward(x, tb_cur, eps_out) enqueues the denoiser for the current step."""
+        stp = Stepper(self, x, tab, bias_table, forward, kind, noises, known)
         T = tab.steps
-        last_updates = not (skip_last_update or kind == "ddpm")     # ddpm: x_t = x_0 at i = 0, no update
+        last_updates = not (skip_last_update or kind in ("ddpm", "complete"))     # ddpm: x_t = x_0 at i = 0, no update
         n_uniform = T if last_updates else T - 1                       # steps that all look the same
         k = 0
         if self.use_graphs and noises is None and n_uniform - 1 >= self.GRAPH_MIN_STEPS:
@@ -264,7 +350,7 @@ class _DiffusionBase(nn.Module):
                 k += 1
         if k < T:
             stp.step(k, False)
-        if kind == "ddpm":
+        if kind in ("ddpm", "complete"):
             self._philox_offset = stp.philox_start + stp.philox_stride * T
         return stp.x0
 
@@ -275,36 +361,47 @@ class Stepper:
     same enqueue is valid for every k.  Long runs capture it once in a HIP graph and replay it (host
     cost per step: one graph launch instead of ~30 kernel launches)."""
 
-    def __init__(self, owner, x, tab: StepTable, bias_table, forward, kind, noises=None):
+    def __init__(self, owner, x, tab: StepTable, bias_table, forward, kind, noises=None, known=None):
         self.lib = _lib.load()
         self.x, self.tab, self.forward, self.kind, self.noises = x, tab, forward, kind, noises
         dev = x.device
         self.T, self.R = tab.steps, tab.width
-        self.rates = torch.stack([tab.n, tab.s, tab.a, tab.b]).contiguous()      # (4, T, R)
+        self.rates = torch.stack(tab.columns()).contiguous()                     # (4, T, R); (7, T, R) for 'complete'
+        self.cols = self.rates.shape[0]
         self.bias_table = bias_table.contiguous()
         self.tb_elems = self.bias_table.shape[1]
         self.counter = torch.zeros(2, dtype=torch.int32, device=dev)
         self.tb_cur = torch.empty(self.tb_elems, dtype=torch.float32, device=dev)
-        self.rates_cur = torch.empty(4 * self.R, dtype=torch.float32, device=dev)
+        self.rates_cur = torch.empty(self.cols * self.R, dtype=torch.float32, device=dev)
         self.eps = torch.empty_like(x)
         self.x0 = torch.empty_like(x)
-        self.z = torch.empty_like(x) if kind == "ddpm" else None
+        self.z = torch.empty_like(x) if kind == "ddpm" or (kind == "complete" and noises is not None) else None
         self.per_shape = x.numel() // x.shape[0]
         self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         shard_off, span = owner._philox_span(x.numel(), x.shape[0])
         self.philox_start = getattr(owner, "_philox_offset", 0)        # the owner's stream position before this run
         self.philox_base = self.philox_start + shard_off              # this process's sub-block of every draw
         self.philox_stride = span                                     # counters one (global) draw consumes
+        if kind == "complete":
+            self.p, self.counts = known
+            self.row_elems = x.shape[-1]
+            self.z2 = torch.empty_like(x) if noises is not None and tab.jumps else None
+            # a run with jumps gives EVERY row two spans (z, then z2: unused where the row has no jump), so one captured
+            # step fits all rows; a run without consumes sample2's counters
+            self.philox_z2 = span
+            self.philox_stride = span * (2 if tab.jumps else 1)
         self.graph = None
 
     def step(self, k: int, update: bool = True):
         lib, x, R = self.lib, self.x, self.R
         st = _lib.stream_ptr()
         rp = self.rates_cur.data_ptr()
-        _lib.check(lib.pcd_step_select(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
-                                       self.tb_cur.data_ptr(), self.rates.data_ptr(), R, rp, st), "step_select")
+        _lib.check(lib.pcd_step_select_cols(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
+                                            self.tb_cur.data_ptr(), self.rates.data_ptr(), self.cols, R, rp, st), "step_select")
         self.forward(x, self.tb_cur, self.eps)
         nxt = x.data_ptr() if update else 0               # in place: every element is read before it is written
+        if self.kind == "complete":
+            return self._complete_update(k, nxt, st)
         if self.kind == "ddim":
             _lib.check(lib.pcd_ddim_update(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
                                            self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st),
@@ -325,6 +422,27 @@ class Stepper:
         _lib.check(lib.pcd_ddpm_update(x.data_ptr(), self.eps.data_ptr(), zp, rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
                                        self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st),
                    "ddpm_update")
+
+    def _complete_update(self, k: int, nxt: int, st: int):
+        lib, x, tab = self.lib, self.x, self.tab
+        rp = self.rates_cur.data_ptr()
+        if self.noises is None:
+            _lib.check(lib.pcd_complete_update_philox(x.data_ptr(), self.eps.data_ptr(), self.p.data_ptr(), self.counts.data_ptr(), rp,
+                                                      self.R, tab.stride, x.numel(), self.per_shape, self.row_elems, int(tab.jumps),
+                                                      self.x0.data_ptr(), nxt, self.seed, self.philox_base, self.philox_stride,
+                                                      self.philox_z2, self.counter.data_ptr(), st), "complete_update_philox")
+            return
+        zp = z2p = 0
+        if nxt:
+            j = tab.draws[k]
+            self.z.copy_(self.noises[j].to(x.device, torch.float32).reshape(self.z.shape))
+            zp = self.z.data_ptr()
+            if tab.rows[k][1] is not None:
+                self.z2.copy_(self.noises[j + 1].to(x.device, torch.float32).reshape(self.z2.shape))
+                z2p = self.z2.data_ptr()
+        _lib.check(lib.pcd_complete_update(x.data_ptr(), self.eps.data_ptr(), zp, z2p, self.p.data_ptr(), self.counts.data_ptr(), rp,
+                                           self.R, tab.stride, x.numel(), self.per_shape, self.row_elems, self.x0.data_ptr(), nxt, st),
+                   "complete_update")
 
     def capture(self, steps: int = 1):
         """Capture `steps` consecutive generic steps in one graph (must follow at least one eager step: kernels
@@ -441,6 +559,45 @@ class PointCloudDiffusion(_DiffusionBase):
         x = self._start(num_samples, num_points, x_T)
         tab = self.ddpm_table(num_steps, num_samples)
         return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddpm", noises=noises)
+
+    @torch.no_grad()
+    def complete(self, partial, num_points, num_steps=1000, known_counts=None, resample=1, jump=10, x_T=None, noises=None):
+        """Shape completion (not in the reference): shape b keeps rows [0, known_counts[b]) of `partial` (B, M, 3), bitwise, as
+        the first rows of the (B, num_points, 3) result, and the remaining rows are generated around them.  The loop is
+        `sample2` on the unknown rows; after every reverse step the known rows are set to the known points noised forward to
+        that step's time.  `resample` > 1 runs RePaint's schedule (cosine schedule only): each time the walk reaches an index
+        in range(0, T - jump, jump) the whole cloud is noised forward `jump` indices and denoised again, `resample - 1` times
+        per index, `T + jump * jumps` network evaluations in all (`completion_rows`).  `x_T` injects the start draw and
+        `noises[k]` the k-th later draw in consumption order (one per row, a jump row's second right after its first).
+        The arithmetic is tests/completion_statement.py."""
+        T, r, j = int(num_steps), int(resample), int(jump)
+        if partial.dim() != 3 or partial.shape[2] != 3 or partial.shape[1] > num_points:
+            raise ValueError(f"partial must be (B, M <= {num_points}, 3), got {tuple(partial.shape)}")
+        B, M = partial.shape[0], partial.shape[1]
+        if T < 1 or r < 1:
+            raise ValueError(f"num_steps and resample must be >= 1, got {num_steps} and {resample}")
+        if r > 1 and (self.noise_schedule != "cosine" or not 1 <= j < T):
+            raise ValueError("resample > 1 needs the cosine schedule (the forward jump relies on s^2 + n^2 = 1) and 1 <= jump < "
+                             f"num_steps; got schedule {self.noise_schedule!r}, jump {jump}, num_steps {num_steps}")
+        if known_counts is None:
+            counts = torch.full((B,), M, dtype=torch.int32)
+        else:
+            counts = torch.as_tensor(known_counts)
+            if counts.dim() != 1 or counts.shape[0] != B or counts.is_floating_point() or counts.is_complex() or counts.dtype == torch.bool:
+                raise ValueError(f"known_counts must be a ({B},) integer tensor, got {tuple(counts.shape)} {counts.dtype}")
+            if B and (int(counts.min()) < 0 or int(counts.max()) > min(M, num_points)):
+                raise ValueError(f"known_counts must lie in [0, {min(M, num_points)}], got [{int(counts.min())}, {int(counts.max())}]")
+        if not bool(torch.isfinite(partial).all()):
+            raise ValueError("partial has non-finite coordinates")
+        self._require_cuda(partial)
+        x = self._start(B, num_points, x_T)
+        p = torch.zeros_like(x)
+        p[:, :M].copy_(partial)
+        counts = counts.to(self.device, torch.int32).contiguous()
+        tab = self.completion_table(T, j, r, B)
+        _lib.check(_lib.load().pcd_complete_start(x.data_ptr(), p.data_ptr(), counts.data_ptr(), tab.n.data_ptr(), tab.s.data_ptr(),
+                                                  tab.stride, x.numel(), num_points * 3, 3, _lib.stream_ptr()), "complete_start")
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "complete", noises=noises, known=(p, counts))
 
     @torch.no_grad()
     def sample3(self, num_samples, num_points, x=None, start_t=None, num_steps=1000):

@@ -131,6 +131,21 @@ def sample_sharded(model, global_batch: int, num_points: int, num_steps: int, x_
     return all_gather_rows(out.contiguous()) if gather else out
 
 
+def complete_sharded(model, partial_global: torch.Tensor, counts_global: Optional[torch.Tensor], num_points: int,
+                     num_steps: int, resample: int = 1, jump: int = 10, x_T_global: Optional[torch.Tensor] = None,
+                     gather: bool = True) -> torch.Tensor:
+    """`model.complete` on this rank's shard of the global batch of partial clouds (same tensors on all ranks); the
+    on-device draws are addressed by global sample index, so the result is independent of the number of ranks."""
+    rank, ws = world()
+    lo, hi = shard_range(partial_global.shape[0], rank, ws)
+    xs = None if x_T_global is None else x_T_global[lo:hi].to(model.device)
+    counts = None if counts_global is None else counts_global[lo:hi]
+    with shard_context(model, lo, partial_global.shape[0]):
+        out = model.complete(partial_global[lo:hi].to(model.device), num_points, num_steps=num_steps, known_counts=counts,
+                             resample=resample, jump=jump, x_T=xs)
+    return all_gather_rows(out.contiguous()) if gather else out
+
+
 def evaluate_sharded(original, reconstructed, use_approximate_gpu_emd: bool = False):
     """Per-sample (CD, EMD, voxel BCE) rows for this rank's samples (test_point_ddpm.py:85-92),
     all-gathered; returns (rows (B_global, 3), their nan-mean).  `original` / `reconstructed` are (B, N, 3)

@@ -173,6 +173,34 @@ int pcd_step_select(int* counter, int n_steps, const float* tb_table, int tb_ele
 /* pcd_randn whose Philox offset is base_offset + per_step_stride * counter[1] (read on the device) */
 int pcd_randn_step(float* out, int64_t n, uint64_t seed, uint64_t base_offset, uint64_t per_step_stride,
                    const int* counter, void* stream);
+/* pcd_step_select over `cols` rate tables instead of four (rate_tables [cols][n_steps][width], rates_cur [cols][width]);
+ * pcd_step_select is this with cols = 4. */
+int pcd_step_select_cols(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_cur,
+                         const float* rate_tables, int cols, int width, float* rates_cur, void* stream);
+
+/* ------------------------------------------------ shape completion (an addition to the reference's surface)
+ * `PointCloudDiffusion.complete`: shape b knows the first counts[b] rows (of row_elems floats) of p, which has the layout
+ * of x; the other rows are generated.  counts: device int32, one per shape.  A row of the step table carries seven
+ * per-shape scalars, rates [7][width] read at [c * width + b * stride]: n, s, coef, s_prev (the four of pcd_ddpm_update),
+ * n_prev, and the RePaint forward jump ja, jb (ja = 0: the row has no jump).  fp32, no FMA contraction: bitwise
+ * tests/completion_statement.py. */
+/* start state, in place on the start draw x: known rows become s*p + n*x */
+int pcd_complete_start(float* x, const float* p, const int* counts, const float* n, const float* s, int stride,
+                       int64_t total, int64_t per_shape, int row_elems, void* stream);
+/* one row: x0 = (x - n*eps)/s; x_next = s_prev*x0 + coef*n*z on unknown rows (bitwise pcd_ddpm_update), s_prev*p + n_prev*z
+ * on known rows; then, if z2 is given and the row's ja != 0, x_next = ja*x_next + jb*z2.  x_next NULL (the last row):
+ * only x0 is written, with its known rows replaced by p.  x_next may be x. */
+int pcd_complete_update(const float* x, const float* eps, const float* z, const float* z2, const float* p,
+                        const int* counts, const float* rates, int width, int stride, int64_t total,
+                        int64_t per_shape, int row_elems, float* x0, float* x_next, void* stream);
+/* the same row with z drawn in place from Philox counter base_offset + per_step_stride * counter[1] + element / 4 and, when
+ * `jumps` and the row's ja != 0, z2 from that counter + z2_offset (pcd_randn_step's arithmetic; neither is stored).
+ * jumps = 0 reads no ja / jb and consumes pcd_ddpm_update_philox's counters. */
+int pcd_complete_update_philox(const float* x, const float* eps, const float* p, const int* counts,
+                               const float* rates, int width, int stride, int64_t total, int64_t per_shape,
+                               int row_elems, int jumps, float* x0, float* x_next, uint64_t seed,
+                               uint64_t base_offset, uint64_t per_step_stride, uint64_t z2_offset,
+                               const int* counter, void* stream);
 
 /* output head: eps[m][j] = sum_k h[m][k]*w[j][k] + b[j], j<3  (networks.py:770 `output.3`),
  * h fp16 [M][k], w fp32 [3][k]; eps fp32 [M][3]. */

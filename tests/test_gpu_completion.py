@@ -1,0 +1,323 @@
+"""Shape completion on the GPU (`PointCloudDiffusion.complete`, `dist.complete_sharded`): the fused row update against the
+float statement (tests/completion_statement.py) bit for bit, the whole loop against the statement over the CPU oracle
+network within the sampler bounds of DESIGN section 4, known rows returned bitwise, the Philox accounting (bitwise `sample2`
+without known rows, stream position, shard invariance) and graph replay against eager stepping.
+
+Shapes: B = 3, N = 128, counts (0, 37, 128) -- nothing known, everything known, and a boundary at element 111 that is aligned
+neither to the 4 normals of a Philox counter nor to a wave; 3 * 128 * 3 elements span several blocks of either kernel form."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import completion_statement as S
+from helpers import as_torch, point_sd, rel_l2
+from oracle import torch_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+
+B, N, T, JUMP, RESAMPLE = 3, 128, 12, 4, 2
+COUNTS = (0, 37, 128)
+ROWS = S.completion_rows(T, JUMP, RESAMPLE)
+N_DRAWS = sum(1 if to is None else 2 for _, to in ROWS[:-1])
+# sampler clouds rel-L2 <= 2e-3 in fp16 (5e-3 over the attention U-Net, as tests/test_gpu_attention.py), and in
+# fp32 mode rel-L2 <= 5e-5 with max-abs <= 1e-3 * max(1, max|x| / 100)
+TOL = {("pointnet", "fp16"): dict(rel=2e-3, maxabs=None), ("pointnet", "fp32"): dict(rel=5e-5, maxabs=1e-3),
+       ("attention", "fp16"): dict(rel=5e-3, maxabs=None), ("attention", "fp32"): dict(rel=5e-5, maxabs=1e-3)}
+
+
+def unit_clouds(b, m, seed):
+    """Clouds as the data contract gives them: centred, scaled into the unit sphere."""
+    g = torch.Generator().manual_seed(seed)
+    c = torch.randn(b, m, 3, generator=g)
+    c = c - c.mean(dim=1, keepdim=True)
+    return c / c.norm(dim=2).max(dim=1).values[:, None, None]
+
+
+def attention_sd():
+    from shapegen_amd import specs
+    return {"model." + k: v for k, v in as_torch(specs.synth_state_dict(specs.unet_attention_spec(), seed=0, gain=0.6)).items()}
+
+
+_models = {}
+
+
+def model_of(backbone, prec, schedule="cosine"):
+    from shapegen_amd.diffusion import PointCloudDiffusion
+    key = (backbone, prec, schedule)
+    if key not in _models:
+        m = PointCloudDiffusion(num_points=N, backbone=backbone, noise_schedule=schedule)
+        m.load_state_dict(point_sd() if backbone == "pointnet" else attention_sd(), strict=True)
+        m = m.to("cuda").eval()
+        m.model.set_precision(prec)
+        _models[key] = m
+    return _models[key]
+
+
+def reseed(m, seed=7):
+    torch.manual_seed(seed)
+    m._philox_offset = 0
+
+
+def inputs(b=B, counts=COUNTS, seed=11):
+    g = torch.Generator().manual_seed(seed)
+    partial = unit_clouds(b, N, seed + 1)
+    x_T = torch.randn(b, N, 3, generator=g)
+    noises = [torch.randn(b, N, 3, generator=g) for _ in range(N_DRAWS)]
+    return partial, torch.tensor(counts[:b]), x_T, noises
+
+
+_refs = {}
+
+
+def reference(backbone):
+    """The statement over the CPU oracle network, computed once per backbone and left unchanged."""
+    if backbone not in _refs:
+        if backbone == "pointnet":
+            sd, b, counts = point_sd(), B, COUNTS
+            net = lambda x, t: O.unet_pointnet_large(sd, "model.", x, t)
+        else:
+            sd, b, counts = attention_sd(), 2, (37, 0)
+            net = lambda x, t: O.unet_attention(sd, "model.", x, t)
+        partial, cnt, x_T, noises = inputs(b, counts)
+        want = S.complete(net, partial, cnt, x_T, T, noises, JUMP, RESAMPLE)
+        _refs[backbone] = (partial, cnt, x_T, noises, want)
+    return _refs[backbone]
+
+
+# ------------------------------------------------------------------ 1. the row update kernel
+def _row_scalars(idx, to):
+    """The statement's scalars of a row at (per-shape) time indices `idx`, jump target `to` (or None): (7, len(idx))."""
+    i = torch.tensor(idx, dtype=torch.float32)
+    n, s = O.offset_cosine_schedule(torch.ones(len(idx)) * i / T)
+    npv, sp = O.offset_cosine_schedule(torch.ones(len(idx)) * (i - 1) / T)
+    ja = jb = torch.zeros(len(idx))
+    if to is not None:
+        _, sb = O.offset_cosine_schedule(torch.ones(len(idx)) * torch.tensor(to, dtype=torch.float32) / T)
+        jad = sb.double() / sp.double()
+        ja, jb = jad.float(), torch.sqrt(1 - jad * jad).float()
+    return torch.stack([n, s, torch.sqrt(npv / n), sp, npv, ja, jb])
+
+
+@pytest.mark.parametrize("width", [1, B])
+@pytest.mark.parametrize("kind", ["plain", "jump", "last"])
+def test_row_update_kernel_is_the_statement_bitwise(kind, width):
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(3)
+    x, eps, z, z2 = (torch.randn(B, N, 3, generator=g) for _ in range(4))
+    p = unit_clouds(B, N, 4)
+    counts = torch.tensor(COUNTS)
+    known = (torch.arange(N)[None, :] < counts[:, None])[:, :, None]
+    idx = [8, 5, 3][:width] if width > 1 else [8]
+    rates = _row_scalars(idx, [i - 1 + JUMP for i in idx] if kind == "jump" else None)
+    n, s, co, sp, npv, ja, jb = rates
+    # the statement's row arithmetic
+    x0 = O.remove_noise(x, eps, n, s)
+    unk = O._bc(sp, x) * x0 + O._bc(co, x) * O._bc(n, x) * z
+    kn = O._bc(sp, x) * p + O._bc(npv, x) * z
+    nxt = torch.where(known, kn, unk)
+    if kind == "jump":
+        assert bool((ja > 0).all() and (ja < 1).all())
+        nxt = O._bc(ja, x) * nxt + O._bc(jb, x) * z2
+    want_x0 = torch.where(known, p, x0) if kind == "last" else x0
+
+    d = lambda t: t.cuda().contiguous()
+    dx, de, dz, dz2, dp, dr = d(x), d(eps), d(z), d(z2), d(p), d(rates)
+    dc = counts.to("cuda", torch.int32)
+    o0, o1 = torch.full_like(dx, 9.0), torch.full_like(dx, 9.0)
+    stride = 0 if width == 1 else 1
+    _lib.check(lib.pcd_complete_update(dx.data_ptr(), de.data_ptr(), 0 if kind == "last" else dz.data_ptr(),
+                                       dz2.data_ptr() if kind == "jump" else 0, dp.data_ptr(), dc.data_ptr(), dr.data_ptr(), width, stride,
+                                       dx.numel(), N * 3, 3, o0.data_ptr(), 0 if kind == "last" else o1.data_ptr(), _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    assert torch.equal(o0.cpu(), want_x0)
+    if kind == "last":
+        assert bool((o1 == 9.0).all())                       # no next state is written on the last row
+        return
+    assert torch.equal(o1.cpu(), nxt)
+    if kind == "plain":
+        # unknown rows are pcd_ddpm_update's bits; z2 given on a row without a jump changes nothing
+        r0, r1 = torch.empty_like(dx), torch.empty_like(dx)
+        rp, w4 = dr.data_ptr(), 4 * width
+        _lib.check(lib.pcd_ddpm_update(dx.data_ptr(), de.data_ptr(), dz.data_ptr(), rp, rp + w4, rp + 2 * w4, rp + 3 * w4, stride,
+                                       dx.numel(), N * 3, r0.data_ptr(), r1.data_ptr(), _lib.stream_ptr()))
+        unknown = ~known.expand(B, N, 3).cuda()
+        assert torch.equal(o1[unknown], r1[unknown]) and torch.equal(o0, r0)
+        o2 = torch.empty_like(dx)
+        _lib.check(lib.pcd_complete_update(dx.data_ptr(), de.data_ptr(), dz.data_ptr(), dz2.data_ptr(), dp.data_ptr(), dc.data_ptr(),
+                                           dr.data_ptr(), width, stride, dx.numel(), N * 3, 3, o0.data_ptr(), o2.data_ptr(),
+                                           _lib.stream_ptr()))
+        assert torch.equal(o2, o1)
+    # the Philox form = pcd_randn_step draws + the pointer form, in place on x
+    seed, base, span, k = 1234, 40, 2 * ((B * N * 3 + 3) // 4) + 5, 3
+    counter = torch.tensor([k + 1, k], dtype=torch.int32, device="cuda")
+    jumps = int(kind == "jump")
+    for buf, off in ((dz, 0), (dz2, span // 2)):
+        _lib.check(lib.pcd_randn_step(buf.data_ptr(), buf.numel(), seed, base + off, span, counter.data_ptr(), _lib.stream_ptr()))
+    _lib.check(lib.pcd_complete_update(dx.data_ptr(), de.data_ptr(), dz.data_ptr(), dz2.data_ptr() if jumps else 0, dp.data_ptr(),
+                                       dc.data_ptr(), dr.data_ptr(), width, stride, dx.numel(), N * 3, 3, o0.data_ptr(), o1.data_ptr(),
+                                       _lib.stream_ptr()))
+    xin, q0 = dx.clone(), torch.empty_like(dx)
+    _lib.check(lib.pcd_complete_update_philox(xin.data_ptr(), de.data_ptr(), dp.data_ptr(), dc.data_ptr(), dr.data_ptr(), width, stride,
+                                              dx.numel(), N * 3, 3, jumps, q0.data_ptr(), xin.data_ptr(), seed, base, span, span // 2,
+                                              counter.data_ptr(), _lib.stream_ptr()))
+    assert torch.equal(q0, o0) and torch.equal(xin, o1)
+
+
+def test_start_state_kernel_is_the_statement_bitwise():
+    from shapegen_amd import _lib
+    partial, counts, x_T, _ = inputs()
+    known = (torch.arange(N)[None, :] < counts[:, None])[:, :, None]
+    for idx in ([11], [11, 7, 2]):
+        n, s = O.offset_cosine_schedule(torch.tensor(idx, dtype=torch.float32) / T)
+        want = torch.where(known, O._bc(s, x_T) * partial + O._bc(n, x_T) * x_T, x_T)
+        x, dn, ds = x_T.cuda(), n.cuda(), s.cuda()
+        _lib.check(_lib.load().pcd_complete_start(x.data_ptr(), partial.cuda().data_ptr(), counts.to("cuda", torch.int32).data_ptr(),
+                                                  dn.data_ptr(), ds.data_ptr(), int(len(idx) > 1), x.numel(), N * 3, 3, _lib.stream_ptr()))
+        assert torch.equal(x.cpu(), want)
+
+
+# ------------------------------------------------------------------ 2. the loop against the statement over the oracle network
+@pytest.mark.parametrize("backbone,prec", [("pointnet", "fp16"), ("pointnet", "fp32"), ("attention", "fp16")])
+def test_complete_with_injected_noise_against_the_statement(backbone, prec):
+    """T = 12, jump = 4, resample = 2: 20 rows, 2 jumps, 21 injected draws.
+    Measured on an MI355X (rel-L2 / max-abs against the statement over the CPU oracle network; max|x| of the statement 60.5, attention
+    37.1): pointnet fp16 2.6e-4 / 2.0e-2, pointnet fp32 5.3e-7 / 3.4e-5, attention fp16 5.5e-6 / 2.8e-4."""
+    partial, counts, x_T, noises, want = reference(backbone)
+    assert len(ROWS) == 20 and len(noises) == 21 and torch.isfinite(want).all()
+    m = model_of(backbone, prec)
+    got = m.complete(partial.cuda(), N, num_steps=T, known_counts=counts, resample=RESAMPLE, jump=JUMP, x_T=x_T.cuda(),
+                     noises=[z.cuda() for z in noises]).cpu()
+    tol = TOL[(backbone, prec)]
+    r, mx = rel_l2(got, want), float((got - want).abs().max())
+    print(f"complete vs statement [{backbone} {prec}]: rel-L2 {r:.3e}  max-abs {mx:.3e}  max|x| {float(want.abs().max()):.3g}")
+    assert r <= tol["rel"], (backbone, prec, r)
+    if tol["maxabs"] is not None:
+        assert mx <= tol["maxabs"] * max(1.0, float(want.abs().max()) / 100.0), (backbone, prec, mx)
+    for b, c in enumerate(counts.tolist()):
+        assert torch.equal(got[b, :c], partial[b, :c])
+
+
+# ------------------------------------------------------------------ 3. known rows come back bitwise
+@pytest.mark.parametrize("prec", ["fp16", "fp32"])
+@pytest.mark.parametrize("backbone", ["pointnet", "attention"])
+def test_known_rows_are_returned_bitwise(backbone, prec):
+    m = model_of(backbone, prec)
+    partial, counts, _, _ = inputs()
+    reseed(m)
+    out = m.complete(partial.cuda(), N, num_steps=T, known_counts=counts.cuda(), resample=RESAMPLE, jump=JUMP).cpu()
+    assert out.shape == (B, N, 3) and torch.isfinite(out).all()
+    for b, c in enumerate(COUNTS):
+        assert torch.equal(out[b, :c], partial[b, :c])
+    assert torch.equal(out[2], partial[2])                            # fully known: the input itself
+    assert not torch.equal(out[1, 37:], partial[1, 37:])              # the rest is generated, not copied
+    # a shorter partial (M < num_points) with the default counts: all M rows known
+    reseed(m)
+    out = m.complete(partial[:, :50].cuda(), N, num_steps=4).cpu()
+    assert torch.equal(out[:, :50], partial[:, :50]) and torch.isfinite(out).all()
+
+
+# ------------------------------------------------------------------ 4. Philox accounting: nothing known = sample2
+@pytest.mark.parametrize("schedule", ["cosine", "linear"])
+def test_complete_without_known_rows_is_sample2_bitwise(schedule):
+    m = model_of("pointnet", "fp16", schedule)
+    reseed(m)
+    want = m.sample2(B, N, num_steps=T)
+    end = m._philox_offset
+    reseed(m)
+    got = m.complete(unit_clouds(B, 20, 5).cuda(), N, num_steps=T, known_counts=torch.zeros(B, dtype=torch.int64), resample=1)
+    assert torch.equal(got, want) and m._philox_offset == end
+    if schedule == "linear":                                          # per-shape rates (R = batch) with known rows
+        partial, counts, _, _ = inputs()
+        out = m.complete(partial.cuda(), N, num_steps=T, known_counts=counts)
+        assert torch.isfinite(out).all() and all(torch.equal(out[b, :c].cpu(), partial[b, :c]) for b, c in enumerate(COUNTS))
+
+
+# ------------------------------------------------------------------ 5. graph replay = eager
+def test_graph_replay_equals_eager_stepping():
+    m = model_of("pointnet", "fp16")
+    partial, counts, _, _ = inputs()
+    assert len(ROWS) - 1 - 1 >= m.GRAPH_MIN_STEPS and m.use_graphs     # _run's condition: the graph path is taken
+    from shapegen_amd.diffusion import Stepper
+    outs, inner = [], Stepper.replay
+    try:
+        for graphs in (True, False):
+            m.use_graphs = graphs
+            seen = []
+            Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+            reseed(m)
+            outs.append(m.complete(partial.cuda(), N, num_steps=T, known_counts=counts, resample=RESAMPLE, jump=JUMP))
+            assert len(seen) == (2 if graphs else 0)                  # 19 uniform rows: one eager, two graphs of 8, two eager
+    finally:
+        Stepper.replay = inner
+        del m.use_graphs                                              # back to the class default
+    assert torch.equal(outs[0], outs[1])
+
+
+# ------------------------------------------------------------------ 6. Philox stream position
+@pytest.mark.parametrize("resample", [1, 2])
+def test_philox_stream_position(resample):
+    m = model_of("pointnet", "fp16")
+    partial, counts, _, _ = inputs()
+    run = lambda: m.complete(partial.cuda(), N, num_steps=T, known_counts=counts, resample=resample, jump=JUMP)
+    reseed(m)
+    a = run()
+    b = run()
+    after_two = m._randn_like(torch.empty(B, N, 3, device="cuda"))
+    reseed(m)
+    c = run()
+    assert torch.equal(a, c) and not torch.equal(a[1, 37:], b[1, 37:])
+    # consumed: the start draw, then one span per row, two per row in a run with jumps
+    span = B * N * 3 // 4
+    rows = len(S.completion_rows(T, JUMP, resample))
+    per_call = span + rows * span * (2 if resample > 1 else 1)
+    assert m._philox_offset == per_call
+    reseed(m)
+    m._philox_offset = 2 * per_call
+    assert torch.equal(m._randn_like(torch.empty(B, N, 3, device="cuda")), after_two)
+
+
+# ------------------------------------------------------------------ 7. shard invariance
+def test_halves_under_shard_context_equal_the_whole_batch():
+    from shapegen_amd import dist as D
+    m = model_of("pointnet", "fp16")
+    counts = torch.tensor([0, 37, 128, 64])
+    partial = unit_clouds(4, N, 21)
+    reseed(m)
+    whole = m.complete(partial.cuda(), N, num_steps=T, known_counts=counts, resample=RESAMPLE, jump=JUMP)
+    end = m._philox_offset
+    halves = []
+    for lo in (0, 2):
+        reseed(m)
+        with D.shard_context(m, lo, 4):
+            halves.append(m.complete(partial[lo:lo + 2].cuda(), N, num_steps=T, known_counts=counts[lo:lo + 2], resample=RESAMPLE,
+                                     jump=JUMP))
+        assert m._philox_offset == end                               # a rank advances by the GLOBAL spans
+    assert torch.equal(torch.cat(halves), whole)
+    assert not torch.equal(halves[0][0], halves[1][0])
+    reseed(m)
+    assert torch.equal(D.complete_sharded(m, partial, counts, N, T, resample=RESAMPLE, jump=JUMP), whole)   # no process group: one shard
+
+
+def test_complete_sharded_as_a_forced_one_rank_world():
+    """`dist.complete_sharded` through the collective branch (one rank, PCD_DIST_FORCE_COLLECTIVE=1, RCCL on device tensors) in a child
+    process, against `complete` of the same seed there."""
+    import socket
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = str(sock.getsockname()[1])
+    env = {k: v for k, v in os.environ.items() if k not in ("PCD_BENCH_SHARE_GPU",)}
+    env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=port, PYTHONPATH=ROOT,
+               HSA_ENABLE_IPC_MODE_LEGACY="0", PCD_DIST_FORCE_COLLECTIVE="1", PCD_COLLECTIVE_TIMEOUT_S="120")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "complete_one_rank_worker.py")], env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
+    res = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    assert res["backend"] == "nccl" and res["world"] == 1
+    for k in ("drawn_equal", "injected_equal", "known_rows_equal", "gathered_copy"):
+        assert res[k] is True, k
