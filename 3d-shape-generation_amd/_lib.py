@@ -140,6 +140,7 @@ _SIGS = {
     "pcd_complete_start": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i32, vp]),
     "pcd_complete_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, i32, vp, vp, vp]),
     "pcd_complete_update_philox": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, i64, i32, i32, vp, vp, u64, u64, u64, u64, vp, vp]),
+    "pcd_dpm_update": (i32, [vp, vp, vp, i32, i32, i64, i64, vp, vp, vp]),
     "pcd_head3": (i32, [vp, i64, i32, vp, vp, vp, vp]),
     "pcd_pw_chain_enc1": (i32, [vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "pcd_pw_chain_enc1_hilo": (i32, [vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),

@@ -642,6 +642,35 @@ __global__ __launch_bounds__(256) void complete_update_kernel(const float* x, co
         xn[i] = xv;
     }
 }
+
+// One step of `sample_dpm` (DPM-Solver++ 2M in data-prediction form; tests/dpm_statement.py).  rates = the step's six per-shape
+// scalars [6][width]: n, s, n_next, s_next, c, q.  hist holds the previous step's x0 and receives this step's (read, then written by the
+// one thread that owns the element).  c = h_k / (2 h_{k-1}) is 0 on the first step and for order 1: the history is then not read and the
+// update is bitwise ddim_update_kernel's.  x and xn may be the same buffer.
+__global__ __launch_bounds__(256) void dpm_update_kernel(const float* x, const float* __restrict__ eps,
+                                                          const float* __restrict__ rates, int width, int stride, int64_t total,
+                                                          int64_t per_shape, float* __restrict__ hist, float* xn) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t b = (i / per_shape) * stride;
+    const float e = eps[i];
+    const float ne = rates[b] * e;
+    const float x0 = (x[i] - ne) / rates[width + b];
+    const float c = rates[4 * width + b];
+    float D = x0, eD = e;
+    if (c != 0.f) {
+        const float w = c * (x0 - hist[i]);
+        const float qw = rates[5 * width + b] * w;
+        D = x0 + w;
+        eD = e - qw;
+    }
+    hist[i] = x0;
+    if (xn != nullptr) {
+        const float a = rates[3 * width + b] * D;
+        const float cc = rates[2 * width + b] * eD;
+        xn[i] = a + cc;
+    }
+}
 #pragma clang fp contract(fast)
 
 // The same row with its normal draws generated in place (thread = 4 consecutive elements = one Philox counter, as in
@@ -724,6 +753,16 @@ extern "C" int pcd_complete_update_philox(const float* x, const float* eps, cons
     hipLaunchKernelGGL(complete_update_philox_kernel, dim3(nblk(ceil_div(total, 4))), dim3(256), 0, (hipStream_t)stream, x, eps,
                        p, counts, rates, width, stride, total, per_shape, row_elems, jumps, x0, x_next, seed, base_offset,
                        per_step_stride, z2_offset, counter);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_dpm_update(const float* x, const float* eps, const float* rates, int width, int stride, int64_t total,
+                              int64_t per_shape, float* hist, float* x_next, void* stream) {
+    PCD_CHECK_ARG(x && eps && rates && hist && width > 0 && total > 0 && per_shape > 0 && total % per_shape == 0);
+    PCD_CHECK_ARG(stride == 0 || (stride == 1 && width == total / per_shape));
+    hipLaunchKernelGGL(dpm_update_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, eps, rates, width, stride, total,
+                       per_shape, hist, x_next);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }

@@ -9,6 +9,7 @@ per-timestep computation runs in HIP kernels (`_lib`).  The training surface (`t
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Optional, Tuple
 
@@ -106,6 +107,20 @@ class CompletionTable(StepTable):
 
     def columns(self) -> List[torch.Tensor]:
         return [self.n, self.s, self.a, self.b, self.n2, self.ja, self.jb]
+
+
+class DpmTable(StepTable):
+    """StepTable of `sample_dpm`: the DDIM columns n, s, n_next, s_next plus the multistep coefficient c = h_k / (2 h_{k-1}) (0 on
+    the first row and for order 1) and q = s / n.  `skip_last_update`: the log-SNR grid ends at t_last and its last row only
+    predicts x_0; the uniform grid's last row updates as `sample`'s does."""
+
+    def __init__(self, t, n, s, n2, s2, c, q, device, skip_last_update: bool):
+        super().__init__(t, n, s, n2, s2, device)
+        self.c, self.q = self._col(c, device), self._col(q, device)
+        self.skip_last_update = skip_last_update
+
+    def columns(self) -> List[torch.Tensor]:
+        return [self.n, self.s, self.a, self.b, self.c, self.q]
 
 
 class _DiffusionBase(nn.Module):
@@ -317,6 +332,57 @@ class _DiffusionBase(nn.Module):
             jas.append(ja); jbs.append(jb)
         return CompletionTable(rows, ts, ns, ss, co, s2, n2, jas, jbs, self.device)
 
+    @staticmethod
+    def _check_dpm_args(num_steps, order, spacing, t_last):
+        if int(num_steps) < 1:
+            raise ValueError(f"num_steps must be >= 1, got {num_steps}")
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order!r}")
+        if spacing not in ("logsnr", "uniform"):
+            raise ValueError(f"spacing must be 'logsnr' or 'uniform', got {spacing!r}")
+        if not 0.0 < float(t_last) < 1.0:
+            raise ValueError(f"t_last must lie in (0, 1), got {t_last}")
+
+    def dpm_table(self, num_steps: int, order: int = 2, spacing: str = "logsnr", t_last: float = 1e-3) -> DpmTable:
+        """`sample_dpm` (not in the reference): DPM-Solver++ 2M on a grid uniform in log-SNR, lambda(t) = log(cos ang / sin ang) with
+        ang = a0 + t (a1 - a0).  "logsnr": lambda_k runs linearly from lambda(1) to lambda(t_last) and t_k is its inverse, formed in
+        float64 and rounded once to fp32 (t_0 = 1 and t_{K-1} = t_last exactly); the rates are the reference schedule's at the fp32
+        time the network sees, and the last row only predicts.  "uniform": `ddim_table`'s rows.  q = s / n, h_k = log(s2 / n2) -
+        log(s / n) and c_k = h_k / (2 h_{k-1}) are formed from the fp32 rates in float64 and rounded once.  tests/dpm_statement.py."""
+        self._check_dpm_args(num_steps, order, spacing, t_last)
+        if self.noise_schedule != "cosine":
+            raise ValueError("sample_dpm needs the cosine schedule (the linear schedule's batch-axis cumprod has no monotone log-SNR); "
+                             f"got schedule {self.noise_schedule!r}")
+        K = int(num_steps)
+        if spacing == "uniform":
+            base = self.ddim_table(K, 1)
+            t, n, s, n2, s2 = (v.cpu().reshape(-1) for v in (base.t, base.n, base.s, base.a, base.b))
+            updates = K
+        else:
+            a0, a1 = math.acos(self.cosine_max_signal_rate), math.acos(self.cosine_min_signal_rate)
+            lam = lambda u: math.log(math.cos(a0 + u * (a1 - a0)) / math.sin(a0 + u * (a1 - a0)))
+            l0, l1 = lam(1.0), lam(float(t_last))
+            ts = [1.0] + [(math.atan(math.exp(-(l0 + (l1 - l0) * k / (K - 1)))) - a0) / (a1 - a0) for k in range(1, K - 1)]
+            if K > 1:
+                ts.append(float(t_last))
+            t = torch.tensor(ts, dtype=torch.float64).to(torch.float32)
+            if K > 1 and not bool((t[1:] < t[:-1]).all()):
+                raise ValueError(f"the log-SNR grid of {K} steps down to t_last = {t_last} is not strictly decreasing in fp32")
+            n, s = self._host_schedule(t)
+            n2, s2 = torch.zeros(K), torch.zeros(K)
+            n2[:-1], s2[:-1] = n[1:], s[1:]
+            updates = K - 1
+        c, q, h_prev = [0.0] * K, [0.0] * K, None
+        for k in range(updates):
+            nk, sk, n2k, s2k = (float(v[k]) for v in (n, s, n2, s2))
+            q[k] = sk / nk
+            h = math.log(s2k / n2k) - math.log(sk / nk)
+            if order == 2 and k > 0:
+                c[k] = h / (2.0 * h_prev)
+            h_prev = h
+        c, q = (torch.tensor(v, dtype=torch.float64).to(torch.float32) for v in (c, q))
+        return DpmTable(t, n, s, n2, s2, c, q, self.device, skip_last_update=updates < K)
+
     vectorized_tables = True     # False: per-step host loop (the literal transcription; kept for the equality test)
 
     # ------------------------------------------------------------------ stepping
@@ -326,7 +392,7 @@ class _DiffusionBase(nn.Module):
 
     def _run(self, x, tab: "StepTable", bias_table: torch.Tensor, forward, kind: str, noises=None,
              skip_last_update: bool = False, known=None):
-        """kind 'ddim' | 'ddpm' | 'complete' (`known` = (p, counts) on the device, `tab` a CompletionTable).
+        """kind 'ddim' | 'ddpm' | 'dpm' (`tab` a DpmTable) | 'complete' (`known` = (p, counts) on the device, `tab` a CompletionTable).
         forward(x, tb_cur, eps_out) enqueues the denoiser for the current step."""
         stp = Stepper(self, x, tab, bias_table, forward, kind, noises, known)
         T = tab.steps
@@ -366,7 +432,7 @@ class Stepper:
         self.x, self.tab, self.forward, self.kind, self.noises = x, tab, forward, kind, noises
         dev = x.device
         self.T, self.R = tab.steps, tab.width
-        self.rates = torch.stack(tab.columns()).contiguous()                     # (4, T, R); (7, T, R) for 'complete'
+        self.rates = torch.stack(tab.columns()).contiguous()                     # (4, T, R); (6, T, R) 'dpm', (7, T, R) 'complete'
         self.cols = self.rates.shape[0]
         self.bias_table = bias_table.contiguous()
         self.tb_elems = self.bias_table.shape[1]
@@ -402,6 +468,10 @@ class Stepper:
         nxt = x.data_ptr() if update else 0               # in place: every element is read before it is written
         if self.kind == "complete":
             return self._complete_update(k, nxt, st)
+        if self.kind == "dpm":                            # x0 is also the history: the previous step's x0 is read, this step's written
+            _lib.check(lib.pcd_dpm_update(x.data_ptr(), self.eps.data_ptr(), rp, R, self.tab.stride, x.numel(), self.per_shape,
+                                          self.x0.data_ptr(), nxt, st), "dpm_update")
+            return
         if self.kind == "ddim":
             _lib.check(lib.pcd_ddim_update(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
                                            self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st),
@@ -552,6 +622,19 @@ class PointCloudDiffusion(_DiffusionBase):
         x = self._start(num_samples, num_points, x_T)
         tab = self.ddim_table(num_steps, num_samples)
         return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim")
+
+    @torch.no_grad()
+    def sample_dpm(self, num_samples, num_points, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, x_T=None):
+        """Second-order multistep sampling of the probability-flow ODE (DPM-Solver++ 2M, not in the reference): `num_steps` network
+        evaluations on a grid uniform in log-SNR from t = 1 to `t_last`.  Returns the last x_0, like `sample`, whose start draw
+        it consumes.  Cosine schedule only.  `order=1, spacing="uniform"` is `sample` bit for bit.  The arithmetic is
+        tests/dpm_statement.py."""
+        self._check_dpm_args(num_steps, order, spacing, t_last)
+        if x_T is not None and tuple(x_T.shape) != (num_samples, num_points, 3):
+            raise ValueError(f"x_T must be {(num_samples, num_points, 3)}, got {tuple(x_T.shape)}")
+        tab = self.dpm_table(num_steps, order, spacing, t_last)
+        x = self._start(num_samples, num_points, x_T)
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update)
 
     @torch.no_grad()
     def sample2(self, num_samples, num_points, num_steps=1000, x_T=None, noises=None):
@@ -770,6 +853,20 @@ class LatentDiffusion(_DiffusionBase):
         z = self._start(num_samples, z_T)
         tab = self.ddim_table(num_steps, num_samples)
         z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim")
+        pcs = self._finish(z0, threshold)
+        return (pcs, z0) if return_latent else pcs
+
+    @torch.no_grad()
+    def sample_dpm(self, num_samples, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, threshold=0.4, z_T=None,
+                   return_latent=False):
+        """`PointCloudDiffusion.sample_dpm` in latent space, then VAE decode and voxel -> points like `sample`.  Runs on the per-layer
+        launches (the persistent kernel implements the DDIM update only)."""
+        self._check_dpm_args(num_steps, order, spacing, t_last)
+        if z_T is not None and tuple(z_T.shape) != (num_samples, self.hparams.latent_dim):
+            raise ValueError(f"z_T must be {(num_samples, self.hparams.latent_dim)}, got {tuple(z_T.shape)}")
+        tab = self.dpm_table(num_steps, order, spacing, t_last)
+        z = self._start(num_samples, z_T)
+        z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update)
         pcs = self._finish(z0, threshold)
         return (pcs, z0) if return_latent else pcs
 

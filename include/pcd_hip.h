@@ -202,6 +202,16 @@ int pcd_complete_update_philox(const float* x, const float* eps, const float* p,
                                uint64_t base_offset, uint64_t per_step_stride, uint64_t z2_offset,
                                const int* counter, void* stream);
 
+/* ------------------------------------------------ second-order multistep sampler (an addition to the reference's surface)
+ * One step of `sample_dpm` (DPM-Solver++ 2M, data-prediction form).  rates [6][width] read at [c * width + b * stride]:
+ * n, s, n_next, s_next, c, q with q = s / n and c = h_k / (2 h_{k-1}) (0 on the first step and for order 1).
+ *   x0 = (x - n*eps)/s;  w = c*(x0 - hist);  D = x0 + w;  eD = eps - q*w;  x_next = s_next*D + n_next*eD;  hist = x0
+ * hist holds the previous step's x0 and receives this step's, in place.  c = 0: hist is not read (it may be unwritten) and
+ * x0, x_next are bitwise pcd_ddim_update's.  x_next NULL: only hist = x0 is written.  x_next may be x.  fp32, no FMA
+ * contraction: bitwise tests/dpm_statement.py. */
+int pcd_dpm_update(const float* x, const float* eps, const float* rates, int width, int stride, int64_t total,
+                   int64_t per_shape, float* hist, float* x_next, void* stream);
+
 /* output head: eps[m][j] = sum_k h[m][k]*w[j][k] + b[j], j<3  (networks.py:770 `output.3`),
  * h fp16 [M][k], w fp32 [3][k]; eps fp32 [M][3]. */
 int pcd_head3(const void* h, int64_t m, int k, const float* w, const float* b, float* eps, void* stream);

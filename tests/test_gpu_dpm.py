@@ -1,0 +1,289 @@
+"""`sample_dpm` on the GPU (DPM-Solver++ 2M on a log-SNR grid): the fused step update against the float statement
+(tests/dpm_statement.py) bit for bit, order 1 on the uniform grid against `sample` bit for bit, the whole loop against the
+statement over the CPU oracle networks within the sampler bounds of DESIGN section 4, graph replay against eager stepping, the
+accuracy claim (20 steps against 100 DDIM steps), the Philox accounting and sharding, the latent process and the entry script.
+
+Shapes: B = 3, N = 128, K = 12 -- the eager warm-up, one 8-step graph, two eager remainder steps and the last row without an
+update; 3 * 128 * 3 = 1152 elements are several blocks and no multiple of 256."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import dpm_statement as S
+from helpers import as_torch, latent_sd, point_sd, rel_l2
+from oracle import torch_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+
+B, N, K = 3, 128, 12
+# sampler clouds rel-L2 <= 2e-3 in fp16, <= 5e-5 in fp32 mode
+TOL = {"fp16": 2e-3, "fp32": 5e-5}
+
+
+def attention_sd():
+    from shapegen_amd import specs
+    return {"model." + k: v for k, v in as_torch(specs.synth_state_dict(specs.unet_attention_spec(), seed=0, gain=0.6)).items()}
+
+
+_models = {}
+
+
+def model_of(backbone, prec):
+    from shapegen_amd.diffusion import PointCloudDiffusion
+    key = (backbone, prec)
+    if key not in _models:
+        m = PointCloudDiffusion(num_points=N, backbone=backbone)
+        m.load_state_dict(point_sd() if backbone == "pointnet" else attention_sd(), strict=True)
+        m = m.to("cuda").eval()
+        m.model.set_precision(prec)
+        _models[key] = m
+    return _models[key]
+
+
+def reseed(m, seed=7):
+    torch.manual_seed(seed)
+    m._philox_offset = 0
+
+
+_refs = {}
+
+
+def reference(backbone):
+    """The statement over the CPU oracle network at K = 12, computed once per backbone and left unchanged."""
+    if backbone not in _refs:
+        if backbone == "pointnet":
+            sd, b = point_sd(), B
+            net = lambda x, t: O.unet_pointnet_large(sd, "model.", x, t)
+        else:
+            sd, b = attention_sd(), 2
+            net = lambda x, t: O.unet_attention(sd, "model.", x, t)
+        x_T = torch.randn(b, N, 3, generator=torch.Generator().manual_seed(11))
+        _refs[backbone] = (x_T, S.sample_dpm(net, x_T, K))
+    return _refs[backbone]
+
+
+# ------------------------------------------------------------------ 1. the step update kernel
+def _rates(width, c_zero):
+    """Rows of the statement's table as the kernel's (6, width) operand: per-shape rows 4, 7, 2 of K = 12 (width 3) or row 4."""
+    rows = S.table(K, 2, "logsnr")
+    pick = [rows[i] for i in ((4, 7, 2)[:width] if width > 1 else (4,))]
+    r = torch.stack([torch.stack([p[f] for p in pick]) for f in ("n", "s", "n2", "s2", "c", "q")])
+    assert bool((r[4] > 0).all())
+    if c_zero:
+        r[4] = 0.0
+    return r
+
+
+@pytest.mark.parametrize("width", [1, B])
+@pytest.mark.parametrize("case", ["history", "no_history", "x0_only", "in_place"])
+def test_dpm_update_kernel_is_the_statement_bitwise(case, width):
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(3)
+    x, eps, hist = (torch.randn(B, N, 3, generator=g) for _ in range(3))
+    if case == "no_history":
+        hist = torch.full_like(x, float("nan"))                # c = 0 must not read it
+    r = _rates(width, case == "no_history")
+    want_x0, want_xn = S.update(x, eps, hist, *r)
+    assert torch.isfinite(want_x0).all() and torch.isfinite(want_xn).all()
+    d = lambda t: t.cuda().contiguous()
+    dx, de, dh, dr = d(x), d(eps), d(hist), d(r)
+    stride = 0 if width == 1 else 1
+    xn = torch.full_like(dx, 9.0)
+    out = {"x0_only": 0, "in_place": dx.data_ptr()}.get(case, xn.data_ptr())
+    _lib.check(lib.pcd_dpm_update(dx.data_ptr(), de.data_ptr(), dr.data_ptr(), width, stride, dx.numel(), N * 3, dh.data_ptr(), out,
+                                  _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    assert torch.equal(dh.cpu(), want_x0)                       # the history buffer now holds this step's x0
+    if case == "x0_only":
+        assert bool((xn == 9.0).all()) and torch.equal(dx.cpu(), x)
+        return
+    assert torch.equal((dx if case == "in_place" else xn).cpu(), want_xn)
+    if case == "history":
+        assert not torch.equal(want_xn, S.update(x, eps, hist, r[0], r[1], r[2], r[3], torch.zeros(width), r[5])[1])
+    if case == "no_history":                                    # bit for bit pcd_ddim_update
+        r0, r1 = torch.empty_like(dx), torch.empty_like(dx)
+        rp, w4 = dr.data_ptr(), 4 * width
+        _lib.check(lib.pcd_ddim_update(dx.data_ptr(), de.data_ptr(), rp, rp + w4, rp + 2 * w4, rp + 3 * w4, stride, dx.numel(), N * 3,
+                                       r0.data_ptr(), r1.data_ptr(), _lib.stream_ptr()))
+        assert torch.equal(dh, r0) and torch.equal(xn, r1)
+
+
+# ------------------------------------------------------------------ 2. order 1 on the uniform grid is `sample`
+@pytest.mark.parametrize("prec", ["fp16", "fp32"])
+def test_order1_uniform_is_sample_bitwise(prec):
+    m = model_of("pointnet", prec)
+    x_T = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(5)).cuda()
+    want = m.sample(B, N, num_steps=K, x_T=x_T)
+    got = m.sample_dpm(B, N, num_steps=K, order=1, spacing="uniform", x_T=x_T)
+    assert torch.isfinite(want).all() and torch.equal(got, want)
+    assert not torch.equal(m.sample_dpm(B, N, num_steps=K, order=2, spacing="uniform", x_T=x_T), want)
+
+
+# ------------------------------------------------------------------ 3. the loop against the statement over the oracle networks
+@pytest.mark.parametrize("backbone,prec", [("pointnet", "fp16"), ("pointnet", "fp32"), ("attention", "fp16")])
+def test_sample_dpm_with_injected_start_against_the_statement(backbone, prec):
+    """K = 12, order 2, log-SNR grid.  Measured on an MI355X (rel-L2 / max-abs against the statement over the CPU oracle network; max|x|
+    of the statement 157, attention 147): pointnet fp16 1.5e-4 / 3.0e-2, pointnet fp32 4.0e-7 / 1.1e-4, attention fp16 1.6e-6 / 3.1e-4."""
+    x_T, want = reference(backbone)
+    assert torch.isfinite(want).all()
+    m = model_of(backbone, prec)
+    got = m.sample_dpm(x_T.shape[0], N, num_steps=K, x_T=x_T.cuda()).cpu()
+    r = rel_l2(got, want)
+    print(f"sample_dpm vs statement [{backbone} {prec}]: rel-L2 {r:.3e}  max-abs {float((got - want).abs().max()):.3e}  "
+          f"max|x| {float(want.abs().max()):.3g}")
+    assert r <= TOL[prec], (backbone, prec, r)
+
+
+# ------------------------------------------------------------------ 4. graph replay = eager
+@pytest.mark.parametrize("steps,replays", [(12, 1), (20, 2)])
+def test_graph_replay_equals_eager_stepping(steps, replays):
+    m = model_of("pointnet", "fp16")
+    assert steps - 1 - 1 >= m.GRAPH_MIN_STEPS and m.use_graphs and m.GRAPH_STEPS == 8
+    from shapegen_amd.diffusion import Stepper
+    x_T = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(6)).cuda()
+    outs, inner = [], Stepper.replay
+    try:
+        for graphs in (True, False):
+            m.use_graphs = graphs
+            seen = []
+            Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+            outs.append(m.sample_dpm(B, N, num_steps=steps, x_T=x_T))
+            assert len(seen) == (replays if graphs else 0)
+    finally:
+        Stepper.replay = inner
+        del m.use_graphs                                              # back to the class default
+    assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
+
+
+# ------------------------------------------------------------------ 5. twenty steps against a hundred
+def test_twenty_steps_are_closer_to_sample_1000_than_sample_100_is():
+    """All on the GPU, fp16 point U-Net, x_T of seed 7.  The same comparison on the CPU oracle in float: 8.3e-4 against 1.21e-2.
+    Measured on an MI355X: 8.4e-4 against 1.21e-2."""
+    m = model_of("pointnet", "fp16")
+    x_T = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(7)).cuda()
+    want = m.sample(B, N, num_steps=1000, x_T=x_T)
+    fast = rel_l2(m.sample_dpm(B, N, num_steps=20, x_T=x_T).cpu(), want.cpu())
+    slow = rel_l2(m.sample(B, N, num_steps=100, x_T=x_T).cpu(), want.cpu())
+    print(f"rel-L2 against sample(1000): sample_dpm(20) {fast:.3e}, sample(100) {slow:.3e}")
+    assert fast < slow, (fast, slow)
+
+
+# ------------------------------------------------------------------ 6. Philox stream and sharding
+def test_philox_stream_position_is_samples():
+    m = model_of("pointnet", "fp16")
+    reseed(m)
+    m.sample(B, N, num_steps=K)
+    end = m._philox_offset
+    after_sample = m._randn_like(torch.empty(B, N, 3, device="cuda"))
+    reseed(m)
+    a = m.sample_dpm(B, N, num_steps=K)
+    assert m._philox_offset == end == B * N * 3 // 4                  # one draw: the start state
+    assert torch.equal(m._randn_like(torch.empty(B, N, 3, device="cuda")), after_sample)
+    b = m.sample_dpm(B, N, num_steps=K)
+    reseed(m)
+    c = m.sample_dpm(B, N, num_steps=K)
+    assert torch.equal(a, c) and not torch.equal(a, b)
+    # the start draw is `sample`'s: order 1 on the uniform grid from the drawn start is `sample` from the drawn start
+    reseed(m)
+    want = m.sample(B, N, num_steps=K)
+    reseed(m)
+    assert torch.equal(m.sample_dpm(B, N, num_steps=K, order=1, spacing="uniform"), want)
+
+
+def test_halves_under_shard_context_equal_the_whole_batch():
+    from shapegen_amd import dist as D
+    m = model_of("pointnet", "fp16")
+    reseed(m)
+    whole = m.sample_dpm(4, N, num_steps=K)
+    end = m._philox_offset
+    halves = []
+    for lo in (0, 2):
+        reseed(m)
+        with D.shard_context(m, lo, 4):
+            halves.append(m.sample_dpm(2, N, num_steps=K))
+        assert m._philox_offset == end                               # a rank advances by the GLOBAL span
+    assert torch.equal(torch.cat(halves), whole)
+    assert not torch.equal(halves[0][0], halves[1][0])
+    reseed(m)
+    assert torch.equal(D.sample_sharded(m, 4, N, K, sampler="sample_dpm"), whole)      # no process group: one shard
+
+
+def test_sample_sharded_as_a_forced_one_rank_world():
+    """`dist.sample_sharded(sampler="sample_dpm")` through the collective branch (one rank, PCD_DIST_FORCE_COLLECTIVE=1, RCCL on
+    device tensors) in a child process, against `sample_dpm` of the same seed there."""
+    import socket
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = str(sock.getsockname()[1])
+    env = {k: v for k, v in os.environ.items() if k not in ("PCD_BENCH_SHARE_GPU",)}
+    env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=port, PYTHONPATH=ROOT,
+               HSA_ENABLE_IPC_MODE_LEGACY="0", PCD_DIST_FORCE_COLLECTIVE="1", PCD_COLLECTIVE_TIMEOUT_S="120")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "dpm_one_rank_worker.py")], env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
+    res = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    assert res["backend"] == "nccl" and res["world"] == 1
+    for k in ("drawn_equal", "injected_equal", "gathered_copy", "finite"):
+        assert res[k] is True, k
+
+
+# ------------------------------------------------------------------ 7. the latent process
+def test_latent_sample_dpm_against_the_statement():
+    """B = 4, K = 12 on the per-layer launches; the bound is the latent samplers' (tests/test_gpu_latent.py: rel-L2 < 5e-3, fp16).
+    Measured on an MI355X: 3.9e-4."""
+    from shapegen_amd.diffusion import LatentDiffusion
+    from shapegen_amd.vae import VAE3DLarge
+    sd = latent_sd()
+    ldm = LatentDiffusion(VAE3DLarge())
+    ldm.load_state_dict(sd, strict=True)
+    ldm = ldm.to("cuda").eval()
+    z_T = torch.randn(4, 256, generator=torch.Generator().manual_seed(3))
+    want = S.sample_dpm(lambda z, t: O.latent_unet(sd, "model.", z, t), z_T, K)
+
+    def no_persist(*a, **k):
+        raise AssertionError("sample_dpm entered the persistent latent kernel")
+    ldm.model.ddim_steps_persist = no_persist
+    pcs, z0 = ldm.sample_dpm(4, num_steps=K, z_T=z_T.cuda(), return_latent=True)
+    r = rel_l2(z0.cpu(), want)
+    print(f"latent sample_dpm vs statement: rel-L2 {r:.3e}")
+    assert z0.shape == (4, 256) and r < 5e-3, r
+    assert len(pcs) == 4 and all(p.dim() == 2 and p.shape[1] == 3 for p in pcs)
+    only = ldm.sample_dpm(4, num_steps=K, z_T=z_T.cuda())
+    assert len(only) == 4 and all(torch.equal(a, b) for a, b in zip(only, pcs))
+    torch.manual_seed(5)
+    ldm._philox_offset = 0
+    _, drawn = ldm.sample_dpm(4, num_steps=K, return_latent=True)
+    assert torch.isfinite(drawn).all() and ldm._philox_offset == 4 * 256 // 4
+
+
+# ------------------------------------------------------------------ 8. the entry script
+def _generate(tmp_path, *extra):
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "generate_point_ddpm.py"), "--num-samples", "2", "--num-points", "128",
+                        "--steps", "12", *extra, "--out", str(tmp_path / "o")], cwd=str(tmp_path), env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    z = np.load(tmp_path / "o" / "generated.npz")
+    assert z["samples"].shape == (2, 128, 3) and np.isfinite(z["samples"]).all()
+    assert str(z["sampler"]) == "dpm" and int(z["steps"]) == 12
+    return z, open(tmp_path / "test" / "logs" / "point_ddpm_generate.log").read()
+
+
+def test_generate_point_ddpm_script(tmp_path):
+    z, log = _generate(tmp_path)
+    assert "compare_chamfer" not in z.files and "sampler dpm, 12 steps" in log
+    assert not np.array_equal(z["samples"][0], z["samples"][1])
+
+
+def test_generate_point_ddpm_script_compares_with_sample(tmp_path):
+    z, log = _generate(tmp_path, "--compare-steps", "24")
+    assert z["compare_chamfer"].shape == (2,) and np.isfinite(z["compare_chamfer"]).all()
+    assert "Chamfer Distance to sample at 24 steps" in log
