@@ -137,6 +137,8 @@ _SIGS = {
     "pcd_step_select": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp]),
     "pcd_randn_step": (i32, [vp, i64, u64, u64, u64, vp, vp]),
     "pcd_step_select_cols": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, vp, vp]),
+    "pcd_step_select_labels": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]),
+    "pcd_cfg_combine": (i32, [vp, vp, vp, i32, i64, i64, vp]),
     "pcd_complete_start": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i32, vp]),
     "pcd_complete_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i64, i32, vp, vp, vp]),
     "pcd_complete_update_philox": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, i64, i32, i32, vp, vp, u64, u64, u64, u64, vp, vp]),
@@ -314,6 +316,8 @@ _SIGS = {
     "pcd_grad_norm_f32": (i32, [vp, i64, f32, f32, i32, f32, f32, vp, vp]),
     "pcd_adamw_guarded_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp]),
     "pcd_grad_accumulate_f32": (i32, [vp, vp, i64, i32, vp]),
+    "pcd_embed_add_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "pcd_embed_rows_backward": (i32, [vp, vp, i32, i32, i32, vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

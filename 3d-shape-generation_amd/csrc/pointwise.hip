@@ -766,3 +766,93 @@ extern "C" int pcd_dpm_update(const float* x, const float* eps, const float* rat
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
+
+// ------------------------------------------------------------ classifier-free guidance
+// step_select_kernel for a class-conditional run: instead of one copy of row k of the time-bias table it writes batch + 1 rows,
+// row b = tb_table[k] + class_bias[labels[b]] and row `batch` = tb_table[k] + class_bias[null_row] (one fp32 add per element), so
+// the conditional forward reads row 0 with shape stride 1 and the unconditional forward row `batch` with stride 0.  A label outside
+// [0, class_rows) is read as null_row.  Rates and counter exactly as step_select_kernel; one block (the counter has one writer).
+__global__ __launch_bounds__(1024) void step_select_labels_kernel(int* __restrict__ counter, int n_steps,
+                                                                   const float* __restrict__ tb_table, int tb_elems,
+                                                                   float* __restrict__ tb_rows, const float* __restrict__ class_bias,
+                                                                   int class_rows, const int* __restrict__ labels, int batch,
+                                                                   int null_row, const float* __restrict__ rate_tables, int cols,
+                                                                   int width, float* __restrict__ rates_cur) {
+    int k = counter[0];
+    k = k < n_steps ? k : n_steps - 1;
+    for (int i = threadIdx.x; i < (batch + 1) * tb_elems; i += blockDim.x) {
+        const int b = i / tb_elems, e = i - b * tb_elems;
+        int c = null_row;
+        if (b < batch) {
+            const int l = labels[b];
+            if (l >= 0 && l < class_rows) c = l;
+        }
+        tb_rows[i] = tb_table[(int64_t)k * tb_elems + e] + class_bias[(int64_t)c * tb_elems + e];
+    }
+    for (int i = threadIdx.x; i < cols * width; i += blockDim.x) {
+        const int tbl = i / width, j = i - tbl * width;
+        rates_cur[i] = rate_tables[((int64_t)tbl * n_steps + k) * width + j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { counter[1] = k; counter[0] = k + 1; }
+}
+
+// eps = eps_u + w * (eps - eps_u) in place, w per shape (w_stride 1) or shared (0).  VEC as in the AdamW kernel: lane i owns the floats
+// [4 i, 4 i + 4) (16-byte accesses, both pointers 16-byte aligned), lane n / 4 the n % 4 tail; not VEC: one element per lane.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float cfg_elem(float ec, float eu, float w) {
+    const float d = ec - eu;
+    const float wd = w * d;
+    return eu + wd;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_combine_kernel(float* eps, const float* __restrict__ eps_u, const float* __restrict__ w,
+                                                           int w_stride, int64_t n, int64_t per_shape) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        if (i < n4) {
+            float4 c = reinterpret_cast<float4*>(eps)[i];
+            const float4 u = reinterpret_cast<const float4*>(eps_u)[i];
+            const int64_t j = i * 4;
+            c.x = cfg_elem(c.x, u.x, w[(j / per_shape) * w_stride]);
+            c.y = cfg_elem(c.y, u.y, w[((j + 1) / per_shape) * w_stride]);
+            c.z = cfg_elem(c.z, u.z, w[((j + 2) / per_shape) * w_stride]);
+            c.w = cfg_elem(c.w, u.w, w[((j + 3) / per_shape) * w_stride]);
+            reinterpret_cast<float4*>(eps)[i] = c;
+        } else if (i == n4) {
+            for (int64_t j = n4 * 4; j < n; ++j) eps[j] = cfg_elem(eps[j], eps_u[j], w[(j / per_shape) * w_stride]);
+        }
+    } else {
+        if (i >= n) return;
+        eps[i] = cfg_elem(eps[i], eps_u[i], w[(i / per_shape) * w_stride]);
+    }
+}
+#pragma clang fp contract(fast)
+
+extern "C" int pcd_step_select_labels(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_rows,
+                                      const float* class_bias, int class_rows, const int* labels, int batch, int null_row,
+                                      const float* rate_tables, int cols, int width, float* rates_cur, void* stream) {
+    PCD_CHECK_ARG(counter && tb_table && tb_rows && class_bias && labels && rate_tables && rates_cur);
+    PCD_CHECK_ARG(n_steps > 0 && tb_elems > 0 && width > 0 && cols > 0 && cols <= 16);
+    PCD_CHECK_ARG(batch > 0 && class_rows > 0 && null_row >= 0 && null_row < class_rows);
+    PCD_CHECK_ARG(((int64_t)batch + 1) * tb_elems <= (int64_t)1 << 30);
+    hipLaunchKernelGGL(step_select_labels_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counter, n_steps, tb_table, tb_elems,
+                       tb_rows, class_bias, class_rows, labels, batch, null_row, rate_tables, cols, width, rates_cur);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_cfg_combine(float* eps, const float* eps_u, const float* w, int w_stride, int64_t n, int64_t per_shape,
+                               void* stream) {
+    PCD_CHECK_ARG(eps && eps_u && w && n > 0 && per_shape > 0 && (w_stride == 0 || w_stride == 1));
+    if ((((uintptr_t)eps | (uintptr_t)eps_u) & 15) == 0)
+        hipLaunchKernelGGL((cfg_combine_kernel<true>), dim3(nblk(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, eps, eps_u, w, w_stride, n,
+                           per_shape);
+    else
+        hipLaunchKernelGGL((cfg_combine_kernel<false>), dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, eps, eps_u, w, w_stride, n,
+                           per_shape);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}

@@ -1364,3 +1364,45 @@ extern "C" int pcd_bias_act_f16(const void* x, const float* bias, int64_t rows, 
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
+
+// ------------------------------------------------------------ class embedding (classifier-free guidance)
+// forward: temb[b][:] += table[labels[b]][:], one lane per element.  backward: dtable[c][j] = the sum of dtemb[b][j] over the shapes
+// with labels[b] == c in ascending b, one lane per (c, j), no atomics: a row without shapes is written as zero and two runs agree
+// bitwise.  A label outside [0, rows) adds nothing and receives nothing (the host validates them).
+__global__ __launch_bounds__(256) void embed_add_rows_kernel(float* __restrict__ temb, const float* __restrict__ table,
+                                                              const int* __restrict__ labels, int batch, int dim, int rows) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)batch * dim) return;
+    const int b = (int)(i / dim), j = (int)(i - (int64_t)b * dim);
+    const int c = labels[b];
+    if (c < 0 || c >= rows) return;
+    temb[i] = temb[i] + table[(int64_t)c * dim + j];
+}
+
+__global__ __launch_bounds__(256) void embed_rows_backward_kernel(const float* __restrict__ dtemb, const int* __restrict__ labels,
+                                                                   int batch, int dim, int rows, float* __restrict__ dtable) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)rows * dim) return;
+    const int c = (int)(i / dim), j = (int)(i - (int64_t)c * dim);
+    float acc = 0.f;
+    for (int b = 0; b < batch; ++b)
+        if (labels[b] == c) acc += dtemb[(int64_t)b * dim + j];
+    dtable[i] = acc;
+}
+
+extern "C" int pcd_embed_add_rows(float* temb, const float* table, const int* labels, int batch, int dim, int rows, void* stream) {
+    PCD_CHECK_ARG(temb && table && labels && batch > 0 && dim > 0 && rows > 0);
+    hipLaunchKernelGGL(embed_add_rows_kernel, dim3(nblk256((int64_t)batch * dim)), dim3(256), 0, (hipStream_t)stream, temb, table, labels,
+                       batch, dim, rows);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+extern "C" int pcd_embed_rows_backward(const float* dtemb, const int* labels, int batch, int dim, int rows, float* dtable,
+                                       void* stream) {
+    PCD_CHECK_ARG(dtemb && labels && dtable && batch > 0 && dim > 0 && rows > 0);
+    hipLaunchKernelGGL(embed_rows_backward_kernel, dim3(nblk256((int64_t)rows * dim)), dim3(256), 0, (hipStream_t)stream, dtemb, labels,
+                       batch, dim, rows, dtable);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}

@@ -71,13 +71,20 @@ def convert_dd_to_npz(src_dir: str, dst_dir: str) -> int:
 
 
 class PointCloudDataModule:
-    """reference data.py:11-46: in-memory clouds -> random 80/20 split -> loaders."""
+    """reference data.py:11-46: in-memory clouds -> random 80/20 split -> loaders.  With `labels` (one integer per cloud,
+    not in the reference) an item is (cloud, int64 label)."""
 
-    def __init__(self, point_clouds, batch_size=32, train_val_split=0.8):
+    def __init__(self, point_clouds, batch_size=32, train_val_split=0.8, labels=None):
         self.point_clouds, self.batch_size, self.train_val_split = point_clouds, batch_size, train_val_split
+        self.labels = labels
+        if labels is not None and len(labels) != len(point_clouds):
+            raise ValueError(f"{len(labels)} labels for {len(point_clouds)} clouds")
 
     def setup(self, stage=None):
-        dataset = TensorDataset(torch.FloatTensor(np.asarray(self.point_clouds)))
+        tensors = [torch.FloatTensor(np.asarray(self.point_clouds))]
+        if self.labels is not None:
+            tensors.append(torch.as_tensor(np.asarray(self.labels), dtype=torch.int64))
+        dataset = TensorDataset(*tensors)
         train_size = int(self.train_val_split * len(dataset))
         self.train_dataset, self.val_dataset = torch.utils.data.random_split(dataset, [train_size, len(dataset) - train_size])
 
@@ -90,10 +97,11 @@ class PointCloudDataModule:
 
 class PointCloudDataset(Dataset):
     """reference data.py:48-311.  Returns a float32 tensor: (1,R,R,R) in 'voxels' output mode, (num_points,3)
-    in 'point_clouds' output mode."""
+    in 'point_clouds' output mode.  `return_labels` (not in the reference; voxel file mode only): an item is (tensor, int64
+    label), the label being the index of the file's category in `categories`, the sorted distinct categories after filtering."""
 
     def __init__(self, data_dir, num_points=2048, transform=None, input_mode="voxels", output_mode="voxels",
-                 normalize=True, jitter=True, rotate=False, resolution=32, relevant_object_categories=None):
+                 normalize=True, jitter=True, rotate=False, resolution=32, relevant_object_categories=None, return_labels=False):
         self.data_dir = data_dir
         self.transform = transform
         self.num_points = num_points
@@ -107,6 +115,16 @@ class PointCloudDataset(Dataset):
         self.relevant_object_categories = ["all"] if relevant_object_categories is None else relevant_object_categories
         self.shapenet_id_to_category = SHAPENET_ID_TO_CATEGORY
         self.filter_file_list()
+        self.return_labels = bool(return_labels)
+        self.categories: List[str] = []
+        if self.return_labels:
+            if input_mode != "voxels":
+                raise ValueError("return_labels needs input_mode='voxels': only those file names carry the ShapeNet synset id")
+            self.categories = sorted({self.category_of(f) for f in self.file_list})
+
+    def category_of(self, file_name: str) -> str:
+        """The ShapeNet category of a voxel file (its synset id is the 5th '_' field of the name)."""
+        return self.shapenet_id_to_category[file_name.split("_")[4]]
 
     def filter_file_list(self):
         """data.py:140-152: keep files whose synset id (5th '_' field) maps to a requested category."""
@@ -119,6 +137,12 @@ class PointCloudDataset(Dataset):
         return len(self.file_list)
 
     def __getitem__(self, idx):
+        item = self._load(idx)
+        if self.return_labels:
+            return item, torch.tensor(self.categories.index(self.category_of(self.file_list[idx])), dtype=torch.int64)
+        return item
+
+    def _load(self, idx):
         file_path = os.path.join(self.data_dir, self.file_list[idx])
         if self.input_mode == "voxels":
             voxels = load_sample_file(file_path)
@@ -219,7 +243,8 @@ class PointCloudDataDirectoryModule:
 
     def __init__(self, data_dir, num_points=2048, batch_size=32, num_workers=4, train_val_split=0.8,
                  file_mode="voxels", output_mode="point_clouds", augmentations=True, normalization=True,
-                 relevant_object_categories: Optional[Sequence[str]] = None):
+                 relevant_object_categories: Optional[Sequence[str]] = None, return_labels=False):
+        self.return_labels = return_labels
         self.data_dir, self.num_points, self.batch_size, self.num_workers = data_dir, num_points, batch_size, num_workers
         self.train_val_split, self.file_mode, self.output_mode = train_val_split, file_mode, output_mode
         self.augmentations, self.normalization = augmentations, normalization
@@ -230,7 +255,10 @@ class PointCloudDataDirectoryModule:
                   normalize=self.normalization, relevant_object_categories=self.relevant_object_categories)
         if not self.augmentations:
             kw.update(rotate=False, jitter=False)
+        if self.return_labels:
+            kw.update(return_labels=True)
         full = PointCloudDataset(self.data_dir, **kw)
+        self.categories = full.categories
         train_size = int(self.train_val_split * len(full))
         self.train_dataset, self.val_dataset = torch.utils.data.random_split(full, [train_size, len(full) - train_size])
 

@@ -391,10 +391,11 @@ class _DiffusionBase(nn.Module):
     use_graphs = True          # 100 us latent step was launch-bound at one step per graph)
 
     def _run(self, x, tab: "StepTable", bias_table: torch.Tensor, forward, kind: str, noises=None,
-             skip_last_update: bool = False, known=None):
+             skip_last_update: bool = False, known=None, guide=None):
         """kind 'ddim' | 'ddpm' | 'dpm' (`tab` a DpmTable) | 'complete' (`known` = (p, counts) on the device, `tab` a CompletionTable).
-        forward(x, tb_cur, eps_out) enqueues the denoiser for the current step."""
-        stp = Stepper(self, x, tab, bias_table, forward, kind, noises, known)
+        forward(x, tb_cur, eps_out) enqueues the denoiser for the current step.  `guide` = (class_bias, labels, w) of a
+        class-conditional run (`PointCloudDiffusion._guide`)."""
+        stp = Stepper(self, x, tab, bias_table, forward, kind, noises, known, guide)
         T = tab.steps
         last_updates = not (skip_last_update or kind in ("ddpm", "complete"))     # ddpm: x_t = x_0 at i = 0, no update
         n_uniform = T if last_updates else T - 1                       # steps that all look the same
@@ -425,9 +426,14 @@ class Stepper:
     """One timestep = select (device side: copy step k's time bias and rates to fixed buffers, k++) ->
     denoiser forward -> fused update, all on fixed pointers and with the state updated in place, so the
     same enqueue is valid for every k.  Long runs capture it once in a HIP graph and replay it (host
-    cost per step: one graph launch instead of ~30 kernel launches)."""
+    cost per step: one graph launch instead of ~30 kernel launches).
 
-    def __init__(self, owner, x, tab: StepTable, bias_table, forward, kind, noises=None, known=None):
+    With `guide` = (class_bias (rows, tb_elems), labels (B,) int32, w (1,) | (B,) fp32 | None) the select composes one bias row
+    per shape plus the null-class row (`pcd_step_select_labels`), the forward is conditional, and unless w is None (every
+    guidance scale exactly 1) a second, unconditional forward of the same x and `pcd_cfg_combine` follow; eps then holds the
+    guided prediction the update kernel reads.  Without `guide` the enqueue is what it was before guidance existed."""
+
+    def __init__(self, owner, x, tab: StepTable, bias_table, forward, kind, noises=None, known=None, guide=None):
         self.lib = _lib.load()
         self.x, self.tab, self.forward, self.kind, self.noises = x, tab, forward, kind, noises
         dev = x.device
@@ -440,6 +446,12 @@ class Stepper:
         self.tb_cur = torch.empty(self.tb_elems, dtype=torch.float32, device=dev)
         self.rates_cur = torch.empty(self.cols * self.R, dtype=torch.float32, device=dev)
         self.eps = torch.empty_like(x)
+        self.guide = guide
+        if guide is not None:
+            self.class_bias, self.labels, self.w = guide
+            self.tb_rows = torch.empty(x.shape[0] + 1, self.tb_elems, dtype=torch.float32, device=dev)
+            self.tb_null = self.tb_rows[x.shape[0]]
+            self.eps_u = torch.empty_like(x) if self.w is not None else None
         self.x0 = torch.empty_like(x)
         self.z = torch.empty_like(x) if kind == "ddpm" or (kind == "complete" and noises is not None) else None
         self.per_shape = x.numel() // x.shape[0]
@@ -462,9 +474,20 @@ class Stepper:
         lib, x, R = self.lib, self.x, self.R
         st = _lib.stream_ptr()
         rp = self.rates_cur.data_ptr()
-        _lib.check(lib.pcd_step_select_cols(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
-                                            self.tb_cur.data_ptr(), self.rates.data_ptr(), self.cols, R, rp, st), "step_select")
-        self.forward(x, self.tb_cur, self.eps)
+        if self.guide is None:
+            _lib.check(lib.pcd_step_select_cols(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
+                                                self.tb_cur.data_ptr(), self.rates.data_ptr(), self.cols, R, rp, st), "step_select")
+            self.forward(x, self.tb_cur, self.eps)
+        else:
+            cb = self.class_bias
+            _lib.check(lib.pcd_step_select_labels(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
+                                                  self.tb_rows.data_ptr(), cb.data_ptr(), cb.shape[0], self.labels.data_ptr(), x.shape[0],
+                                                  cb.shape[0] - 1, self.rates.data_ptr(), self.cols, R, rp, st), "step_select_labels")
+            self.forward(x, self.tb_rows, self.eps, 1)
+            if self.w is not None:                        # same x, same workspace: eps_u, then eps = eps_u + w (eps - eps_u)
+                self.forward(x, self.tb_null, self.eps_u, 0)
+                _lib.check(lib.pcd_cfg_combine(self.eps.data_ptr(), self.eps_u.data_ptr(), self.w.data_ptr(), int(self.w.numel() > 1),
+                                               x.numel(), self.per_shape, st), "cfg_combine")
         nxt = x.data_ptr() if update else 0               # in place: every element is read before it is written
         if self.kind == "complete":
             return self._complete_update(k, nxt, st)
@@ -532,16 +555,28 @@ class PointCloudDiffusion(_DiffusionBase):
     """Drop-in for reference diffusion.py:14-358 (sampling surface)."""
     _sample_dims = 2   # one sample is (N, 3)
 
-    def __init__(self, num_points, dim=256, time_dim=256, lr=1e-4, noise_schedule="cosine", backbone="pointnet"):
-        """`backbone` is this build's one addition to the reference signature: "pointnet" =
+    def __init__(self, num_points, dim=256, time_dim=256, lr=1e-4, noise_schedule="cosine", backbone="pointnet", num_classes=0,
+                 p_uncond=0.1):
+        """`num_classes` > 0 (not in the reference) makes the denoiser class-conditional (`UNetPointNetLarge.class_emb`, pointnet
+        backbone only): the samplers take `labels` and `guidance_scale` (classifier-free guidance), and training replaces each
+        label by the null class `num_classes` with probability `p_uncond`.  Both enter `hparams` only for a class model.
+        `backbone` is this build's other addition to the reference signature: "pointnet" =
         UNetPointNetLarge, the denoiser diffusion.py:28 wires in; "attention" = UNetAttentionPointExperimental
         (networks.py:597-722), which the reference only reaches by editing the import at diffusion.py:11.  The
         state_dict keys are `model.*` of the chosen class either way."""
         super().__init__()
         self.hparams = _HParams(num_points=num_points, dim=dim, time_dim=time_dim, lr=lr,
                                 noise_schedule=noise_schedule)
+        num_classes = int(num_classes)
+        if num_classes < 0 or not 0.0 <= float(p_uncond) <= 1.0:
+            raise ValueError(f"num_classes must be >= 0 and p_uncond in [0, 1], got {num_classes} and {p_uncond}")
+        if num_classes and backbone != "pointnet":
+            raise ValueError(f"class conditioning (num_classes={num_classes}) is available for backbone 'pointnet' only, got {backbone!r}")
+        if num_classes:
+            self.hparams["num_classes"], self.hparams["p_uncond"] = num_classes, float(p_uncond)
+        self.num_classes, self.p_uncond = num_classes, float(p_uncond)
         if backbone == "pointnet":
-            self.model = UNetPointNetLarge(dim, time_dim)
+            self.model = UNetPointNetLarge(dim, time_dim, num_classes)
         elif backbone == "attention":
             from .networks import UNetAttentionPointExperimental
             self.model = UNetAttentionPointExperimental(num_points, dim=dim, time_dim=time_dim)
@@ -560,12 +595,55 @@ class PointCloudDiffusion(_DiffusionBase):
         from .checkpoint import load_lightning_checkpoint
         hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
-        obj = cls(**{k: hp[k] for k in ("num_points", "dim", "time_dim", "lr", "noise_schedule", "backbone") if k in hp})
+        obj = cls(**{k: hp[k] for k in ("num_points", "dim", "time_dim", "lr", "noise_schedule", "backbone", "num_classes", "p_uncond")
+                     if k in hp})
         obj.load_state_dict(sd, strict=True)
         return obj
 
     def _forward_fn(self):
-        return lambda x, tb_cur, eps: self.model.forward_with_bias(x, tb_cur, 0, out=eps)
+        return lambda x, tb_cur, eps, stride=0: self.model.forward_with_bias(x, tb_cur, stride, out=eps)
+
+    # ------------------------------------------------------------------ class conditioning
+    def _guide(self, labels, guidance_scale, batch: int):
+        """Validate `labels` / `guidance_scale` on the host.  None for a model without classes (labels or a scale other
+        than 1 raise), else the Stepper's (class_bias, labels (B,) int32, w): w is None when every scale is exactly 1 (the
+        unconditional forward is skipped), a (1,) fp32 tensor for one scale, (B,) for one per shape."""
+        w = torch.as_tensor(guidance_scale).detach().to("cpu")
+        if w.is_complex() or w.dtype == torch.bool or w.dim() > 1 or (w.dim() == 1 and w.shape[0] != batch):
+            raise ValueError(f"guidance_scale must be a number or a ({batch},) tensor, got {tuple(w.shape)} {w.dtype}")
+        w = w.to(torch.float32)
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("guidance_scale must be finite")
+        off = bool((w == 1.0).all())
+        if not self.num_classes:
+            if labels is not None:
+                raise ValueError("labels were given to a model without classes (num_classes=0)")
+            if not off:
+                raise ValueError("guidance_scale other than 1 needs a class-conditional model (num_classes > 0)")
+            return None
+        lab = self.model.check_labels(labels, batch)
+        return self.model.class_bias(), lab, None if off else w.reshape(-1).to(self.device).contiguous()
+
+    def _split_batch(self, batch):
+        """(clouds, labels or None) of a training batch: a tensor, or a (clouds, labels) pair."""
+        if isinstance(batch, (tuple, list)):
+            if len(batch) != 2:
+                raise ValueError(f"a labelled batch is (clouds, labels), got {len(batch)} entries")
+            return batch[0], batch[1]
+        return batch, None
+
+    def _training_labels(self, labels, batch: int, drop: bool):
+        """Device labels of a training (drop: each replaced by the null class with probability p_uncond, one torch.rand draw
+        after t's) or validation batch.  A model without classes draws nothing and returns None."""
+        if not self.num_classes:
+            if labels is not None:
+                raise ValueError("a labelled batch was given to a model without classes (num_classes=0)")
+            return None
+        lab = self.model.check_labels(labels, batch)
+        if drop:
+            null = torch.full_like(lab, self.num_classes)
+            lab = torch.where(torch.rand(batch, device=self.device) < self.p_uncond, null, lab)
+        return lab
 
     # ------------------------------------------------------------------ training surface (diffusion.py:56-86, 170-186)
     def configure_optimizers(self):
@@ -578,16 +656,23 @@ class PointCloudDiffusion(_DiffusionBase):
         return {"optimizer": self._trainer,
                 "lr_scheduler": {"scheduler": ReduceLROnPlateau(self._trainer, factor=0.5, patience=5), "monitor": "val_loss"}}
 
-    def diffusion_loss(self, x_0, t, noise=None):
+    def diffusion_loss(self, x_0, t, noise=None, labels=None):
         """diffusion.py:170-186: L1 between the drawn noise and the prediction at x_t.  In train() mode the forward
         uses batch statistics and the parameter gradients are left in the trainer (loss and backward are one pass:
-        there is no autograd graph to keep); in eval() mode it is the sampler's folded forward."""
+        there is no autograd graph to keep); in eval() mode it is the sampler's folded forward.  `labels`: the classes of a
+        class-conditional model's batch (None = the null class)."""
         x_t, noise, _, _ = self.add_noise(x_0, t, noise)
         if self.training:
             tr = self.configure_optimizers()["optimizer"]
-            tr.forward(x_t, t.to(self.device, torch.float32))
+            if self.num_classes or labels is not None:
+                tr.forward(x_t, t.to(self.device, torch.float32), labels=labels)
+            else:
+                tr.forward(x_t, t.to(self.device, torch.float32))
             return tr.backward(noise)
-        pred = self.model(x_t, t.to(self.device, torch.float32))
+        if self.num_classes or labels is not None:
+            pred = self.model(x_t, t.to(self.device, torch.float32), labels)
+        else:
+            pred = self.model(x_t, t.to(self.device, torch.float32))
         lib = _lib.load()
         out = torch.empty(1, dtype=torch.float32, device=self.device)
         scratch = torch.empty_like(pred)
@@ -597,15 +682,17 @@ class PointCloudDiffusion(_DiffusionBase):
 
     def training_step(self, batch, batch_idx=0):
         """diffusion.py:70-86: t ~ U(0,1) per shape; returns the loss (gradients are ready for `optimizer.step`)."""
-        x_0 = batch.to(self.device)
+        x_0, labels = self._split_batch(batch)
+        x_0 = x_0.to(self.device)
         t = torch.rand(x_0.shape[0], device=self.device)
-        return self.diffusion_loss(x_0, t)
+        return self.diffusion_loss(x_0, t, labels=self._training_labels(labels, x_0.shape[0], True))
 
     def validation_step(self, batch, batch_idx=0):
         """diffusion.py:88-100 (loss part; the TensorBoard figures of :106-135 are not reproduced)."""
-        x_0 = batch.to(self.device)
+        x_0, labels = self._split_batch(batch)
+        x_0 = x_0.to(self.device)
         t = torch.rand(x_0.shape[0], device=self.device)
-        return self.diffusion_loss(x_0, t)
+        return self.diffusion_loss(x_0, t, labels=self._training_labels(labels, x_0.shape[0], False))
 
     def _start(self, num_samples, num_points, x_T):
         self.eval()
@@ -617,34 +704,44 @@ class PointCloudDiffusion(_DiffusionBase):
         return x_T.to(torch.float32).contiguous().clone()
 
     @torch.no_grad()
-    def sample(self, num_samples, num_points, num_steps=1000, x_T=None):
-        """DDIM (diffusion.py:261-289).  Returns the last x_0.  `x_T` injects the start noise."""
+    def sample(self, num_samples, num_points, num_steps=1000, x_T=None, labels=None, guidance_scale=1.0):
+        """DDIM (diffusion.py:261-289).  Returns the last x_0.  `x_T` injects the start noise.  Class-conditional models:
+        `labels` (B,) integers in [0, num_classes] (num_classes, or None, = unconditional) and `guidance_scale` w, a number or
+        (B,) tensor: eps = eps_u + w (eps_c - eps_u) (classifier-free guidance; w = 1 costs one forward per step).  The
+        arithmetic is tests/cfg_statement.py."""
+        guide = self._guide(labels, guidance_scale, num_samples)
         x = self._start(num_samples, num_points, x_T)
         tab = self.ddim_table(num_steps, num_samples)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim")
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim", guide=guide)
 
     @torch.no_grad()
-    def sample_dpm(self, num_samples, num_points, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, x_T=None):
+    def sample_dpm(self, num_samples, num_points, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, x_T=None, labels=None,
+                   guidance_scale=1.0):
         """Second-order multistep sampling of the probability-flow ODE (DPM-Solver++ 2M, not in the reference): `num_steps` network
         evaluations on a grid uniform in log-SNR from t = 1 to `t_last`.  Returns the last x_0, like `sample`, whose start draw
         it consumes.  Cosine schedule only.  `order=1, spacing="uniform"` is `sample` bit for bit.  The arithmetic is
-        tests/dpm_statement.py."""
+        tests/dpm_statement.py.  `labels`, `guidance_scale`: as in `sample`."""
         self._check_dpm_args(num_steps, order, spacing, t_last)
         if x_T is not None and tuple(x_T.shape) != (num_samples, num_points, 3):
             raise ValueError(f"x_T must be {(num_samples, num_points, 3)}, got {tuple(x_T.shape)}")
+        guide = self._guide(labels, guidance_scale, num_samples)
         tab = self.dpm_table(num_steps, order, spacing, t_last)
         x = self._start(num_samples, num_points, x_T)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update)
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update,
+                         guide=guide)
 
     @torch.no_grad()
-    def sample2(self, num_samples, num_points, num_steps=1000, x_T=None, noises=None):
-        """DDPM ancestral sampling (diffusion.py:225-259).  `noises[j]` injects the j-th draw."""
+    def sample2(self, num_samples, num_points, num_steps=1000, x_T=None, noises=None, labels=None, guidance_scale=1.0):
+        """DDPM ancestral sampling (diffusion.py:225-259).  `noises[j]` injects the j-th draw.  `labels`, `guidance_scale`: as in
+        `sample`."""
+        guide = self._guide(labels, guidance_scale, num_samples)
         x = self._start(num_samples, num_points, x_T)
         tab = self.ddpm_table(num_steps, num_samples)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddpm", noises=noises)
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddpm", noises=noises, guide=guide)
 
     @torch.no_grad()
-    def complete(self, partial, num_points, num_steps=1000, known_counts=None, resample=1, jump=10, x_T=None, noises=None):
+    def complete(self, partial, num_points, num_steps=1000, known_counts=None, resample=1, jump=10, x_T=None, noises=None,
+                 labels=None, guidance_scale=1.0):
         """Shape completion (not in the reference): shape b keeps rows [0, known_counts[b]) of `partial` (B, M, 3), bitwise, as
         the first rows of the (B, num_points, 3) result, and the remaining rows are generated around them.  The loop is
         `sample2` on the unknown rows; after every reverse step the known rows are set to the known points noised forward to
@@ -652,7 +749,8 @@ class PointCloudDiffusion(_DiffusionBase):
         in range(0, T - jump, jump) the whole cloud is noised forward `jump` indices and denoised again, `resample - 1` times
         per index, `T + jump * jumps` network evaluations in all (`completion_rows`).  `x_T` injects the start draw and
         `noises[k]` the k-th later draw in consumption order (one per row, a jump row's second right after its first).
-        The arithmetic is tests/completion_statement.py."""
+        The arithmetic is tests/completion_statement.py.  `labels`, `guidance_scale`: as in `sample` (the known rows stay bitwise
+        the given points whatever the guidance)."""
         T, r, j = int(num_steps), int(resample), int(jump)
         if partial.dim() != 3 or partial.shape[2] != 3 or partial.shape[1] > num_points:
             raise ValueError(f"partial must be (B, M <= {num_points}, 3), got {tuple(partial.shape)}")
@@ -672,6 +770,7 @@ class PointCloudDiffusion(_DiffusionBase):
                 raise ValueError(f"known_counts must lie in [0, {min(M, num_points)}], got [{int(counts.min())}, {int(counts.max())}]")
         if not bool(torch.isfinite(partial).all()):
             raise ValueError("partial has non-finite coordinates")
+        guide = self._guide(labels, guidance_scale, B)
         self._require_cuda(partial)
         x = self._start(B, num_points, x_T)
         p = torch.zeros_like(x)
@@ -680,7 +779,8 @@ class PointCloudDiffusion(_DiffusionBase):
         tab = self.completion_table(T, j, r, B)
         _lib.check(_lib.load().pcd_complete_start(x.data_ptr(), p.data_ptr(), counts.data_ptr(), tab.n.data_ptr(), tab.s.data_ptr(),
                                                   tab.stride, x.numel(), num_points * 3, 3, _lib.stream_ptr()), "complete_start")
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "complete", noises=noises, known=(p, counts))
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "complete", noises=noises, known=(p, counts),
+                         guide=guide)
 
     @torch.no_grad()
     def sample3(self, num_samples, num_points, x=None, start_t=None, num_steps=1000):
@@ -702,8 +802,11 @@ class LatentDiffusion(_DiffusionBase):
     _sample_dims = 1   # one sample is (latent_dim,)
 
     def __init__(self, vae, latent_dim=256, dim=512, time_dim=256, lr=1e-4, noise_schedule="cosine",
-                 is_voxel_based=True):
+                 is_voxel_based=True, num_classes=0):
         super().__init__()
+        if num_classes:
+            raise ValueError("class conditioning is available for PointCloudDiffusion(backbone='pointnet') only: the persistent latent "
+                             "launch carries one time-bias row per step")
         from .networks import SimpleLatentUNetPointNet
         self.hparams = _HParams(latent_dim=latent_dim, dim=dim, time_dim=time_dim, lr=lr,
                                 noise_schedule=noise_schedule, is_voxel_based=is_voxel_based)

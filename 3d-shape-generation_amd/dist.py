@@ -118,22 +118,38 @@ class shard_context:
         return False
 
 
+def _guidance_shard(labels_global, guidance_scale, lo: int, hi: int) -> dict:
+    """The `labels` / `guidance_scale` keywords of this rank's shard [lo, hi) (none when both are at their defaults, so
+    models without the keywords are called as before): labels and a per-shape scale are sliced with the shard."""
+    scale = guidance_scale
+    if isinstance(scale, (torch.Tensor, list, tuple)):
+        scale = torch.as_tensor(scale)
+        if scale.dim() == 1:
+            scale = scale[lo:hi]
+    elif scale == 1.0 and labels_global is None:
+        return {}
+    labels = None if labels_global is None else torch.as_tensor(labels_global)[lo:hi]
+    return {"labels": labels, "guidance_scale": scale}
+
+
 def sample_sharded(model, global_batch: int, num_points: int, num_steps: int, x_T_global: Optional[torch.Tensor] = None,
-                   sampler: str = "sample", gather: bool = True) -> torch.Tensor:
+                   sampler: str = "sample", gather: bool = True, labels_global=None, guidance_scale=1.0) -> torch.Tensor:
     """Each rank denoises its shard of the global batch (zero per-step traffic); the clouds are
     all-gathered at the end when `gather`.  With `x_T_global` (host tensor, same on all ranks) the
-    result is independent of the number of ranks."""
+    result is independent of the number of ranks.  `labels_global` / `guidance_scale` (class-conditional models, same on
+    all ranks) are sliced with the shard."""
     rank, ws = world()
     lo, hi = shard_range(global_batch, rank, ws)
     xs = None if x_T_global is None else x_T_global[lo:hi].to(model.device)
     with shard_context(model, lo, global_batch):
-        out = getattr(model, sampler)(hi - lo, num_points, num_steps=num_steps, x_T=xs)
+        out = getattr(model, sampler)(hi - lo, num_points, num_steps=num_steps, x_T=xs,
+                                      **_guidance_shard(labels_global, guidance_scale, lo, hi))
     return all_gather_rows(out.contiguous()) if gather else out
 
 
 def complete_sharded(model, partial_global: torch.Tensor, counts_global: Optional[torch.Tensor], num_points: int,
                      num_steps: int, resample: int = 1, jump: int = 10, x_T_global: Optional[torch.Tensor] = None,
-                     gather: bool = True) -> torch.Tensor:
+                     gather: bool = True, labels_global=None, guidance_scale=1.0) -> torch.Tensor:
     """`model.complete` on this rank's shard of the global batch of partial clouds (same tensors on all ranks); the
     on-device draws are addressed by global sample index, so the result is independent of the number of ranks."""
     rank, ws = world()
@@ -142,7 +158,8 @@ def complete_sharded(model, partial_global: torch.Tensor, counts_global: Optiona
     counts = None if counts_global is None else counts_global[lo:hi]
     with shard_context(model, lo, partial_global.shape[0]):
         out = model.complete(partial_global[lo:hi].to(model.device), num_points, num_steps=num_steps, known_counts=counts,
-                             resample=resample, jump=jump, x_T=xs)
+                             resample=resample, jump=jump, x_T=xs,
+                             **_guidance_shard(labels_global, guidance_scale, lo, hi))
     return all_gather_rows(out.contiguous()) if gather else out
 
 

@@ -211,12 +211,21 @@ def _time_embed(m: _HandleDenoiser, t: torch.Tensor, mlp_dim: int, c1: int = 0) 
 # ------------------------------------------------------------------ UNetPointNetLarge
 class UNetPointNetLarge(_HandleDenoiser):
     """Drop-in for reference networks.py:724-838: eps = model(x (B,N,3), t (B,)).  fp16 mode: csrc/unet.hip, fp32 mode:
-    csrc/unet_f32.hip (see `_Denoiser`).  The constructor signature stays the reference's."""
+    csrc/unet_f32.hip (see `_Denoiser`).  The constructor signature stays the reference's but for `num_classes` (not in the
+    reference): with num_classes > 0 the module owns `class_emb`, an nn.Embedding(num_classes + 1, dim) registered after the
+    reference's modules (row `num_classes` is the null class of classifier-free guidance), and
+    temb_b = time_mlp(sinusoid(t_b)) + class_emb[label_b].  time enters only as the per-shape bias of enc1.conv1 and that product
+    is linear, so the class term is one more hoisted bias (`class_bias`)."""
 
-    def __init__(self, dim: int = 512, time_dim: int = 256):
+    def __init__(self, dim: int = 512, time_dim: int = 256, num_classes: int = 0):
         super().__init__()
         self.dim, self.time_dim = dim, time_dim
+        self.num_classes = int(num_classes)
+        if self.num_classes < 0:
+            raise ValueError(f"num_classes must be >= 0, got {num_classes}")
         self._build_from_spec(specs.unet_pointnet_large_spec(dim, time_dim))
+        if self.num_classes:
+            self.class_emb = nn.Embedding(self.num_classes + 1, dim)
         # fp16 mode: the narrow layers at the two ends of the U-net (enc1.conv2/3, enc2.conv3, dec1.*, output.0: the direct route from
         # the coordinates to the predicted noise) carry hi / lo weights -- the fp16 weights and the fp16 of their rounding residuals,
         # two MFMA passes, < 2 % of the FLOPs -- because the fp16 rounding of THESE weights is what the 1000-step DDPM trajectory
@@ -277,14 +286,56 @@ class UNetPointNetLarge(_HandleDenoiser):
         """time_mlp(get_timestep_embedding(t)) (networks.py:791-792), for parity tests."""
         return _time_embed(self, t, self.dim)
 
-    def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    def class_bias(self) -> torch.Tensor:
+        """Hoisted class half of enc1.conv1: the folded time columns applied to every row of `class_emb`, without the bias
+        term (`time_bias` carries it), (num_classes + 1, 64) fp32.  It goes through the packed weights `time_bias` uses and
+        is kept with them, so it is rebuilt whenever they are."""
+        if not self.num_classes:
+            raise RuntimeError("class_bias needs a class-conditional model (num_classes > 0)")
+        pk = self._ensure_packed()
+        if "class_bias" not in pk:
+            emb = self.class_emb.weight.detach().to(torch.float32).contiguous()
+            out = torch.empty(emb.shape[0], 64, dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().pcd_linear_f32(emb.data_ptr(), emb.shape[0], self.dim, pk["e1w_t"].data_ptr(), None, 64, out.data_ptr(),
+                                                  _lib.stream_ptr()), "linear_f32")
+            pk["class_bias"] = out
+        return pk["class_bias"]
+
+    def check_labels(self, labels, batch: int) -> Optional[torch.Tensor]:
+        """Host-side validation of a label argument: None on a model without classes, else (batch,) int32 on the device with
+        values in [0, num_classes] (`None` = the null class `num_classes` for every shape)."""
+        if not self.num_classes:
+            if labels is not None:
+                raise ValueError("labels were given to a model without classes (num_classes=0)")
+            return None
+        if labels is None:
+            return torch.full((batch,), self.num_classes, dtype=torch.int32, device=self.device)
+        lab = torch.as_tensor(labels)
+        if lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f"labels must be integers, got {lab.dtype}")
+        if lab.dim() != 1 or lab.shape[0] != batch:
+            raise ValueError(f"labels must be ({batch},), got {tuple(lab.shape)}")
+        if batch and (int(lab.min()) < 0 or int(lab.max()) > self.num_classes):
+            raise ValueError(f"labels must lie in [0, {self.num_classes}] ({self.num_classes} = unconditional), got "
+                             f"[{int(lab.min())}, {int(lab.max())}]")
+        return lab.to(self.device, torch.int32).contiguous()
+
+    def forward(self, x: torch.Tensor, t: torch.Tensor, labels=None) -> torch.Tensor:
         self._need_cuda(x, t)
         if x.dim() != 3 or x.shape[2] != 3:
             raise ValueError(f"x must be (B, N, 3), got {tuple(x.shape)}")
         if t.dim() != 1 or t.shape[0] != x.shape[0]:
             raise ValueError(f"t must be (B,), got {tuple(t.shape)} for batch {x.shape[0]}")
         x = x.to(torch.float32).contiguous()
-        return self.forward_with_bias(x, self.time_bias(t), 1)
+        tb = self.time_bias(t)
+        if getattr(self, "num_classes", 0) or labels is not None:
+            if not hasattr(self, "check_labels"):
+                raise ValueError("labels were given to a model without classes")
+            lab = self.check_labels(labels, x.shape[0])
+            cb = self.class_bias()
+            _lib.check(_lib.load().pcd_embed_add_rows(tb.data_ptr(), cb.data_ptr(), lab.data_ptr(), x.shape[0], 64, cb.shape[0],
+                                                      _lib.stream_ptr()), "embed_add_rows")
+        return self.forward_with_bias(x, tb, 1)
 
     _TAP_WIDTHS = {"x1": 128, "x2": 256, "x3": 512, "x4": 1024, "d4": 512, "d3": 256, "d2": 128, "d1": 64}
 

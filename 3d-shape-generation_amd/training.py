@@ -565,8 +565,9 @@ class PointTrainer(_Trainer):
                                            z0.data_ptr(), self._st()), "enc1_linear")
         return self._bn_relu(self.enc[0][0], z0, self.m, update_stats)
 
-    def forward(self, x_t: torch.Tensor, t: torch.Tensor, update_stats: bool = True) -> torch.Tensor:
-        """eps_hat (B, N, 3) fp32 with the network in train() mode; keeps what backward needs."""
+    def forward(self, x_t: torch.Tensor, t: torch.Tensor, update_stats: bool = True, labels=None) -> torch.Tensor:
+        """eps_hat (B, N, 3) fp32 with the network in train() mode; keeps what backward needs.  `labels`: the classes of a
+        class-conditional model's shapes (None = the null class); their embedding rows are added to the time embedding."""
         lib, st = self.lib, self._st()
         b, n, _ = x_t.shape
         m = b * n
@@ -576,6 +577,15 @@ class PointTrainer(_Trainer):
         self.x = x_t.to(torch.float32).contiguous()
         p = self.p
         temb = self._time_embedding(t)
+        self.labels = None
+        if getattr(self.model, "num_classes", 0):
+            # temb_b += class_emb[label_b]: in place on the buffer enc1.conv1's weight gradient reads (time_mlp.2's backward reads its input)
+            self.labels = self.model.check_labels(labels, b)
+            table = p["class_emb.weight"]
+            self._chk(lib.pcd_embed_add_rows(temb.data_ptr(), table.data_ptr(), self.labels.data_ptr(), b, temb.shape[1], table.shape[0], st),
+                      "embed_add_rows")
+        elif labels is not None:
+            raise ValueError("labels were given to a model without classes (num_classes=0)")
         # enc1.conv1: [xyz | temb] -> 64; the time columns give a per-shape bias
         a = self._enc1(self._lin("enc1.conv1", [(temb, 256)], col0=3), update_stats)
         skips = []
@@ -728,11 +738,15 @@ class PointTrainer(_Trainer):
         dtb = self._enc1_backward(self._chain_backward(self.enc[0][:0:-1], dskip[128], m))
         dtemb = self._buf("bwd.dtemb", (b, 256), torch.float32)
         self._lin_backward("enc1.conv1", dtb, [("set", dtemb)])
+        if self.labels is not None:            # class_emb: the ordered sum of dtemb's rows per class
+            gt = g["class_emb.weight"]
+            self._chk(lib.pcd_embed_rows_backward(dtemb.data_ptr(), self.labels.data_ptr(), b, gt.shape[1], gt.shape[0], gt.data_ptr(), st),
+                      "embed_rows_backward")
         self._time_mlp_backward(dtemb)
         return loss_sum[0] / float(m * 3)
 
-    def train_step(self, x_t: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
-        self.forward(x_t, t, update_stats=True)
+    def train_step(self, x_t: torch.Tensor, t: torch.Tensor, noise: torch.Tensor, labels=None) -> torch.Tensor:
+        self.forward(x_t, t, update_stats=True, **({} if labels is None else {"labels": labels}))
         loss = self.backward(noise)
         self.micro_step()
         return loss
@@ -1497,7 +1511,8 @@ def fit(model, data_module, max_epochs: int = 500, ckpt_dir: Optional[str] = Non
         tl = []
         group = []                             # data parallel: consecutive usable batches are dealt out `world` at a time
         for i, batch in enumerate(data_module.train_dataloader()):
-            if batch.dim() == 3 and batch.shape[0] * batch.shape[1] % 64:
+            clouds = batch[0] if isinstance(batch, (tuple, list)) else batch       # a labelled batch is (clouds, labels)
+            if clouds.dim() == 3 and clouds.shape[0] * clouds.shape[1] % 64:
                 continue                       # ragged last point-cloud batch: the backward-weight GEMM reduces over B*N in 64s
             group.append((i, batch))
             if len(group) < world:

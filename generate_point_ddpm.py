@@ -1,13 +1,16 @@
-"""Generation entry point: draw clouds from a trained unconditional point DDPM with the sampler of choice and save them.
+"""Generation entry point: draw clouds from a trained point DDPM with the sampler of choice and save them.
 
     python generate_point_ddpm.py [--ckpt-dir DIR] [--sampler dpm|ddim|ddpm] [--steps N] [--order 2] [--num-samples 16]
-                                  [--num-points 2048] [--compare-steps 1000] [--out DIR]
+                                  [--num-points 2048] [--compare-steps 1000] [--out DIR] [--label K [--guidance W]]
 
 `--sampler dpm` (default, 20 steps) is `PointCloudDiffusion.sample_dpm`, the second-order multistep solver on a log-SNR grid;
 `ddim` and `ddpm` are the reference's `sample` and `sample2` (default 1000 steps).  With `--compare-steps T` the start state is
 drawn on the host and the Chamfer distance between the result and `sample` at T steps from the same start is logged per
 cloud.  Every `.ckpt` of `--ckpt-dir` is used; without checkpoints (none ship with the reference) a model with deterministic
-synthetic weights runs, so the plumbing is exercised end to end.  Multi-GPU: launch with torch.distributed.run; clouds are
+synthetic weights runs, so the plumbing is exercised end to end.  `--label K` asks a class-conditional checkpoint
+(`train_point_ddpm.py --class-conditional`) for class K, with classifier-free guidance of scale `--guidance W` (1 = off, one
+forward per step; larger trades diversity for fidelity at two forwards per step); the synthetic-weights model then has K + 1
+classes.  Multi-GPU: launch with torch.distributed.run; clouds are
 sharded across ranks and all-gathered.
 """
 from __future__ import annotations
@@ -31,18 +34,19 @@ LOG = "generate_logger_point_ddpm"
 DEFAULT_STEPS = {"dpm": 20, "ddim": 1000, "ddpm": 1000}
 
 
-def generate(model, sampler, total, num_points, steps, order, x_T=None):
+def generate(model, sampler, total, num_points, steps, order, x_T=None, label=None, guidance=1.0):
     """This rank's shard of the global batch, all-gathered: every rank returns all `total` clouds."""
     rank, world = D.world()
     lo, hi = D.shard_range(total, rank, world)
     xs = None if x_T is None else x_T[lo:hi].to(model.device)
+    guide = {} if label is None else {"labels": torch.full((hi - lo,), int(label), dtype=torch.int64), "guidance_scale": guidance}
     with torch.no_grad(), D.shard_context(model, lo, total):
         if sampler == "dpm":
-            out = model.sample_dpm(hi - lo, num_points, num_steps=steps, order=order, x_T=xs)
+            out = model.sample_dpm(hi - lo, num_points, num_steps=steps, order=order, x_T=xs, **guide)
         elif sampler == "ddim":
-            out = model.sample(hi - lo, num_points, num_steps=steps, x_T=xs)
+            out = model.sample(hi - lo, num_points, num_steps=steps, x_T=xs, **guide)
         else:
-            out = model.sample2(hi - lo, num_points, num_steps=steps, x_T=xs)
+            out = model.sample2(hi - lo, num_points, num_steps=steps, x_T=xs, **guide)
     return D.all_gather_rows(out.contiguous())
 
 
@@ -56,7 +60,11 @@ def main():
     ap.add_argument("--num-points", type=int, default=2048)
     ap.add_argument("--compare-steps", type=int, default=0, help="also run `sample` at this many steps from the same start and log the Chamfer distance")
     ap.add_argument("--out", default=os.path.join("test", "outputs"))
+    ap.add_argument("--label", type=int, default=None, metavar="K", help="class to generate (class-conditional models)")
+    ap.add_argument("--guidance", type=float, default=1.0, metavar="W", help="classifier-free guidance scale (needs --label)")
     args = ap.parse_args()
+    if args.label is None and args.guidance != 1.0:
+        ap.error("--guidance needs --label")
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.sampler]
     torch.manual_seed(24)
     rank, world, local = D.init_from_env()
@@ -66,22 +74,29 @@ def main():
     models = [(os.path.basename(path)[:-5], PointCloudDiffusion.load_from_checkpoint(path))
               for path in sorted(glob.glob(os.path.join(args.ckpt_dir, "*.ckpt")))]
     if not models:
-        m = PointCloudDiffusion(num_points=args.num_points)
-        sd = specs.synth_state_dict(specs.unet_pointnet_large_spec(prefix="model."), seed=0, gain=1.3)
+        classes = 0 if args.label is None else args.label + 1
+        m = PointCloudDiffusion(num_points=args.num_points, num_classes=classes)
+        spec = specs.unet_pointnet_large_spec(prefix="model.")
+        if classes:
+            spec = spec + [("model.class_emb.weight", (classes + 1, 256), "w")]
+        sd = specs.synth_state_dict(spec, seed=0, gain=1.3)
         m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
         models.append(("synthetic_weights", m))
     x_T = None
     if args.compare_steps > 0:                                  # the same start on every rank and for both runs
         x_T = torch.randn(args.num_samples, args.num_points, 3, generator=torch.Generator().manual_seed(24))
     result = {"sampler": args.sampler, "steps": steps}
+    if args.label is not None:
+        result.update(label=args.label, guidance=args.guidance)
     for name, model in models:
         model = model.to(device).eval()
-        out = generate(model, args.sampler, args.num_samples, args.num_points, steps, args.order, x_T)
-        log.info(f"{name}: {args.num_samples} clouds of {args.num_points} points, sampler {args.sampler}, {steps} steps")
+        out = generate(model, args.sampler, args.num_samples, args.num_points, steps, args.order, x_T, args.label, args.guidance)
+        log.info(f"{name}: {args.num_samples} clouds of {args.num_points} points, sampler {args.sampler}, {steps} steps"
+                 + ("" if args.label is None else f", class {args.label}, guidance {args.guidance}"))
         tag = "" if len(models) == 1 else "_" + name
         result["samples" + tag] = out.cpu().numpy()
         if x_T is not None:
-            ref = generate(model, "ddim", args.num_samples, args.num_points, args.compare_steps, 1, x_T)
+            ref = generate(model, "ddim", args.num_samples, args.num_points, args.compare_steps, 1, x_T, args.label, args.guidance)
             cd = chamfer_per_sample(out, ref)
             for i, v in enumerate(cd.tolist()):
                 log.info(f"{name} sample {i}: Chamfer Distance to sample at {args.compare_steps} steps {v:.3f}")

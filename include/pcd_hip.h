@@ -178,6 +178,20 @@ int pcd_randn_step(float* out, int64_t n, uint64_t seed, uint64_t base_offset, u
 int pcd_step_select_cols(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_cur,
                          const float* rate_tables, int cols, int width, float* rates_cur, void* stream);
 
+/* ------------------------------------------------ class conditioning with classifier-free guidance (an addition to the
+ * reference's surface).  pcd_step_select_cols for a class-conditional run: with the class-bias table class_bias
+ * [class_rows][tb_elems] and the device int32 labels[batch] it writes tb_rows [batch + 1][tb_elems]: row b = tb_table[k] +
+ * class_bias[labels[b]], row `batch` = tb_table[k] + class_bias[null_row], one fp32 add per element.  The conditional forward
+ * reads row 0 with shape stride 1, the unconditional forward row `batch` with stride 0.  A label outside [0, class_rows) is read
+ * as null_row.  Rates and counter as pcd_step_select_cols, so one captured step serves every k. */
+int pcd_step_select_labels(int* counter, int n_steps, const float* tb_table, int tb_elems, float* tb_rows,
+                           const float* class_bias, int class_rows, const int* labels, int batch, int null_row,
+                           const float* rate_tables, int cols, int width, float* rates_cur, void* stream);
+/* the guidance combine, in place on the conditional prediction: eps[i] = eps_u[i] + w[(i / per_shape) * w_stride] * (eps[i] -
+ * eps_u[i]); w_stride 0 (one scale) or 1 (one per shape).  fp32, no FMA contraction: bitwise the expression as written.  16-byte
+ * accesses when both pointers are 16-byte aligned (the n % 4 tail element by element), else one element per lane. */
+int pcd_cfg_combine(float* eps, const float* eps_u, const float* w, int w_stride, int64_t n, int64_t per_shape, void* stream);
+
 /* ------------------------------------------------ shape completion (an addition to the reference's surface)
  * `PointCloudDiffusion.complete`: shape b knows the first counts[b] rows (of row_elems floats) of p, which has the layout
  * of x; the other rows are generated.  counts: device int32, one per shape.  A row of the step table carries seven
@@ -902,6 +916,14 @@ int pcd_adamw_guarded_step(float* params, const float* grads, float* exp_avg, fl
                            const void* state, void* stream);
 /* acc[i] = grads[i] if first, else acc[i] + grads[i]  (gradient accumulation over micro-batches) */
 int pcd_grad_accumulate_f32(float* acc, const float* grads, int64_t n, int first, void* stream);
+
+/* ------------------------------------------------ class embedding of the class-conditional point denoiser
+ * temb[b][:] += table[labels[b]][:] for temb [batch][dim], table [rows][dim], device int32 labels[batch]; a label outside
+ * [0, rows) adds nothing */
+int pcd_embed_add_rows(float* temb, const float* table, const int* labels, int batch, int dim, int rows, void* stream);
+/* its backward: dtable[c][:] = the sum of dtemb[b][:] over the shapes with labels[b] == c, added in ascending b in fp32, one
+ * lane per (c, column), no atomics (bitwise repeatable); a row without shapes is written as zero */
+int pcd_embed_rows_backward(const float* dtemb, const int* labels, int batch, int dim, int rows, float* dtable, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoint
     python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt weights.ckpt] [--max-steps N]
                                [--backbone {pointnet,attention}] [--resume last.ckpt] [--save-last] [--ema-decay D]
                                [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
+                               [--class-conditional [--p-uncond 0.1]]
 
 `--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
 import); `--ckpt` starts a new run from a checkpoint's weights (with the backbone stored in its hyper-parameters).
@@ -17,6 +18,11 @@ average of the weights, saved next to the raw ones (`PointCloudDiffusion.load_fr
 `--grad-clip` and `--accumulate-grad-batches` are `pl.Trainer(gradient_clip_val=..., accumulate_grad_batches=...)`;
 `--skip-nonfinite` (implied by `--grad-clip`) drops an optimizer step whose gradient holds a NaN or an infinity.  The epoch
 log line then carries the last gradient norm and the clipped / skipped counts.
+
+`--class-conditional` trains a class-conditional model for classifier-free guidance: the data layer labels every cloud with
+its category's index (`--category` takes a comma-separated list, or `all`), the model gets one embedding row per category plus
+the null class, and each label is replaced by the null class with probability `--p-uncond`.  The samples drawn at the end cycle
+through the classes.
 
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
@@ -54,6 +60,29 @@ def synthetic_clouds(count: int, num_points: int, seed: int = 24) -> np.ndarray:
     return out
 
 
+SYNTHETIC_FAMILIES = 3
+
+
+def synthetic_labelled_clouds(count: int, num_points: int, seed: int = 24):
+    """(clouds, labels) for --class-conditional without a data directory: `synthetic_clouds`' recipe in SYNTHETIC_FAMILIES
+    shape families, family f (= cloud index mod the family count, the cloud's label) being the union of f + 1 ellipsoids."""
+    rng = np.random.default_rng(seed)
+    zz, yy, xx = np.meshgrid(*[np.arange(32)] * 3, indexing="ij")
+    out = np.zeros((count, num_points, 3), np.float32)
+    labels = np.arange(count, dtype=np.int64) % SYNTHETIC_FAMILIES
+    for i in range(count):
+        blobs = int(labels[i]) + 1
+        c, r = rng.uniform(8, 24, (blobs, 3)), rng.uniform(3, 9, (blobs, 3))
+        occ = np.zeros((32, 32, 32), bool)
+        for j in range(blobs):
+            occ |= ((zz - c[j, 0]) / r[j, 0]) ** 2 + ((yy - c[j, 1]) / r[j, 1]) ** 2 + ((xx - c[j, 2]) / r[j, 2]) ** 2 <= 1
+        pts = np.stack(np.where(occ), 1).astype(np.float32)
+        pts -= pts.mean(0)
+        pts /= np.linalg.norm(pts, axis=1).max()
+        out[i] = pts[rng.choice(len(pts), num_points, replace=len(pts) < num_points)]
+    return out, labels
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default=None, help="reference-layout .ckpt whose weights start a new run (weights only: see --resume)")
@@ -75,14 +104,29 @@ def main():
     ap.add_argument("--out", default=os.path.join("samples", "point_cloud_diffusion"))
     ap.add_argument("--backbone", choices=("pointnet", "attention"), default="pointnet",
                     help="denoiser of a new model (a resumed checkpoint keeps its own)")
+    ap.add_argument("--class-conditional", action="store_true",
+                    help="train a class-conditional model (classifier-free guidance): one class per category of --category")
+    ap.add_argument("--p-uncond", type=float, default=0.1, help="probability of replacing a training label by the null class")
     args = ap.parse_args()
     torch.manual_seed(24)
     timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     logger = setup_logger("train_point_ddpm", os.path.join("train", "logs", f"train_point_ddpm_log_{timestamp}.log"))
+    num_classes = 0
     if os.path.isdir(args.data_dir):
+        categories = args.category.split(",")
         dm = PointCloudDataDirectoryModule(args.data_dir, num_points=args.num_points, batch_size=args.batch_size, file_mode="voxels",
                                            output_mode="point_clouds", augmentations=False,
-                                           relevant_object_categories=[args.category])
+                                           relevant_object_categories=categories, return_labels=args.class_conditional)
+        if args.class_conditional:
+            from shapegen_amd.data import PointCloudDataset
+            found = PointCloudDataset(args.data_dir, input_mode="voxels", relevant_object_categories=categories, return_labels=True).categories
+            num_classes = len(found)
+            logger.info(f"class-conditional over {num_classes} categories: {found}")
+    elif args.class_conditional:
+        logger.info(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic clouds of {SYNTHETIC_FAMILIES} shape families")
+        clouds, labels = synthetic_labelled_clouds(args.synthetic_shapes, args.num_points)
+        dm = _Unwrap(PointCloudDataModule(clouds, batch_size=args.batch_size, labels=labels))
+        num_classes = SYNTHETIC_FAMILIES
     else:
         logger.info(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic clouds")
         dm = _Unwrap(PointCloudDataModule(synthetic_clouds(args.synthetic_shapes, args.num_points), batch_size=args.batch_size))
@@ -92,8 +136,11 @@ def main():
         assert model.num_points == args.num_points
         if model.backbone != args.backbone:
             logger.info(f"checkpoint backbone {model.backbone!r} is used (--backbone {args.backbone} ignored)")
+        if model.num_classes != num_classes:
+            raise SystemExit(f"the checkpoint's model has {model.num_classes} classes, the data {num_classes} "
+                             "(--class-conditional and --category must match the run that wrote it)")
     else:
-        model = PointCloudDiffusion(num_points=args.num_points, backbone=args.backbone)
+        model = PointCloudDiffusion(num_points=args.num_points, backbone=args.backbone, num_classes=num_classes, p_uncond=args.p_uncond)
     model = model.to("cuda")
     logger.info("Starting Diffusion Training")
     # a resumed run keeps writing where the file it resumed from lies: the restored top-k list prunes the files it names
@@ -102,7 +149,8 @@ def main():
         save_last=args.save_last, ema_decay=args.ema_decay, gradient_clip_val=args.grad_clip,
         accumulate_grad_batches=args.accumulate_grad_batches, skip_nonfinite=args.skip_nonfinite)
     model.eval()
-    samples = model.sample(num_samples=10, num_points=args.num_points, num_steps=args.sample_steps)   # train_point_ddpm.py:91-93
+    guide = {"labels": torch.arange(10) % num_classes} if num_classes else {}
+    samples = model.sample(num_samples=10, num_points=args.num_points, num_steps=args.sample_steps, **guide)   # train_point_ddpm.py:91-93
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "samples.npy"), samples.cpu().numpy())
     print(f"wrote {samples.shape[0]} clouds of {samples.shape[1]} points to {args.out}")
@@ -119,10 +167,10 @@ class _Unwrap:
         self.train_dataset, self.val_dataset = self.dm.train_dataset, self.dm.val_dataset     # their index lists identify the split
 
     def train_dataloader(self):
-        return (b[0] for b in self.dm.train_dataloader())
+        return (b[0] if len(b) == 1 else tuple(b) for b in self.dm.train_dataloader())      # labelled: (clouds, labels)
 
     def val_dataloader(self):
-        return (b[0] for b in self.dm.val_dataloader())
+        return (b[0] if len(b) == 1 else tuple(b) for b in self.dm.val_dataloader())
 
 
 if __name__ == "__main__":
