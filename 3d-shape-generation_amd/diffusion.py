@@ -34,35 +34,30 @@ def _offset_cosine(t: torch.Tensor, min_signal: float, max_signal: float):
     return torch.sin(ang), torch.cos(ang)
 
 
-def _linear(t: torch.Tensor, lo: float, hi: float):
-    """diffusion.py:189-205 (bug-for-bug: cumprod over the batch axis)."""
+def _linear(t: torch.Tensor, lo: float, hi: float, dim: int = 0):
+    """diffusion.py:189-205 (bug-for-bug: cumprod over the batch axis, which is `dim` of t)."""
     betas = lo + t.clone() * (hi - lo)
-    abar = torch.cumprod(1 - betas, dim=0)
+    abar = torch.cumprod(1 - betas, dim=dim)
     return 1 - abar, abar
 
 
 class StepTable:
     """Per-step scalars of one sampler run as fp32 device matrices (T, R): R = 1 when every
     shape shares the rates (cosine schedule), R = batch for the linear schedule whose
-    batch-axis cumprod (diffusion.py:202) gives each shape its own rates."""
+    batch-axis cumprod (diffusion.py:202) gives each shape its own rates.  `skip_last_update`:
+    the last row only predicts x_0 (the reference's `sample` alone updates the state after its last prediction)."""
 
     @staticmethod
-    def _col(rows, device):
-        if isinstance(rows, torch.Tensor):                         # already (T, R): the vectorised cosine tables
-            return rows.to(torch.float32).reshape(rows.shape[0], -1).contiguous().to(device)
-        return torch.stack([torch.as_tensor(x, dtype=torch.float32).reshape(-1) for x in rows]).contiguous().to(device)
+    def _col(v: torch.Tensor, device):
+        return v.to(torch.float32).reshape(v.shape[0], -1).contiguous().to(device)
 
-    def __init__(self, t, n, s, a, b, device):
-        f = lambda rows: self._col(rows, device)
-        if isinstance(t, torch.Tensor):
-            t = t.reshape(t.shape[0], -1)[:, :1]
-        else:
-            t = [x.reshape(-1)[:1] for x in t]
-        self.t, self.n, self.s, self.a, self.b = f(t), f(n), f(s), f(a), f(b)
-        self.t = self.t.reshape(-1)
-        self.steps = len(t)
+    def __init__(self, t, n, s, a, b, device, skip_last_update: bool = False):
+        f = lambda v: self._col(v, device)
+        self.t, self.n, self.s, self.a, self.b = f(t.reshape(t.shape[0], -1)[:, :1]).reshape(-1), f(n), f(s), f(a), f(b)
+        self.steps = t.shape[0]
         self.width = self.n.shape[1]
         self.stride = 0 if self.width == 1 else 1
+        self.skip_last_update = skip_last_update
 
     def offset(self, k: int) -> int:
         return 4 * k * self.width
@@ -96,7 +91,7 @@ class CompletionTable(StepTable):
     one).  `draws[k]` is the index of row k's first normal draw in consumption order; a jump row uses `draws[k] + 1` too."""
 
     def __init__(self, rows, t, n, s, a, b, n2, ja, jb, device):
-        super().__init__(t, n, s, a, b, device)
+        super().__init__(t, n, s, a, b, device, skip_last_update=True)
         self.n2, self.ja, self.jb = (self._col(c, device) for c in (n2, ja, jb))
         self.rows = rows
         self.jumps = any(to is not None for _, to in rows)
@@ -115,9 +110,8 @@ class DpmTable(StepTable):
     predicts x_0; the uniform grid's last row updates as `sample`'s does."""
 
     def __init__(self, t, n, s, n2, s2, c, q, device, skip_last_update: bool):
-        super().__init__(t, n, s, n2, s2, device)
+        super().__init__(t, n, s, n2, s2, device, skip_last_update)
         self.c, self.q = self._col(c, device), self._col(q, device)
-        self.skip_last_update = skip_last_update
 
     def columns(self) -> List[torch.Tensor]:
         return [self.n, self.s, self.a, self.b, self.c, self.q]
@@ -222,115 +216,69 @@ class _DiffusionBase(nn.Module):
     def _width(self, batch: int) -> int:
         return 1 if self.noise_schedule == "cosine" else batch
 
-    def _host_schedule(self, t_cpu: torch.Tensor):
+    def _host_schedule(self, t: torch.Tensor, width: int = 1):
+        """Rates of the (T,) times `t` as (T, width) matrices, all T steps in one set of elementwise ops: row k holds what the
+        reference's schedule call returns for a (width,) vector of t[k] (the same fp32 operations per element; the linear
+        schedule's batch-axis cumprod runs along the row, and over a row of one element -- `sample3`'s 0-d t -- is the identity).
+        tests/table_statement.py is the per-step loop these are checked against, bit for bit."""
+        t = t[:, None].expand(-1, width)
         if self.noise_schedule == "cosine":
-            return _offset_cosine(t_cpu, self.cosine_min_signal_rate, self.cosine_max_signal_rate)
-        return _linear(t_cpu, self.linear_min_rate, self.linear_max_rate)
+            return _offset_cosine(t, self.cosine_min_signal_rate, self.cosine_max_signal_rate)
+        return _linear(t, self.linear_min_rate, self.linear_max_rate, dim=-1)
 
     def ddim_table(self, num_steps: int, batch: int = 1) -> StepTable:
-        """`sample` (diffusion.py:277-286): t_k = 1 - k/T, next_t = t_k - 1/T."""
+        """`sample` (diffusion.py:277-286): t_k = 1 - k/T, next_t = t_k - 1/T.  k * step is formed in float64 and rounded
+        once, like the Python scalar in the reference's `ones - k * step`."""
         w = self._width(batch)
         step = 1.0 / num_steps
-        if w == 1 and self.vectorized_tables:
-            # all T steps in one set of elementwise ops: the same fp32 operations per element as the loop below
-            # (k * step is formed in float64 and rounded once, like the Python scalar in `ones - k * step`), 30 us
-            # of host time per step saved; tests/test_oracle_golden.py checks both forms are bit-identical
-            t = torch.ones(num_steps) - (torch.arange(num_steps, dtype=torch.float64) * step).to(torch.float32)
-            n, s = self._host_schedule(t)
-            nn_, sn = self._host_schedule(t - step)
-            return StepTable(t, n, s, nn_, sn, self.device)
-        ts, ns, ss, n2, s2 = [], [], [], [], []
-        for k in range(num_steps):
-            t = torch.ones(w) - k * step
-            n, s = self._host_schedule(t)
-            nn_, sn = self._host_schedule(t - step)
-            ts.append(t); ns.append(n); ss.append(s); n2.append(nn_); s2.append(sn)
-        return StepTable(ts, ns, ss, n2, s2, self.device)
+        t = torch.ones(num_steps) - (torch.arange(num_steps, dtype=torch.float64) * step).to(torch.float32)
+        n, s = self._host_schedule(t, w)
+        n2, s2 = self._host_schedule(t - step, w)
+        return StepTable(t, n, s, n2, s2, self.device)
+
+    def _ddpm_columns(self, i: torch.Tensor, num_steps: int, width: int):
+        """`sample2`'s scalars (diffusion.py:241-255) at the fp32 time indices `i`, of which only the last is 0:
+        t = i/T, n, s, a = sqrt(n_prev/n), b = s_prev, n_prev."""
+        one = torch.ones(i.shape[0])
+        t = one * i / num_steps
+        n, s = self._host_schedule(t, width)
+        npv, sp = self._host_schedule(one * (i - 1) / num_steps, width)
+        co = torch.sqrt(npv / n)
+        return t, n, s, co, sp, npv
 
     def ddpm_table(self, num_steps: int, batch: int = 1) -> StepTable:
         """`sample2` (diffusion.py:241-255): t = i/T for i = T-1..0; a = sqrt(n_prev/n), b = s_prev."""
-        w = self._width(batch)
-        if w == 1 and self.vectorized_tables:
-            i = torch.arange(num_steps - 1, -1, -1, dtype=torch.float32)
-            t = torch.ones(num_steps) * i / num_steps
-            n, s = self._host_schedule(t)
-            npv, sp = self._host_schedule(torch.ones(num_steps) * (i - 1) / num_steps)
-            co = torch.sqrt(npv / n)
-            co[-1], sp[-1] = 0.0, 0.0                              # i = 0: x_t = x_0, no update
-            return StepTable(t, n, s, co, sp, self.device)
-        ts, ns, ss, co, s2 = [], [], [], [], []
-        for i in reversed(range(num_steps)):
-            t = torch.ones(w) * i / num_steps
-            n, s = self._host_schedule(t)
-            ts.append(t); ns.append(n); ss.append(s)
-            if i > 0:
-                npv, sp = self._host_schedule(torch.ones(w) * (i - 1) / num_steps)
-                co.append(torch.sqrt(npv / n)); s2.append(sp)
-            else:
-                co.append(torch.zeros(w)); s2.append(torch.zeros(w))
-        return StepTable(ts, ns, ss, co, s2, self.device)
+        i = torch.arange(num_steps - 1, -1, -1, dtype=torch.float32)
+        t, n, s, co, sp, _ = self._ddpm_columns(i, num_steps, self._width(batch))
+        co[-1], sp[-1] = 0.0, 0.0                                  # i = 0: x_t = x_0, no update
+        return StepTable(t, n, s, co, sp, self.device, skip_last_update=True)
 
     def from_state_table(self, start_t0, num_steps: int) -> StepTable:
         """`sample3` (diffusion.py:323-335): linspace(start_t[0], 0, T); only start_t[0] is used,
         and the schedule sees a 0-d t, so the rates are shared by the batch for both schedules."""
         steps = torch.linspace(torch.as_tensor(start_t0, dtype=torch.float32).cpu().reshape(()),
                                torch.zeros(1)[0], num_steps)
-        if self.noise_schedule == "cosine" and self.vectorized_tables:
-            n, s = self._host_schedule(steps)
-            n2, s2 = torch.zeros(num_steps), torch.zeros(num_steps)
-            n2[:-1], s2[:-1] = n[1:], s[1:]
-            return StepTable(steps, n, s, n2, s2, self.device)
-        ts, ns, ss, n2, s2 = [], [], [], [], []
-        for i in range(num_steps):
-            n, s = self._host_schedule(steps[i])
-            ts.append(steps[i]); ns.append(n); ss.append(s)
-            if i < num_steps - 1:
-                nn_, sn = self._host_schedule(steps[i + 1])
-                n2.append(nn_); s2.append(sn)
-            else:
-                n2.append(torch.zeros(())); s2.append(torch.zeros(()))
-        return StepTable(ts, ns, ss, n2, s2, self.device)
+        n, s = self._host_schedule(steps)
+        n2, s2 = torch.zeros_like(n), torch.zeros_like(s)
+        n2[:-1], s2[:-1] = n[1:], s[1:]
+        return StepTable(steps, n, s, n2, s2, self.device, skip_last_update=True)
 
     def completion_table(self, num_steps: int, jump: int = 10, resample: int = 1, batch: int = 1) -> CompletionTable:
         """`complete`: one row per network evaluation (`completion_rows`).  n, s, a, b are `ddpm_table`'s at the row's index i,
         n_prev goes with s_prev, and a row that jumps to index `to` carries ja = s(to/T) / s_prev, jb = sqrt(1 - ja^2), formed in
         float64 and rounded once (exact for the cosine schedule, s^2 + n^2 = 1); ja = jb = 0 marks a row without a jump."""
         w = self._width(batch)
-        T = num_steps
-        rows = completion_rows(T, jump, resample)
+        rows = completion_rows(num_steps, jump, resample)
         L = len(rows)
-        if w == 1 and self.vectorized_tables:
-            i = torch.tensor([r[0] for r in rows], dtype=torch.float32)
-            t = torch.ones(L) * i / T
-            n, s = self._host_schedule(t)
-            npv, sp = self._host_schedule(torch.ones(L) * (i - 1) / T)
-            co = torch.sqrt(npv / n)
-            to = torch.tensor([r[0] if r[1] is None else r[1] for r in rows], dtype=torch.float32)
-            _, sb = self._host_schedule(torch.ones(L) * to / T)
-            ja = sb.double() / sp.double()
-            jb = torch.sqrt(1 - ja * ja)
-            has = torch.tensor([r[1] is not None for r in rows])
-            ja, jb = torch.where(has, ja.float(), torch.zeros(L)), torch.where(has, jb.float(), torch.zeros(L))
-            co[-1], sp[-1], npv[-1] = 0.0, 0.0, 0.0                 # i = 0: the result is x_0, no update
-            return CompletionTable(rows, t, n, s, co, sp, npv, ja, jb, self.device)
-        ts, ns, ss, co, s2, n2, jas, jbs = [], [], [], [], [], [], [], []
-        for i, to in rows:
-            t = torch.ones(w) * i / T
-            n, s = self._host_schedule(t)
-            ts.append(t); ns.append(n); ss.append(s)
-            ja, jb = torch.zeros(w), torch.zeros(w)
-            if i > 0:
-                npv, sp = self._host_schedule(torch.ones(w) * (i - 1) / T)
-                co.append(torch.sqrt(npv / n)); s2.append(sp); n2.append(npv)
-                if to is not None:
-                    _, sb = self._host_schedule(torch.ones(w) * to / T)
-                    ja = sb.double() / sp.double()
-                    jb = torch.sqrt(1 - ja * ja).float()
-                    ja = ja.float()
-            else:
-                co.append(torch.zeros(w)); s2.append(torch.zeros(w)); n2.append(torch.zeros(w))
-            jas.append(ja); jbs.append(jb)
-        return CompletionTable(rows, ts, ns, ss, co, s2, n2, jas, jbs, self.device)
+        t, n, s, co, sp, npv = self._ddpm_columns(torch.tensor([r[0] for r in rows], dtype=torch.float32), num_steps, w)
+        to = torch.tensor([r[0] if r[1] is None else r[1] for r in rows], dtype=torch.float32)
+        _, sb = self._host_schedule(torch.ones(L) * to / num_steps, w)
+        ja = sb.double() / sp.double()
+        jb = torch.sqrt(1 - ja * ja)
+        has = torch.tensor([r[1] is not None for r in rows])[:, None]
+        ja, jb = torch.where(has, ja.float(), torch.zeros(())), torch.where(has, jb.float(), torch.zeros(()))
+        co[-1], sp[-1], npv[-1] = 0.0, 0.0, 0.0                     # i = 0: the result is x_0, no update
+        return CompletionTable(rows, t, n, s, co, sp, npv, ja, jb, self.device)
 
     @staticmethod
     def _check_dpm_args(num_steps, order, spacing, t_last):
@@ -368,7 +316,7 @@ class _DiffusionBase(nn.Module):
             t = torch.tensor(ts, dtype=torch.float64).to(torch.float32)
             if K > 1 and not bool((t[1:] < t[:-1]).all()):
                 raise ValueError(f"the log-SNR grid of {K} steps down to t_last = {t_last} is not strictly decreasing in fp32")
-            n, s = self._host_schedule(t)
+            n, s = (v.reshape(-1) for v in self._host_schedule(t))
             n2, s2 = torch.zeros(K), torch.zeros(K)
             n2[:-1], s2[:-1] = n[1:], s[1:]
             updates = K - 1
@@ -383,22 +331,18 @@ class _DiffusionBase(nn.Module):
         c, q = (torch.tensor(v, dtype=torch.float64).to(torch.float32) for v in (c, q))
         return DpmTable(t, n, s, n2, s2, c, q, self.device, skip_last_update=updates < K)
 
-    vectorized_tables = True     # False: per-step host loop (the literal transcription; kept for the equality test)
-
     # ------------------------------------------------------------------ stepping
     GRAPH_MIN_STEPS = 8
     GRAPH_STEPS = 8            # timesteps captured per HIP graph (one graph launch costs ~10 us of host time: the
     use_graphs = True          # 100 us latent step was launch-bound at one step per graph)
 
-    def _run(self, x, tab: "StepTable", bias_table: torch.Tensor, forward, kind: str, noises=None,
-             skip_last_update: bool = False, known=None, guide=None):
+    def _run(self, x, tab: "StepTable", bias_table: torch.Tensor, forward, kind: str, noises=None, known=None, guide=None):
         """kind 'ddim' | 'ddpm' | 'dpm' (`tab` a DpmTable) | 'complete' (`known` = (p, counts) on the device, `tab` a CompletionTable).
         forward(x, tb_cur, eps_out) enqueues the denoiser for the current step.  `guide` = (class_bias, labels, w) of a
         class-conditional run (`PointCloudDiffusion._guide`)."""
         stp = Stepper(self, x, tab, bias_table, forward, kind, noises, known, guide)
         T = tab.steps
-        last_updates = not (skip_last_update or kind in ("ddpm", "complete"))     # ddpm: x_t = x_0 at i = 0, no update
-        n_uniform = T if last_updates else T - 1                       # steps that all look the same
+        n_uniform = T - 1 if tab.skip_last_update else T              # steps that all look the same
         k = 0
         if self.use_graphs and noises is None and n_uniform - 1 >= self.GRAPH_MIN_STEPS:
             stp.step(0, True)                                          # eager warm-up (loads every kernel)
@@ -408,18 +352,36 @@ class _DiffusionBase(nn.Module):
             while k + per <= n_uniform:
                 stp.replay()
                 k += per
-            while k < n_uniform:                                       # remainder: eager, same enqueue
-                stp.step(k, True)
-                k += 1
-        else:
-            while k < n_uniform:
-                stp.step(k, True)
-                k += 1
+        while k < n_uniform:                                           # without graphs, or their remainder: eager, same enqueue
+            stp.step(k, True)
+            k += 1
         if k < T:
             stp.step(k, False)
-        if kind in ("ddpm", "complete"):
+        if stp.spans:                                                  # every row consumed its spans, the last one's unread
             self._philox_offset = stp.philox_start + stp.philox_stride * T
         return stp.x0
+
+    def _run_table(self, x, tab: "StepTable", kind: str, **kw):
+        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), kind, **kw)
+
+    def _run_from_state(self, num_samples, fresh, x, start_t, num_steps):
+        """`sample3` (diffusion.py:306-337): DDIM from the given state and time, or (x None) from `fresh()` at t = 1."""
+        self.eval()
+        if x is None:
+            x, start_t = fresh(), None
+        else:
+            x = x.to(self.device, torch.float32).contiguous().clone()
+        if start_t is None:
+            start_t = torch.ones(num_samples)
+        return self._run_table(x, self.from_state_table(start_t.reshape(-1)[0], num_steps), "ddim")
+
+    def _l1_loss(self, pred, noise):
+        """mean |pred - noise| of an eval-mode `diffusion_loss`."""
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        scratch = torch.empty_like(pred)
+        _lib.check(_lib.load().pcd_l1_loss(pred.data_ptr(), noise.data_ptr(), pred.numel(), 1.0, out.data_ptr(), scratch.data_ptr(),
+                                           _lib.stream_ptr()), "l1_loss")
+        return out[0] / pred.numel()
 
 
 class Stepper:
@@ -433,7 +395,11 @@ class Stepper:
     guidance scale exactly 1) a second, unconditional forward of the same x and `pcd_cfg_combine` follow; eps then holds the
     guided prediction the update kernel reads.  Without `guide` the enqueue is what it was before guidance existed."""
 
+    KINDS = ("ddim", "ddpm", "dpm", "complete")
+
     def __init__(self, owner, x, tab: StepTable, bias_table, forward, kind, noises=None, known=None, guide=None):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {', '.join(map(repr, self.KINDS))}, got {kind!r}")
         self.lib = _lib.load()
         self.x, self.tab, self.forward, self.kind, self.noises = x, tab, forward, kind, noises
         dev = x.device
@@ -453,89 +419,104 @@ class Stepper:
             self.tb_null = self.tb_rows[x.shape[0]]
             self.eps_u = torch.empty_like(x) if self.w is not None else None
         self.x0 = torch.empty_like(x)
-        self.z = torch.empty_like(x) if kind == "ddpm" or (kind == "complete" and noises is not None) else None
         self.per_shape = x.numel() // x.shape[0]
         self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        shard_off, span = owner._philox_span(x.numel(), x.shape[0])
+        shard_off, span = owner._philox_span(x.numel(), x.shape[0])   # counters one (global) draw consumes
         self.philox_start = getattr(owner, "_philox_offset", 0)        # the owner's stream position before this run
         self.philox_base = self.philox_start + shard_off              # this process's sub-block of every draw
-        self.philox_stride = span                                     # counters one (global) draw consumes
-        if kind == "complete":
-            self.p, self.counts = known
-            self.row_elems = x.shape[-1]
-            self.z2 = torch.empty_like(x) if noises is not None and tab.jumps else None
+        # What a kind is, besides its table's columns and last-row rule: the update entry, the scratch its injected draws need,
+        # and the Philox spans a row consumes.
+        buf = lambda: torch.empty_like(x) if noises is not None else None
+        self.z = self.z2 = None
+        if kind == "ddim":
+            self._update, self.spans = self._ddim, 0
+        elif kind == "dpm":
+            self._update, self.spans = self._dpm, 0
+        elif kind == "ddpm":
+            self._update, self.spans = self._ddpm_philox if noises is None else self._ddpm_injected, 1
+            self.z = buf()
+        else:
             # a run with jumps gives EVERY row two spans (z, then z2: unused where the row has no jump), so one captured
             # step fits all rows; a run without consumes sample2's counters
+            self._update, self.spans = self._complete_philox if noises is None else self._complete_injected, 2 if tab.jumps else 1
+            self.p, self.counts = known
+            self.row_elems = x.shape[-1]
+            self.z = buf()
+            self.z2 = buf() if tab.jumps else None
             self.philox_z2 = span
-            self.philox_stride = span * (2 if tab.jumps else 1)
+        self.philox_stride = span * self.spans
         self.graph = None
 
     def step(self, k: int, update: bool = True):
-        lib, x, R = self.lib, self.x, self.R
+        lib, x = self.lib, self.x
         st = _lib.stream_ptr()
         rp = self.rates_cur.data_ptr()
         if self.guide is None:
             _lib.check(lib.pcd_step_select_cols(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
-                                                self.tb_cur.data_ptr(), self.rates.data_ptr(), self.cols, R, rp, st), "step_select")
+                                                self.tb_cur.data_ptr(), self.rates.data_ptr(), self.cols, self.R, rp, st), "step_select")
             self.forward(x, self.tb_cur, self.eps)
         else:
             cb = self.class_bias
             _lib.check(lib.pcd_step_select_labels(self.counter.data_ptr(), self.T, self.bias_table.data_ptr(), self.tb_elems,
                                                   self.tb_rows.data_ptr(), cb.data_ptr(), cb.shape[0], self.labels.data_ptr(), x.shape[0],
-                                                  cb.shape[0] - 1, self.rates.data_ptr(), self.cols, R, rp, st), "step_select_labels")
+                                                  cb.shape[0] - 1, self.rates.data_ptr(), self.cols, self.R, rp, st), "step_select_labels")
             self.forward(x, self.tb_rows, self.eps, 1)
             if self.w is not None:                        # same x, same workspace: eps_u, then eps = eps_u + w (eps - eps_u)
                 self.forward(x, self.tb_null, self.eps_u, 0)
                 _lib.check(lib.pcd_cfg_combine(self.eps.data_ptr(), self.eps_u.data_ptr(), self.w.data_ptr(), int(self.w.numel() > 1),
                                                x.numel(), self.per_shape, st), "cfg_combine")
-        nxt = x.data_ptr() if update else 0               # in place: every element is read before it is written
-        if self.kind == "complete":
-            return self._complete_update(k, nxt, st)
-        if self.kind == "dpm":                            # x0 is also the history: the previous step's x0 is read, this step's written
-            _lib.check(lib.pcd_dpm_update(x.data_ptr(), self.eps.data_ptr(), rp, R, self.tab.stride, x.numel(), self.per_shape,
-                                          self.x0.data_ptr(), nxt, st), "dpm_update")
-            return
-        if self.kind == "ddim":
-            _lib.check(lib.pcd_ddim_update(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
-                                           self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st),
-                       "ddim_update")
-            return
-        zp = 0
-        if update:
-            if self.noises is not None:
-                self.z.copy_(self.noises[k].to(x.device, torch.float32).reshape(self.z.shape))
-            else:
-                # on-device noise: the draw and the update are one launch (z is never stored; bitwise pcd_randn_step + pcd_ddpm_update)
-                _lib.check(lib.pcd_ddpm_update_philox(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
-                                                      self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, self.seed,
-                                                      self.philox_base, self.philox_stride, self.counter.data_ptr(), st),
-                           "ddpm_update_philox")
-                return
-            zp = self.z.data_ptr()
-        _lib.check(lib.pcd_ddpm_update(x.data_ptr(), self.eps.data_ptr(), zp, rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
-                                       self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st),
-                   "ddpm_update")
+        self._update(k, x.data_ptr() if update else 0, st)   # in place: every element is read before it is written
 
-    def _complete_update(self, k: int, nxt: int, st: int):
-        lib, x, tab = self.lib, self.x, self.tab
-        rp = self.rates_cur.data_ptr()
-        if self.noises is None:
-            _lib.check(lib.pcd_complete_update_philox(x.data_ptr(), self.eps.data_ptr(), self.p.data_ptr(), self.counts.data_ptr(), rp,
-                                                      self.R, tab.stride, x.numel(), self.per_shape, self.row_elems, int(tab.jumps),
-                                                      self.x0.data_ptr(), nxt, self.seed, self.philox_base, self.philox_stride,
-                                                      self.philox_z2, self.counter.data_ptr(), st), "complete_update_philox")
-            return
+    # ---- the update entries: (row k, x_next pointer or 0 on a row that only predicts x_0, stream)
+    def _inject(self, buf, j: int) -> int:
+        buf.copy_(self.noises[j].to(self.x.device, torch.float32).reshape(buf.shape))
+        return buf.data_ptr()
+
+    def _ddim(self, k: int, nxt: int, st: int):
+        x, R, rp = self.x, self.R, self.rates_cur.data_ptr()
+        _lib.check(self.lib.pcd_ddim_update(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
+                                            self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st), "ddim_update")
+
+    def _dpm(self, k: int, nxt: int, st: int):            # x0 is also the history: the previous step's x0 is read, this step's written
+        x = self.x
+        _lib.check(self.lib.pcd_dpm_update(x.data_ptr(), self.eps.data_ptr(), self.rates_cur.data_ptr(), self.R, self.tab.stride,
+                                           x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st), "dpm_update")
+
+    def _ddpm_injected(self, k: int, nxt: int, st: int):
+        x, R, rp = self.x, self.R, self.rates_cur.data_ptr()
+        zp = self._inject(self.z, k) if nxt else 0
+        _lib.check(self.lib.pcd_ddpm_update(x.data_ptr(), self.eps.data_ptr(), zp, rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
+                                            self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, st), "ddpm_update")
+
+    def _ddpm_philox(self, k: int, nxt: int, st: int):
+        if not nxt:                                       # the last row draws nothing: the plain kernel predicts x_0
+            return self._ddpm_injected(k, 0, st)
+        # on-device noise: the draw and the update are one launch (z is never stored; bitwise pcd_randn_step + pcd_ddpm_update)
+        x, R, rp = self.x, self.R, self.rates_cur.data_ptr()
+        _lib.check(self.lib.pcd_ddpm_update_philox(x.data_ptr(), self.eps.data_ptr(), rp, rp + 4 * R, rp + 8 * R, rp + 12 * R,
+                                                   self.tab.stride, x.numel(), self.per_shape, self.x0.data_ptr(), nxt, self.seed,
+                                                   self.philox_base, self.philox_stride, self.counter.data_ptr(), st),
+                   "ddpm_update_philox")
+
+    def _complete_philox(self, k: int, nxt: int, st: int):
+        x, tab = self.x, self.tab
+        _lib.check(self.lib.pcd_complete_update_philox(x.data_ptr(), self.eps.data_ptr(), self.p.data_ptr(), self.counts.data_ptr(),
+                                                       self.rates_cur.data_ptr(), self.R, tab.stride, x.numel(), self.per_shape,
+                                                       self.row_elems, int(tab.jumps), self.x0.data_ptr(), nxt, self.seed,
+                                                       self.philox_base, self.philox_stride, self.philox_z2, self.counter.data_ptr(),
+                                                       st), "complete_update_philox")
+
+    def _complete_injected(self, k: int, nxt: int, st: int):
+        x, tab = self.x, self.tab
         zp = z2p = 0
         if nxt:
             j = tab.draws[k]
-            self.z.copy_(self.noises[j].to(x.device, torch.float32).reshape(self.z.shape))
-            zp = self.z.data_ptr()
+            zp = self._inject(self.z, j)
             if tab.rows[k][1] is not None:
-                self.z2.copy_(self.noises[j + 1].to(x.device, torch.float32).reshape(self.z2.shape))
-                z2p = self.z2.data_ptr()
-        _lib.check(lib.pcd_complete_update(x.data_ptr(), self.eps.data_ptr(), zp, z2p, self.p.data_ptr(), self.counts.data_ptr(), rp,
-                                           self.R, tab.stride, x.numel(), self.per_shape, self.row_elems, self.x0.data_ptr(), nxt, st),
-                   "complete_update")
+                z2p = self._inject(self.z2, j + 1)
+        _lib.check(self.lib.pcd_complete_update(x.data_ptr(), self.eps.data_ptr(), zp, z2p, self.p.data_ptr(), self.counts.data_ptr(),
+                                                self.rates_cur.data_ptr(), self.R, tab.stride, x.numel(), self.per_shape, self.row_elems,
+                                                self.x0.data_ptr(), nxt, st), "complete_update")
 
     def capture(self, steps: int = 1):
         """Capture `steps` consecutive generic steps in one graph (must follow at least one eager step: kernels
@@ -673,12 +654,7 @@ class PointCloudDiffusion(_DiffusionBase):
             pred = self.model(x_t, t.to(self.device, torch.float32), labels)
         else:
             pred = self.model(x_t, t.to(self.device, torch.float32))
-        lib = _lib.load()
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        scratch = torch.empty_like(pred)
-        _lib.check(lib.pcd_l1_loss(pred.data_ptr(), noise.data_ptr(), pred.numel(), 1.0, out.data_ptr(), scratch.data_ptr(),
-                                   _lib.stream_ptr()), "l1_loss")
-        return out[0] / pred.numel()
+        return self._l1_loss(pred, noise)
 
     def training_step(self, batch, batch_idx=0):
         """diffusion.py:70-86: t ~ U(0,1) per shape; returns the loss (gradients are ready for `optimizer.step`)."""
@@ -695,12 +671,12 @@ class PointCloudDiffusion(_DiffusionBase):
         return self.diffusion_loss(x_0, t, labels=self._training_labels(labels, x_0.shape[0], False))
 
     def _start(self, num_samples, num_points, x_T):
+        if x_T is not None and tuple(x_T.shape) != (num_samples, num_points, 3):
+            raise ValueError(f"x_T must be {(num_samples, num_points, 3)}, got {tuple(x_T.shape)}")
         self.eval()
         self._require_cuda(x_T)
         if x_T is None:
             return self._randn_like(torch.empty(num_samples, num_points, 3, device=self.device))
-        if tuple(x_T.shape) != (num_samples, num_points, 3):
-            raise ValueError(f"x_T must be {(num_samples, num_points, 3)}, got {tuple(x_T.shape)}")
         return x_T.to(torch.float32).contiguous().clone()
 
     @torch.no_grad()
@@ -711,8 +687,7 @@ class PointCloudDiffusion(_DiffusionBase):
         arithmetic is tests/cfg_statement.py."""
         guide = self._guide(labels, guidance_scale, num_samples)
         x = self._start(num_samples, num_points, x_T)
-        tab = self.ddim_table(num_steps, num_samples)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim", guide=guide)
+        return self._run_table(x, self.ddim_table(num_steps, num_samples), "ddim", guide=guide)
 
     @torch.no_grad()
     def sample_dpm(self, num_samples, num_points, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, x_T=None, labels=None,
@@ -721,14 +696,9 @@ class PointCloudDiffusion(_DiffusionBase):
         evaluations on a grid uniform in log-SNR from t = 1 to `t_last`.  Returns the last x_0, like `sample`, whose start draw
         it consumes.  Cosine schedule only.  `order=1, spacing="uniform"` is `sample` bit for bit.  The arithmetic is
         tests/dpm_statement.py.  `labels`, `guidance_scale`: as in `sample`."""
-        self._check_dpm_args(num_steps, order, spacing, t_last)
-        if x_T is not None and tuple(x_T.shape) != (num_samples, num_points, 3):
-            raise ValueError(f"x_T must be {(num_samples, num_points, 3)}, got {tuple(x_T.shape)}")
         guide = self._guide(labels, guidance_scale, num_samples)
         tab = self.dpm_table(num_steps, order, spacing, t_last)
-        x = self._start(num_samples, num_points, x_T)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update,
-                         guide=guide)
+        return self._run_table(self._start(num_samples, num_points, x_T), tab, "dpm", guide=guide)
 
     @torch.no_grad()
     def sample2(self, num_samples, num_points, num_steps=1000, x_T=None, noises=None, labels=None, guidance_scale=1.0):
@@ -736,8 +706,7 @@ class PointCloudDiffusion(_DiffusionBase):
         `sample`."""
         guide = self._guide(labels, guidance_scale, num_samples)
         x = self._start(num_samples, num_points, x_T)
-        tab = self.ddpm_table(num_steps, num_samples)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddpm", noises=noises, guide=guide)
+        return self._run_table(x, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises, guide=guide)
 
     @torch.no_grad()
     def complete(self, partial, num_points, num_steps=1000, known_counts=None, resample=1, jump=10, x_T=None, noises=None,
@@ -779,22 +748,12 @@ class PointCloudDiffusion(_DiffusionBase):
         tab = self.completion_table(T, j, r, B)
         _lib.check(_lib.load().pcd_complete_start(x.data_ptr(), p.data_ptr(), counts.data_ptr(), tab.n.data_ptr(), tab.s.data_ptr(),
                                                   tab.stride, x.numel(), num_points * 3, 3, _lib.stream_ptr()), "complete_start")
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "complete", noises=noises, known=(p, counts),
-                         guide=guide)
+        return self._run_table(x, tab, "complete", noises=noises, known=(p, counts), guide=guide)
 
     @torch.no_grad()
     def sample3(self, num_samples, num_points, x=None, start_t=None, num_steps=1000):
         """DDIM from a given state/time (diffusion.py:291-337)."""
-        self.eval()
-        if x is None:
-            x = self._start(num_samples, num_points, None)
-            start_t = torch.ones(num_samples)
-        else:
-            x = x.to(self.device, torch.float32).contiguous().clone()
-            if start_t is None:
-                start_t = torch.ones(num_samples)
-        tab = self.from_state_table(start_t.reshape(-1)[0], num_steps)
-        return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim", skip_last_update=True)
+        return self._run_from_state(num_samples, lambda: self._start(num_samples, num_points, None), x, start_t, num_steps)
 
 
 class LatentDiffusion(_DiffusionBase):
@@ -876,7 +835,7 @@ class LatentDiffusion(_DiffusionBase):
                 return False
         return self.model.persist_supported(x.shape[0])
 
-    def _run(self, x, tab, bias_table, forward, kind, noises=None, skip_last_update=False):
+    def _run(self, x, tab, bias_table, forward, kind, noises=None, **kw):
         if kind == "ddim" and noises is None and self._persistent_allowed(x):
             # A non-finite start state cannot go through the kernel's exchange (a value IS its own ready flag: NaN / set sign bits
             # mean "not written yet"), so such a call takes the per-layer launches, where GroupNorm keeps the damage inside its row.
@@ -885,7 +844,7 @@ class LatentDiffusion(_DiffusionBase):
                 rates = torch.stack([tab.n, tab.s, tab.a, tab.b]).contiguous()           # (4, T, R)
                 counter = torch.zeros(2, dtype=torch.int32, device=x.device)
                 x0 = torch.empty_like(x)
-                # the last step's update of z is computed and discarded when `skip_last_update` (sample3): x0 is the result
+                # the last step's update of z is computed and discarded when `tab.skip_last_update` (sample3): x0 is the result
                 self.model.ddim_steps_persist(x, x0, bias_table.contiguous(), rates, counter, tab.steps)
                 status = self.model.persist_status()
                 if status == 0:
@@ -898,7 +857,7 @@ class LatentDiffusion(_DiffusionBase):
                               RuntimeWarning, stacklevel=3)
                 self.use_persistent = False
                 x.copy_(start)
-        return super()._run(x, tab, bias_table, forward, kind, noises, skip_last_update)
+        return super()._run(x, tab, bias_table, forward, kind, noises, **kw)
 
     # ------------------------------------------------------------------ training surface (diffusion.py:410-443, 522-537)
     def configure_optimizers(self, max_epochs: int = 100):
@@ -917,12 +876,7 @@ class LatentDiffusion(_DiffusionBase):
             tr = self.configure_optimizers()["optimizer"]
             tr.forward(z_t, t.to(self.device, torch.float32), dropout_mask)
             return tr.backward(noise)
-        pred = self.model(z_t, t.to(self.device, torch.float32))
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        scratch = torch.empty_like(pred)
-        _lib.check(_lib.load().pcd_l1_loss(pred.data_ptr(), noise.data_ptr(), pred.numel(), 1.0, out.data_ptr(), scratch.data_ptr(),
-                                           _lib.stream_ptr()), "l1_loss")
-        return out[0] / pred.numel()
+        return self._l1_loss(self.model(z_t, t.to(self.device, torch.float32)), noise)
 
     def training_step(self, batch, batch_idx=0):
         """diffusion.py:424-443: z = reparameterize(encode(x)) through the frozen VAE, t ~ U(0,1), L1 loss."""
@@ -941,11 +895,12 @@ class LatentDiffusion(_DiffusionBase):
             return self._randn_like(torch.empty(num_samples, self.hparams.latent_dim, device=self.device))
         return z_T.to(self.device, torch.float32).contiguous().clone()
 
-    def _finish(self, z_0, threshold):
+    def _finish(self, z_0, threshold, return_latent=False):
         from .utils import voxel_tensor_to_point_clouds
         x_0 = self.vae.decode(z_0)
         if self.hparams.is_voxel_based:
-            return voxel_tensor_to_point_clouds(x_0, threshold=threshold)
+            pcs = voxel_tensor_to_point_clouds(x_0, threshold=threshold)
+            return (pcs, z_0) if return_latent else pcs
         # the reference's sample()/sample3() leave `point_clouds` unbound here (diffusion.py:650-653)
         raise UnboundLocalError("local variable 'point_clouds' referenced before assignment "
                                 "(is_voxel_based=False is not supported by the reference's samplers either)")
@@ -954,46 +909,26 @@ class LatentDiffusion(_DiffusionBase):
     def sample(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, return_latent=False):
         """DDIM in latent space, VAE decode, voxel -> points (diffusion.py:619-653)."""
         z = self._start(num_samples, z_T)
-        tab = self.ddim_table(num_steps, num_samples)
-        z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim")
-        pcs = self._finish(z0, threshold)
-        return (pcs, z0) if return_latent else pcs
+        return self._finish(self._run_table(z, self.ddim_table(num_steps, num_samples), "ddim"), threshold, return_latent)
 
     @torch.no_grad()
     def sample_dpm(self, num_samples, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, threshold=0.4, z_T=None,
                    return_latent=False):
         """`PointCloudDiffusion.sample_dpm` in latent space, then VAE decode and voxel -> points like `sample`.  Runs on the per-layer
         launches (the persistent kernel implements the DDIM update only)."""
-        self._check_dpm_args(num_steps, order, spacing, t_last)
         if z_T is not None and tuple(z_T.shape) != (num_samples, self.hparams.latent_dim):
             raise ValueError(f"z_T must be {(num_samples, self.hparams.latent_dim)}, got {tuple(z_T.shape)}")
         tab = self.dpm_table(num_steps, order, spacing, t_last)
-        z = self._start(num_samples, z_T)
-        z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "dpm", skip_last_update=tab.skip_last_update)
-        pcs = self._finish(z0, threshold)
-        return (pcs, z0) if return_latent else pcs
+        return self._finish(self._run_table(self._start(num_samples, z_T), tab, "dpm"), threshold, return_latent)
 
     @torch.no_grad()
     def sample2(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, noises=None, return_latent=False):
         """DDPM in latent space (diffusion.py:575-616)."""
         z = self._start(num_samples, z_T)
-        tab = self.ddpm_table(num_steps, num_samples)
-        z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddpm", noises=noises)
-        pcs = self._finish(z0, threshold)
-        return (pcs, z0) if return_latent else pcs
+        return self._finish(self._run_table(z, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises), threshold, return_latent)
 
     @torch.no_grad()
     def sample3(self, num_samples, z=None, start_t=None, num_steps=1000, threshold=0.4, return_latent=False):
         """DDIM from a given latent/time (diffusion.py:655-707)."""
-        self.eval()
-        if z is None:
-            z = self._start(num_samples, None)
-            start_t = torch.ones(num_samples)
-        else:
-            z = z.to(self.device, torch.float32).contiguous().clone()
-            if start_t is None:
-                start_t = torch.ones(num_samples)
-        tab = self.from_state_table(start_t.reshape(-1)[0], num_steps)
-        z0 = self._run(z, tab, self.model.time_bias(tab.t), self._forward_fn(), "ddim", skip_last_update=True)
-        pcs = self._finish(z0, threshold)
-        return (pcs, z0) if return_latent else pcs
+        z0 = self._run_from_state(num_samples, lambda: self._start(num_samples, None), z, start_t, num_steps)
+        return self._finish(z0, threshold, return_latent)

@@ -1,4 +1,6 @@
-"""Shared test helpers: synthetic weights as torch tensors, tolerances."""
+"""Shared test helpers: synthetic weights as torch tensors, tolerances, the graph-replay counter."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -63,3 +65,18 @@ def synth_voxels(b, seed):
             m = ((zz - c[0]) / r[0]) ** 2 + ((yy - c[1]) / r[1]) ** 2 + ((xx - c[2]) / r[2]) ** 2 <= 1
             v[i, 0][m] = 1
     return torch.from_numpy(v)
+
+
+@contextlib.contextmanager
+def counted_replays(m, graphs):
+    """Inside, module `m` samples with HIP graphs on (`graphs`) or off; yields the list that grows by one entry per
+    `Stepper.replay`.  On leaving, `Stepper.replay` and the class default of `use_graphs` are back."""
+    from shapegen_amd.diffusion import Stepper
+    seen, inner = [], Stepper.replay
+    m.use_graphs = graphs
+    Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+    try:
+        yield seen
+    finally:
+        Stepper.replay = inner
+        del m.use_graphs

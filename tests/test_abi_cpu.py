@@ -164,20 +164,43 @@ def test_linear_schedule_bug_for_bug():
 
 @pytest.mark.parametrize("T", [1, 2, 7, 100, 1000])
 def test_vectorized_step_tables_equal_the_per_step_loop(T):
-    """The cosine-schedule step tables are built with one set of elementwise ops over all T steps; the literal
-    per-step transcription of the reference loops (diffusion.py:241-255, 277-286, 323-335) must give the same bits."""
+    """The step tables are built with one set of elementwise ops over all T steps and the whole width; the literal
+    per-step transcription of the reference loops (diffusion.py:241-255, 277-286, 323-335; tests/table_statement.py, over
+    the oracle's schedules) must give the same bits: cosine (width 1 whatever the batch) and linear (width = batch, each
+    row the batch-axis cumprod the reference's loop saw; a 0-d time, hence width 1, from a state)."""
+    import table_statement as S
+    from oracle import torch_oracle as O
     from shapegen_amd.diffusion import PointCloudDiffusion
+    for schedule, batches in (("cosine", (4,)), ("linear", (1, 3, 4, 64))):
+        m = PointCloudDiffusion(num_points=8, noise_schedule=schedule)
+        sched = O.schedule_fn(schedule)
+        pairs = [(m.from_state_table(st, T), S.from_state(st, T, sched), 1) for st in (torch.tensor(0.37), 1.0, torch.tensor(0.3))]
+        for B in batches:
+            w = 1 if schedule == "cosine" else B
+            pairs += [(m.ddim_table(T, B), S.ddim(T, w, sched), w), (m.ddpm_table(T, B), S.ddpm(T, w, sched), w)]
+        for a, b, w in pairs:
+            assert a.steps == T and a.width == w and a.stride == (0 if w == 1 else 1)
+            for f in ("t", "n", "s", "a", "b"):
+                assert torch.equal(getattr(a, f), b[f]), (schedule, w, f)
+
+
+def test_stepper_refuses_an_unknown_kind_before_touching_the_device():
+    """A kind is looked up once, at construction: a misspelt one raises and names the four, before the library is loaded or
+    anything is allocated (a CPU state and a two-row table get that far)."""
+    from shapegen_amd import _lib
+    from shapegen_amd.diffusion import PointCloudDiffusion, Stepper
     m = PointCloudDiffusion(num_points=8)
-    builders = [lambda: m.ddim_table(T, 4), lambda: m.ddpm_table(T, 4), lambda: m.from_state_table(torch.tensor(0.37), T),
-                lambda: m.from_state_table(1.0, T)]
-    for fn in builders:
-        m.vectorized_tables = True
-        a = fn()
-        m.vectorized_tables = False
-        b = fn()
-        assert a.steps == b.steps == T and a.width == b.width == 1 and a.stride == b.stride
-        for f in ("t", "n", "s", "a", "b"):
-            assert torch.equal(getattr(a, f), getattr(b, f)), f
+    tab = m.ddim_table(2, 1)
+    x, bias = torch.zeros(1, 8, 3), torch.zeros(2, 64)
+    loaded = _lib.load
+    _lib.load = lambda: pytest.fail("the library was loaded before the kind was checked")
+    try:
+        with pytest.raises(ValueError, match="'ddim', 'ddpm', 'dpm', 'complete'.*'dim'"):
+            Stepper(m, x, tab, bias, m._forward_fn(), "dim")
+        with pytest.raises(ValueError, match="'ddim', 'ddpm', 'dpm', 'complete'"):
+            m._run(x, tab, bias, m._forward_fn(), "DDPM")
+    finally:
+        _lib.load = loaded
 
 
 def test_persistent_latent_plan_is_a_partition():

@@ -70,13 +70,11 @@ def test_statement_returns_known_rows_bitwise(jump, resample):
     assert not torch.equal(out[1, 37:], partial[1, 37:])
 
 
-@pytest.mark.parametrize("vectorized", [True, False])
 @pytest.mark.parametrize("T,jump,resample", [(12, 4, 2), (20, 5, 3), (7, 1, 1)])
-def test_completion_table_holds_the_statements_scalars(T, jump, resample, vectorized):
+def test_completion_table_holds_the_statements_scalars(T, jump, resample):
     """Every column of the uploaded table is, bit for bit, the scalar the statement forms at that row."""
     from shapegen_amd.diffusion import PointCloudDiffusion
     m = PointCloudDiffusion(num_points=8)
-    m.vectorized_tables = vectorized
     tab = m.completion_table(T, jump, resample, batch=3)
     rows = S.completion_rows(T, jump, resample)
     assert tab.steps == len(rows) and tab.width == 1 and tab.stride == 0 and tab.rows == rows
@@ -111,6 +109,21 @@ def test_completion_table_linear_schedule_has_batch_width():
         assert torch.equal(a, b)
     n_prev, _ = O.linear_schedule(torch.ones(3) * 2 / 5)
     assert torch.equal(tab.n2[1], n_prev)
+
+
+@pytest.mark.parametrize("schedule,args,batch", [("linear", (5, 10, 1), 3), ("cosine", (12, 4, 2), 3)])
+def test_completion_table_equals_the_per_step_loop(schedule, args, batch):
+    """The table is built for all rows and the whole width at once; the statement's walk, one schedule call per row on the
+    (width,) vector (tests/table_statement.py), gives the same bits -- on the linear schedule each row is its own batch-axis
+    cumprod."""
+    import table_statement as TS
+    from shapegen_amd.diffusion import PointCloudDiffusion
+    m = PointCloudDiffusion(num_points=8, noise_schedule=schedule)
+    tab = m.completion_table(*args, batch=batch)
+    want = TS.completion(*args, tab.width, O.schedule_fn(schedule))
+    assert tab.width == (batch if schedule == "linear" else 1) and tab.steps == len(want["t"]) and tab.skip_last_update
+    for f in ("t", "n", "s", "a", "b", "n2", "ja", "jb"):
+        assert torch.equal(getattr(tab, f), want[f]), f
 
 
 def test_new_symbols_declared_exported_and_bound():

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 import cfg_statement as S
 import resume_runs as R
-from helpers import point_sd, rel_l2
+from helpers import counted_replays, point_sd, rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -271,24 +271,17 @@ def test_null_labels_with_guidance_agree_with_scale_one():
 @pytest.mark.parametrize("kind", ["ddim", "ddpm"])
 def test_graph_replay_equals_eager_stepping(kind):
     """(2, 64), 20 steps: one eager step, two graphs of 8, the rest eager; DDIM and DDPM with on-device noise."""
-    from shapegen_amd.diffusion import Stepper
     m = model_of("fp16", 64)
     steps = 20
     assert steps - 2 >= m.GRAPH_MIN_STEPS and m.use_graphs
     x_T = torch.randn(2, 64, 3, generator=torch.Generator().manual_seed(13)).to(DEV)
     fn = m.sample if kind == "ddim" else m.sample2
-    outs, inner = [], Stepper.replay
-    try:
-        for graphs in (True, False):
-            m.use_graphs = graphs
-            seen = []
-            Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+    outs = []
+    for graphs in (True, False):
+        with counted_replays(m, graphs) as seen:
             reseed(m)
             outs.append(fn(2, 64, num_steps=steps, x_T=x_T, labels=[1, NULL], guidance_scale=torch.tensor([2.0, 1.5])))
             assert len(seen) == (2 if graphs else 0)
-    finally:
-        Stepper.replay = inner
-        del m.use_graphs
     assert torch.equal(outs[0], outs[1]) and torch.isfinite(outs[0]).all()
 
 

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import completion_statement as S
-from helpers import as_torch, point_sd, rel_l2
+from helpers import as_torch, counted_replays, point_sd, rel_l2
 from oracle import torch_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -243,19 +243,12 @@ def test_graph_replay_equals_eager_stepping():
     m = model_of("pointnet", "fp16")
     partial, counts, _, _ = inputs()
     assert len(ROWS) - 1 - 1 >= m.GRAPH_MIN_STEPS and m.use_graphs     # _run's condition: the graph path is taken
-    from shapegen_amd.diffusion import Stepper
-    outs, inner = [], Stepper.replay
-    try:
-        for graphs in (True, False):
-            m.use_graphs = graphs
-            seen = []
-            Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+    outs = []
+    for graphs in (True, False):
+        with counted_replays(m, graphs) as seen:
             reseed(m)
             outs.append(m.complete(partial.cuda(), N, num_steps=T, known_counts=counts, resample=RESAMPLE, jump=JUMP))
             assert len(seen) == (2 if graphs else 0)                  # 19 uniform rows: one eager, two graphs of 8, two eager
-    finally:
-        Stepper.replay = inner
-        del m.use_graphs                                              # back to the class default
     assert torch.equal(outs[0], outs[1])
 
 

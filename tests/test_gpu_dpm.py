@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import dpm_statement as S
-from helpers import as_torch, latent_sd, point_sd, rel_l2
+from helpers import as_torch, counted_replays, latent_sd, point_sd, rel_l2
 from oracle import torch_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,19 +147,12 @@ def test_sample_dpm_with_injected_start_against_the_statement(backbone, prec):
 def test_graph_replay_equals_eager_stepping(steps, replays):
     m = model_of("pointnet", "fp16")
     assert steps - 1 - 1 >= m.GRAPH_MIN_STEPS and m.use_graphs and m.GRAPH_STEPS == 8
-    from shapegen_amd.diffusion import Stepper
     x_T = torch.randn(B, N, 3, generator=torch.Generator().manual_seed(6)).cuda()
-    outs, inner = [], Stepper.replay
-    try:
-        for graphs in (True, False):
-            m.use_graphs = graphs
-            seen = []
-            Stepper.replay = lambda self: (seen.append(1), inner(self))[1]
+    outs = []
+    for graphs in (True, False):
+        with counted_replays(m, graphs) as seen:
             outs.append(m.sample_dpm(B, N, num_steps=steps, x_T=x_T))
             assert len(seen) == (replays if graphs else 0)
-    finally:
-        Stepper.replay = inner
-        del m.use_graphs                                              # back to the class default
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
 
 
