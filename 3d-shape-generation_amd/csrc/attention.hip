@@ -95,20 +95,6 @@ __device__ __forceinline__ float xhalf_max(float v) {
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
-__device__ __forceinline__ void aglds16(const half_t* g, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// Same LDS-DMA, issued from inline asm so the compiler does not know LDS is being written behind its back:
-// with the builtin it puts s_waitcnt vmcnt(0) in front of every ds_read_b64_tr_b16 that follows (it cannot
-// prove the transpose read does not alias the DMA), which serialises a DMA meant to stay in flight for
-// three phases.  The caller owns the vmcnt wait and the barrier.
-__device__ __forceinline__ void aglds16_asm(const half_t* g, char* lds_wave_base) {
-    const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds_wave_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0v) : "memory", "m0");
-}
-
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 // Swizzles (applied to the LDS-DMA source address and again on the reads).  K tile (ds_read_b128
@@ -141,8 +127,8 @@ __device__ __forceinline__ void stage_tile(const half_t* __restrict__ src, int64
         const int logical = VSW ? v_swz<RB>(row, lane % CPR) : k_swz<RB>(row, lane % CPR);
         int grow = row0 + row;
         grow = grow < row_limit ? grow : row_limit - 1;
-        if (ASM) aglds16_asm(src + (int64_t)grow * ld + logical * 8, lds + ins * 1024);
-        else aglds16(src + (int64_t)grow * ld + logical * 8, lds + ins * 1024);
+        if (ASM) lds_dma16(src + (int64_t)grow * ld + logical * 8, lds + ins * 1024);
+        else lds_dma16_builtin(src + (int64_t)grow * ld + logical * 8, lds + ins * 1024);
     }
 }
 
@@ -308,13 +294,13 @@ __global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __rest
     const int full_tiles = n / KT;
     stage(0, 0);
     for (int kt = 0; kt < full_tiles; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         if (kt + 1 < ntiles) stage(kt + 1, (kt + 1) & 1);
         tile_body(kt, std::false_type{});
     }
     if (full_tiles < ntiles) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         tile_body(full_tiles, std::true_type{});
     }
@@ -618,7 +604,7 @@ __global__ __launch_bounds__(64 * NW, 2) void set_attention_sp_kernel(const half
         vf[0][0][e] = vf[0][1][e] = vf[1][0][e] = vf[1][1][e] = (half_t)0.f;
     }
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     // the first 32 keys fix the running max exactly: S(0) - rowmax, seed accumulators = -rowmax
     load_k(0, kf);
@@ -658,10 +644,10 @@ __global__ __launch_bounds__(64 * NW, 2) void set_attention_sp_kernel(const half
             // (lgkmcnt(0): this wave's own fragment reads have RETURNED before the barrier behind which another wave's LDS-DMA refills a slot --
             // the compiler's barrier fence says so at three of the four barriers of a group, not at the loop-carried one: tools/check_barrier_reads.py)
             if (!LAST || u < 2) {
-                if constexpr (NW == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+                if constexpr (NW == 4) wait_vmcnt_lgkm0<4>();
+                else wait_vmcnt_lgkm0<2>();
             }
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            else wait_vmcnt_lgkm0<0>();
             __syncthreads();
             const int cur = u * STAGE, nxt = ((u + 1) % NSLOT) * STAGE;   // last tile: nxt holds stale bytes, S(i+1) unused
             const int st = t0 + u + AHEAD + 1, sslot = (u + AHEAD + 1) % NSLOT;   // tile to stage; its slot == slot of tile t-1
@@ -930,7 +916,7 @@ __global__ __launch_bounds__(256, 3) void set_attention_spn_kernel(const half_t*
         vf[0][e] = vf[1][e] = (half_t)0.f;
     }
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     // the first 32 keys fix the running max exactly: S(0) - rowmax, seed accumulators = -rowmax
     load_k(0, kf);
@@ -965,10 +951,10 @@ __global__ __launch_bounds__(256, 3) void set_attention_spn_kernel(const half_t*
             // tile t+1 has landed (all but the youngest stage's PPW LDS-DMA pieces of this wave), this wave's own fragment reads have returned
             if constexpr (!(ABL & 4)) {
                 if (!LAST || u < 2) {
-                    if constexpr (PPW == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+                    if constexpr (PPW == 2) wait_vmcnt_lgkm0<2>();
+                    else wait_vmcnt_lgkm0<1>();
                 } else {
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                    wait_vmcnt_lgkm0<0>();
                 }
                 __syncthreads();
             }
@@ -1155,13 +1141,13 @@ __global__ __launch_bounds__(256, 2) void set_attention_om_kernel(const half_t* 
     const int full_tiles = n / KT;
     stage(0, 0);
     for (int kt = 0; kt < full_tiles; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         if (kt + 1 < ntiles) stage(kt + 1, (kt + 1) & 1);
         tile_body(kt, std::false_type{});
     }
     if (full_tiles < ntiles) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         tile_body(full_tiles, std::true_type{});
     }

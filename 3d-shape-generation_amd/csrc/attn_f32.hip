@@ -15,7 +15,6 @@ using namespace pcd;
 
 namespace {
 
-size_t up(size_t v) { return (v + 255) / 256 * 256; }
 
 // LayerNorm over C (eps 1e-5, biased variance, affine): one wave per row, C <= 256
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, int64_t rows, int c, const float* __restrict__ g,
@@ -165,10 +164,10 @@ struct SabWs { size_t t1, t2, qkv, ffh, total; };
 SabWs sab_carve(int64_t rows, int dim) {
     SabWs w{};
     size_t o = 0;
-    w.t1 = o; o += up((size_t)rows * dim * 4);
-    w.t2 = o; o += up((size_t)rows * dim * 4);
-    w.qkv = o; o += up((size_t)rows * 3 * dim * 4);
-    w.ffh = o; o += up((size_t)rows * 4 * dim * 4);
+    w.t1 = o; o += align_up((size_t)rows * dim * 4);
+    w.t2 = o; o += align_up((size_t)rows * dim * 4);
+    w.qkv = o; o += align_up((size_t)rows * 3 * dim * 4);
+    w.ffh = o; o += align_up((size_t)rows * 4 * dim * 4);
     w.total = o;
     return w;
 }
@@ -195,18 +194,16 @@ int sab_run(const pcd_sab_desc_t& d, const float* x, int batch, int n, int heads
     const SabWs w = sab_carve(m, C);
     float *t1 = (float*)(ws + w.t1), *t2 = (float*)(ws + w.t2), *qkv = (float*)(ws + w.qkv), *ffh = (float*)(ws + w.ffh);
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
     hipLaunchKernelGGL(layernorm_f32_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, x, m, C, d.ln1_g, d.ln1_b, t1);
-    RUN(lin(t1, C, nullptr, 0, d.w_in, d.b_in, 0, m, 3 * C, qkv, s));
-    RUN(attention(qkv, batch, n, C, heads, t2, s));
-    RUN(lin(t2, C, nullptr, 0, d.w_out, d.b_out, 0, m, C, t1, s));
+    PCD_RUN(lin(t1, C, nullptr, 0, d.w_in, d.b_in, 0, m, 3 * C, qkv, s));
+    PCD_RUN(attention(qkv, batch, n, C, heads, t2, s));
+    PCD_RUN(lin(t2, C, nullptr, 0, d.w_out, d.b_out, 0, m, C, t1, s));
     hipLaunchKernelGGL(add_f32_kernel, dim3(nblk(m * C)), dim3(256), 0, s, x, t1, t1, m * C);                 // t1 = x + out_proj(.)
     hipLaunchKernelGGL(layernorm_f32_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, t1, m, C, d.ln2_g, d.ln2_b, t2);
-    RUN(lin(t2, C, nullptr, 0, d.w_ff1, d.b_ff1, 1, m, 4 * C, ffh, s));
-    RUN(lin(ffh, 4 * C, nullptr, 0, d.w_ff2, d.b_ff2, 0, m, C, t2, s));
+    PCD_RUN(lin(t2, C, nullptr, 0, d.w_ff1, d.b_ff1, 1, m, 4 * C, ffh, s));
+    PCD_RUN(lin(ffh, 4 * C, nullptr, 0, d.w_ff2, d.b_ff2, 0, m, C, t2, s));
     hipLaunchKernelGGL(add_f32_kernel, dim3(nblk(m * C)), dim3(256), 0, s, t1, t2, y, m * C);
     PCD_CHECK_LAUNCH();
-#undef RUN
     return PCD_OK;
 }
 
@@ -220,12 +217,12 @@ AuWs au_carve(int64_t batch, int64_t n) {
     const size_t m = (size_t)batch * (size_t)n;
     AuWs w{};
     size_t o = 0;
-    w.x1 = o; o += up(m * 64 * 4);
-    w.x2 = o; o += up(m * 128 * 4);
-    w.x3 = o; o += up(m * 256 * 4);
-    w.p0 = o; o += up(m * 256 * 4);
-    w.p1 = o; o += up(m * 256 * 4);
-    w.p2 = o; o += up(m * 256 * 4);
+    w.x1 = o; o += align_up(m * 64 * 4);
+    w.x2 = o; o += align_up(m * 128 * 4);
+    w.x3 = o; o += align_up(m * 256 * 4);
+    w.p0 = o; o += align_up(m * 256 * 4);
+    w.p1 = o; o += align_up(m * 256 * 4);
+    w.p2 = o; o += align_up(m * 256 * 4);
     w.sab = o; o += sab_carve((int64_t)m, 256).total;
     w.total = o;
     return w;
@@ -293,33 +290,31 @@ extern "C" int pcd_attn_unet_f32_forward(pcd_attn_unet_f32_t* h, const float* x,
     const int rps = tbias_shape_stride ? N : (int)m;
     const float *tb_e1 = tbias, *tb_e2 = tbias + 64, *tb_e3 = tbias + 128, *tb_d3 = tbias + 256, *tb_d2 = tbias + 512, *tb_d1 = tbias + 640;
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
-#define LIN(i, a1, a2, k2, out) RUN(lin(a1, d.lin[i].k - (k2), a2, k2, d.lin[i].w, d.lin[i].b, 1, m, d.lin[i].c, out, s))
+#define LIN(i, a1, a2, k2, out) PCD_RUN(lin(a1, d.lin[i].k - (k2), a2, k2, d.lin[i].w, d.lin[i].b, 1, m, d.lin[i].c, out, s))
 #define EMB(src, c, tb, dst) hipLaunchKernelGGL(add_shape_bias_f32_kernel, dim3(nblk(m * (c))), dim3(256), 0, s, src, m, c, rps, tb, estr, dst)
     hipLaunchKernelGGL(au_enc1_f32_kernel, dim3(nblk(m * 64)), dim3(256), 0, s, x, m, rps, d.e1w, tb_e1, estr, p0);
     LIN(0, p0, nullptr, 0, p1);
     LIN(1, p1, nullptr, 0, p0);
-    RUN(sab_run(d.sab[0], p0, batch, N, H, p1, sws, s));                                  // att1
+    PCD_RUN(sab_run(d.sab[0], p0, batch, N, H, p1, sws, s));                                  // att1
     EMB(p1, 64, tb_e2, x1);                                                               // x1 + emb2
     LIN(2, x1, nullptr, 0, p0); LIN(3, p0, nullptr, 0, p1); LIN(4, p1, nullptr, 0, p0);   // enc2
-    RUN(sab_run(d.sab[1], p0, batch, N, H, p1, sws, s));                                  // att2
+    PCD_RUN(sab_run(d.sab[1], p0, batch, N, H, p1, sws, s));                                  // att2
     EMB(p1, 128, tb_e3, x2);                                                              // x2 + emb3
     LIN(5, x2, nullptr, 0, p0); LIN(6, p0, nullptr, 0, p1); LIN(7, p1, nullptr, 0, p0);   // enc3
-    RUN(sab_run(d.sab[2], p0, batch, N, H, x3, sws, s));                                  // att3 -> x3
-    RUN(sab_run(d.sab[3], x3, batch, N, H, p0, sws, s));                                  // bottleneck
+    PCD_RUN(sab_run(d.sab[2], p0, batch, N, H, x3, sws, s));                                  // att3 -> x3
+    PCD_RUN(sab_run(d.sab[3], x3, batch, N, H, p0, sws, s));                                  // bottleneck
     EMB(p0, 256, tb_d3, p1);
-    RUN(sab_run(d.sab[4], p1, batch, N, H, p0, sws, s));                                  // att_dec3
+    PCD_RUN(sab_run(d.sab[4], p1, batch, N, H, p0, sws, s));                                  // att_dec3
     LIN(8, p0, x3, 256, p1); LIN(9, p1, nullptr, 0, p2); LIN(10, p2, nullptr, 0, p1);     // dec3 on cat[xb | x3]
     EMB(p1, 128, tb_d2, p0);
-    RUN(sab_run(d.sab[5], p0, batch, N, H, p1, sws, s));                                  // att_dec2
+    PCD_RUN(sab_run(d.sab[5], p0, batch, N, H, p1, sws, s));                                  // att_dec2
     LIN(11, p1, x2, 128, p0); LIN(12, p0, nullptr, 0, p2); LIN(13, p2, nullptr, 0, p0);   // dec2 on cat[. | x2]
     EMB(p0, 64, tb_d1, p1);
-    RUN(sab_run(d.sab[6], p1, batch, N, H, p0, sws, s));                                  // att_dec1
+    PCD_RUN(sab_run(d.sab[6], p1, batch, N, H, p0, sws, s));                                  // att_dec1
     hipLaunchKernelGGL(au_tail3_f32_kernel, dim3(nblk(m)), dim3(256), 0, s, p0, 64, x1, 64, m, d.t_w1, d.t_b1, d.t_w234, d.t_b234, eps);
     PCD_CHECK_LAUNCH();
 #undef EMB
 #undef LIN
-#undef RUN
     return PCD_OK;
 }
 

@@ -47,34 +47,6 @@ struct ConvParams {
     ConvVariant var[MAX_VARIANTS];
 };
 
-__device__ __forceinline__ void cglds16(const half_t* g, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// The same LDS-DMA from inline asm.  The compiler models the builtin as a FLAT access that may touch both
-// memory and LDS, and while one is pending it turns every later s_waitcnt into vmcnt(0) / lgkmcnt(0) -- which
-// drains the fragment prefetch of the halo kernel below.  Issued from asm, the DMA is invisible to that
-// bookkeeping; the caller owns the vmcnt wait and the barrier.
-__device__ __forceinline__ void cglds16_asm(const half_t* g, char* lds_wave_base) {
-    const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds_wave_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0v) : "memory", "m0");
-}
-
-template <int N>
-__device__ __forceinline__ void conv_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Before a barrier behind which ANOTHER wave's LDS-DMA refills the ring stage this wave has just read: the wave's own ds_reads must have
-// RETURNED, not just been issued.  The compiler sinks a stage's last MFMAs (and the lgkmcnt wait in front of them) below the raw s_barrier,
-// so a wave would pass it with fragment reads of that stage still queued in the LDS pipe; nothing orders them against the DMA's write, and with
-// two workgroups per CU queueing reads and L1-resident weights coming back fast the write did win now and then (conv3d_k4s2_halo_kernel, batch 16:
-// one encode in seven differed from the others by 1e-3..5e-3; tools/diag_vae_batch.py).  tools/check_barrier_reads.py scans the built code for it.
-__device__ __forceinline__ void conv_reads_landed() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // K tile BKT (64 or 32 halfs: 128- or 64-byte LDS rows) in a ring of NST stages.  A stage is requested NST - 1 K tiles before
 // the barrier that publishes it and NST - 2 younger stages stay in flight behind that barrier's counted vmcnt: with two
 // stages the gather of K tile kt+1 has one K tile of MFMAs (~500 cycles per wave) to come back from L2, and the waves
@@ -170,7 +142,7 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(ConvParams p) {
             const int c2 = kidx - p.kt2 * CBK;
 #pragma unroll
             for (int r = 0; r < AR; ++r)
-                cglds16_asm(p.in2 + (((rbase[r] >> p.cin_shift) << p.cin2_shift) + c2), base + (r * RPI + wave * RPW) * CROWB);
+                lds_dma16(p.in2 + (((rbase[r] >> p.cin_shift) << p.cin2_shift) + c2), base + (r * RPI + wave * RPW) * CROWB);
         } else {
             const int4 te = taps_s[kidx >> p.cin_shift];
             const int dc = te.z + (kidx & (p.Cin - 1));
@@ -179,12 +151,12 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(ConvParams p) {
                 const bool ok = (((rp1[r] + te.x) & (rp2[r] + te.y)) & 0x808080) == 0x808080;
                 const half_t* g = p.in + (rbase[r] + dc);
                 g = ok ? g : zlane;
-                cglds16_asm(g, base + (r * RPI + wave * RPW) * CROWB);
+                lds_dma16(g, base + (r * RPI + wave * RPW) * CROWB);
             }
         }
         if ((ABL & 1) && !first) return;
 #pragma unroll
-        for (int r = 0; r < BR; ++r) cglds16_asm(wrow[r] + kidx, base + BM * CROWB + (r * RPI + wave * RPW) * CROWB);
+        for (int r = 0; r < BR; ++r) lds_dma16(wrow[r] + kidx, base + BM * CROWB + (r * RPI + wave * RPW) * CROWB);
     };
 
     f32x4 acc[MI][NI];
@@ -210,10 +182,10 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(ConvParams p) {
     for (int kt = kt0; kt < kt1; ++kt) {
         // stage kt must have landed; up to NST - 2 younger stages stay in flight
         const int younger = min(NST - 2, kt1 - 1 - kt);
-        if (NST >= 4 && younger == 2) conv_wait_vmcnt<2 * LPT>();
-        else if (NST >= 3 && younger == 1) conv_wait_vmcnt<LPT>();
-        else conv_wait_vmcnt<0>();
-        conv_reads_landed();
+        if (NST >= 4 && younger == 2) wait_vmcnt<2 * LPT>();
+        else if (NST >= 3 && younger == 1) wait_vmcnt<LPT>();
+        else wait_vmcnt<0>();
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();      // every wave's share of K tile kt is in LDS; the buffer of K tile kt-1 is free
         if (kt + NST - 1 < kt1) {
             int nb = buf + NST - 1;
@@ -421,7 +393,7 @@ __global__ __launch_bounds__(64 * NW) void conv3d_halo_kernel(HaloParams p) {
             const int lch = (lane % CPR) ^ (RB == 128 ? (n >> 1) & 7 : (-(n >> 2)) & 3);
             int nn = n0 + n;
             nn = nn < p.Cout ? nn : p.Cout - 1;
-            cglds16_asm(p.w + (int64_t)nn * p.kpad + (s * G + g) * CIN + lch * 8,
+            lds_dma16(p.w + (int64_t)nn * p.kpad + (s * G + g) * CIN + lch * 8,
                         real ? base + it * 1024 : smem + HALO_BYTES + NSTAGE * BST);
         }
     };
@@ -493,19 +465,19 @@ __global__ __launch_bounds__(64 * NW) void conv3d_halo_kernel(HaloParams p) {
     static_assert(NSTAGE == 3 || NSTAGE == 4, "the prefetch protocol below is written for three or four weight buffers");
     if (NSTAGE == 4 && NS > 2) {
         stageB(2, 2);
-        conv_wait_vmcnt<2 * U>();
+        wait_vmcnt<2 * U>();
     } else {
-        conv_wait_vmcnt<(NS > 1) ? U : 0>();
+        wait_vmcnt<(NS > 1) ? U : 0>();
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm0();
     __builtin_amdgcn_s_barrier();
     readA(0, 0, 0);
     readB(0, smem, 0, 0);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         if (s + 1 < NS) {
-            if (NSTAGE == 4 && s + 2 < NS) conv_wait_vmcnt<U>(); else conv_wait_vmcnt<0>();
-            conv_reads_landed();
+            if (NSTAGE == 4 && s + 2 < NS) wait_vmcnt<U>(); else wait_vmcnt<0>();
+            wait_lgkm0();
             __builtin_amdgcn_s_barrier();   // raw: __syncthreads() adds its own waits
             if (s + NSTAGE - 1 < NS) stageB(s + NSTAGE - 1, (s + NSTAGE - 1) % NSTAGE);
         }
@@ -683,7 +655,7 @@ __global__ __launch_bounds__(512) void convT3d_halo_kernel(ConvTHaloParams p) {
         for (int u = 0; u < U; ++u) {
             const int n = wave * 8 + (lane >> 3);
             const int lch = (lane & 7) ^ ((n >> 1) & 7);
-            cglds16_asm(p.w[2 * pair + u] + n * (8 * CIN) + tap * CIN + kh * 64 + lch * 8, base + (wave + NW * u) * 1024);
+            lds_dma16(p.w[2 * pair + u] + n * (8 * CIN) + tap * CIN + kh * 64 + lch * 8, base + (wave + NW * u) * 1024);
         }
     };
     stageW(0, 0);
@@ -717,8 +689,8 @@ __global__ __launch_bounds__(512) void convT3d_halo_kernel(ConvTHaloParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    conv_wait_vmcnt<2 * U>();                          // stage 0 (and, before it, the halo loads) landed; stages 1, 2 in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_vmcnt<2 * U>();                          // stage 0 (and, before it, the halo loads) landed; stages 1, 2 in flight
+    wait_lgkm0();
     __builtin_amdgcn_s_barrier();
 
     const int OD = 2 * p.D, OH = 2 * p.H, OW = 2 * p.W;
@@ -731,13 +703,13 @@ __global__ __launch_bounds__(512) void convT3d_halo_kernel(ConvTHaloParams p) {
             if (S + 1 < NSTG) {
                 // publish stage S + 1: behind it at most stage S + 2 (and, right after a pair's epilogue, that epilogue's stores) may stay in flight
                 if (st < 2) {
-                    if (pair > 0) conv_wait_vmcnt<U + NSTORE>(); else conv_wait_vmcnt<U>();
+                    if (pair > 0) wait_vmcnt<U + NSTORE>(); else wait_vmcnt<U>();
                 } else if (st == 14 && pair == 3) {
-                    conv_wait_vmcnt<0>();
+                    wait_vmcnt<0>();
                 } else {
-                    conv_wait_vmcnt<U>();
+                    wait_vmcnt<U>();
                 }
-                conv_reads_landed();
+                wait_lgkm0();
                 __builtin_amdgcn_s_barrier();
                 if (S + 3 < NSTG) stageW(S + 3, (S + 3) & 3);
             }
@@ -886,7 +858,7 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_halo_kernel(ConvS2HaloParams 
         for (int u = 0; u < U; ++u) {
             const int n = (wave * U + u) * 8 + (lane >> 3);
             const int lch = (lane & 7) ^ ((n >> 1) & 7);
-            cglds16_asm(p.w + (int64_t)n * p.kpad + t4 * CIN + lch * 8, base + (wave * U + u) * 1024);
+            lds_dma16(p.w + (int64_t)n * p.kpad + t4 * CIN + lch * 8, base + (wave * U + u) * 1024);
         }
     };
 
@@ -897,7 +869,7 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_halo_kernel(ConvS2HaloParams 
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[i][r] = p.bias != nullptr ? p.bias[wn * 32 + i * 16 + q * 4 + r] : 0.f;
     halo_request(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     halo_store();
     stageW(0, 0);
     stageW(1, 1);
@@ -921,8 +893,8 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_halo_kernel(ConvS2HaloParams 
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    conv_wait_vmcnt<2 * U>();                          // stage 0 landed; stages 1, 2 in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_vmcnt<2 * U>();                          // stage 0 landed; stages 1, 2 in flight
+    wait_lgkm0();
     __builtin_amdgcn_s_barrier();
 
 #pragma unroll 1
@@ -933,10 +905,10 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_halo_kernel(ConvS2HaloParams 
             if (S + 1 < NSTG) {
                 // publish stage S + 1: behind it stage S + 2 may stay in flight -- and, at a class's taps 1 and 2, the next class's eight halo loads,
                 // issued behind stage S + 3 at tap 0
-                if ((st == 1 || st == 2) && cls < 7) conv_wait_vmcnt<U + HIT>();
-                else if (S + 2 < NSTG) conv_wait_vmcnt<U>();
-                else conv_wait_vmcnt<0>();
-                conv_reads_landed();
+                if ((st == 1 || st == 2) && cls < 7) wait_vmcnt<U + HIT>();
+                else if (S + 2 < NSTG) wait_vmcnt<U>();
+                else wait_vmcnt<0>();
+                wait_lgkm0();
                 __builtin_amdgcn_s_barrier();
                 if (S + 3 < NSTG) stageW(S + 3, (S + 3) & 3);
             }
@@ -959,10 +931,10 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_halo_kernel(ConvS2HaloParams 
         }
         if (cls < 7) {
             // swap the halo: every wave has read the last tap's fragments; the next class's chunks landed long ago (tap 3's wait retired them)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm0();
             __builtin_amdgcn_s_barrier();
             halo_store();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // (published by the next tap's barrier)
+            wait_lgkm0();     // (published by the next tap's barrier)
         }
     }
     // epilogue: bias, ReLU, fp16; channel blocks 0 / 1 trade halves, lane group q stores 8 consecutive channels of block (q & 1) at offset 8 (q >> 1)

@@ -39,11 +39,6 @@ struct GemmParams {
 
 constexpr int BK = 64;          // K granularity required by the API (k1, k2 multiples of 64)
 
-// LDS-DMA from inline asm (common.h): with the builtin form pending, the compiler treats it as a FLAT access and drains vmcnt and
-// lgkmcnt in front of the fragment reads that follow; the kernel owns its vmcnt waits and barriers anyway (+0.7-1 % on the step,
-// A/B on one box; +25 % on the implicit-GEMM convolution, where it was found)
-__device__ __forceinline__ void glds16(const half_t* g, char* lds_wave_base) { lds_dma16(g, lds_wave_base); }
-
 // XOR swizzle of the 16-B chunk index inside a staged row (applied to the LDS-DMA source address and
 // again on the fragment reads): makes the four 16-lane groups of a ds_read_b128 hit 16 distinct
 // 16-B bank slots for the 16x16x32 operand map (lane -> row lane&15, chunk lane>>4).
@@ -71,16 +66,11 @@ __device__ __forceinline__ void stage_rows(const half_t* __restrict__ src, int64
         int grow = row0 + row;
         grow = grow < row_limit ? grow : row_limit - 1;   // clamp: rows past the edge are masked in the epilogue
         const half_t* g = src + (int64_t)grow * ld + kofs + logical * 8;
-        glds16(g, lds_tile + (r * RPR + wave * RPI) * (BKT * 2));
+        lds_dma16(g, lds_tile + (r * RPR + wave * RPI) * (BKT * 2));
     }
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// the same with a wave-uniform run-time count (0 .. 31): a scalar branch tree in front of the immediate forms
+// wait_vmcnt with a wave-uniform run-time count (0 .. 31): a scalar branch tree in front of the immediate forms
 __device__ __forceinline__ void wait_vmcnt_rt(int n) {
     switch (n) {
 #define PCD_W(k) case k: wait_vmcnt<k>(); break;

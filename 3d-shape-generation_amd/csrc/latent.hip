@@ -48,7 +48,6 @@ __global__ __launch_bounds__(256) void groupnorm_relu_kernel(const float* __rest
     }
 }
 
-static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct LatWs { size_t z16, z1, z2, z3, z4, g0, g1, d, tmp32, total; };
 
@@ -123,7 +122,6 @@ extern "C" int pcd_latent_forward(pcd_latent_t* h, const float* z, int batch, co
     const pcd_latent_desc_t& d = h->d;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
     // one Linear (+GroupNorm+ReLU): weight-streaming split-K GEMM into fp32 slabs, then the finishing
     // kernel (fixed-order slab sum + bias + GroupNorm + ReLU).  mode as in pcd_skinny_finish.
     auto lin = [&](int idx, const void* a1, const void* a2, int k2, const float* bias, const float* row_bias,
@@ -145,20 +143,19 @@ extern "C" int pcd_latent_forward(pcd_latent_t* h, const float* z, int batch, co
     // enc1: reads the fp32 state directly (rounded to fp16 on load); time half hoisted into tbias (one row, or one
     // row per sample)
     (void)z16;
-    RUN(pcd_skinny_fused_f32in(z, d.lin[0].k, d.lin[0].w, d.lin[0].k, batch, d.lin[0].c,
+    PCD_RUN(pcd_skinny_fused_f32in(z, d.lin[0].k, d.lin[0].w, d.lin[0].k, batch, d.lin[0].c,
                                tbias_shape_stride ? nullptr : tbias, tbias_shape_stride ? tbias : nullptr, 0, 8,
                                d.gn_gamma[0], d.gn_beta[0], z1, nullptr, s));
-    RUN(lin_gn(1, z1, nullptr, 0, d.lin[1].b, nullptr, z2));
-    RUN(lin_gn(2, z2, nullptr, 0, d.lin[2].b, nullptr, z3));
-    RUN(lin_gn(3, z3, nullptr, 0, d.lin[3].b, nullptr, z4));
-    RUN(lin_gn(4, z4, nullptr, 0, d.lin[4].b, nullptr, g0));
-    RUN(lin_gn(5, g0, nullptr, 0, d.lin[5].b, nullptr, g1));
-    RUN(lin_gn(6, g1, z4, 1024, d.lin[6].b, nullptr, da));
-    RUN(lin_gn(7, da, z3, 512, d.lin[7].b, nullptr, db));
-    RUN(lin_gn(8, db, z2, 256, d.lin[8].b, nullptr, da));
-    RUN(lin_gn(9, da, z1, 128, d.lin[9].b, nullptr, db));
-    RUN(lin(10, db, nullptr, 0, d.lin[10].b, nullptr, 1, da, nullptr));     // output.0 + ReLU
-    RUN(lin(11, da, nullptr, 0, d.lin[11].b, nullptr, 2, nullptr, eps));    // output.2 -> eps fp32
-#undef RUN
+    PCD_RUN(lin_gn(1, z1, nullptr, 0, d.lin[1].b, nullptr, z2));
+    PCD_RUN(lin_gn(2, z2, nullptr, 0, d.lin[2].b, nullptr, z3));
+    PCD_RUN(lin_gn(3, z3, nullptr, 0, d.lin[3].b, nullptr, z4));
+    PCD_RUN(lin_gn(4, z4, nullptr, 0, d.lin[4].b, nullptr, g0));
+    PCD_RUN(lin_gn(5, g0, nullptr, 0, d.lin[5].b, nullptr, g1));
+    PCD_RUN(lin_gn(6, g1, z4, 1024, d.lin[6].b, nullptr, da));
+    PCD_RUN(lin_gn(7, da, z3, 512, d.lin[7].b, nullptr, db));
+    PCD_RUN(lin_gn(8, db, z2, 256, d.lin[8].b, nullptr, da));
+    PCD_RUN(lin_gn(9, da, z1, 128, d.lin[9].b, nullptr, db));
+    PCD_RUN(lin(10, db, nullptr, 0, d.lin[10].b, nullptr, 1, da, nullptr));     // output.0 + ReLU
+    PCD_RUN(lin(11, da, nullptr, 0, d.lin[11].b, nullptr, 2, nullptr, eps));    // output.2 -> eps fp32
     return PCD_OK;
 }

@@ -19,23 +19,22 @@ namespace {
 const int kK[PCD_LATENT_NLIN] = {256, 128, 256, 512, 1024, 2048, 5120, 1536, 768, 384, 128, 128};
 const int kC[PCD_LATENT_NLIN] = {128, 256, 512, 1024, 2048, 4096, 1024, 512, 256, 128, 128, 256};
 
-size_t up(size_t v) { return (v + 255) / 256 * 256; }
 
 struct Ws { size_t z1, z2, z3, z4, g0, g1, da, db, pre, stats, total; };
 
 Ws carve(int64_t b) {
     Ws w{};
     size_t o = 0;
-    w.z1 = o; o += up(b * 128 * 4);
-    w.z2 = o; o += up(b * 256 * 4);
-    w.z3 = o; o += up(b * 512 * 4);
-    w.z4 = o; o += up(b * 1024 * 4);
-    w.g0 = o; o += up(b * 2048 * 4);
-    w.g1 = o; o += up(b * 4096 * 4);
-    w.da = o; o += up(b * 1024 * 4);
-    w.db = o; o += up(b * 1024 * 4);
-    w.pre = o; o += up(b * 4096 * 4);          // a layer's pre-norm output
-    w.stats = o; o += up(b * 8 * 4) * 2;       // (mean, rstd) per (row, group): written by the GroupNorm kernel, not used further
+    w.z1 = o; o += align_up(b * 128 * 4);
+    w.z2 = o; o += align_up(b * 256 * 4);
+    w.z3 = o; o += align_up(b * 512 * 4);
+    w.z4 = o; o += align_up(b * 1024 * 4);
+    w.g0 = o; o += align_up(b * 2048 * 4);
+    w.g1 = o; o += align_up(b * 4096 * 4);
+    w.da = o; o += align_up(b * 1024 * 4);
+    w.db = o; o += align_up(b * 1024 * 4);
+    w.pre = o; o += align_up(b * 4096 * 4);          // a layer's pre-norm output
+    w.stats = o; o += align_up(b * 8 * 4) * 2;       // (mean, rstd) per (row, group): written by the GroupNorm kernel, not used further
     w.total = o;
     return w;
 }
@@ -70,10 +69,9 @@ extern "C" int pcd_latent_f32_forward(pcd_latent_f32_t* h, const float* z, int b
     char* ws = (char*)workspace;
     auto F = [&](size_t off) { return (float*)(ws + off); };
     float *z1 = F(w.z1), *z2 = F(w.z2), *z3 = F(w.z3), *z4 = F(w.z4), *g0 = F(w.g0), *g1 = F(w.g1), *da = F(w.da), *db = F(w.db);
-    float *pre = F(w.pre), *mean = F(w.stats), *rstd = F(w.stats + up((size_t)batch * 8 * 4));
+    float *pre = F(w.pre), *mean = F(w.stats), *rstd = F(w.stats + align_up((size_t)batch * 8 * 4));
     const pcd_latent_desc_t& d = h->d;
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
     // Linear (bias, or one bias row per sample) [+ GroupNorm(8) + ReLU | + ReLU | identity]
     auto lin = [&](int idx, const float* a1, const float* a2, int k2, const float* bias, const float* row_bias, int mode, float* out) -> int {
         const pcd_linear_desc_t& L = d.lin[idx];
@@ -83,18 +81,17 @@ extern "C" int pcd_latent_f32_forward(pcd_latent_f32_t* h, const float* z, int b
         if (r || mode != 0) return r;
         return pcd_groupnorm_f32(pre, batch, L.c, 8, d.gn_gamma[idx], d.gn_beta[idx], 1e-5f, 1, out, mean, rstd, stream);
     };
-    RUN(lin(0, z, nullptr, 0, tbias_shape_stride ? nullptr : tbias, tbias_shape_stride ? tbias : nullptr, 0, z1));
-    RUN(lin(1, z1, nullptr, 0, d.lin[1].b, nullptr, 0, z2));
-    RUN(lin(2, z2, nullptr, 0, d.lin[2].b, nullptr, 0, z3));
-    RUN(lin(3, z3, nullptr, 0, d.lin[3].b, nullptr, 0, z4));
-    RUN(lin(4, z4, nullptr, 0, d.lin[4].b, nullptr, 0, g0));
-    RUN(lin(5, g0, nullptr, 0, d.lin[5].b, nullptr, 0, g1));
-    RUN(lin(6, g1, z4, 1024, d.lin[6].b, nullptr, 0, da));
-    RUN(lin(7, da, z3, 512, d.lin[7].b, nullptr, 0, db));
-    RUN(lin(8, db, z2, 256, d.lin[8].b, nullptr, 0, da));
-    RUN(lin(9, da, z1, 128, d.lin[9].b, nullptr, 0, db));
-    RUN(lin(10, db, nullptr, 0, d.lin[10].b, nullptr, 1, da));
-    RUN(lin(11, da, nullptr, 0, d.lin[11].b, nullptr, 2, eps));
-#undef RUN
+    PCD_RUN(lin(0, z, nullptr, 0, tbias_shape_stride ? nullptr : tbias, tbias_shape_stride ? tbias : nullptr, 0, z1));
+    PCD_RUN(lin(1, z1, nullptr, 0, d.lin[1].b, nullptr, 0, z2));
+    PCD_RUN(lin(2, z2, nullptr, 0, d.lin[2].b, nullptr, 0, z3));
+    PCD_RUN(lin(3, z3, nullptr, 0, d.lin[3].b, nullptr, 0, z4));
+    PCD_RUN(lin(4, z4, nullptr, 0, d.lin[4].b, nullptr, 0, g0));
+    PCD_RUN(lin(5, g0, nullptr, 0, d.lin[5].b, nullptr, 0, g1));
+    PCD_RUN(lin(6, g1, z4, 1024, d.lin[6].b, nullptr, 0, da));
+    PCD_RUN(lin(7, da, z3, 512, d.lin[7].b, nullptr, 0, db));
+    PCD_RUN(lin(8, db, z2, 256, d.lin[8].b, nullptr, 0, da));
+    PCD_RUN(lin(9, da, z1, 128, d.lin[9].b, nullptr, 0, db));
+    PCD_RUN(lin(10, db, nullptr, 0, d.lin[10].b, nullptr, 1, da));
+    PCD_RUN(lin(11, da, nullptr, 0, d.lin[11].b, nullptr, 2, eps));
     return PCD_OK;
 }

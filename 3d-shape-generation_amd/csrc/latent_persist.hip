@@ -105,19 +105,6 @@ struct LpArgs {
 };
 
 // ------------------------------------------------------------------------------------------------ device helpers
-__device__ __forceinline__ int lp_swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
-
-// LDS-DMA of rows [row0, row0 + 32) x 128 bytes at halfs column k0 of w[rows][ld] into a swizzled 4-KiB image
-// (instruction i of 4 covers rows 8 i .. 8 i + 7); same image format as csrc/skinny.hip
-__device__ __forceinline__ void lp_stage(const half_t* base, int64_t ld, int row0, int k0, char* img, int i, int lane) {
-    const int row = 8 * i + (lane >> 3), ch = lane & 7;
-    lds_dma16(base + (int64_t)(row0 + row) * ld + k0 + lp_swz(row, ch) * 8, img + i * 1024);
-}
-
-__device__ __forceinline__ half8 lp_wfrag(const char* img, int row, int hh, int j) {
-    return *(const half8*)(img + row * 128 + (lp_swz(row, 4 * hh + j) << 4));
-}
-
 __device__ __forceinline__ bool lp_poison16(u32x4 v) { return ((v.x | v.y | v.z | v.w) & 0x80008000u) != 0u; }
 // signed fp16 data (the latent state): poison = NaN halves.  (h & 0x7fff) > 0x7c00 <=> bit 15 of (h & 0x7fff) + 0x03ff, per half, no carry
 __device__ __forceinline__ bool lp_nan16(u32x4 v) {
@@ -339,7 +326,7 @@ __device__ __forceinline__ bool lp_run_gemm(const LpCtx& c, const LpLayer& L, co
                         const half8 a = __builtin_bit_cast(half8, pc[i][j]);
 #pragma unroll
                         for (int t = 0; t < CT; ++t)
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, lp_wfrag(wimg + (t * U.nchunks + cl) * 4096, c.r, c.hh, j), acc[t], 0, 0, 0);
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, frag128(wimg + (t * U.nchunks + cl) * 4096, c.r, c.hh, j), acc[t], 0, 0, 0);
                     }
                 }
             }
@@ -423,7 +410,7 @@ __device__ __forceinline__ bool lp_run_gemm(const LpCtx& c, const LpLayer& L, co
             if (A.x0 != nullptr) *(float4*)(A.x0 + (int64_t)(S.r0 + row) * 256 + U.col0 + 4 * q) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's poison stores are complete before its data stores leave
+    wait_vmcnt<0>();        // this wave's poison stores are complete before its data stores leave
     if (c.tr != nullptr && c.tid == 0) c.tr[3] = lp_now();
     lp_gemm_store<CT>(c, L, U, S.set_off, v, false);
     return true;
@@ -547,7 +534,7 @@ __device__ __forceinline__ bool lp_run_finish(const LpCtx& c, const LpLayer& L, 
 #pragma unroll
         for (int i = 0; i < CPT; ++i) x[i] = (x[i] - mean) * rstd * pst[q * CPT + i] + pst[L.gsz + q * CPT + i];
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     if (c.tr != nullptr && c.tid == 0) c.tr[3] = lp_now();
     lp_finish_store<CPT, TPR>(c, L, U, S.set_off, x, false);
     return true;
@@ -654,7 +641,7 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
                 for (int cl = 0; cl < U.nchunks; ++cl)
                     for (int i = 0; i < 4; ++i, ++task)
                         if ((task & 3) == c.wave)
-                            lp_stage(L.w, L.ldw, U.col0 + 32 * t, (U.chunk0 + cl) * 64, lp_smem + U.lds_w + (t * U.nchunks + cl) * 4096, i, c.lane);
+                            stage_rows32x128(L.w, L.ldw, U.col0 + 32 * t, (U.chunk0 + cl) * 64, lp_smem + U.lds_w + (t * U.nchunks + cl) * 4096, i, c.lane);
         }
     }
     // per-column constants of this workgroup's units -> LDS: gemm units that finish their layer [bias | gamma | beta] x 64 columns,
@@ -701,7 +688,7 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
             lp_gemm_store<1>(c, L, U, LP_CTRL_BYTES + (st * 3 + 2) * A.set_bytes, v1, false);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
 
     const int total = A.forward_only ? 1 : A.nsteps;
@@ -747,7 +734,7 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
         } else {
             ok = lp_dispatch_finish(c, L, U, S, A, poisoned, units);
         }
-        if (ok && TRACE && c.tr != nullptr && c.tid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); c.tr[2] = lp_now(); }
+        if (ok && TRACE && c.tr != nullptr && c.tid == 0) { wait_vmcnt<0>(); c.tr[2] = lp_now(); }
         return ok;
     };
     if constexpr (NS == 1) {

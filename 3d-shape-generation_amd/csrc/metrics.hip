@@ -8,22 +8,6 @@ namespace pcd {
 
 #pragma clang fp contract(off)
 
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [blockDim/64] */) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    T r = scratch[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = op(r, scratch[w]);
-    return r;
-}
-
-struct MaxOp { __device__ float operator()(float a, float b) const { return fmaxf(a, b); } };
-struct MinOp { __device__ float operator()(float a, float b) const { return fminf(a, b); } };
-
 // one block per cloud
 __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict__ pts, int n, float* __restrict__ out) {
     __shared__ float scratch[4];

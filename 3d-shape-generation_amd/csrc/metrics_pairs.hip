@@ -17,21 +17,6 @@ namespace pcd {
 
 #pragma clang fp contract(off)
 
-struct PMaxOp { __device__ float operator()(float a, float b) const { return fmaxf(a, b); } };
-struct PMinOp { __device__ float operator()(float a, float b) const { return fminf(a, b); } };
-template <typename Op>
-__device__ __forceinline__ float pblock_reduce(float v, Op op, float* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) scratch[wave] = v;
-    __syncthreads();
-    float r = scratch[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = op(r, scratch[w]);
-    return r;
-}
-
 // grid (P, 2): cloud 0 = a, 1 = b of pair blockIdx.x; same arithmetic as normalize_kernel (metrics.py:7-21)
 __global__ __launch_bounds__(256) void pair_normalize_kernel(const float* __restrict__ a, const int* __restrict__ na, int NA,
                                                               const float* __restrict__ b, const int* __restrict__ nb, int NB,
@@ -52,15 +37,15 @@ __global__ __launch_bounds__(256) void pair_normalize_kernel(const float* __rest
     float c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float hi = pblock_reduce(mx[k], PMaxOp(), scratch);
-        const float lo = pblock_reduce(mn[k], PMinOp(), scratch);
+        const float hi = block_reduce(mx[k], MaxOp(), scratch);
+        const float lo = block_reduce(mn[k], MinOp(), scratch);
         c[k] = (hi + lo) / 2.f;
     }
     float am = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x)
 #pragma unroll
         for (int k = 0; k < 3; ++k) am = fmaxf(am, fabsf(src[i * 3 + k] - c[k]));
-    const float scale = pblock_reduce(am, PMaxOp(), scratch);
+    const float scale = block_reduce(am, MaxOp(), scratch);
     for (int i = threadIdx.x; i < n; i += blockDim.x)
 #pragma unroll
         for (int k = 0; k < 3; ++k) dst[i * 3 + k] = (src[i * 3 + k] - c[k]) / scale;

@@ -58,27 +58,6 @@ struct SabTailParams {
     int split;                // 1: one wave per SIMD requests a stage's LDS-DMA pieces (pcd_sab_tail_config bit 1)
 };
 
-__device__ __forceinline__ void st_dma(const char* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory", "m0");
-}
-
-// v0 / v1: the four values (already biased / normalised / clamped) of accumulator groups 2 gp and 2 gp + 1 of one 32-channel tile.  Lane half 0
-// ends with the tile's channels 16 gp .. + 7, lane half 1 with 16 gp + 8 .. + 15: the next product's B fragment / one 16-byte output piece.
-__device__ __forceinline__ half8 st_pack_swap(const float (&v0)[4], const float (&v1)[4]) {
-    unsigned f[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        half2_ pa, pb;
-        pa.x = (half_t)v0[2 * h]; pa.y = (half_t)v0[2 * h + 1];
-        pb.x = (half_t)v1[2 * h]; pb.y = (half_t)v1[2 * h + 1];
-        const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, pa), __builtin_bit_cast(unsigned, pb), false, false);
-        f[h] = r[0];
-        f[2 + h] = r[1];
-    }
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    return __builtin_bit_cast(half8, (u4){f[0], f[1], f[2], f[3]});
-}
-
 template <int C>
 __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p) {
     using K = StCfg<C>;
@@ -92,47 +71,17 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p
         const float* src = (const float*)(p.packed + (size_t)K::NSTG * K::STAGE);
         for (int i = threadIdx.x; i < K::NPAR; i += ST_THREADS) par[i] = src[i];
     }
-    const unsigned lds0 = (unsigned)(size_t)st_smem;
     const int64_t ntiles = p.m / ST_TILE;
     const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
     const int total_stages = my_tiles * K::NSTG;
-    // stage n of this workgroup's run = image n % NSTG; wave w moves pieces PPW w .. PPW w + PPW - 1
-    // (p.split: the pieces of stage n are requested by ONE wave of each SIMD -- waves 0-3 for even stages, 4-7 for odd ones, 2 PPW pieces each -- so that its SIMD partner
-    // issues MFMAs meanwhile: round 5, as csrc/wideffn.hip)
+    // stage n of this workgroup's run = image n % NSTG (StageRing, device_prims.h; the request form is chosen at run time)
     const bool split = p.split != 0;
-    auto issue = [&](int n) __attribute__((always_inline)) {
-        if (n < total_stages) {
-            if (split) {
-                if ((wave >> 2) == (n & 1)) {
-                    const int w4 = wave & 3;
-                    const char* src = p.packed + (size_t)(n % K::NSTG) * K::STAGE + (size_t)(2 * K::PPW * w4) * 1024 + lane * 16;
-                    const unsigned dst = lds0 + (n % ST_RING) * K::STAGE + (2 * K::PPW * w4) * 1024;
-#pragma unroll
-                    for (int i = 0; i < 2 * K::PPW; ++i) st_dma(src + i * 1024, dst + i * 1024);
-                }
-            } else {
-                const char* src = p.packed + (size_t)(n % K::NSTG) * K::STAGE + (size_t)(K::PPW * wave) * 1024 + lane * 16;
-                const unsigned dst = lds0 + (n % ST_RING) * K::STAGE + (K::PPW * wave) * 1024;
-#pragma unroll
-                for (int i = 0; i < K::PPW; ++i) st_dma(src + i * 1024, dst + i * 1024);
-            }
-        }
-    };
-    issue(0);
-    issue(1);
     int n = 0;                                                 // next stage to consume
-    // stage n has landed (all but this wave's PPW youngest pieces), this wave's reads of stage n - 1 have RETURNED (the refill of its slot is
-    // issued right behind the barrier: tools/check_barrier_reads.py) and every wave is past them: the slot takes stage n + 2
-    auto acquire = [&]() __attribute__((always_inline)) -> const char* {
-        if (split) {
-            if ((wave >> 2) == (n & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else if (n + 1 < total_stages) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K::PPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();
-        issue(n + 2);
-        return st_smem + (n % ST_RING) * K::STAGE + lane * 16;
-    };
+    const StageRing<K::STAGE, K::PPW, ST_RING> ring{p.packed, st_smem, total_stages, wave, lane, K::NSTG, split};
+    ring.issue(0);
+    ring.issue(1);
+    // (a closure over n: with ring.acquire(n) at the sites themselves the kernels' register numbering changes, profiles/device_prims_isa.md)
+    auto acquire = [&]() __attribute__((always_inline)) -> const char* { return ring.acquire(n); };
     for (int ti = 0; ti < my_tiles; ++ti) {
         const int64_t tile = blockIdx.x + (int64_t)ti * gridDim.x;
         const int64_t pt = tile * ST_TILE + wave * 32 + pnt;
@@ -202,7 +151,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p
             for (int e = 0; e < 16; ++e) { const float dv = acc[t][e] - mean; ssq += dv * dv; }
         ssq += __shfl_xor(ssq, 32);
         const float rstd = rsqrtf(ssq * (1.f / C) + 1e-5f);
-        // ---- LN2(x1) -> B fragments (k step 2 t + gp); then the accumulators take b_ff2 and go on as y
+        // ---- LN2(x1) -> B fragments (k step 2 t + gp), from the fp32 accumulators (PCD_LN_FRAGMENTS normalises fp16 B fragments); then the accumulators take b_ff2 and go on as y
         half8 lnf[KS];
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -217,7 +166,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[u][e] = __builtin_amdgcn_fmed3f((acc[t][4 * g + e] - mean) * rstd * ga[e] + be[e], -65504.f, 65504.f);
                 }
-                lnf[2 * t + gp] = st_pack_swap(v[0], v[1]);
+                lnf[2 * t + gp] = regroup_swap(v[0], v[1]);
             }
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -258,7 +207,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[w][e] = __builtin_amdgcn_fmed3f(h[u][4 * g + e] + bb[e], 0.f, 65504.f);
                     }
-                    hf[2 * u + gp] = st_pack_swap(v[0], v[1]);
+                    hf[2 * u + gp] = regroup_swap(v[0], v[1]);
                 }
             const char* img2 = img + K::W2OFF;
 #pragma unroll
@@ -291,7 +240,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_tail_kernel(SabTailParams p
                         for (int e = 0; e < 4; ++e) v[w][e] = __builtin_amdgcn_fmed3f((float)(half_t)v[w][e] + ev[e], -65504.f, 65504.f);
                     }
                 }
-                *(half8*)(orow + 32 * t + 16 * gp) = st_pack_swap(v[0], v[1]);
+                *(half8*)(orow + 32 * t + 16 * gp) = regroup_swap(v[0], v[1]);
             }
     }
 }
@@ -321,43 +270,16 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_head_kernel(SabHeadParams p
         const float* src = (const float*)(p.packed + (size_t)3 * K::HSTAGE);
         for (int i = threadIdx.x; i < K::HNPAR; i += ST_THREADS) par[i] = src[i];
     }
-    const unsigned lds0 = (unsigned)(size_t)st_smem;
     const int64_t ntiles = p.m / ST_TILE;
     const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
     const int total_stages = my_tiles * 3;
     const bool split = p.split != 0;
-    auto issue = [&](int n) __attribute__((always_inline)) {
-        if (n < total_stages) {
-            if (split) {
-                if ((wave >> 2) == (n & 1)) {
-                    const int w4 = wave & 3;
-                    const char* src = p.packed + (size_t)(n % 3) * K::HSTAGE + (size_t)(2 * K::HPPW * w4) * 1024 + lane * 16;
-                    const unsigned dst = lds0 + (n % ST_RING) * K::HSTAGE + (2 * K::HPPW * w4) * 1024;
-#pragma unroll
-                    for (int i = 0; i < 2 * K::HPPW; ++i) st_dma(src + i * 1024, dst + i * 1024);
-                }
-            } else {
-                const char* src = p.packed + (size_t)(n % 3) * K::HSTAGE + (size_t)(K::HPPW * wave) * 1024 + lane * 16;
-                const unsigned dst = lds0 + (n % ST_RING) * K::HSTAGE + (K::HPPW * wave) * 1024;
-#pragma unroll
-                for (int i = 0; i < K::HPPW; ++i) st_dma(src + i * 1024, dst + i * 1024);
-            }
-        }
-    };
-    issue(0);
-    issue(1);
-    __syncthreads();                                           // the LayerNorm affine is read before the first stage barrier
     int n = 0;
-    auto acquire = [&]() __attribute__((always_inline)) -> const char* {
-        if (split) {
-            if ((wave >> 2) == (n & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else if (n + 1 < total_stages) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K::HPPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();
-        issue(n + 2);
-        return st_smem + (n % ST_RING) * K::HSTAGE + lane * 16;
-    };
+    const StageRing<K::HSTAGE, K::HPPW, ST_RING> ring{p.packed, st_smem, total_stages, wave, lane, 3, split};
+    ring.issue(0);
+    ring.issue(1);
+    __syncthreads();                                           // the LayerNorm affine is read before the first stage barrier
+    auto acquire = [&]() __attribute__((always_inline)) -> const char* { return ring.acquire(n); };
     for (int ti = 0; ti < my_tiles; ++ti) {
         const int64_t tile = blockIdx.x + (int64_t)ti * gridDim.x;
         const int64_t pt = tile * ST_TILE + wave * 32 + pnt;
@@ -379,44 +301,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_head_kernel(SabHeadParams p
                 }
             }
         }
-        {
-            // variance about the mean in a second pass over the packed fp16 pairs (sum(x^2) - C mean^2 cancels when |mean| >> std): subtract
-            // mh = fp16(mean) in packed fp16 and remove the shift exactly, sum (x - mh)^2 = sum (x - mean)^2 + C (mean - mh)^2  (widechain.hip)
-            float sum = 0.f, sq = 0.f;
-            half2_ one2; one2.x = one2.y = (half_t)1.f;
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    half2_ v; v.x = bf[s][2 * e]; v.y = bf[s][2 * e + 1];
-                    sum = __builtin_amdgcn_fdot2(v, one2, sum, false);
-                }
-            sum += __shfl_xor(sum, 32);
-            const float mean = sum * (1.f / C);
-            const half_t mh = (half_t)__builtin_amdgcn_fmed3f(mean, -65504.f, 65504.f);
-            half2_ mh2; mh2.x = mh2.y = mh;
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    half2_ v; v.x = bf[s][2 * e]; v.y = bf[s][2 * e + 1];
-                    const half2_ d = v - mh2;
-                    sq = __builtin_amdgcn_fdot2(d, d, sq, false);
-                }
-            sq += __shfl_xor(sq, 32);
-            const float shift = mean - (float)mh;
-            const float rstd = rsqrtf(fmaxf(sq - C * shift * shift, 0.f) * (1.f / C) + 1e-5f);
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const f32x4 g0 = *(const f32x4*)&par[K::HGA + 16 * s + 8 * hh], g1 = *(const f32x4*)&par[K::HGA + 16 * s + 8 * hh + 4];
-                const f32x4 b0 = *(const f32x4*)&par[K::HBE + 16 * s + 8 * hh], b1 = *(const f32x4*)&par[K::HBE + 16 * s + 8 * hh + 4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bf[s][e] = (half_t)__builtin_amdgcn_fmed3f(((float)bf[s][e] - mean) * rstd * g0[e] + b0[e], -65504.f, 65504.f);
-                    bf[s][4 + e] = (half_t)__builtin_amdgcn_fmed3f(((float)bf[s][4 + e] - mean) * rstd * g1[e] + b1[e], -65504.f, 65504.f);
-                }
-            }
-        }
+        PCD_LN_FRAGMENTS(bf, C, par, K::HGA, par, K::HBE, hh);
         half_t* orow = p.qkv + pt * (3 * C) + 8 * hh;
 #pragma unroll 1
         for (int pass = 0; pass < 3; ++pass) {
@@ -448,7 +333,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_head_kernel(SabHeadParams p
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[w][e] = __builtin_amdgcn_fmed3f(acc[t][4 * g + e] + b4[e], -65504.f, 65504.f);
                     }
-                    *(half8*)(orow + pass * C + 32 * t + 16 * gp) = st_pack_swap(v[0], v[1]);
+                    *(half8*)(orow + pass * C + 32 * t + 16 * gp) = regroup_swap(v[0], v[1]);
                 }
         }
     }

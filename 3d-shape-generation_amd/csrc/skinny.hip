@@ -85,22 +85,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(SkinnyParams p) {
 // LDS-DMA instructions in full 128-byte lines (8 rows each), ALL chunks of the slice requested at kernel entry, with the
 // XOR swizzle of the attention K tile on the source address so that the ds_read_b128 fragment reads are conflict free.
 // Same products, same summation order as skinny_gemm_kernel<1>: bitwise identical slabs.
-__device__ __forceinline__ int sk_swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
-
-// stage rows [0, 32) x 128 bytes at byte column `kbyte` of a row-major fp16 matrix (row stride `ld` halfs, rows clamped
-// to `row_limit - 1`) into the 4-KiB image at `img`: instruction i of 4 covers rows 8 i .. 8 i + 7
-__device__ __forceinline__ void sk_stage_chunk(const half_t* base, int64_t ld, int row0, int row_limit, int k0, char* img,
-                                               int i, int lane) {
-    const int row = 8 * i + (lane >> 3), ch = lane & 7;
-    int gr = row0 + row;
-    gr = gr < row_limit ? gr : row_limit - 1;
-    lds_dma16(base + (int64_t)gr * ld + k0 + sk_swz(row, ch) * 8, img + i * 1024);
-}
-
-__device__ __forceinline__ half8 sk_frag(const char* img, int row, int hh, int j) {
-    return *(const half8*)(img + row * 128 + (sk_swz(row, 4 * hh + j) << 4));
-}
-
 __global__ __launch_bounds__(256) void skinny_gemm_dma_kernel(SkinnyParams p) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];     // [chunks][W image 4 KiB | A image 4 KiB]; reused for the reduction
     const int lane = threadIdx.x & 63;
@@ -116,14 +100,14 @@ __global__ __launch_bounds__(256) void skinny_gemm_dma_kernel(SkinnyParams p) {
         const int k = kbeg + ch * 64;
         char* img = sk_smem + ch * 8192;
         if (i < 4) {
-            sk_stage_chunk(p.w, p.ldw, n0, p.c, k, img, i, lane);
+            stage_rows32x128(p.w, p.ldw, n0, p.c, k, img, i, lane);
         } else {
             const half_t* src = k < p.k1 ? p.a1 : p.a2;
             const int lda = k < p.k1 ? p.k1 : p.k2;
-            sk_stage_chunk(src, lda, 0, p.m, k < p.k1 ? k : k - p.k1, img + 4096, i - 4, lane);
+            stage_rows32x128(src, lda, 0, p.m, k < p.k1 ? k : k - p.k1, img + 4096, i - 4, lane);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     f32x16 acc;
 #pragma unroll
@@ -132,7 +116,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_dma_kernel(SkinnyParams p) {
         const char* img = sk_smem + ch * 8192;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(sk_frag(img + 4096, r, hh, j), sk_frag(img, r, hh, j), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag128(img + 4096, r, hh, j), frag128(img, r, hh, j), acc, 0, 0, 0);
     }
     __syncthreads();                                    // the images are dead: the reduction reuses their space
     float (*red)[32][33] = (float (*)[32][33])sk_smem;

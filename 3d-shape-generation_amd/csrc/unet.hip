@@ -53,7 +53,6 @@ int pw_chain_enc1_impl(const float* x, int64_t m, int rows_per_shape, const floa
                        const void* w_conv2, const float* b_conv2, const void* w_conv3, const float* b_conv3, void* x1, bool hilo,
                        float* zero, int64_t zero_n, void* stream);
 
-static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct UnetWs {
     size_t x1, x2, x3, x4, s0, s1, pooled, pooled16, gbias, total;
@@ -234,7 +233,6 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
     hipStream_t s = (hipStream_t)stream;
     const pcd_unet_desc_t& d = h->d;
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
     const bool chains = (g_unet_chains & 1) != 0;
     bool pooled_cleared = false;
     const bool wide = (g_unet_chains & 2) != 0 && m % 256 == 0;     // enc3 / dec2 as register-resident chains (whole 256-point tiles only)
@@ -243,36 +241,36 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
         const unsigned e1 = d.hilo_mask & 3u;              // lin 0, 1 travel together (one launch)
         if (e1 == 3u || e1 == 0u) {
             // the same launch clears the pooled maxima that global_feat.3's column-max epilogue accumulates into further down
-            RUN(pw_chain_enc1_impl(x, m, n_points, d.e1w_xyz, tbias, tbias_shape_stride, d.lin[0].w, d.lin[0].b, d.lin[1].w, d.lin[1].b, x1,
+            PCD_RUN(pw_chain_enc1_impl(x, m, n_points, d.e1w_xyz, tbias, tbias_shape_stride, d.lin[0].w, d.lin[0].b, d.lin[1].w, d.lin[1].b, x1,
                                    e1 == 3u, pooled, (int64_t)batch * 4096, s));
             pooled_cleared = true;
         } else {
-            RUN(pcd_enc1_xyz(x, m, n_points, d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, s));
-            RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
-            RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
+            PCD_RUN(pcd_enc1_xyz(x, m, n_points, d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, s));
+            PCD_RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
+            PCD_RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
         }
-        RUN(pcd_pw_chain_128(x1, m, d.lin[2].w, d.lin[2].b, d.lin[3].w, d.lin[3].b, s1, s));
+        PCD_RUN(pcd_pw_chain_128(x1, m, d.lin[2].w, d.lin[2].b, d.lin[3].w, d.lin[3].b, s1, s));
     } else {
-        RUN(pcd_enc1_xyz(x, m, n_points, d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, s));
-        RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
-        RUN(run_lin(d, 2, m, x1, nullptr, 0, nullptr, 0, s0, s));
-        RUN(run_lin(d, 3, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(pcd_enc1_xyz(x, m, n_points, d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, s));
+        PCD_RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
+        PCD_RUN(run_lin(d, 2, m, x1, nullptr, 0, nullptr, 0, s0, s));
+        PCD_RUN(run_lin(d, 3, m, s0, nullptr, 0, nullptr, 0, s1, s));
     }
-    RUN(run_lin(d, 4, m, s1, nullptr, 0, nullptr, 0, x2, s));
+    PCD_RUN(run_lin(d, 4, m, s1, nullptr, 0, nullptr, 0, x2, s));
     if (wide) {
-        RUN(pcd_pw_wide_chain(0, x2, nullptr, m, h->wide[0], x3, s));
+        PCD_RUN(pcd_pw_wide_chain(0, x2, nullptr, m, h->wide[0], x3, s));
     } else {
-        RUN(run_lin(d, 5, m, x2, nullptr, 0, nullptr, 0, s0, s));
-        RUN(run_lin(d, 6, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        RUN(run_lin(d, 7, m, s1, nullptr, 0, nullptr, 0, x3, s));
+        PCD_RUN(run_lin(d, 5, m, x2, nullptr, 0, nullptr, 0, s0, s));
+        PCD_RUN(run_lin(d, 6, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(run_lin(d, 7, m, s1, nullptr, 0, nullptr, 0, x3, s));
     }
-    RUN(run_lin(d, 8, m, x3, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[8]));
-    RUN(run_lin(d, 9, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[9]));
-    RUN(run_lin(d, 10, m, s1, nullptr, 0, nullptr, 0, x4, s, h->lin_frag[10]));
-    RUN(run_lin(d, 11, m, x4, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[11]));
+    PCD_RUN(run_lin(d, 8, m, x3, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[8]));
+    PCD_RUN(run_lin(d, 9, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[9]));
+    PCD_RUN(run_lin(d, 10, m, s1, nullptr, 0, nullptr, 0, x4, s, h->lin_frag[10]));
+    PCD_RUN(run_lin(d, 11, m, x4, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[11]));
     {   // global_feat.3 + max over the N points of each shape
-        if (!pooled_cleared) RUN(pcd_fill_zero(pooled, (size_t)batch * 4096 * sizeof(float), s));
+        if (!pooled_cleared) PCD_RUN(pcd_fill_zero(pooled, (size_t)batch * 4096 * sizeof(float), s));
         pcd_gemm_desc_t g{};
         g.a1 = s0; g.k1 = 2048; g.lda1 = 2048; g.w = d.lin[12].w; g.ldw = 2048; g.bias = d.lin[12].b;
         g.relu = 1; g.m = (int)m; g.c = 4096;
@@ -288,62 +286,61 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
         // whole 256 x 256 tiles, a multiple of 256 of them, shapes of whole 128-row wave tiles: the weights-from-global kernel; else the LDS-staged one
         const int64_t tiles = (m / 256) * 16;
         if (h->gf3_frag != nullptr && pcd_gemm_wfrag_enabled() && m % 256 == 0 && tiles >= 256 && tiles % 256 == 0 && n_points % 128 == 0)
-            RUN(pcd_gemm_f16_colmax_wfrag(&g, h->gf3_frag, pooled, n_points, s));
+            PCD_RUN(pcd_gemm_f16_colmax_wfrag(&g, h->gf3_frag, pooled, n_points, s));
         else
-            RUN(pcd_gemm_f16_colmax(&g, pooled, n_points, s));
+            PCD_RUN(pcd_gemm_f16_colmax(&g, pooled, n_points, s));
         if (prof) { PCD_CHECK_HIP(hipEventRecord(h->ev1[h->prof_n], s)); ++h->prof_n; }
     }
     {   // hoisted global half of dec4.conv1: per-shape bias [B][1024] = pooled . Wg^T + folded bias
-        RUN(pcd_f32_to_f16(pooled, pooled16, (int64_t)batch * 4096, s));
+        PCD_RUN(pcd_f32_to_f16(pooled, pooled16, (int64_t)batch * 4096, s));
         if (batch <= 256) {
             // few rows: weight-streaming split-K kernel (csrc/skinny.hip), slabs live in the free s1 buffer
-            RUN(pcd_skinny_gemm_f16(pooled16, 4096, nullptr, 0, d.wg, 4096, batch, 1024, (float*)s1, s));
-            RUN(pcd_skinny_finish((const float*)s1, pcd_skinny_slabs(4096, 1024), batch, 1024, d.lin[13].b, nullptr, 2, 8,
+            PCD_RUN(pcd_skinny_gemm_f16(pooled16, 4096, nullptr, 0, d.wg, 4096, batch, 1024, (float*)s1, s));
+            PCD_RUN(pcd_skinny_finish((const float*)s1, pcd_skinny_slabs(4096, 1024), batch, 1024, d.lin[13].b, nullptr, 2, 8,
                                   nullptr, nullptr, nullptr, gbias, s));
         } else {
             pcd_gemm_desc_t g{};
             g.a1 = pooled16; g.k1 = 4096; g.lda1 = 4096; g.w = d.wg; g.ldw = 4096; g.bias = d.lin[13].b;
             g.relu = 0; g.m = batch; g.c = 1024;
-            RUN(pcd_gemm_f16_out32(&g, gbias, 1024, s));
+            PCD_RUN(pcd_gemm_f16_out32(&g, gbias, 1024, s));
         }
     }
-    RUN(run_lin(d, 13, m, x4, nullptr, 0, gbias, n_points, s1, s, h->lin_frag[13]));
-    RUN(run_lin(d, 14, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[14]));
-    RUN(run_lin(d, 15, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[15]));
+    PCD_RUN(run_lin(d, 13, m, x4, nullptr, 0, gbias, n_points, s1, s, h->lin_frag[13]));
+    PCD_RUN(run_lin(d, 14, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[14]));
+    PCD_RUN(run_lin(d, 15, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[15]));
 #define TAP(i, buf, ch) do { if (h->dec_tap[i]) PCD_CHECK_HIP(hipMemcpyAsync(h->dec_tap[i], buf, (size_t)m * (ch) * 2, \
                                                                              hipMemcpyDeviceToDevice, s)); } while (0)
     TAP(0, s1, 512);
-    RUN(run_lin(d, 16, m, s1, x3, 512, nullptr, 0, s0, s, h->lin_frag[16]));
-    RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
-    RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
+    PCD_RUN(run_lin(d, 16, m, s1, x3, 512, nullptr, 0, s0, s, h->lin_frag[16]));
+    PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
+    PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
     TAP(1, s0, 256);
     if (wide) {
-        RUN(pcd_pw_wide_chain(1, s0, x2, m, h->wide[1], s1, s));
+        PCD_RUN(pcd_pw_wide_chain(1, s0, x2, m, h->wide[1], s1, s));
     } else {
-        RUN(run_lin(d, 19, m, s0, x2, 256, nullptr, 0, s1, s));
-        RUN(run_lin(d, 20, m, s1, nullptr, 0, nullptr, 0, s0, s));
-        RUN(run_lin(d, 21, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(run_lin(d, 19, m, s0, x2, 256, nullptr, 0, s1, s));
+        PCD_RUN(run_lin(d, 20, m, s1, nullptr, 0, nullptr, 0, s0, s));
+        PCD_RUN(run_lin(d, 21, m, s0, nullptr, 0, nullptr, 0, s1, s));
     }
     TAP(2, s1, 128);
-    RUN(run_lin(d, 22, m, s1, x1, 128, nullptr, 0, s0, s));
+    PCD_RUN(run_lin(d, 22, m, s1, x1, 128, nullptr, 0, s0, s));
     const unsigned tl = (d.hilo_mask >> 23) & 7u;         // lin 23, 24, 25 travel together (one launch)
     if (chains && h->dec_tap[3] == nullptr && (tl == 0u || tl == 7u)) {
         // dec1.conv2 -> conv3 -> output.0 -> output.3 (128 -> 128 -> 64 -> 64 -> 3): one launch
         if (tl == 7u)
-            RUN(pcd_pw_chain_tail_hilo(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
+            PCD_RUN(pcd_pw_chain_tail_hilo(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
                                        d.head_b, eps, s));
         else
-            RUN(pcd_pw_chain_tail(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
+            PCD_RUN(pcd_pw_chain_tail(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
                                   d.head_b, eps, s));
     } else {
-        RUN(run_lin(d, 23, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        RUN(run_lin(d, 24, m, s1, nullptr, 0, nullptr, 0, s0, s));
+        PCD_RUN(run_lin(d, 23, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(run_lin(d, 24, m, s1, nullptr, 0, nullptr, 0, s0, s));
         TAP(3, s0, 64);       // dec1's output exists only inside the chained tail: a capture runs the tail as per-layer launches (same bits)
-        RUN(run_lin(d, 25, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        RUN(pcd_head3(s1, m, 64, d.head_w, d.head_b, eps, s));
+        PCD_RUN(run_lin(d, 25, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        PCD_RUN(pcd_head3(s1, m, 64, d.head_w, d.head_b, eps, s));
     }
 #undef TAP
-#undef RUN
     return PCD_OK;
 }
 

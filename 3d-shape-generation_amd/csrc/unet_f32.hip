@@ -202,25 +202,24 @@ struct Ws32 {
     size_t x1, x2, x3, x4, s0, s1, pooled, gbias, d4, d3, d2, d1, total;
 };
 
-size_t up(size_t v) { return (v + 255) / 256 * 256; }
 
 Ws32 carve32(int64_t batch, int64_t n) {
     const size_t m = (size_t)batch * (size_t)n;
     Ws32 w{};
     size_t o = 0;
-    w.x1 = o; o += up(m * 128 * 4);
-    w.x2 = o; o += up(m * 256 * 4);
-    w.x3 = o; o += up(m * 512 * 4);
-    w.x4 = o; o += up(m * 1024 * 4);
-    w.s0 = o; o += up(m * 2048 * 4);
-    w.s1 = o; o += up(m * 1024 * 4);
-    w.pooled = o; o += up((size_t)batch * 4096 * 4);
-    w.gbias = o; o += up((size_t)batch * 1024 * 4);
+    w.x1 = o; o += align_up(m * 128 * 4);
+    w.x2 = o; o += align_up(m * 256 * 4);
+    w.x3 = o; o += align_up(m * 512 * 4);
+    w.x4 = o; o += align_up(m * 1024 * 4);
+    w.s0 = o; o += align_up(m * 2048 * 4);
+    w.s1 = o; o += align_up(m * 1024 * 4);
+    w.pooled = o; o += align_up((size_t)batch * 4096 * 4);
+    w.gbias = o; o += align_up((size_t)batch * 1024 * 4);
     // decoder-block outputs are kept (not ping-ponged away) so that every tap of a forward can be read afterwards
-    w.d4 = o; o += up(m * 512 * 4);
-    w.d3 = o; o += up(m * 256 * 4);
-    w.d2 = o; o += up(m * 128 * 4);
-    w.d1 = o; o += up(m * 64 * 4);
+    w.d4 = o; o += align_up(m * 512 * 4);
+    w.d3 = o; o += align_up(m * 256 * 4);
+    w.d2 = o; o += align_up(m * 128 * 4);
+    w.d1 = o; o += align_up(m * 64 * 4);
     w.total = o;
     return w;
 }
@@ -289,7 +288,6 @@ extern "C" int pcd_unet_f32_forward(pcd_unet_f32_t* h, const float* x, int batch
     hipStream_t s = (hipStream_t)stream;
     const pcd_unet_desc_t& d = h->d;
     int rc;
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
     auto lin = [&](int idx, const float* a1, const float* a2, int k2, const float* shape_bias, float* out) {
         const pcd_linear_desc_t& L = d.lin[idx];
         GemmF32 g{a1, L.k - k2, L.k - k2, a2, k2, k2, (const float*)L.w, L.k, shape_bias ? nullptr : L.b, shape_bias,
@@ -299,45 +297,44 @@ extern "C" int pcd_unet_f32_forward(pcd_unet_f32_t* h, const float* x, int batch
     hipLaunchKernelGGL(enc1_xyz_f32_kernel, dim3((unsigned)ceil_div(m * 64, 256)), dim3(256), 0, s, x, m, n_points,
                        d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, (int)((h->round_mask >> 26) & 1u));
     PCD_CHECK_LAUNCH();
-    RUN(lin(0, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(1, s1, nullptr, 0, nullptr, x1));
-    RUN(lin(2, x1, nullptr, 0, nullptr, s0));
-    RUN(lin(3, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(4, s1, nullptr, 0, nullptr, x2));
-    RUN(lin(5, x2, nullptr, 0, nullptr, s0));
-    RUN(lin(6, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(7, s1, nullptr, 0, nullptr, x3));
-    RUN(lin(8, x3, nullptr, 0, nullptr, s0));
-    RUN(lin(9, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(10, s1, nullptr, 0, nullptr, x4));
-    RUN(lin(11, x4, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(0, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(1, s1, nullptr, 0, nullptr, x1));
+    PCD_RUN(lin(2, x1, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(3, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(4, s1, nullptr, 0, nullptr, x2));
+    PCD_RUN(lin(5, x2, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(6, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(7, s1, nullptr, 0, nullptr, x3));
+    PCD_RUN(lin(8, x3, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(9, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(10, s1, nullptr, 0, nullptr, x4));
+    PCD_RUN(lin(11, x4, nullptr, 0, nullptr, s0));
     PCD_CHECK_HIP(hipMemsetAsync(pooled, 0, (size_t)batch * 4096 * sizeof(float), s));
     {   // global_feat.3 + max over the N points of each shape
         GemmF32 g{s0, 2048, 2048, nullptr, 0, 0, (const float*)d.lin[12].w, 2048, d.lin[12].b, nullptr, n_points, 1, (int)m,
                   4096, nullptr, 0, pooled};
-        RUN(launch_gemm(g, true, s));
+        PCD_RUN(launch_gemm(g, true, s));
     }
     {   // hoisted global half of dec4.conv1: per-shape bias [B][1024] = pooled . Wg^T + folded bias
         GemmF32 g{pooled, 4096, 4096, nullptr, 0, 0, (const float*)d.wg, 4096, d.lin[13].b, nullptr, 0, 0, batch, 1024, gbias,
                   1024, nullptr};
-        RUN(launch_gemm(g, false, s));
+        PCD_RUN(launch_gemm(g, false, s));
     }
-    RUN(lin(13, x4, nullptr, 0, gbias, s1));
-    RUN(lin(14, s1, nullptr, 0, nullptr, s0));
-    RUN(lin(15, s0, nullptr, 0, nullptr, d4));
-    RUN(lin(16, d4, x3, 512, nullptr, s0));
-    RUN(lin(17, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(18, s1, nullptr, 0, nullptr, d3));
-    RUN(lin(19, d3, x2, 256, nullptr, s0));
-    RUN(lin(20, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(21, s1, nullptr, 0, nullptr, d2));
-    RUN(lin(22, d2, x1, 128, nullptr, s0));
-    RUN(lin(23, s0, nullptr, 0, nullptr, s1));
-    RUN(lin(24, s1, nullptr, 0, nullptr, d1));
-    RUN(lin(25, d1, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(13, x4, nullptr, 0, gbias, s1));
+    PCD_RUN(lin(14, s1, nullptr, 0, nullptr, s0));
+    PCD_RUN(lin(15, s0, nullptr, 0, nullptr, d4));
+    PCD_RUN(lin(16, d4, x3, 512, nullptr, s0));
+    PCD_RUN(lin(17, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(18, s1, nullptr, 0, nullptr, d3));
+    PCD_RUN(lin(19, d3, x2, 256, nullptr, s0));
+    PCD_RUN(lin(20, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(21, s1, nullptr, 0, nullptr, d2));
+    PCD_RUN(lin(22, d2, x1, 128, nullptr, s0));
+    PCD_RUN(lin(23, s0, nullptr, 0, nullptr, s1));
+    PCD_RUN(lin(24, s1, nullptr, 0, nullptr, d1));
+    PCD_RUN(lin(25, d1, nullptr, 0, nullptr, s0));
     hipLaunchKernelGGL(head3_f32_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s, s0, m, d.head_w, d.head_b, eps);
     PCD_CHECK_LAUNCH();
-#undef RUN
     return PCD_OK;
 }
 

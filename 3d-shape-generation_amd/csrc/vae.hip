@@ -240,7 +240,6 @@ extern "C" size_t pcd_vae_workspace_bytes(int batch) {
     hipStream_t s = (hipStream_t)stream;                                                      \
     const Runner R{d, batch, ws + w.scratch, w.scratch_bytes, s};                             \
     int rc
-#define RUN(expr) do { rc = (expr); if (rc) return rc; } while (0)
 #define SWAP(a, b) do { t_ = a; a = b; b = t_; } while (0)
 
 extern "C" int pcd_vae_encode(pcd_vae_t* h, const float* vox, int batch, float* mu_logvar, void* workspace,
@@ -249,17 +248,17 @@ extern "C" int pcd_vae_encode(pcd_vae_t* h, const float* vox, int batch, float* 
     VAE_PROLOGUE();
     // encoder.0/1: Conv3d(1, 32, k3, p1) + ReLU straight from the fp32 occupancy grid
     // a residual block leaves its output in x, whichever buffer that is
-    RUN(pcd_conv3d_first(vox, batch, 32, 32, 32, 1, d.enc0_w, d.enc0_b, 32, x, s));
-    RUN(R.res(d.enc_res[0], x, 32, hb, r, h->wf_enc2c1, h->wf_enc2c2));           // encoder.2   32 -> 64 @ 32^3
-    RUN(R.conv(d.enc_down[0], x, 32, 2, d.taps4s2, 16, 1, nullptr, hb));          // encoder.3/4 k4 s2 -> 16^3
+    PCD_RUN(pcd_conv3d_first(vox, batch, 32, 32, 32, 1, d.enc0_w, d.enc0_b, 32, x, s));
+    PCD_RUN(R.res(d.enc_res[0], x, 32, hb, r, h->wf_enc2c1, h->wf_enc2c2));           // encoder.2   32 -> 64 @ 32^3
+    PCD_RUN(R.conv(d.enc_down[0], x, 32, 2, d.taps4s2, 16, 1, nullptr, hb));          // encoder.3/4 k4 s2 -> 16^3
     SWAP(x, hb);
-    RUN(R.res(d.enc_res[1], x, 16, hb, r, h->wf_enc5c1, h->wf_enc5c2));           // encoder.5   64 -> 128
-    RUN(R.conv(d.enc_down[1], x, 16, 2, d.taps4s2, 8, 1, nullptr, hb));           // encoder.6/7 -> 8^3
+    PCD_RUN(R.res(d.enc_res[1], x, 16, hb, r, h->wf_enc5c1, h->wf_enc5c2));           // encoder.5   64 -> 128
+    PCD_RUN(R.conv(d.enc_down[1], x, 16, 2, d.taps4s2, 8, 1, nullptr, hb));           // encoder.6/7 -> 8^3
     SWAP(x, hb);
-    RUN(R.res(d.enc_res[2], x, 8, hb, r));                                        // encoder.8   128 -> 256
-    RUN(R.conv(d.enc_down[2], x, 8, 2, d.taps4s2, 4, 1, nullptr, hb));            // encoder.9/10 -> 4^3
+    PCD_RUN(R.res(d.enc_res[2], x, 8, hb, r));                                        // encoder.8   128 -> 256
+    PCD_RUN(R.conv(d.enc_down[2], x, 8, 2, d.taps4s2, 4, 1, nullptr, hb));            // encoder.9/10 -> 4^3
     SWAP(x, hb);
-    RUN(R.res(d.enc_res[3], x, 4, hb, r));                                        // encoder.11  256 -> 512
+    PCD_RUN(R.res(d.enc_res[3], x, 4, hb, r));                                        // encoder.11  256 -> 512
     void* const B = x; void* const A = hb;                                       // below: B = encoder.11's output, A = scratch
     (void)r;
     // encoder.12/13: k4 p0 on a 4^3 grid = one row of 32768 inputs per sample -> (B, 512).  With <= 256 samples that is the
@@ -268,23 +267,23 @@ extern "C" int pcd_vae_encode(pcd_vae_t* h, const float* vox, int batch, float* 
     const size_t slab_bytes = (size_t)pcd_skinny_slabs(k_last, d.enc_last.cout) * batch * d.enc_last.cout * sizeof(float);
     if (batch <= 256 && d.enc_last.kpad == k_last && slab_bytes <= w.scratch_bytes) {
         float* slabs = (float*)(ws + w.scratch);
-        RUN(pcd_skinny_gemm_f16(B, k_last, nullptr, 0, d.enc_last.w, d.enc_last.kpad, batch, d.enc_last.cout, slabs, s));
-        RUN(pcd_skinny_finish(slabs, pcd_skinny_slabs(k_last, d.enc_last.cout), batch, d.enc_last.cout, d.enc_last.b, nullptr,
+        PCD_RUN(pcd_skinny_gemm_f16(B, k_last, nullptr, 0, d.enc_last.w, d.enc_last.kpad, batch, d.enc_last.cout, slabs, s));
+        PCD_RUN(pcd_skinny_finish(slabs, pcd_skinny_slabs(k_last, d.enc_last.cout), batch, d.enc_last.cout, d.enc_last.b, nullptr,
                               1, 0, nullptr, nullptr, A, nullptr, s));
     } else {
-        RUN(R.conv(d.enc_last, B, 4, 1, d.taps4p0, 1, 1, nullptr, A));
+        PCD_RUN(R.conv(d.enc_last, B, 4, 1, d.taps4p0, 1, 1, nullptr, A));
     }
     // [fc_mu ; fc_logvar]: 512 -> 2 * latent, fp32 out
     const int c_fc = 2 * d.latent_dim, s_fc = pcd_skinny_slabs(512, c_fc);
     if (batch <= 256 && (size_t)s_fc * batch * c_fc * sizeof(float) <= w.scratch_bytes) {
         float* slabs = (float*)(ws + w.scratch);
-        RUN(pcd_skinny_gemm_f16(A, 512, nullptr, 0, d.fc_w, 512, batch, c_fc, slabs, s));
-        RUN(pcd_skinny_finish(slabs, s_fc, batch, c_fc, d.fc_b, nullptr, 2, 0, nullptr, nullptr, nullptr, mu_logvar, s));
+        PCD_RUN(pcd_skinny_gemm_f16(A, 512, nullptr, 0, d.fc_w, 512, batch, c_fc, slabs, s));
+        PCD_RUN(pcd_skinny_finish(slabs, s_fc, batch, c_fc, d.fc_b, nullptr, 2, 0, nullptr, nullptr, nullptr, mu_logvar, s));
     } else {
         pcd_gemm_desc_t g{};
         g.a1 = A; g.k1 = 512; g.lda1 = 512; g.w = d.fc_w; g.ldw = 512; g.bias = d.fc_b; g.relu = 0; g.m = batch;
         g.c = c_fc;
-        RUN(pcd_gemm_f16_out32(&g, mu_logvar, c_fc, s));
+        PCD_RUN(pcd_gemm_f16_out32(&g, mu_logvar, c_fc, s));
     }
     return PCD_OK;
 }
@@ -294,26 +293,25 @@ extern "C" int pcd_vae_decode(pcd_vae_t* h, const float* z, int batch, float* ou
     PCD_CHECK_ARG(h && z && out && workspace && batch > 0);
     VAE_PROLOGUE();
     void* z16 = ws + w.small;
-    RUN(pcd_f32_to_f16(z, z16, (int64_t)batch * d.latent_dim, s));
+    PCD_RUN(pcd_f32_to_f16(z, z16, (int64_t)batch * d.latent_dim, s));
     pcd_gemm_desc_t g{};                                                         // decoder_input, columns already in NDHWC order
     g.a1 = z16; g.k1 = d.latent_dim; g.lda1 = d.latent_dim; g.w = d.din_w; g.ldw = d.latent_dim; g.bias = d.din_b;
     g.relu = 0; g.m = batch; g.c = 512 * 64;
-    RUN(pcd_gemm_f16(&g, x, 512 * 64, s));                                       // (B, 4,4,4, 512)
-    RUN(R.convT(d.dec_up[0], x, 4, hb));                                          // decoder.0/1  512 -> 256 @ 8^3
+    PCD_RUN(pcd_gemm_f16(&g, x, 512 * 64, s));                                       // (B, 4,4,4, 512)
+    PCD_RUN(R.convT(d.dec_up[0], x, 4, hb));                                          // decoder.0/1  512 -> 256 @ 8^3
     SWAP(x, hb);
-    RUN(R.res(d.dec_res[0], x, 8, hb, r));                                        // decoder.2
-    RUN(R.convT(d.dec_up[1], x, 8, hb));                                          // decoder.3/4  256 -> 128 @ 16^3
+    PCD_RUN(R.res(d.dec_res[0], x, 8, hb, r));                                        // decoder.2
+    PCD_RUN(R.convT(d.dec_up[1], x, 8, hb));                                          // decoder.3/4  256 -> 128 @ 16^3
     SWAP(x, hb);
-    RUN(R.res(d.dec_res[1], x, 16, hb, r, h->wf_dec5c1, h->wf_dec5c2));           // decoder.5
-    RUN(R.convT(d.dec_up[2], x, 16, hb));                                         // decoder.6/7  128 -> 64 @ 32^3
+    PCD_RUN(R.res(d.dec_res[1], x, 16, hb, r, h->wf_dec5c1, h->wf_dec5c2));           // decoder.5
+    PCD_RUN(R.convT(d.dec_up[2], x, 16, hb));                                         // decoder.6/7  128 -> 64 @ 32^3
     SWAP(x, hb);
-    RUN(R.res(d.dec_res[2], x, 32, hb, r, h->wf_dec8c1, h->wf_dec8c2));           // decoder.8
-    RUN(R.conv(d.dec_conv9, x, 32, 1, d.taps3, 32, 1, nullptr, hb, nullptr, 0, h->wf_dec9));   // decoder.9/10  64 -> 32
+    PCD_RUN(R.res(d.dec_res[2], x, 32, hb, r, h->wf_dec8c1, h->wf_dec8c2));           // decoder.8
+    PCD_RUN(R.conv(d.dec_conv9, x, 32, 1, d.taps3, 32, 1, nullptr, hb, nullptr, 0, h->wf_dec9));   // decoder.9/10  64 -> 32
     SWAP(x, hb);
-    RUN(R.res(d.dec_res[3], x, 32, hb, r, h->wf_dec11c1, h->wf_dec11c2));         // decoder.11
-    RUN(pcd_conv3d_last_sigmoid_packed(x, batch, 32, 32, 32, 32, d.last_w, h->wf_last, d.last_b, out, s));   // decoder.12/13
+    PCD_RUN(R.res(d.dec_res[3], x, 32, hb, r, h->wf_dec11c1, h->wf_dec11c2));         // decoder.11
+    PCD_RUN(pcd_conv3d_last_sigmoid_packed(x, batch, 32, 32, 32, 32, d.last_w, h->wf_last, d.last_b, out, s));   // decoder.12/13
     return PCD_OK;
 }
 #undef SWAP
-#undef RUN
 #undef VAE_PROLOGUE

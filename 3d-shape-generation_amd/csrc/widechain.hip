@@ -45,42 +45,9 @@ struct WcParams {
     WcSeg seg[WC_MAXSEG];
 };
 
-__device__ __forceinline__ void wc_dma(const char* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory", "m0");
-}
-
-// two accumulator groups (same channel tile, g = 2 gp and 2 gp + 1) -> the 8 consecutive channels a lane needs as the next B fragment /
-// as one 16-byte output piece: lane half 0 ends with channels 16 s .. + 7, lane half 1 with 16 s + 8 .. + 15 (s = 2 t + gp)
-__device__ __forceinline__ half8 wc_regroup(const f32x16& acc, int gp, const float* bias_t, int hh, float lo = 0.f) {
-    // group g holds channels 8 g + 4 hh + e of the 32-channel tile
-    unsigned p[2], q[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int g0 = 2 * gp, g1 = 2 * gp + 1;
-        const float a0 = acc[4 * g0 + 2 * h] + bias_t[8 * g0 + 4 * hh + 2 * h], a1 = acc[4 * g0 + 2 * h + 1] + bias_t[8 * g0 + 4 * hh + 2 * h + 1];
-        const float b0 = acc[4 * g1 + 2 * h] + bias_t[8 * g1 + 4 * hh + 2 * h], b1 = acc[4 * g1 + 2 * h + 1] + bias_t[8 * g1 + 4 * hh + 2 * h + 1];
-        half2_ pa, pb;
-        pa.x = (half_t)__builtin_amdgcn_fmed3f(a0, lo, 65504.f); pa.y = (half_t)__builtin_amdgcn_fmed3f(a1, lo, 65504.f);
-        pb.x = (half_t)__builtin_amdgcn_fmed3f(b0, lo, 65504.f); pb.y = (half_t)__builtin_amdgcn_fmed3f(b1, lo, 65504.f);
-        p[h] = __builtin_bit_cast(unsigned, pa);
-        q[h] = __builtin_bit_cast(unsigned, pb);
-    }
-    // registers P = (half 0: X0, half 1: X1), Q = (half 0: Y0, half 1: Y1)  ->  (X0, Y0) and (X1, Y1): swap P's upper lanes with Q's lower lanes
-    unsigned f[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const auto r = __builtin_amdgcn_permlane32_swap(p[h], q[h], false, false);
-        f[h] = r[0];            // half 0: X0[h], half 1: Y0[h]
-        f[2 + h] = r[1];        // half 0: X1[h], half 1: Y1[h]
-    }
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    return __builtin_bit_cast(half8, (u4){f[0], f[1], f[2], f[3]});
-}
-
 // LN = false: the chains of UNetPointNetLarge; LN = true: LayerNorm + Linear (pcd_pw_wide_ln_linear) -- its own instantiation so that the chains keep their
 // register allocation (246 registers, no spill)
-// SPLIT: an image's 32 LDS-DMA pieces are requested by ONE wave of each SIMD (waves 0-3 for even images of the workgroup's run, 4-7 for odd ones, 8 pieces each) instead of
-// 4 pieces by every wave, so that the requesting wave's SIMD partner issues MFMAs meanwhile (round 5, as csrc/wideffn.hip)
+// SPLIT: the request form of the weight-image ring (StageRing, device_prims.h)
 template <bool LN, bool SPLIT>
 __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p) {
     extern __shared__ __attribute__((aligned(16))) char wc_smem[];          // [WC_RING][WC_STAGE] | bias copy
@@ -93,32 +60,14 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p
     float* ln_lds = bias_lds + WC_MAXSEG * 256;                // (present when p.ln: the host sizes the allocation)
     if constexpr (LN)
         for (int i = threadIdx.x; i < 512; i += WC_THREADS) ln_lds[i] = p.ln[i];
-    const unsigned lds0 = (unsigned)(size_t)wc_smem;
     const int64_t ntiles = p.m / WC_TILE;
     const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
     const int nstage_seq = p.nseg * 4;                         // stages per tile of points
     const int total_stages = my_tiles * nstage_seq;
-    // stage n of this workgroup's run = image (n % nstage_seq); wave w moves pieces 4 w .. 4 w + 3 of its 32
-    auto issue = [&](int n) __attribute__((always_inline)) {
-        if (n < total_stages) {
-            if constexpr (SPLIT) {
-                if ((wave >> 2) == (n & 1)) {
-                    const int w4 = wave & 3;
-                    const char* src = p.wpacked + (size_t)(n % nstage_seq) * WC_STAGE + (size_t)(8 * w4) * 1024 + lane * 16;
-                    const unsigned dst = lds0 + (n % WC_RING) * WC_STAGE + (8 * w4) * 1024;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) wc_dma(src + i * 1024, dst + i * 1024);
-                }
-            } else {
-                const char* src = p.wpacked + (size_t)(n % nstage_seq) * WC_STAGE + (size_t)(4 * wave) * 1024 + lane * 16;
-                const unsigned dst = lds0 + (n % WC_RING) * WC_STAGE + (4 * wave) * 1024;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wc_dma(src + i * 1024, dst + i * 1024);
-            }
-        }
-    };
-    issue(0);
-    issue(1);
+    // stage n of this workgroup's run = image (n % nstage_seq)
+    const StageRing<WC_STAGE, 4, WC_RING> ring{p.wpacked, wc_smem, total_stages, wave, lane, nstage_seq, SPLIT};
+    ring.issue(0);
+    ring.issue(1);
     if constexpr (LN) __syncthreads();                         // ln_lds is read before the first stage barrier
     int n = 0;                                                 // next stage to consume
     for (int ti = 0; ti < my_tiles; ++ti) {
@@ -134,50 +83,9 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p
                 const half_t* row = (S.src == 1 ? p.in1 : p.in2) + pt * 256 + 8 * hh;
 #pragma unroll
                 for (int s = 0; s < 16; ++s) bf[s] = *(const half8*)(row + 16 * s);
-                if constexpr (LN) {
-                    // LayerNorm of the point's 256 channels (this lane holds 128 of them, lane ^ 32 the others): fp32 statistics, result in fp16
-                    // like pcd_layernorm_f16's.  (The first barrier below orders these reads of ln_lds behind its fill; at the first tile of a
-                    // workgroup the fill is ordered by the __syncthreads() in front of the tile loop.)
-                    // Statistics straight from the packed fp16 pairs by v_dot2_f32_f16 with fp32 accumulation (a pass over converted values would keep
-                    // 128 more registers alive and spill).  Two passes, the variance about the mean: sum(x^2) - 256 mean^2 cancels when |mean| >> std
-                    // (post-ReLU rows near the fp16 range).  The second pass subtracts mh = fp16(mean) in packed fp16 (exact or 1 ulp of a small
-                    // difference) and removes the shift exactly: sum (x - mh)^2 = sum (x - mean)^2 + 256 (mean - mh)^2 because sum (x - mean) = 0.
-                    float sum = 0.f, sq = 0.f;
-                    half2_ one2; one2.x = one2.y = (half_t)1.f;
-#pragma unroll
-                    for (int s = 0; s < 16; ++s)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            half2_ v; v.x = bf[s][2 * e]; v.y = bf[s][2 * e + 1];
-                            sum = __builtin_amdgcn_fdot2(v, one2, sum, false);
-                        }
-                    sum += __shfl_xor(sum, 32);
-                    const float mean = sum * (1.f / 256.f);
-                    const half_t mh = (half_t)__builtin_amdgcn_fmed3f(mean, -65504.f, 65504.f);
-                    half2_ mh2; mh2.x = mh2.y = mh;
-#pragma unroll
-                    for (int s = 0; s < 16; ++s)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            half2_ v; v.x = bf[s][2 * e]; v.y = bf[s][2 * e + 1];
-                            const half2_ d = v - mh2;
-                            sq = __builtin_amdgcn_fdot2(d, d, sq, false);
-                        }
-                    sq += __shfl_xor(sq, 32);
-                    const float shift = mean - (float)mh;
-                    const float ssq = fmaxf(sq - 256.f * shift * shift, 0.f);
-                    const float rstd = rsqrtf(ssq * (1.f / 256.f) + 1e-5f);
-#pragma unroll
-                    for (int s = 0; s < 16; ++s) {
-                        const f32x4 g0 = *(const f32x4*)&ln_lds[16 * s + 8 * hh], g1 = *(const f32x4*)&ln_lds[16 * s + 8 * hh + 4];
-                        const f32x4 b0 = *(const f32x4*)&ln_lds[256 + 16 * s + 8 * hh], b1 = *(const f32x4*)&ln_lds[256 + 16 * s + 8 * hh + 4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            bf[s][e] = (half_t)__builtin_amdgcn_fmed3f(((float)bf[s][e] - mean) * rstd * g0[e] + b0[e], -65504.f, 65504.f);
-                            bf[s][4 + e] = (half_t)__builtin_amdgcn_fmed3f(((float)bf[s][4 + e] - mean) * rstd * g1[e] + b1[e], -65504.f, 65504.f);
-                        }
-                    }
-                }
+                // LayerNorm of the point's 256 channels.  (The first barrier below orders these reads of ln_lds behind its fill; at the first tile of a
+                // workgroup the fill is ordered by the __syncthreads() in front of the tile loop.)
+                if constexpr (LN) PCD_LN_FRAGMENTS(bf, 256, ln_lds, 0, ln_lds, 256, hh);
             }
             if (!S.cont) {
 #pragma unroll
@@ -187,19 +95,7 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p
             }
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
-                // stage n has landed (all but this wave's 4 youngest LDS-DMA pieces), every wave is done with stage n - 1: its
-                // slot takes stage n + 2
-                if constexpr (SPLIT) {
-                    // the group that requested stage n waits for all its pieces; the other group's pieces (stage n + 1) stay in flight; the barrier publishes
-                    if ((wave >> 2) == (n & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                } else {
-                    if (n + 1 < total_stages) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");     // (lgkmcnt: tools/check_barrier_reads.py)
-                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                }
-                __syncthreads();
-                issue(n + 2);
-                const char* img = wc_smem + (n % WC_RING) * WC_STAGE + lane * 16;
+                const char* img = ring.acquire(n);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     half8 af[8];
@@ -218,14 +114,14 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p
 #pragma unroll
                 for (int t = 0; t < 8; ++t)
 #pragma unroll
-                    for (int gp = 0; gp < 2; ++gp) bf[2 * t + gp] = wc_regroup(acc[t], gp, bseg + 32 * t, hh, lo);
+                    for (int gp = 0; gp < 2; ++gp) bf[2 * t + gp] = regroup_bias_clamp(acc[t], gp, bseg + 32 * t, hh, lo);
             } else {
                 half_t* orow = p.out + pt * p.ldo + S.coff + 8 * hh;
 #pragma unroll
                 for (int t = 0; t < 8; ++t)
 #pragma unroll
                     for (int gp = 0; gp < 2; ++gp) {
-                        const half8 v = wc_regroup(acc[t], gp, bseg + 32 * t, hh, lo);
+                        const half8 v = regroup_bias_clamp(acc[t], gp, bseg + 32 * t, hh, lo);
                         if (32 * t + 16 * gp < S.cvalid) *(half8*)(orow + 32 * t + 16 * gp) = v;
                     }
             }

@@ -34,38 +34,8 @@ struct WfParams {
     int64_t estride; int rps;
 };
 
-__device__ __forceinline__ void wf_dma(const char* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory", "m0");
-}
-
-// two accumulator groups of one 32-channel block (g = 2 gp, 2 gp + 1) -> the 8 consecutive channels 16 gp + 8 hh .. + 7 of the block a lane holds as a B fragment /
-// output piece (widechain.hip's regroup: accumulator register 4 g + e = channel 8 g + 4 hh + e of the block, point = lane & 31)
-__device__ __forceinline__ half8 wf_regroup(const f32x16& acc, int gp, const float* bias_blk, int hh, float lo) {
-    unsigned p[2], q[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int g0 = 2 * gp, g1 = 2 * gp + 1;
-        const float a0 = acc[4 * g0 + 2 * h] + bias_blk[8 * g0 + 4 * hh + 2 * h], a1 = acc[4 * g0 + 2 * h + 1] + bias_blk[8 * g0 + 4 * hh + 2 * h + 1];
-        const float b0 = acc[4 * g1 + 2 * h] + bias_blk[8 * g1 + 4 * hh + 2 * h], b1 = acc[4 * g1 + 2 * h + 1] + bias_blk[8 * g1 + 4 * hh + 2 * h + 1];
-        half2_ pa, pb;
-        pa.x = (half_t)__builtin_amdgcn_fmed3f(a0, lo, 65504.f); pa.y = (half_t)__builtin_amdgcn_fmed3f(a1, lo, 65504.f);
-        pb.x = (half_t)__builtin_amdgcn_fmed3f(b0, lo, 65504.f); pb.y = (half_t)__builtin_amdgcn_fmed3f(b1, lo, 65504.f);
-        p[h] = __builtin_bit_cast(unsigned, pa);
-        q[h] = __builtin_bit_cast(unsigned, pb);
-    }
-    unsigned f[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const auto r = __builtin_amdgcn_permlane32_swap(p[h], q[h], false, false);
-        f[h] = r[0];
-        f[2 + h] = r[1];
-    }
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    return __builtin_bit_cast(half8, (u4){f[0], f[1], f[2], f[3]});
-}
-
-// SPLIT: the 32 LDS-DMA pieces of an image are requested by ONE wave of each SIMD (waves 0-3 for even images, 4-7 for odd ones, 8 pieces each) instead of 4 pieces by
-// every wave: a piece holds its wave's issue for 60-180 cycles, and with every wave requesting behind the barrier no wave of a SIMD issues MFMAs meanwhile
+// SPLIT: the request form of the weight-image ring (the protocol and both forms: StageRing, device_prims.h): with every wave requesting behind the barrier no wave of a
+// SIMD issues MFMAs meanwhile
 // ABL: timing ablations for tools/bench_wide_ffn.py (pcd_wide_ffn_config(16 + bits); OUTPUTS ARE WRONG while set): 1 = no image requests in the loop (the ring keeps the
 // first three images), 2 = no fragment reads (every MFMA takes the fragments of the first one), 4 = no waits / barriers in the loop, 8 = no MFMAs
 template <bool SPLIT, int ABL = 0>
@@ -86,7 +56,9 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
     const int64_t ntiles = p.m / WF_TILE;
     const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
     const int total_stages = my_tiles * WF_STAGES_PER_TILE;
-    // image n of this workgroup's run = stage image n % 32; wave w moves pieces 4 w .. 4 w + 3 of its 32 (SPLIT: the waves of group n & 1 move 8 w' .. 8 w' + 7)
+    // image n of this workgroup's run = stage image n % 32; wave w moves pieces 4 w .. 4 w + 3 of its 32 (SPLIT: the waves of group n & 1 move 8 w' .. 8 w' + 7).
+    // StageRing's protocol spelled out here, not the shared struct: through it the ablation instantiations 10 and 11 change their register counts, and without a
+    // compile-time request form in the struct the SPLIT ones change their instruction order (profiles/device_prims_isa.md)
     auto issue = [&](int n) __attribute__((always_inline)) {
         if ((ABL & 1) && n >= WF_RING) return;
         if (n < total_stages) {
@@ -96,13 +68,13 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
                     const char* src = p.wpacked + (size_t)(n % WF_STAGES_PER_TILE) * WF_STAGE + (size_t)(8 * w4) * 1024 + lane * 16;
                     const unsigned dst = lds0 + (n % WF_RING) * WF_STAGE + (8 * w4) * 1024;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) wf_dma(src + i * 1024, dst + i * 1024);
+                    for (int i = 0; i < 8; ++i) lds_dma16(src + i * 1024, dst + i * 1024);
                 }
             } else {
                 const char* src = p.wpacked + (size_t)(n % WF_STAGES_PER_TILE) * WF_STAGE + (size_t)(4 * wave) * 1024 + lane * 16;
                 const unsigned dst = lds0 + (n % WF_RING) * WF_STAGE + (4 * wave) * 1024;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) wf_dma(src + i * 1024, dst + i * 1024);
+                for (int i = 0; i < 4; ++i) lds_dma16(src + i * 1024, dst + i * 1024);
             }
         }
     };
@@ -110,8 +82,6 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
     issue(1);
     __syncthreads();                                           // the constants are read before the first stage barrier
     int n = 0;                                                 // next image to consume
-    // image n has landed (all but this wave's 4 youngest LDS-DMA pieces; SPLIT: every piece of the group that requested it), every wave is done with image n - 1
-    // (its LDS reads included): its slot takes image n + 2
     auto acquire = [&]() __attribute__((always_inline)) -> const char* {
         if constexpr ((ABL & 4) != 0) {
             issue(n + 2);
@@ -120,11 +90,11 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
             return img0;
         }
         if constexpr (SPLIT) {
-            if ((wave >> 2) == (n & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if ((wave >> 2) == (n & 1)) wait_vmcnt_lgkm0<0>();
+            else wait_lgkm0();
         } else {
-            if (n + 1 < total_stages) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            if (n + 1 < total_stages) wait_vmcnt_lgkm0<4>();
+            else wait_vmcnt_lgkm0<0>();
         }
         __syncthreads();
         issue(n + 2);
@@ -148,43 +118,7 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
     for (int ti = 0; ti < my_tiles; ++ti) {
         const int64_t tile = blockIdx.x + (int64_t)ti * gridDim.x;
         const int64_t pt = tile * WF_TILE + pair * 32 + pnt;
-        // ---- LayerNorm on the fragments (widechain.hip's LN prologue: two passes, fp32 statistics)
-        {
-            float sum = 0.f, sq = 0.f;
-            half2_ one2; one2.x = one2.y = (half_t)1.f;
-#pragma unroll
-            for (int s = 0; s < 16; ++s)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    half2_ v; v.x = xin[s][2 * e]; v.y = xin[s][2 * e + 1];
-                    sum = __builtin_amdgcn_fdot2(v, one2, sum, false);
-                }
-            sum += __shfl_xor(sum, 32);
-            const float mean = sum * (1.f / 256.f);
-            const half_t mh = (half_t)__builtin_amdgcn_fmed3f(mean, -65504.f, 65504.f);
-            half2_ mh2; mh2.x = mh2.y = mh;
-#pragma unroll
-            for (int s = 0; s < 16; ++s)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    half2_ v; v.x = xin[s][2 * e]; v.y = xin[s][2 * e + 1];
-                    const half2_ d = v - mh2;
-                    sq = __builtin_amdgcn_fdot2(d, d, sq, false);
-                }
-            sq += __shfl_xor(sq, 32);
-            const float shift = mean - (float)mh;
-            const float rstd = rsqrtf(fmaxf(sq - 256.f * shift * shift, 0.f) * (1.f / 256.f) + 1e-5f);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const f32x4 g0 = *(const f32x4*)&gam[16 * s + 8 * hh], g1 = *(const f32x4*)&gam[16 * s + 8 * hh + 4];
-                const f32x4 c0 = *(const f32x4*)&bet[16 * s + 8 * hh], c1 = *(const f32x4*)&bet[16 * s + 8 * hh + 4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xin[s][e] = (half_t)__builtin_amdgcn_fmed3f(((float)xin[s][e] - mean) * rstd * g0[e] + c0[e], -65504.f, 65504.f);
-                    xin[s][4 + e] = (half_t)__builtin_amdgcn_fmed3f(((float)xin[s][4 + e] - mean) * rstd * g1[e] + c1[e], -65504.f, 65504.f);
-                }
-            }
-        }
+        PCD_LN_FRAGMENTS(xin, 256, gam, 0, bet, 0, hh);
         f32x16 accY[4];
 #pragma unroll
         for (int b = 0; b < 4; ++b)
@@ -225,7 +159,7 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
                     for (int gp = 0; gp < 2; ++gp) {
-                        hown[2 * b + gp] = wf_regroup(accH[b], gp, bb + 32 * b, hh, 0.f);
+                        hown[2 * b + gp] = regroup_bias_clamp(accH[b], gp, bb + 32 * b, hh, 0.f);
                         *(half8*)(my_slot + (2 * b + gp) * 1024) = hown[2 * b + gp];
                     }
             }
@@ -261,7 +195,7 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
             for (int b = 0; b < 4; ++b)
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
-                    half8 v = wf_regroup(accY[b], gp, b2 + 128 * h + 32 * b, hh, -65504.f);
+                    half8 v = regroup_bias_clamp(accY[b], gp, b2 + 128 * h + 32 * b, hh, -65504.f);
                     const half8 r = *(const half8*)(xrow + 32 * b + 16 * gp);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = to_half_sat((float)v[e] + (float)r[e]);

@@ -643,3 +643,93 @@ def test_sab_head_tail_with_folded_time_embeddings_bitwise(C, shared):
     # misaligned / bad stride is refused
     assert lib.pcd_sab_tail_bias_f16(C, desc.tail_packed, a.data_ptr(), x.data_ptr(), rows, rps_arg, e[1:].data_ptr(), None, stride, y1.data_ptr(), st) != 0
     assert lib.pcd_sab_head_bias_f16(C, desc.tail_packed, x.data_ptr(), rows, rps_arg, pre.data_ptr(), 702, qkv_f.data_ptr(), st) != 0
+
+
+def _ring_kernel(kernel):
+    """(config entry, default, other, rows per tile, grid cap, inputs(rows), run(inputs) -> output) of one kernel that streams its weights through the
+    three-slot LDS-DMA ring; the cap is the launch code's (csrc/widechain.hip, wideffn.hip, sab_tail.hip)."""
+    import ctypes as C_
+    from shapegen_amd import _lib
+    from shapegen_amd.networks import _PackedSAB
+    lib = _lib.load()
+    st = _lib.stream_ptr()
+    g = torch.Generator().manual_seed(sum(map(ord, kernel)))
+    dev = lambda t: t.cuda().contiguous()
+    rnd = lambda rows, c, scale=1.0, shift=0.0: dev((torch.randn(rows, c, generator=g) * scale + shift).half())
+    nan = lambda rows, c: torch.full((rows, c), float("nan"), dtype=torch.float16, device="cuda")
+    if kernel in ("chain0", "chain1"):
+        chain = int(kernel[-1])
+        shapes = [(256, 256), (256, 256), (512, 256)] if chain == 0 else [(256, 512), (256, 256), (128, 256)]
+        ws = [dev((torch.randn(s, generator=g) / s[1] ** 0.5).half()) for s in shapes]
+        bs = [dev(torch.randn(s[0], generator=g) * 0.1) for s in shapes]
+        packed = torch.empty(int(lib.pcd_pw_wide_packed_bytes(chain)), dtype=torch.uint8, device="cuda")
+        wp = (C_.c_void_p * 3)(*[t.data_ptr() for t in ws])
+        bp = (C_.c_void_p * 3)(*[t.data_ptr() for t in bs])
+        _lib.check(lib.pcd_pw_wide_pack(chain, wp, bp, packed.data_ptr(), st))
+
+        def run(xs):
+            out = nan(xs[0].shape[0], shapes[2][0])
+            _lib.check(lib.pcd_pw_wide_chain(chain, xs[0].data_ptr(), xs[1].data_ptr() if chain else 0, xs[0].shape[0], packed.data_ptr(), out.data_ptr(), st))
+            return out
+        return lib.pcd_pw_wide_config, 1, 0, 256, 256, lambda rows: (rnd(rows, 256).clamp_min(0), rnd(rows, 256).clamp_min(0)), run
+    if kernel == "ln_linear":
+        passes = 3
+        w, b = dev((torch.randn(256 * passes, 256, generator=g) / 16).half()), dev(torch.randn(256 * passes, generator=g) * 0.1)
+        ga, be = dev(1 + 0.2 * torch.randn(256, generator=g)), dev(0.1 * torch.randn(256, generator=g))
+        packed = torch.empty(lib.pcd_pw_wide_ln_linear_packed_bytes(passes), dtype=torch.uint8, device="cuda")
+        _lib.check(lib.pcd_pw_wide_ln_linear_pack(w.data_ptr(), b.data_ptr(), passes, ga.data_ptr(), be.data_ptr(), packed.data_ptr(), st))
+
+        def run(x):
+            out = nan(x.shape[0], 256 * passes)
+            _lib.check(lib.pcd_pw_wide_ln_linear(packed.data_ptr(), passes, 0, x.data_ptr(), x.shape[0], out.data_ptr(), st))
+            return out
+        return lib.pcd_pw_wide_config, 1, 2, 256, 256, lambda rows: rnd(rows, 256, 1.7, 0.4), run
+    if kernel == "wide_ffn":
+        sd = sab_sd(256)
+        t = [dev(sd["ff.0.weight"].half()), dev(sd["ff.0.bias"].float()), dev(sd["ff.2.weight"].half()), dev(sd["ff.2.bias"].float()),
+             dev(sd["ln2.weight"].float()), dev(sd["ln2.bias"].float())]
+        packed = torch.empty(lib.pcd_wide_ffn_packed_bytes(), dtype=torch.uint8, device="cuda")
+        _lib.check(lib.pcd_wide_ffn_pack(*[v.data_ptr() for v in t], packed.data_ptr(), st))
+
+        def run(x):
+            y = nan(x.shape[0], 256)
+            _lib.check(lib.pcd_wide_ffn_f16(packed.data_ptr(), x.data_ptr(), x.shape[0], y.data_ptr(), st))
+            return y
+        return lib.pcd_wide_ffn_config, 1, 0, 128, 256, lambda rows: rnd(rows, 256, 1.4, 0.2), run
+    part, C = kernel.rsplit("_", 1)
+    C = int(C)
+    pk = _PackedSAB(sab_sd(C), "", C, torch.device("cuda"))
+    desc = pk.fill(_lib.SabDesc())
+    assert desc.tail_packed
+
+    def run(ax, pk=pk):                                        # (pk owns the packed image behind desc)
+        a, x = ax
+        if part == "sab_tail":
+            y = nan(x.shape[0], C)
+            _lib.check(lib.pcd_sab_tail_f16(C, desc.tail_packed, a.data_ptr(), x.data_ptr(), x.shape[0], y.data_ptr(), st))
+        else:
+            y = nan(x.shape[0], 3 * C)
+            _lib.check(lib.pcd_sab_head_f16(C, desc.tail_packed, x.data_ptr(), x.shape[0], y.data_ptr(), st))
+        return y
+    cap = 256 if C == 128 else (512 if part == "sab_tail" else 768)
+    return lib.pcd_sab_tail_config, 1, 3, 256, cap, lambda rows: (rnd(rows, C, 0.7), rnd(rows, C, 1.5, 0.3)), run
+
+
+@pytest.mark.parametrize("kernel", ["chain0", "chain1", "ln_linear", "wide_ffn", "sab_tail_64", "sab_tail_128", "sab_head_64", "sab_head_128"])
+def test_weight_ring_request_forms_bitwise(kernel):
+    """Who requests an LDS-DMA piece of a weight image (every wave its share, or one wave of each SIMD the whole of it) does not enter the arithmetic: the
+    same seeded input under the default request form and under the other one gives the same BITS.  At one tile, and at grid cap + 1 tiles: exactly one
+    workgroup runs a second tile, so the ring wraps across a tile boundary, the last stage takes the vmcnt(0) branch and the workgroups' tile counts differ."""
+    from shapegen_amd import _lib
+    config, default, other, tile, cap, inputs, run = _ring_kernel(kernel)
+    for rows in (tile, (cap + 1) * tile):
+        x = inputs(rows)
+        try:
+            _lib.check(config(default))
+            a = run(x)
+            _lib.check(config(other))
+            b = run(x)
+        finally:
+            _lib.check(config(default))
+        assert torch.isfinite(a).all() and a.float().abs().max() > 0
+        assert torch.equal(a, b), (kernel, rows)

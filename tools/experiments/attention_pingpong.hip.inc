@@ -78,7 +78,7 @@ __global__ __launch_bounds__(512) void set_attention_pp_kernel(const half_t* __r
         const int logical = isv ? v_swz<KRB>(row, lane % CPR) : k_swz<KRB>(row, lane % CPR);
         int grow = kt * PKT + row;
         grow = grow < n ? grow : n - 1;
-        aglds16_asm((isv ? vbase : kbase) + (int64_t)grow * ld + logical * 8,
+        lds_dma16((isv ? vbase : kbase) + (int64_t)grow * ld + logical * 8,
                     smem + (kt & (NSLOT - 1)) * STAGE + (isv ? KBYTES : 0) + ins * 1024);
     };
     stage(0);
