@@ -103,6 +103,17 @@ class VaeDesc(C.Structure):
                 ("taps3", vp), ("taps4s2", vp), ("taps4p0", vp), ("taps1", vp), ("zero_page", vp)]
 
 
+# offsets[] of pcd_pair_metrics_workspace_layout, in the order of the header's PCD_PAIR_WS_* enum
+PCD_PAIR_WS = ("an", "bn", "mins", "alpha", "beta", "rowc", "cmax", "err", "bits", "total")
+
+
+def pair_metrics_workspace_layout(pairs: int, na_max: int, nb_max: int) -> dict:
+    """Byte offsets of the stage buffers `pcd_pair_metrics` leaves in its workspace (include/pcd_hip.h), by name."""
+    off = (sz * len(PCD_PAIR_WS))()
+    check(load().pcd_pair_metrics_workspace_layout(pairs, na_max, nb_max, off), "pair_metrics_workspace_layout")
+    return dict(zip(PCD_PAIR_WS, (int(v) for v in off)))
+
+
 # name -> (restype, argtypes).  Kept in the order of include/pcd_hip.h.
 _SIGS = {
     "pcd_last_error": (C.c_char_p, []),
@@ -285,6 +296,7 @@ _SIGS = {
     "pcd_sinkhorn_cost": (i32, [vp, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),
     "pcd_pair_metrics_workspace_bytes": (sz, [i32, i32, i32]),
     "pcd_pair_metrics": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
+    "pcd_pair_metrics_workspace_layout": (i32, [i32, i32, i32, C.POINTER(sz)]),
     "pcd_colsum_f16": (i32, [vp, i64, i32, i32, vp, vp]),
     "pcd_bn_batch_stats": (i32, [vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]),
     "pcd_bn_apply_f16": (i32, [vp, i64, i32, vp, vp, vp, vp, f32, i32, vp, vp]),

@@ -335,6 +335,16 @@ extern "C" size_t pcd_pair_metrics_workspace_bytes(int pairs, int na_max, int nb
     return pm_carve(pairs, na_max, nb_max).total;
 }
 
+// Byte offsets of the stage buffers pcd_pair_metrics leaves in its workspace, in the order of PCD_PAIR_WS_* (include/pcd_hip.h);
+// host arithmetic only, the same carve the launch uses.
+extern "C" int pcd_pair_metrics_workspace_layout(int pairs, int na_max, int nb_max, size_t* offsets) {
+    PCD_CHECK_ARG(offsets && pairs > 0 && na_max > 0 && nb_max > 0);
+    const PmWs w = pm_carve(pairs, na_max, nb_max);
+    const size_t f[PCD_PAIR_WS_FIELDS] = {w.an, w.bn, w.mins, w.alpha, w.beta, w.rowc, w.cmax, w.err, w.bits, w.total};
+    for (int i = 0; i < PCD_PAIR_WS_FIELDS; ++i) offsets[i] = f[i];
+    return PCD_OK;
+}
+
 extern "C" int pcd_pair_metrics(const float* a, const int* na, int na_max, const float* b, const int* nb, int nb_max, int pairs,
                                 int with_sinkhorn, float epsilon, float thresh, int max_iter, const float* log_mu,
                                 const float* log_nu, float* rows, void* workspace, size_t workspace_bytes, void* stream) {

@@ -799,6 +799,21 @@ size_t pcd_pair_metrics_workspace_bytes(int pairs, int na_max, int nb_max);
 int pcd_pair_metrics(const float* a, const int* na, int na_max, const float* b, const int* nb, int nb_max, int pairs,
                      int with_sinkhorn, float epsilon, float thresh, int max_iter, const float* log_mu,
                      const float* log_nu, float* rows, void* workspace, size_t workspace_bytes, void* stream);
+/* What pcd_pair_metrics leaves in its workspace, for callers that want the stages and not only the rows.  Fills
+ * offsets[PCD_PAIR_WS_FIELDS] with byte offsets (each a multiple of 256) in this order, NQ = max(na_max, nb_max):
+ *   AN, BN      the normalised clouds, fp32 [P][na_max][3] / [P][nb_max][3] (rows past a pair's count are not written)
+ *   MINS        min_j |q - t_j|^2 per query, fp32 [P][2][NQ]: [p][0] queries a against b, [p][1] queries b against a
+ *   ALPHA, BETA the duals after the last iteration the pair ran, fp32 [P][na_max] / [P][nb_max]
+ *   ROWC        sum_j P_ij C_ij per row of a, fp32 [P][na_max] (rows[p][1] is its sum)
+ *   CMAX        the pair's max_ij |a_i - b_j| of the normalised clouds, fp32 [P]
+ *   ERR         the two error slots (alpha, beta) of both iteration parities, fp32 [2][P][2]: parity (max_iter - 1) & 1 holds what the
+ *               last enqueued iteration left (its errors, or zeros for a pair that had stopped before it), the other parity is cleared
+ *   BITS        the 32^3 occupancy bit sets of the raw clouds, uint32 [P][2][1024], voxel (x*32 + y)*32 + z = bit (v & 31) of word v >> 5
+ *   TOTAL       = pcd_pair_metrics_workspace_bytes(pairs, na_max, nb_max)
+ * ALPHA .. ERR are written only by a call with with_sinkhorn.  Host arithmetic only: no device is touched. */
+enum { PCD_PAIR_WS_AN = 0, PCD_PAIR_WS_BN, PCD_PAIR_WS_MINS, PCD_PAIR_WS_ALPHA, PCD_PAIR_WS_BETA, PCD_PAIR_WS_ROWC,
+       PCD_PAIR_WS_CMAX, PCD_PAIR_WS_ERR, PCD_PAIR_WS_BITS, PCD_PAIR_WS_TOTAL, PCD_PAIR_WS_FIELDS };
+int pcd_pair_metrics_workspace_layout(int pairs, int na_max, int nb_max, size_t* offsets);
 
 /* ------------------------------------------------ training step of the point denoiser
  * diffusion.py:70-86,170-186 (add_noise -> model in train() mode -> F.l1_loss -> AdamW, diffusion.py:60).

@@ -210,3 +210,27 @@ def test_persistent_latent_plan_is_a_partition():
     from shapegen_amd import _lib
     set_bytes = _lib.load().pcd_latent_persist_plan_check()
     assert set_bytes > 0 and set_bytes % 4096 == 0 and set_bytes < 8 << 20
+
+
+def test_pair_metrics_workspace_layout_without_gpu():
+    """`pcd_pair_metrics_workspace_layout` is host arithmetic: the stage buffers come in the header's PCD_PAIR_WS_* order, every one
+    256-byte aligned and large enough for its documented shape, and the last field is `pcd_pair_metrics_workspace_bytes`."""
+    import ctypes as C
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "pcd_hip.h")).read()
+    enum = re.search(r"enum\s*\{\s*(PCD_PAIR_WS_AN[^}]*)\}", header).group(1)
+    names = [n.split("=")[0].strip()[len("PCD_PAIR_WS_"):].lower() for n in enum.split(",")]
+    assert names[-1] == "fields" and tuple(names[:-1]) == _lib.PCD_PAIR_WS
+    for P, na, nb in ((1, 1, 1), (6, 1300, 1300), (3, 96, 80), (256, 1100, 1300), (512, 8, 7)):
+        lay = _lib.pair_metrics_workspace_layout(P, na, nb)
+        assert list(lay) == list(_lib.PCD_PAIR_WS) and lay["an"] == 0
+        assert lay["total"] == lib.pcd_pair_metrics_workspace_bytes(P, na, nb)
+        nq = max(na, nb)
+        need = dict(an=P * na * 12, bn=P * nb * 12, mins=P * 2 * nq * 4, alpha=P * na * 4, beta=P * nb * 4, rowc=P * na * 4,
+                    cmax=P * 4, err=2 * P * 2 * 4, bits=P * 2 * 1024 * 4)
+        order = list(_lib.PCD_PAIR_WS)
+        for k, nxt in zip(order[:-1], order[1:]):
+            assert lay[k] % 256 == 0 and lay[nxt] - lay[k] >= need[k], (P, na, nb, k)
+    off = (C.c_size_t * len(_lib.PCD_PAIR_WS))()
+    assert lib.pcd_pair_metrics_workspace_layout(0, 4, 4, off) == -1 and lib.pcd_pair_metrics_workspace_layout(1, 4, 4, None) == -1
