@@ -330,6 +330,8 @@ _SIGS = {
     "pcd_grad_accumulate_f32": (i32, [vp, vp, i64, i32, vp]),
     "pcd_embed_add_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "pcd_embed_rows_backward": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "pcd_voxel_batch_clouds": (i32, [vp, i32, vp, i32, i32, u64, u64, i32, f32, f32, vp, vp, vp]),
+    "pcd_voxel_batch_grids": (i32, [vp, i32, vp, i32, vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

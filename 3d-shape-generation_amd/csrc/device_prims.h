@@ -1,5 +1,5 @@
 // Device primitives shared by the kernels of this library (included from common.h): the LDS-DMA instruction, counted waits, the weight-image ring
-// of the register-resident chains, LayerNorm and regrouping on MFMA fragments, the swizzled 32 x 128-byte image, block reductions.  One definition
+// of the register-resident chains, LayerNorm and regrouping on MFMA fragments, the swizzled 32 x 128-byte image, block reductions, Philox.  One definition
 // of each: an invariant found in one kernel is kept for all of them here.
 #pragma once
 
@@ -227,6 +227,46 @@ __device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [blockDim/64
     T r = scratch[0];
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = op(r, scratch[w]);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------ Philox4x32-10
+// One round; counter c, key (k0, k1).  The stream of a 64-bit counter `ctr` under a 64-bit `seed`: c = {lo(ctr), hi(ctr), 0, 0}, key = {lo(seed), hi(seed)},
+// ten rounds with the key bumped by (0x9E3779B9, 0xBB67AE85) after each.
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    const uint32_t n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+// the four 32-bit words of counter `ctr`
+__device__ __forceinline__ void philox_words4(uint64_t ctr, uint64_t seed, uint32_t (&c)[4]) {
+    c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = 0u; c[3] = 0u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// Philox4x32-10 on counter `ctr` + Box-Muller: the 4 standard normals of one counter
+__device__ __forceinline__ void philox_normals4(uint64_t ctr, uint64_t seed, float (&v)[4]) {
+    uint32_t c[4];
+    philox_words4(ctr, seed, c);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
+        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float r = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.28318530717958647692f * u2, &sn, &cs);
+        v[2 * h] = r * cs;
+        v[2 * h + 1] = r * sn;
+    }
 }
 
 }  // namespace pcd

@@ -7,6 +7,8 @@ method names, constructor arguments and defaults follow the reference so its ent
 Differences, both deliberate:
   * no Lightning: `PointCloudDataModule` / `PointCloudDataDirectoryModule` are plain objects with the same
     `setup()` / `train_dataloader()` / `val_dataloader()` surface;
+  * `DeviceVoxelDataModule` (not in the reference): the same directory read once, the grids bit-packed on the GPU and each batch
+    assembled by one kernel launch (csrc/dataset.hip); opt-in, the host modules are unchanged;
   * file format: the reference stores each sample as a deepdish HDF5 file `*.dd` read with
     `dd.io.load(path)['data']` (data.py:176).  deepdish/h5py are not part of this image, so besides `.dd`
     (read through h5py when it is importable) the dataset accepts `.npz` (key `data`) and `.npy` files with
@@ -267,3 +269,169 @@ class PointCloudDataDirectoryModule:
 
     def val_dataloader(self):
         return DataLoader(self.val_dataset, batch_size=self.batch_size, num_workers=self.num_workers)
+
+
+# ---------------------------------------------------------------------------------------------- device-resident voxel data
+VOXEL_WORDS = 1024                       # a 32^3 grid as 32-bit words: word z * 32 + y, bit x (include/pcd_hip.h)
+VOXEL_CTR_SPAN = 1 << 24                 # Philox counters owned by one batch slot (PCD_VOXEL_CTR_SPAN)
+VOXEL_NORMALIZE, VOXEL_ROTATE, VOXEL_JITTER = 1, 2, 4
+VAL_KEY = 0x5EED                         # the validation loader's fixed Philox key
+
+
+def minmax_grid(voxels: np.ndarray) -> np.ndarray:
+    """`PointCloudDataset._load`'s min-max normalisation of one grid, its `lo == hi` case included."""
+    lo, hi = np.min(voxels), np.max(voxels)
+    return np.full_like(voxels, lo) if lo == hi else (voxels - lo) / (hi - lo)
+
+
+def pack_grids(occupied: np.ndarray) -> np.ndarray:
+    """(S, 32, 32, 32) boolean occupancy [z][y][x] -> (S, 1024) uint32, word z * 32 + y, bit x."""
+    occ = np.asarray(occupied, dtype=bool).reshape(-1, VOXEL_WORDS, 32)
+    return np.packbits(occ, axis=2, bitorder="little").view("<u4").reshape(-1, VOXEL_WORDS).astype(np.uint32, copy=False)
+
+
+def unpack_grids(packed: np.ndarray) -> np.ndarray:
+    """Inverse of `pack_grids`: (S, 1024) uint32 -> (S, 32, 32, 32) bool."""
+    w = np.asarray(packed, dtype=np.uint32).reshape(-1, VOXEL_WORDS, 1)
+    return ((w >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(-1, 32, 32, 32)
+
+
+class _Rows(Dataset):
+    """The dataset `random_split` sees: row numbers of the packed table."""
+
+    def __init__(self, count: int):
+        self.count = count
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, idx):
+        return idx
+
+
+class _DeviceLoader:
+    """One pass over `rows` in batches, every batch one kernel launch.  Shuffled: the permutation and a 63-bit Philox key are drawn from
+    the global torch generator when the iteration starts (where DataLoader's RandomSampler draws its seed)."""
+
+    def __init__(self, module: "DeviceVoxelDataModule", rows: Sequence[int], shuffle: bool):
+        self.module, self.rows, self.shuffle = module, torch.as_tensor(list(rows), dtype=torch.int64), shuffle
+
+    def __len__(self):
+        return (len(self.rows) + self.module.batch_size - 1) // self.module.batch_size
+
+    def __iter__(self):
+        m, rows, key = self.module, self.rows, VAL_KEY
+        if self.shuffle:
+            rows = rows[torch.randperm(len(rows))]
+            key = int(torch.empty((), dtype=torch.int64).random_().item())
+        rows = rows.to(m.packed.device)
+        rows32 = rows.to(torch.int32)
+        for i, lo in enumerate(range(0, len(rows), m.batch_size)):
+            item = m.batch(rows32[lo:lo + m.batch_size], seed=key, offset=i * m.batch_size * VOXEL_CTR_SPAN)
+            yield (item, m.labels_device[rows[lo:lo + m.batch_size]]) if m.return_labels else item
+
+
+class DeviceVoxelDataModule:
+    """`PointCloudDataDirectoryModule` for voxel files with the data resident on the GPU: `setup()` reads every file once, applies the
+    dataset's min-max and `> 0.5` threshold, packs each 32^3 grid into 1024 words and uploads the table (4 KB a shape); a batch is one
+    launch of `pcd_voxel_batch_clouds` (scan order -> centroid -> unit radius -> resample; `augmentations` adds the dataset's jitter
+    before the normalisation, as the host module does, which never rotates; `rotate=True`, not an argument of the host module, adds the
+    dataset's `rotate_around_vertical_axis` in front of it) or, in `output_mode="voxels"`, of `pcd_voxel_batch_grids`.  The split, the labels and `categories` are those of the
+    host module under the same seed.  Two deliberate differences from the host path: the random draws are Philox streams keyed per epoch
+    from the global torch generator (not python's / numpy's generators), and a subset of a cloud with more than `num_points` voxels comes
+    out in scan order (the host's `random.sample` order is random).
+    `grids=` (S, 32, 32, 32) with optional integer `labels=` replaces `data_dir` (tests, synthetic runs); `device="cpu"` keeps the packed
+    table on the host, where `setup()` works and the loaders do not."""
+
+    def __init__(self, data_dir=None, num_points=2048, batch_size=32, num_workers=4, train_val_split=0.8,
+                 file_mode="voxels", output_mode="point_clouds", augmentations=True, normalization=True,
+                 relevant_object_categories: Optional[Sequence[str]] = None, return_labels=False, device="cuda",
+                 grids=None, labels=None, rotate=False, jitter_sigma=0.01, jitter_clip=0.05):
+        if file_mode != "voxels":
+            raise ValueError("DeviceVoxelDataModule reads voxel files only (file_mode='voxels')")
+        if output_mode not in ("point_clouds", "voxels"):
+            raise ValueError("Invalid output_mode for DeviceVoxelDataModule")
+        if (data_dir is None) == (grids is None):
+            raise ValueError("give either data_dir or grids")
+        if output_mode == "voxels" and (augmentations or rotate):
+            raise ValueError("output_mode='voxels' is served without augmentations only (pass augmentations=False)")
+        if return_labels and grids is not None and labels is None:
+            raise ValueError("return_labels with grids= needs labels=")
+        self.return_labels = return_labels
+        self.data_dir, self.num_points, self.batch_size, self.num_workers = data_dir, num_points, batch_size, num_workers
+        self.train_val_split, self.file_mode, self.output_mode = train_val_split, file_mode, output_mode
+        self.augmentations, self.normalization = augmentations, normalization
+        self.relevant_object_categories = relevant_object_categories
+        self.device, self.grids, self.labels = torch.device(device), grids, labels
+        self.jitter_sigma, self.jitter_clip = float(jitter_sigma), float(jitter_clip)
+        # PointCloudDataDirectoryModule switches jitter and rotation off without `augmentations` and otherwise leaves the dataset's
+        # defaults, jitter=True, rotate=False: `augmentations` means jitter
+        self.rotate = bool(rotate)
+        self.flags = ((VOXEL_NORMALIZE if normalization else 0) | (VOXEL_JITTER if augmentations else 0)
+                      | (VOXEL_ROTATE if rotate else 0))
+        self._counts = None
+        self.categories: List[str] = []
+
+    def _occupancy(self, voxels: np.ndarray, name: str) -> np.ndarray:
+        voxels = np.asarray(voxels)
+        if voxels.shape != (32, 32, 32):
+            raise ValueError(f"{name}: the grid is {tuple(voxels.shape)}, not (32, 32, 32)")
+        v = minmax_grid(voxels)
+        occ = v > 0.5
+        if self.output_mode == "voxels" and not np.all((v == 0) | (v == 1)):
+            raise ValueError(f"{name}: the grid is not binary after min-max normalisation; the packed table holds occupancy bits only")
+        if int(occ.sum()) < 2:
+            raise ValueError(f"{name}: {int(occ.sum())} occupied voxels; a point cloud needs at least 2 (its radius would be zero)")
+        return occ
+
+    def setup(self, stage=None):
+        if self.grids is not None:
+            names = [f"grids[{i}]" for i in range(len(self.grids))]
+            raw = self.grids
+            labels = None if self.labels is None else [int(v) for v in self.labels]
+            if labels is not None and len(labels) != len(names):
+                raise ValueError(f"{len(labels)} labels for {len(names)} grids")
+        else:
+            # the host dataset lists, filters and labels the files: same order, same categories
+            full = PointCloudDataset(self.data_dir, num_points=self.num_points, input_mode="voxels", output_mode=self.output_mode,
+                                     relevant_object_categories=self.relevant_object_categories, return_labels=self.return_labels)
+            self.file_list, self.categories = full.file_list, full.categories
+            names = [os.path.join(self.data_dir, f) for f in full.file_list]
+            raw = (load_sample_file(p) for p in names)
+            labels = [full.categories.index(full.category_of(f)) for f in full.file_list] if self.return_labels else None
+        self.packed_host = np.zeros((len(names), VOXEL_WORDS), dtype=np.uint32)      # packed grid by grid: 4 KB a shape on the host too
+        self.counts = np.zeros(len(names), dtype=np.int64)
+        for i, (name, voxels) in enumerate(zip(names, raw)):
+            occ = self._occupancy(voxels, name)
+            self.packed_host[i], self.counts[i] = pack_grids(occ)[0], occ.sum()
+        self.packed = torch.from_numpy(self.packed_host.view(np.int32)).to(self.device)
+        self.labels_device = None if labels is None else torch.as_tensor(labels, dtype=torch.int64, device=self.device)
+        rows = _Rows(len(names))
+        train_size = int(self.train_val_split * len(rows))
+        self.train_dataset, self.val_dataset = torch.utils.data.random_split(rows, [train_size, len(rows) - train_size])
+
+    def batch(self, index: torch.Tensor, seed: int, offset: int) -> torch.Tensor:
+        """The batch of the packed rows `index` (device int32) under Philox key `seed`, slot b's counters starting at
+        `offset + b * VOXEL_CTR_SPAN`: (B, num_points, 3) clouds, or (B, 1, 32, 32, 32) grids in voxel mode."""
+        from . import _lib
+        if self.packed.device.type != "cuda":
+            raise RuntimeError("DeviceVoxelDataModule assembles batches on the GPU: construct it with device='cuda' (no CPU path)")
+        lib, b = _lib.load(), int(index.numel())
+        if self.output_mode == "voxels":
+            out = torch.empty((b, 1, 32, 32, 32), dtype=torch.float32, device=self.packed.device)
+            _lib.check(lib.pcd_voxel_batch_grids(_lib.ptr(self.packed), self.packed.shape[0], _lib.ptr(index), b, _lib.ptr(out),
+                                                 _lib.stream_ptr()), "voxel_batch_grids")
+            return out
+        out = torch.empty((b, self.num_points, 3), dtype=torch.float32, device=self.packed.device)
+        if self._counts is None or self._counts.numel() < b:                         # the kernel's M per slot; one buffer per module
+            self._counts = torch.empty((max(b, self.batch_size),), dtype=torch.int32, device=self.packed.device)
+        _lib.check(lib.pcd_voxel_batch_clouds(_lib.ptr(self.packed), self.packed.shape[0], _lib.ptr(index), b, self.num_points,
+                                              seed & 0xFFFFFFFFFFFFFFFF, offset & 0xFFFFFFFFFFFFFFFF, self.flags, self.jitter_sigma,
+                                              self.jitter_clip, _lib.ptr(out), _lib.ptr(self._counts), _lib.stream_ptr()), "voxel_batch_clouds")
+        return out
+
+    def train_dataloader(self):
+        return _DeviceLoader(self, self.train_dataset.indices, shuffle=True)
+
+    def val_dataloader(self):
+        return _DeviceLoader(self, self.val_dataset.indices, shuffle=False)

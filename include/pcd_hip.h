@@ -940,6 +940,49 @@ int pcd_embed_add_rows(float* temb, const float* table, const int* labels, int b
  * lane per (c, column), no atomics (bitwise repeatable); a row without shapes is written as zero */
 int pcd_embed_rows_backward(const float* dtemb, const int* labels, int batch, int dim, int rows, float* dtable, void* stream);
 
+/* ------------------------------------------------ device-resident voxel dataset (csrc/dataset.hip)
+ * grids: [n_grids][1024] 32-bit words, one 32^3 occupancy grid each: word z * 32 + y, bit x.  Ascending (word, bit) is
+ * numpy.where's row-major order of grid[z][y][x], the scan order of PointCloudDataset.voxel_to_point_cloud, and a point is the
+ * integer triple (z, y, x) in that column order.  index[batch]: device int32 grid numbers; one outside [0, n_grids) reads
+ * nothing, gives zero rows and counts[b] = -1.
+ *
+ * Randomness is Philox4x32-10 as in pcd_randn: counter words {lo(ctr), hi(ctr), 0, 0}, key {lo(seed), hi(seed)}.  Batch slot b
+ * owns the PCD_VOXEL_CTR_SPAN counters from offset + b * PCD_VOXEL_CTR_SPAN; inside its span (counter numbers relative to it)
+ *   [PCD_VOXEL_CTR_KEY,    + 8192)    subset keys: the key of point i (its ordinal in scan order) is word i & 3 of counter i >> 2
+ *    PCD_VOXEL_CTR_ANGLE               rotation: angle = 2 pi u, u = ((word 0 >> 8) + 0.5) / 2^24
+ *   [PCD_VOXEL_CTR_JITTER, + 32768)   jitter: counter i gives point i its normals, pcd_randn's Box-Muller values 0, 1, 2 of the
+ *                                     counter for columns 0, 1, 2 (value 3 is not used)
+ *   [PCD_VOXEL_CTR_DRAW,   SPAN)      draws with replacement: draw j is word j & 3 of counter j >> 2
+ * so slot b's rows depend on (grid, seed, offset, b, num_points, flags) only, not on the rest of the batch. */
+#define PCD_VOXEL_NORMALIZE 1
+#define PCD_VOXEL_ROTATE 2
+#define PCD_VOXEL_JITTER 4
+#define PCD_VOXEL_CTR_KEY 0ull
+#define PCD_VOXEL_CTR_ANGLE 8192ull
+#define PCD_VOXEL_CTR_JITTER 16384ull
+#define PCD_VOXEL_CTR_DRAW 65536ull
+#define PCD_VOXEL_CTR_SPAN (1ull << 24)
+#define PCD_VOXEL_MAX_POINTS (1 << 24)          /* 4 draws per counter: far inside the draw range */
+/* out[batch][num_points][3], counts[batch] = M, the occupied voxels of each slot's grid; one workgroup per slot, no host
+ * synchronisation.  PointCloudDataset._load's chain for voxel files and point-cloud output:
+ *   rotate     centre on the centroid and scale to unit radius (as below), then right-multiply by the rotation about column 1
+ *   jitter     add clip(sigma * normal, -clip, clip) to every coordinate of all M points
+ *   normalize  p = (p - mean) / radius, radius = max |p - mean|.  Without rotate and jitter the column sums are integers
+ *              < 2^24 (exact): mean = float(sum) / float(M), radius = sqrt(max((dz dz + dy dy) + dx dx)), all in fp32 without
+ *              contraction, division and root correctly rounded: bit-exact against the same numpy operations.  After an
+ *              augmentation the sums are fp32, added in a fixed order (bitwise repeatable).
+ *   resample   M = num_points: every point in scan order.  M > num_points: the num_points smallest (key, i) pairs, written in
+ *              ascending i (a uniform subset without replacement, in scan order; the cut is found by a radix select over the
+ *              keys, which are regenerated in every pass and never stored).  M < num_points: every point in scan order, then
+ *              num_points - M draws in draw order, draw -> point (word * M) >> 32.
+ * M = 0 gives zero rows.  A cloud of radius 0 under normalize or rotate (M = 1) gives NaN rows, 0 / 0 as in the host's
+ * normalize_point_cloud: callers keep such grids out of the table (DeviceVoxelDataModule refuses them).
+ * num_points <= PCD_VOXEL_MAX_POINTS. */
+int pcd_voxel_batch_clouds(const uint32_t* grids, int n_grids, const int* index, int batch, int num_points, uint64_t seed,
+                           uint64_t offset, int flags, float sigma, float clip, float* out, int* counts, void* stream);
+/* out[batch][1][32][32][32] = 0.f / 1.f, [z][y][x]: the indexed grids unpacked (an index outside the table gives zeros) */
+int pcd_voxel_batch_grids(const uint32_t* grids, int n_grids, const int* index, int batch, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoint
     python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt weights.ckpt] [--max-steps N]
                                [--backbone {pointnet,attention}] [--resume last.ckpt] [--save-last] [--ema-decay D]
                                [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
-                               [--class-conditional [--p-uncond 0.1]]
+                               [--class-conditional [--p-uncond 0.1]] [--device-data]
 
 `--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
 import); `--ckpt` starts a new run from a checkpoint's weights (with the backbone stored in its hyper-parameters).
@@ -24,6 +24,9 @@ its category's index (`--category` takes a comma-separated list, or `all`), the 
 the null class, and each label is replaced by the null class with probability `--p-uncond`.  The samples drawn at the end cycle
 through the classes.
 
+`--device-data` feeds the trainer from `DeviceVoxelDataModule`: the directory is read once, the grids stay bit-packed on the GPU and
+every batch is one kernel launch (Philox draws, subsets in scan order; `shapegen_amd.data`).  Without it nothing changes.
+
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
 """
@@ -37,7 +40,7 @@ import numpy as np
 import torch
 
 import shapegen_amd  # noqa: F401
-from shapegen_amd.data import PointCloudDataDirectoryModule, PointCloudDataModule
+from shapegen_amd.data import DeviceVoxelDataModule, PointCloudDataDirectoryModule, PointCloudDataModule
 from shapegen_amd.diffusion import PointCloudDiffusion
 from shapegen_amd.training import fit
 from shapegen_amd.utils import setup_logger
@@ -61,6 +64,21 @@ def synthetic_clouds(count: int, num_points: int, seed: int = 24) -> np.ndarray:
 
 
 SYNTHETIC_FAMILIES = 3
+
+
+def synthetic_grids(count: int, seed: int = 24, families: int = 0):
+    """(grids, labels) for --device-data without a data directory: the occupancy grids behind `synthetic_clouds` (families = 0, three
+    ellipsoids each, labels None) or `synthetic_labelled_clouds` (family f = grid index mod `families`: f + 1 ellipsoids)."""
+    rng = np.random.default_rng(seed)
+    zz, yy, xx = np.meshgrid(*[np.arange(32)] * 3, indexing="ij")
+    grids = np.zeros((count, 32, 32, 32), np.float32)
+    labels = np.arange(count, dtype=np.int64) % families if families else None
+    for i in range(count):
+        blobs = int(labels[i]) + 1 if families else 3
+        c, r = rng.uniform(8, 24, (blobs, 3)), rng.uniform(3, 9, (blobs, 3))
+        for j in range(blobs):
+            grids[i][((zz - c[j, 0]) / r[j, 0]) ** 2 + ((yy - c[j, 1]) / r[j, 1]) ** 2 + ((xx - c[j, 2]) / r[j, 2]) ** 2 <= 1] = 1
+    return grids, labels
 
 
 def synthetic_labelled_clouds(count: int, num_points: int, seed: int = 24):
@@ -107,6 +125,8 @@ def main():
     ap.add_argument("--class-conditional", action="store_true",
                     help="train a class-conditional model (classifier-free guidance): one class per category of --category")
     ap.add_argument("--p-uncond", type=float, default=0.1, help="probability of replacing a training label by the null class")
+    ap.add_argument("--device-data", action="store_true",
+                    help="keep the voxel grids on the GPU and assemble every batch there in one launch (DeviceVoxelDataModule)")
     args = ap.parse_args()
     torch.manual_seed(24)
     timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -114,14 +134,21 @@ def main():
     num_classes = 0
     if os.path.isdir(args.data_dir):
         categories = args.category.split(",")
-        dm = PointCloudDataDirectoryModule(args.data_dir, num_points=args.num_points, batch_size=args.batch_size, file_mode="voxels",
-                                           output_mode="point_clouds", augmentations=False,
-                                           relevant_object_categories=categories, return_labels=args.class_conditional)
+        module = DeviceVoxelDataModule if args.device_data else PointCloudDataDirectoryModule
+        dm = module(args.data_dir, num_points=args.num_points, batch_size=args.batch_size, file_mode="voxels",
+                    output_mode="point_clouds", augmentations=False,
+                    relevant_object_categories=categories, return_labels=args.class_conditional)
         if args.class_conditional:
             from shapegen_amd.data import PointCloudDataset
             found = PointCloudDataset(args.data_dir, input_mode="voxels", relevant_object_categories=categories, return_labels=True).categories
             num_classes = len(found)
             logger.info(f"class-conditional over {num_classes} categories: {found}")
+    elif args.device_data:
+        logger.info(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic grids kept on the GPU")
+        grids, labels = synthetic_grids(args.synthetic_shapes, families=SYNTHETIC_FAMILIES if args.class_conditional else 0)
+        dm = DeviceVoxelDataModule(grids=grids, labels=labels, num_points=args.num_points, batch_size=args.batch_size,
+                                   augmentations=False, return_labels=args.class_conditional)
+        num_classes = SYNTHETIC_FAMILIES if args.class_conditional else 0
     elif args.class_conditional:
         logger.info(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic clouds of {SYNTHETIC_FAMILIES} shape families")
         clouds, labels = synthetic_labelled_clouds(args.synthetic_shapes, args.num_points)

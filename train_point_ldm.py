@@ -6,14 +6,15 @@ latent trainer (frozen VAE encode -> L1 loss -> AdamW + cosine schedule).
     python train_point_ldm.py [--vae-ckpt vae.ckpt | --train-vae-epochs N] [--diffusion-ckpt ldm.ckpt | --train-diffusion-epochs N]
                               [--data-dir DIR] [--category table] [--steps 1000]
                               [--resume-vae last.ckpt | --resume last.ckpt] [--save-last] [--ema-decay D]
-                              [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
+                              [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite] [--device-data]
 
 `--vae-ckpt` / `--diffusion-ckpt` load weights only.  `--resume` continues an interrupted latent-diffusion training exactly
 (`--resume-vae` the VAE's): optimizer moments, scheduler, epoch, top-k list and random streams come from the file, and
 checkpoints keep going into the directory the file lies in.  `--save-last` writes `<name>-last.ckpt` after every epoch;
 `--ema-decay` keeps an exponential moving average of the latent denoiser's weights next to the raw ones.
 `--grad-clip`, `--accumulate-grad-batches` and `--skip-nonfinite` (gradient-norm clipping, one optimizer step per K batches,
-dropping a step with a non-finite gradient) apply to both trainings.
+dropping a step with a non-finite gradient) apply to both trainings.  `--device-data` feeds both from `DeviceVoxelDataModule`
+(the directory read once, the grids bit-packed on the GPU, a batch unpacked by one launch).
 """
 from __future__ import annotations
 
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--synthetic-shapes", type=int, default=160)
     ap.add_argument("--out", default=os.path.join("samples", "point_ldm"))
+    ap.add_argument("--device-data", action="store_true",
+                    help="with a data directory: keep its voxel grids on the GPU and assemble every batch there (DeviceVoxelDataModule)")
     args = ap.parse_args()
     guard = dict(gradient_clip_val=args.grad_clip, accumulate_grad_batches=args.accumulate_grad_batches, skip_nonfinite=args.skip_nonfinite)
     torch.manual_seed(24)
@@ -95,9 +98,10 @@ def main():
 def _data_module(args):
     """Voxel batches: the reference's data module (train_point_ldm.py:166-168) or synthetic occupancy grids."""
     if os.path.isdir(args.data_dir):
-        from shapegen_amd.data import PointCloudDataDirectoryModule
-        return PointCloudDataDirectoryModule(args.data_dir, num_points=2048, batch_size=args.batch_size, file_mode="voxels",
-                                             output_mode="voxels", augmentations=False, relevant_object_categories=[args.category])
+        from shapegen_amd.data import DeviceVoxelDataModule, PointCloudDataDirectoryModule
+        module = DeviceVoxelDataModule if args.device_data else PointCloudDataDirectoryModule
+        return module(args.data_dir, num_points=2048, batch_size=args.batch_size, file_mode="voxels",
+                      output_mode="voxels", augmentations=False, relevant_object_categories=[args.category])
     print(f"{args.data_dir} not found: training on {args.synthetic_shapes} synthetic occupancy grids")
     return _SyntheticVoxels(args.synthetic_shapes, args.batch_size)
 
