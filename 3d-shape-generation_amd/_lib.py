@@ -164,6 +164,9 @@ _SIGS = {
     "pcd_pw_wide_packed_bytes": (sz, [i32]),
     "pcd_pw_wide_pack": (i32, [i32, vp, vp, vp, vp]),
     "pcd_pw_wide_chain": (i32, [i32, vp, vp, i64, vp, vp, vp]),
+    "pcd_pw_wide_ends_packed_bytes": (sz, [i32, i32]),
+    "pcd_pw_wide_ends_pack": (i32, [i32, i32, vp, vp, vp, vp]),
+    "pcd_pw_wide_ends": (i32, [i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]),
     "pcd_conv1x1_supported": (i32, [i32, i32]),
     "pcd_conv1x1_f16": (i32, [vp, i64, i32, vp, i64, vp, i32, i32, vp, vp]),
     "pcd_unet_create": (i32, [C.POINTER(UnetDesc), C.POINTER(vp)]),
@@ -185,7 +188,8 @@ _SIGS = {
     "pcd_groupnorm_relu_f16": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "pcd_skinny_slabs": (i32, [i32, i32]),
     "pcd_skinny_gemm_f16": (i32, [vp, i32, vp, i32, vp, i64, i32, i32, vp, vp]),
-    "pcd_skinny_finish": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "pcd_skinny_gemm_f32in": (i32, [vp, i32, vp, i64, i32, i32, vp, vp]),
+    "pcd_skinny_finish":(i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "pcd_skinny_config": (i32, [i32]),
     "pcd_skinny_fused_supported": (i32, [i32, i32, i32, i32]),
     "pcd_skinny_fused": (i32, [vp, i32, vp, i32, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),

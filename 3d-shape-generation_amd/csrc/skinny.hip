@@ -19,9 +19,10 @@ struct SkinnyParams {
     const half_t* w; int ldw;
     int m, c, ks;
     float* slabs;          // [S][M][C]
+    const float* a1_f32;   // if set: the first source in fp32 [m][k1], rounded to fp16 as it is loaded (a1 is then unused)
 };
 
-template <int MT>   // number of 32-row tiles (M <= 32*MT)
+template <int MT, bool F32 = false>   // number of 32-row tiles (M <= 32*MT); F32: the first source is p.a1_f32 (its own instantiations: the fp16 ones keep their code)
 __global__ __launch_bounds__(256) void skinny_gemm_kernel(SkinnyParams p) {
     __shared__ float red[4][32][33];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -52,12 +53,23 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(SkinnyParams p) {
             int row = t * 32 + r;
             row = row < p.m ? row : p.m - 1;
             const half_t* arow = src + (int64_t)row * lda + ka;
+            half8 af[4];
+            if (F32 && k < p.k1) {
+                // the conversion of f32_to_f16_kernel (saturating, round to nearest even), which this replaces in front of the pooled product
+                const float* frow = p.a1_f32 + (int64_t)row * p.k1 + k;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const half8 af = *(const half8*)(arow + 8 * j);
-                // D[row = x-row][col = weight-row]: A = activations, B = weights
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, wf[j], acc[t], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) {
+                    const float4 lo = *(const float4*)(frow + 8 * j), hi = *(const float4*)(frow + 8 * j + 4);
+                    af[j] = (half8){to_half_sat(lo.x), to_half_sat(lo.y), to_half_sat(lo.z), to_half_sat(lo.w),
+                                    to_half_sat(hi.x), to_half_sat(hi.y), to_half_sat(hi.z), to_half_sat(hi.w)};
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) af[j] = *(const half8*)(arow + 8 * j);
             }
+            // D[row = x-row][col = weight-row]: A = activations, B = weights
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j], wf[j], acc[t], 0, 0, 0);
         }
     }
     // cross-wave reduction, one 32x32 tile at a time; accumulator register e of lane (r, hh) is
@@ -355,14 +367,16 @@ extern "C" int pcd_skinny_slabs(int k, int c) {
     return k / pick_ks(k, c);
 }
 
-extern "C" int pcd_skinny_gemm_f16(const void* a1, int k1, const void* a2, int k2, const void* w, int64_t ldw, int m,
-                                   int c, float* slabs, void* stream) {
-    PCD_CHECK_ARG(a1 && w && slabs && m > 0 && m <= 256 && c > 0);
+static int skinny_gemm_launch(const void* a1, const float* a1_f32, int k1, const void* a2, int k2, const void* w, int64_t ldw, int m, int c, float* slabs,
+                              void* stream) {
+    PCD_CHECK_ARG((a1 || a1_f32) && w && slabs && m > 0 && m <= 256 && c > 0);
     PCD_CHECK_ARG(k1 > 0 && k1 % 64 == 0 && k2 >= 0 && k2 % 64 == 0 && (k2 == 0 || a2 != nullptr));
     PCD_CHECK_ARG(ldw >= k1 + k2 && ldw % 8 == 0);
     SkinnyParams p{};
     p.a1 = (const half_t*)a1; p.k1 = k1; p.a2 = (const half_t*)a2; p.k2 = k2;
     p.w = (const half_t*)w; p.ldw = (int)ldw; p.m = m; p.c = c;
+    p.a1_f32 = a1_f32;
+    if (a1_f32 != nullptr) p.a1 = (const half_t*)a1_f32;               // never dereferenced as fp16 (k < k1 takes the fp32 branch)
     p.ks = pick_ks(k1 + k2, c);
     // a 64-chunk must not straddle the two sources: k1 is a multiple of 64 (checked above)
     p.slabs = slabs;
@@ -370,14 +384,32 @@ extern "C" int pcd_skinny_gemm_f16(const void* a1, int k1, const void* a2, int k
     hipStream_t s = (hipStream_t)stream;
     const int mt = (int)ceil_div(m, 32);
     const size_t dma_lds = (size_t)(p.ks / 64) * 8192;                 // >= the 4 x 32 x 33 floats of the reduction
-    if (mt <= 1 && g_skinny_dma && dma_lds >= sizeof(float) * 4 * 32 * 33 && dma_lds <= 65536)
+    // (the LDS-DMA form copies fp16 rows as they are: an fp32 source takes the register-fragment kernel, which gives the same slabs)
+    if (mt <= 1 && a1_f32 == nullptr && g_skinny_dma && dma_lds >= sizeof(float) * 4 * 32 * 33 && dma_lds <= 65536)
         hipLaunchKernelGGL(skinny_gemm_dma_kernel, grid, dim3(256), dma_lds, s, p);
+    else if (a1_f32 != nullptr) {
+        if (mt <= 1) hipLaunchKernelGGL((skinny_gemm_kernel<1, true>), grid, dim3(256), 0, s, p);
+        else if (mt <= 2) hipLaunchKernelGGL((skinny_gemm_kernel<2, true>), grid, dim3(256), 0, s, p);
+        else if (mt <= 4) hipLaunchKernelGGL((skinny_gemm_kernel<4, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((skinny_gemm_kernel<8, true>), grid, dim3(256), 0, s, p);
+    }
     else if (mt <= 1) hipLaunchKernelGGL((skinny_gemm_kernel<1>), grid, dim3(256), 0, s, p);
     else if (mt <= 2) hipLaunchKernelGGL((skinny_gemm_kernel<2>), grid, dim3(256), 0, s, p);
     else if (mt <= 4) hipLaunchKernelGGL((skinny_gemm_kernel<4>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((skinny_gemm_kernel<8>), grid, dim3(256), 0, s, p);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
+}
+
+extern "C" int pcd_skinny_gemm_f16(const void* a1, int k1, const void* a2, int k2, const void* w, int64_t ldw, int m,
+                                   int c, float* slabs, void* stream) {
+    PCD_CHECK_ARG(a1 != nullptr);
+    return skinny_gemm_launch(a1, nullptr, k1, a2, k2, w, ldw, m, c, slabs, stream);
+}
+
+extern "C" int pcd_skinny_gemm_f32in(const float* a, int k, const void* w, int64_t ldw, int m, int c, float* slabs, void* stream) {
+    PCD_CHECK_ARG(a != nullptr);
+    return skinny_gemm_launch(nullptr, a, k, nullptr, 0, w, ldw, m, c, slabs, stream);
 }
 
 extern "C" int pcd_skinny_finish(const float* slabs, int nslabs, int m, int c, const float* bias,

@@ -38,6 +38,8 @@ struct pcd_unet {
     int ev_created = 0;
     // packed stage images + biases of the two 256-channel chains (csrc/widechain.hip): enc3 and dec2
     void* wide[2] = {nullptr, nullptr};
+    // the same for the chains that take the narrow ends along: E23 (enc2 + enc3) and D21 (dec2 + dec1.conv1); hi / lo as the descriptor's mask says for lin 4 / 22
+    void* ends[2] = {nullptr, nullptr};
     // fragment-order copy of global_feat.3's weights for gemm_xw_kernel (csrc/gemm_f16.hip), made at create; null: the LDS-staged kernel runs
     void* gf3_frag = nullptr;
     // the same for the store GEMMs with K >= 512 and C >= 256 (enc4.conv1-3, global_feat.0, dec4.conv1-3, dec3.conv1-3: gemm_xs_kernel); null: pcd_gemm_f16
@@ -55,7 +57,7 @@ int pw_chain_enc1_impl(const float* x, int64_t m, int rows_per_shape, const floa
 
 
 struct UnetWs {
-    size_t x1, x2, x3, x4, s0, s1, pooled, pooled16, gbias, total;
+    size_t x1, x2, x3, x4, s0, s1, pooled, pooled16, gbias, total;      // pooled16: only above 256 shapes (the dense GEMM for the pooled product reads fp16)
 };
 
 static UnetWs carve(int64_t batch, int64_t n) {
@@ -69,7 +71,7 @@ static UnetWs carve(int64_t batch, int64_t n) {
     w.s0 = o; o += align_up(m * 2048 * 2);
     w.s1 = o; o += align_up(m * 1024 * 2);
     w.pooled = o; o += align_up((size_t)batch * 4096 * 4);
-    w.pooled16 = o; o += align_up((size_t)batch * 4096 * 2);
+    w.pooled16 = o; if (batch > 256) o += align_up((size_t)batch * 4096 * 2);
     w.gbias = o; o += align_up((size_t)batch * 1024 * 4);
     w.total = o;
     return w;
@@ -85,7 +87,7 @@ static const int kLinC[PCD_UNET_NLIN] = {64, 128, 128, 128, 256, 256, 256, 512, 
                                          1024, 1024, 512, 512, 512, 256, 256, 256, 128, 128, 128, 64, 64};
 
 static int g_unet_chains = 3;        // tuning / testing hook (pcd_unet_config): bit 0 = the narrow chains (csrc/chain.hip), bit 1 = the
-                                     // 256-channel chains enc3 / dec2 (csrc/widechain.hip); 0 = one GEMM launch per layer
+                                     // 256-channel chains (csrc/widechain.hip): enc2 + enc3 and dec2 + dec1.conv1 on whole 256-point tiles; 0 = one GEMM launch per layer
 
 extern "C" int pcd_unet_config(int use_chains) {
     g_unet_chains = use_chains & 3;
@@ -153,6 +155,20 @@ extern "C" int pcd_unet_create(const pcd_unet_desc_t* desc, pcd_unet_t** out) {
             h->lin_frag[i] = nullptr;
         }
     }
+    // E23 = lin 2 .. 7, D21 = lin 19 .. 22: packed like the two above; a failed allocation only means E3 / D2 and the launches around them keep running
+    for (int c = 0; c < 2; ++c) {
+        const int first = c == 0 ? 2 : 19, nl = c == 0 ? 6 : 4;
+        const int hilo = (int)((desc->hilo_mask >> (c == 0 ? 4 : 22)) & 1u);
+        const void* w[6];
+        const float* b[6];
+        for (int i = 0; i < nl; ++i) { w[i] = desc->lin[first + i].w; b[i] = desc->lin[first + i].b; }
+        if (!here || hipMalloc(&h->ends[c], pcd_pw_wide_ends_packed_bytes(c, hilo)) != hipSuccess ||
+            pcd_pw_wide_ends_pack(c, hilo, w, b, h->ends[c], nullptr) != PCD_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->ends[c]) (void)hipFree(h->ends[c]);
+            h->ends[c] = nullptr;
+        }
+    }
     *out = h;
     return PCD_OK;
 }
@@ -162,6 +178,7 @@ extern "C" void pcd_unet_destroy(pcd_unet_t* h) {
     if (h->gf3_frag) (void)hipFree(h->gf3_frag);
     for (int i = 0; i < PCD_UNET_NLIN; ++i) if (h->lin_frag[i]) (void)hipFree(h->lin_frag[i]);
     for (int k = 0; k < 2; ++k) if (h->wide[k]) (void)hipFree(h->wide[k]);
+    for (int k = 0; k < 2; ++k) if (h->ends[k]) (void)hipFree(h->ends[k]);
     for (int i = 0; i < h->ev_created; ++i) { (void)hipEventDestroy(h->ev0[i]); (void)hipEventDestroy(h->ev1[i]); }
     delete h;
 }
@@ -228,7 +245,6 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
     char* ws = (char*)workspace;
     void *x1 = ws + w.x1, *x2 = ws + w.x2, *x3 = ws + w.x3, *x4 = ws + w.x4, *s0 = ws + w.s0, *s1 = ws + w.s1;
     float* pooled = (float*)(ws + w.pooled);
-    void* pooled16 = ws + w.pooled16;
     float* gbias = (float*)(ws + w.gbias);
     hipStream_t s = (hipStream_t)stream;
     const pcd_unet_desc_t& d = h->d;
@@ -236,6 +252,10 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
     const bool chains = (g_unet_chains & 1) != 0;
     bool pooled_cleared = false;
     const bool wide = (g_unet_chains & 2) != 0 && m % 256 == 0;     // enc3 / dec2 as register-resident chains (whole 256-point tiles only)
+    // ... with the narrow layers next to them in the same launch: E23 = enc2 + enc3, D21 = dec2 + dec1.conv1 (dec2's output then never exists in memory:
+    // a capture of it runs D2 and dec1.conv1 apart)
+    const bool e23 = wide && h->ends[0] != nullptr;
+    const bool d21 = wide && h->ends[1] != nullptr && h->dec_tap[2] == nullptr;
     if (chains) {
         // enc1 (xyz -> 64 -> 64 -> 128) and enc2.conv1-2 (128 -> 128 -> 128): one launch each, intermediates in LDS
         const unsigned e1 = d.hilo_mask & 3u;              // lin 0, 1 travel together (one launch)
@@ -249,21 +269,28 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
             PCD_RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
             PCD_RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
         }
-        PCD_RUN(pcd_pw_chain_128(x1, m, d.lin[2].w, d.lin[2].b, d.lin[3].w, d.lin[3].b, s1, s));
+        if (!e23) PCD_RUN(pcd_pw_chain_128(x1, m, d.lin[2].w, d.lin[2].b, d.lin[3].w, d.lin[3].b, s1, s));
     } else {
         PCD_RUN(pcd_enc1_xyz(x, m, n_points, d.e1w_xyz, 64, tbias, tbias_shape_stride, s0, s));
         PCD_RUN(run_lin(d, 0, m, s0, nullptr, 0, nullptr, 0, s1, s));
         PCD_RUN(run_lin(d, 1, m, s1, nullptr, 0, nullptr, 0, x1, s));
-        PCD_RUN(run_lin(d, 2, m, x1, nullptr, 0, nullptr, 0, s0, s));
-        PCD_RUN(run_lin(d, 3, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        if (!e23) {
+            PCD_RUN(run_lin(d, 2, m, x1, nullptr, 0, nullptr, 0, s0, s));
+            PCD_RUN(run_lin(d, 3, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        }
     }
-    PCD_RUN(run_lin(d, 4, m, s1, nullptr, 0, nullptr, 0, x2, s));
-    if (wide) {
-        PCD_RUN(pcd_pw_wide_chain(0, x2, nullptr, m, h->wide[0], x3, s));
+    if (e23) {
+        // enc2 and enc3 in one launch: x1 -> x2 (stored for dec2's skip) -> x3
+        PCD_RUN(pcd_pw_wide_ends(0, (int)((d.hilo_mask >> 4) & 1u), x1, nullptr, nullptr, m, h->ends[0], x3, x2, s));
     } else {
-        PCD_RUN(run_lin(d, 5, m, x2, nullptr, 0, nullptr, 0, s0, s));
-        PCD_RUN(run_lin(d, 6, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        PCD_RUN(run_lin(d, 7, m, s1, nullptr, 0, nullptr, 0, x3, s));
+        PCD_RUN(run_lin(d, 4, m, s1, nullptr, 0, nullptr, 0, x2, s));
+        if (wide) {
+            PCD_RUN(pcd_pw_wide_chain(0, x2, nullptr, m, h->wide[0], x3, s));
+        } else {
+            PCD_RUN(run_lin(d, 5, m, x2, nullptr, 0, nullptr, 0, s0, s));
+            PCD_RUN(run_lin(d, 6, m, s0, nullptr, 0, nullptr, 0, s1, s));
+            PCD_RUN(run_lin(d, 7, m, s1, nullptr, 0, nullptr, 0, x3, s));
+        }
     }
     PCD_RUN(run_lin(d, 8, m, x3, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[8]));
     PCD_RUN(run_lin(d, 9, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[9]));
@@ -292,13 +319,14 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
         if (prof) { PCD_CHECK_HIP(hipEventRecord(h->ev1[h->prof_n], s)); ++h->prof_n; }
     }
     {   // hoisted global half of dec4.conv1: per-shape bias [B][1024] = pooled . Wg^T + folded bias
-        PCD_RUN(pcd_f32_to_f16(pooled, pooled16, (int64_t)batch * 4096, s));
         if (batch <= 256) {
-            // few rows: weight-streaming split-K kernel (csrc/skinny.hip), slabs live in the free s1 buffer
-            PCD_RUN(pcd_skinny_gemm_f16(pooled16, 4096, nullptr, 0, d.wg, 4096, batch, 1024, (float*)s1, s));
+            // few rows: weight-streaming split-K kernel (csrc/skinny.hip), which rounds the fp32 maxima to fp16 as it loads them; slabs live in the free s1 buffer
+            PCD_RUN(pcd_skinny_gemm_f32in(pooled, 4096, d.wg, 4096, batch, 1024, (float*)s1, s));
             PCD_RUN(pcd_skinny_finish((const float*)s1, pcd_skinny_slabs(4096, 1024), batch, 1024, d.lin[13].b, nullptr, 2, 8,
                                   nullptr, nullptr, nullptr, gbias, s));
         } else {
+            void* pooled16 = ws + w.pooled16;
+            PCD_RUN(pcd_f32_to_f16(pooled, pooled16, (int64_t)batch * 4096, s));
             pcd_gemm_desc_t g{};
             g.a1 = pooled16; g.k1 = 4096; g.lda1 = 4096; g.w = d.wg; g.ldw = 4096; g.bias = d.lin[13].b;
             g.relu = 0; g.m = batch; g.c = 1024;
@@ -315,30 +343,37 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
     PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
     PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
     TAP(1, s0, 256);
-    if (wide) {
-        PCD_RUN(pcd_pw_wide_chain(1, s0, x2, m, h->wide[1], s1, s));
+    void *ta = s0, *tb = s1;                              // dec1.conv1's output and the other ping-pong buffer
+    if (d21) {
+        // dec2 and dec1.conv1 in one launch (rows of another width than the input's: not in place, so the tail reads s1)
+        PCD_RUN(pcd_pw_wide_ends(1, (int)((d.hilo_mask >> 22) & 1u), s0, x2, x1, m, h->ends[1], s1, nullptr, s));
+        ta = s1; tb = s0;
     } else {
-        PCD_RUN(run_lin(d, 19, m, s0, x2, 256, nullptr, 0, s1, s));
-        PCD_RUN(run_lin(d, 20, m, s1, nullptr, 0, nullptr, 0, s0, s));
-        PCD_RUN(run_lin(d, 21, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        if (wide) {
+            PCD_RUN(pcd_pw_wide_chain(1, s0, x2, m, h->wide[1], s1, s));
+        } else {
+            PCD_RUN(run_lin(d, 19, m, s0, x2, 256, nullptr, 0, s1, s));
+            PCD_RUN(run_lin(d, 20, m, s1, nullptr, 0, nullptr, 0, s0, s));
+            PCD_RUN(run_lin(d, 21, m, s0, nullptr, 0, nullptr, 0, s1, s));
+        }
+        TAP(2, s1, 128);
+        PCD_RUN(run_lin(d, 22, m, s1, x1, 128, nullptr, 0, s0, s));
     }
-    TAP(2, s1, 128);
-    PCD_RUN(run_lin(d, 22, m, s1, x1, 128, nullptr, 0, s0, s));
     const unsigned tl = (d.hilo_mask >> 23) & 7u;         // lin 23, 24, 25 travel together (one launch)
     if (chains && h->dec_tap[3] == nullptr && (tl == 0u || tl == 7u)) {
         // dec1.conv2 -> conv3 -> output.0 -> output.3 (128 -> 128 -> 64 -> 64 -> 3): one launch
         if (tl == 7u)
-            PCD_RUN(pcd_pw_chain_tail_hilo(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
+            PCD_RUN(pcd_pw_chain_tail_hilo(ta, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
                                        d.head_b, eps, s));
         else
-            PCD_RUN(pcd_pw_chain_tail(s0, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
+            PCD_RUN(pcd_pw_chain_tail(ta, m, d.lin[23].w, d.lin[23].b, d.lin[24].w, d.lin[24].b, d.lin[25].w, d.lin[25].b, d.head_w,
                                   d.head_b, eps, s));
     } else {
-        PCD_RUN(run_lin(d, 23, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        PCD_RUN(run_lin(d, 24, m, s1, nullptr, 0, nullptr, 0, s0, s));
-        TAP(3, s0, 64);       // dec1's output exists only inside the chained tail: a capture runs the tail as per-layer launches (same bits)
-        PCD_RUN(run_lin(d, 25, m, s0, nullptr, 0, nullptr, 0, s1, s));
-        PCD_RUN(pcd_head3(s1, m, 64, d.head_w, d.head_b, eps, s));
+        PCD_RUN(run_lin(d, 23, m, ta, nullptr, 0, nullptr, 0, tb, s));
+        PCD_RUN(run_lin(d, 24, m, tb, nullptr, 0, nullptr, 0, ta, s));
+        TAP(3, ta, 64);       // dec1's output exists only inside the chained tail: a capture runs the tail as per-layer launches (same bits)
+        PCD_RUN(run_lin(d, 25, m, ta, nullptr, 0, nullptr, 0, tb, s));
+        PCD_RUN(pcd_head3(tb, m, 64, d.head_w, d.head_b, eps, s));
     }
 #undef TAP
     return PCD_OK;

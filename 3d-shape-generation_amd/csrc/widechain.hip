@@ -13,6 +13,7 @@
 //     64 k in fragment order), they arrive by LDS-DMA into a 3-deep ring, one barrier per 64-deep K tile for the 8 waves
 //     (256 points) of a workgroup; a 256 x 256 tile of work per 32 KB of LDS fill = 256 FLOP per filled byte, twice the GEMM's.
 // Output rows leave as 16-byte pieces (8 consecutive channels per lane after the same swap).  M must be a multiple of 256.
+// Further down, the same engine with a shape per segment takes the narrow layers next to these chains along (pw_wide_ends_kernel: E23, D21).
 #include "common.h"
 
 namespace pcd {
@@ -154,11 +155,221 @@ __global__ __launch_bounds__(256) void wc_pack_kernel(const half_t* __restrict__
     *(half8*)(img + (size_t)id * 16) = v;
 }
 
+// ------------------------------------------------------------------------------------------------ the narrow ends: enc2 + enc3 and dec2 + dec1.conv1
+// The same engine with a shape per segment: K in {128, 256} input channels (K / 16 B fragments) x C in {128, 256} output channels (C / 32 accumulator
+// tiles).  A stage image is always 32 pieces of 1 KiB = [C / 32 channel tiles][NQ k-steps], NQ = 1024 / C: 256 channels x 64 k or 128 channels x 128 k,
+// so a stage is 32 MFMAs at any shape.  A chain's segment list is a compile-time constant and its segments are unrolled: every register-array index is a
+// constant, and a 128-wide segment leaves the registers it does not use free (profiles/wide_chain_ends.md has what a run-time table cost).
+//   E23: x1 [M][128] -> enc2.conv1 -> conv2 -> conv3 (x2 [M][256] stored AND kept as fragments) -> enc3.conv1 -> conv2 -> conv3 -> x3 [M][512]
+//   D21: [dec3 out [M][256] | x2 [M][256]] -> dec2.conv1 -> conv2 -> conv3 -> dec1.conv1 on [registers 128 | x1 [M][128]] -> [M][128]
+// A hi / lo layer is two segments on the same accumulators and the same B fragments: all hi K passes, then all lo passes (the order of pcd_gemm_f16_hilo).
+constexpr int WE_MAXSEG = 8, WE_MAXBIAS = 1536;
+enum { WE_K128_C128 = 0, WE_K128_C256 = 1, WE_K256_C128 = 2, WE_K256_C256 = 3 };
+
+struct WeSeg {
+    int kind;         // WE_K*_C*: 1, 2, 2, 4 stage images
+    int src;          // 0: the registers hold the input; 1 / 2: all K channels from in1 / in2 ([M][K]); 3: the first 128 stay in registers, the second 128 from in3 ([M][128])
+    int cont;         // 1: keep accumulating (second source of a two-source layer, lo pass of a hi / lo layer)
+    int finish;       // 0: more K to come; 1: epilogue -> next layer's fragments; 2: -> out at channel offset `coff`; 3: -> next layer's fragments and out2
+    int coff;
+    int bias_off;
+};
+
+// A chain as its segments in execution order: one description for the kernel (a constant there: the segments are unrolled, so that a register no segment of
+// the moment needs is free), for the packer (which weights each segment's images hold) and for the launcher
+struct WeSegSrc { int layer; int ldw; int c0; int k0; };      // index into w[] / b[]; row stride of w; first output channel and first k of the segment
+struct WePlan {
+    int nseg, nstage, nbias, nlayer;
+    WeSeg seg[WE_MAXSEG];
+    WeSegSrc from[WE_MAXSEG];
+    int layer_c[6], layer_bias[6];                             // channels and bias offset of every layer
+};
+constexpr int we_kind_images(int kind) { return kind == WE_K128_C128 ? 1 : (kind == WE_K256_C256 ? 4 : 2); }
+constexpr void we_add(WePlan& P, int kind, int src, int cont, int finish, int coff, int layer, int ldw, int c0, int k0) {
+    P.seg[P.nseg] = WeSeg{kind, src, cont, finish, coff, P.layer_bias[layer] + c0};
+    P.from[P.nseg] = WeSegSrc{layer, ldw, c0, k0};
+    P.nstage += we_kind_images(kind);
+    ++P.nseg;
+}
+constexpr WePlan we_plan(int chain, int hilo) {
+    WePlan P{};
+    if (chain == 0) {
+        const int c[6] = {128, 128, 256, 256, 256, 512};
+        P.nlayer = 6;
+        for (int i = 0; i < 6; ++i) { P.layer_c[i] = c[i]; P.layer_bias[i] = P.nbias; P.nbias += c[i]; }
+        we_add(P, WE_K128_C128, 1, 0, 1, 0, 0, 128, 0, 0);                             // enc2.conv1
+        we_add(P, WE_K128_C128, 0, 0, 1, 0, 1, 128, 0, 0);                             // enc2.conv2
+        if (hilo) {                                                                    // enc2.conv3 -> x2 (stored, and on into enc3)
+            we_add(P, WE_K128_C256, 0, 0, 0, 0, 2, 256, 0, 0);
+            we_add(P, WE_K128_C256, 0, 1, 3, 0, 2, 256, 0, 128);
+        } else {
+            we_add(P, WE_K128_C256, 0, 0, 3, 0, 2, 128, 0, 0);
+        }
+        we_add(P, WE_K256_C256, 0, 0, 1, 0, 3, 256, 0, 0);                             // enc3.conv1
+        we_add(P, WE_K256_C256, 0, 0, 1, 0, 4, 256, 0, 0);                             // enc3.conv2
+        we_add(P, WE_K256_C256, 0, 0, 2, 0, 5, 256, 0, 0);                             // enc3.conv3, channels 0 .. 255
+        we_add(P, WE_K256_C256, 0, 0, 2, 256, 5, 256, 256, 0);                         //             channels 256 .. 511 (same B fragments)
+    } else {
+        const int c[4] = {256, 256, 128, 128};
+        P.nlayer = 4;
+        for (int i = 0; i < 4; ++i) { P.layer_c[i] = c[i]; P.layer_bias[i] = P.nbias; P.nbias += c[i]; }
+        we_add(P, WE_K256_C256, 1, 0, 0, 0, 0, 512, 0, 0);                             // dec2.conv1, dec3's half
+        we_add(P, WE_K256_C256, 2, 1, 1, 0, 0, 512, 0, 256);                           //             x2's half
+        we_add(P, WE_K256_C256, 0, 0, 1, 0, 1, 256, 0, 0);                             // dec2.conv2
+        we_add(P, WE_K256_C128, 0, 0, 1, 0, 2, 256, 0, 0);                             // dec2.conv3
+        if (hilo) {                                                                    // dec1.conv1 on [registers | x1]
+            we_add(P, WE_K256_C128, 3, 0, 0, 0, 3, 512, 0, 0);
+            we_add(P, WE_K256_C128, 0, 1, 2, 0, 3, 512, 0, 256);
+        } else {
+            we_add(P, WE_K256_C128, 3, 0, 2, 0, 3, 256, 0, 0);
+        }
+    }
+    return P;
+}
+
+struct WeParams {
+    const half_t* in1; const half_t* in2; const half_t* in3;
+    const char* wpacked;                       // stage images in execution order
+    const float* bias;                         // fp32, indexed by bias_off + channel
+    half_t* out;                               // E23: x3 [M][512], D21: [M][128]
+    half_t* out2;                              // E23: x2 [M][256]
+    int64_t m;
+};
+
+// segment SG of the chain, then the ones behind it
+template <int CHAIN, bool HILO, int SG, typename Ring>
+__device__ __forceinline__ void we_segments(const WeParams& p, const Ring& ring, int& n, int64_t row0, int lrow, int hh, const float* bias_lds, half8 (&bf)[16],
+                                            f32x16 (&acc)[8]) {
+    constexpr WePlan P = we_plan(CHAIN, HILO);
+    if constexpr (SG < P.nseg) {
+        constexpr WeSeg S = P.seg[SG];
+        constexpr int K = (S.kind == WE_K128_C128 || S.kind == WE_K128_C256) ? 128 : 256, C = (S.kind == WE_K128_C128 || S.kind == WE_K256_C128) ? 128 : 256;
+        constexpr int NT = C / 32, NQ = 32 / NT, NS = K / (16 * NQ);       // channel tiles; k-steps per stage; stages
+        // row addresses as a wave-uniform tile base (scalar registers) + a 32-bit lane offset: 64-bit lane addresses of three matrices carried through
+        // the chain do not fit next to 64 + 128 + 32 registers of fragments and accumulators
+        auto at = [&row0, &lrow, &hh](auto* base, int ld, int col) { return base + row0 * ld + (unsigned)(lrow * ld + col + 8 * hh); };
+        if constexpr (S.src == 1 || S.src == 2) {
+            const half_t* row = at(S.src == 1 ? p.in1 : p.in2, K, 0);
+#pragma unroll
+            for (int s = 0; s < K / 16; ++s) bf[s] = *(const half8*)(row + 16 * s);
+        }
+        if constexpr (S.src == 3) {
+            const half_t* row = at(p.in3, 128, 0);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) bf[8 + s] = *(const half8*)(row + 16 * s);
+        }
+        if constexpr (!S.cont) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+        }
+#pragma unroll
+        for (int ks = 0; ks < NS; ++ks) {
+            // (the stage counter kept opaque: with the segments unrolled, n % period is a constant per stage, and the compiler then keeps every stage's
+            // per-lane request address live over the whole tile loop -- in scratch)
+            asm volatile("" : "+s"(n));
+            const char* img = ring.acquire(n);
+#pragma unroll
+            for (int f0 = 0; f0 < 32; f0 += 8) {                                       // fragment f of the stage: k-step f / NT, channel tile f % NT
+                half8 af[8];
+#pragma unroll
+                for (int f = f0; f < f0 + 8; ++f) af[f - f0] = *(const half8*)(img + ((f % NT) * NQ + f / NT) * 1024);
+#pragma unroll
+                for (int f = f0; f < f0 + 8; ++f)
+                    acc[f % NT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[f - f0], bf[NQ * ks + f / NT], acc[f % NT], 0, 0, 0);
+            }
+            ++n;
+        }
+        // (opaque for the same reason: one base register per epilogue and small immediate offsets, as with a run-time segment table, not a hoisted
+        // register per 32-channel tile of every layer)
+        int boff = S.bias_off;
+        asm volatile("" : "+s"(boff));
+        const float* bseg = bias_lds + boff;
+        if constexpr (S.finish == 1) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) bf[2 * t + gp] = regroup_bias_clamp(acc[t], gp, bseg + 32 * t, hh, 0.f);
+        } else if constexpr (S.finish == 2) {
+            half_t* orow = at(p.out, CHAIN == 0 ? 512 : 128, S.coff);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) *(half8*)(orow + 32 * t + 16 * gp) = regroup_bias_clamp(acc[t], gp, bseg + 32 * t, hh, 0.f);
+        } else if constexpr (S.finish == 3) {
+            half_t* orow = at(p.out2, 256, 0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) {
+                    bf[2 * t + gp] = regroup_bias_clamp(acc[t], gp, bseg + 32 * t, hh, 0.f);
+                    *(half8*)(orow + 32 * t + 16 * gp) = bf[2 * t + gp];
+                }
+        }
+        we_segments<CHAIN, HILO, SG + 1>(p, ring, n, row0, lrow, hh, bias_lds, bf, acc);
+    }
+}
+
+// CHAIN 0: E23, 1: D21; HILO: the chain's narrow layer has hi | lo weights; SPLIT: the request form of the ring, as above
+template <int CHAIN, bool HILO, bool SPLIT>
+__global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_ends_kernel(WeParams p) {
+    extern __shared__ __attribute__((aligned(16))) char wc_smem[];          // [WC_RING][WC_STAGE] | bias copy
+    constexpr WePlan P = we_plan(CHAIN, HILO);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pnt = lane & 31, hh = lane >> 5;
+    float* bias_lds = (float*)(wc_smem + WC_RING * WC_STAGE);
+    for (int i = threadIdx.x; i < P.nbias; i += WC_THREADS) bias_lds[i] = p.bias[i];      // (first read behind the first stage barrier)
+    const int64_t ntiles = p.m / WC_TILE;
+    const int my_tiles = (int)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+    const int nstage_seq = P.nstage;
+    const int total_stages = my_tiles * nstage_seq;
+    const StageRing<WC_STAGE, 4, WC_RING> ring{p.wpacked, wc_smem, total_stages, wave, lane, nstage_seq, SPLIT};
+    ring.issue(0);
+    ring.issue(1);
+    int n = 0;
+#pragma unroll 1
+    for (int ti = 0; ti < my_tiles; ++ti) {
+        const int64_t tile = blockIdx.x + (int64_t)ti * gridDim.x;
+        int64_t row0 = tile * WC_TILE;
+        asm volatile("" : "+s"(row0));                        // (opaque: no per-lane 64-bit row pointers stepped from tile to tile)
+        half8 bf[16];
+        f32x16 acc[8];
+        we_segments<CHAIN, HILO, 0>(p, ring, n, row0, wave * 32 + pnt, hh, bias_lds, bf, acc);
+    }
+}
+
+constexpr size_t WE_LDS = (size_t)WC_RING * WC_STAGE + (size_t)WE_MAXBIAS * sizeof(float);
+template <int CHAIN, bool HILO>
+static hipError_t we_launch(bool split, dim3 grid, size_t lds, hipStream_t s, const WeParams& p) {
+    static PcdLdsOnce once[2];
+    hipError_t e = pcd_allow_lds(once[0], (const void*)pw_wide_ends_kernel<CHAIN, HILO, false>, (int)WE_LDS);
+    if (e == hipSuccess) e = pcd_allow_lds(once[1], (const void*)pw_wide_ends_kernel<CHAIN, HILO, true>, (int)WE_LDS);
+    if (e != hipSuccess) return e;
+    if (split) hipLaunchKernelGGL((pw_wide_ends_kernel<CHAIN, HILO, true>), grid, dim3(WC_THREADS), lds, s, p);
+    else hipLaunchKernelGGL((pw_wide_ends_kernel<CHAIN, HILO, false>), grid, dim3(WC_THREADS), lds, s, p);
+    return hipGetLastError();
+}
+
+// wc_pack_kernel for either image shape: nq = 4 (256 channels x 64 k, the same image) or 8 (128 channels x 128 k); piece id = (t * nq + q) * 64 + lane
+__global__ __launch_bounds__(256) void we_pack_kernel(const half_t* __restrict__ w, int64_t ldw, int c0, int c_limit, int k0, int nq, char* __restrict__ img) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= 32 * 64) return;
+    const int lane = id & 63, tq = id >> 6, t = tq / nq, q = tq % nq;
+    const int ch = c0 + 32 * t + (lane & 31);
+    half8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (half_t)0.f;
+    if (ch < c_limit) v = *(const half8*)(w + (int64_t)ch * ldw + k0 + 16 * q + 8 * (lane >> 5));
+    *(half8*)(img + (size_t)id * 16) = v;
+}
+
 }  // namespace pcd
 
 using namespace pcd;
 
-static int g_wc_split = 1;          // pcd_pw_wide_config: which waves request the weight images (0: every wave 4 pieces; 1, default: one wave per SIMD 8 in the chains;
+static int g_wc_split = 1;         // pcd_pw_wide_config: which waves request the weight images (0: every wave 4 pieces; 1, default: one wave per SIMD 8 in the chains;
                                     // 2: in the LN + Linear launches too)
 extern "C" int pcd_pw_wide_config(int split) { g_wc_split = split < 0 ? 0 : (split > 2 ? 2 : split); return PCD_OK; }
 
@@ -272,5 +483,57 @@ extern "C" int pcd_pw_wide_ln_linear(const void* packed, int passes, int relu, c
     if (g_wc_split == 2) hipLaunchKernelGGL((pw_wide_chain_kernel<true, true>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((pw_wide_chain_kernel<true, false>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
     PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
+// ---- the narrow ends of UNetPointNetLarge as one launch each (pw_wide_ends_kernel): chain 0 = E23, enc2.conv1-3 + enc3.conv1-3 (w[0..5], b[0..5]: x1 [M][128] ->
+// x2 [M][256] and x3 [M][512]); chain 1 = D21, dec2.conv1-3 + dec1.conv1 (w[0..3]: [in1 [M][256] | in2 [M][256]] -> ... -> [. | in3 [M][128]] -> out [M][128]).
+// hilo: the chain's narrow layer (enc2.conv3 / dec1.conv1) carries [c][2 k] hi | lo weights.  packed = the stage images in execution order | the layers' biases.
+extern "C" size_t pcd_pw_wide_ends_packed_bytes(int chain, int hilo) {
+    if (chain != 0 && chain != 1) return 0;
+    const WePlan P = we_plan(chain, hilo ? 1 : 0);
+    return (size_t)P.nstage * WC_STAGE + (size_t)P.nbias * sizeof(float);
+}
+
+extern "C" int pcd_pw_wide_ends_pack(int chain, int hilo, const void* const* w, const float* const* b, void* packed, void* stream) {
+    PCD_CHECK_ARG((chain == 0 || chain == 1) && w && b && packed);
+    const WePlan P = we_plan(chain, hilo ? 1 : 0);
+    for (int i = 0; i < P.nlayer; ++i) PCD_CHECK_ARG(w[i] != nullptr && b[i] != nullptr);
+    hipStream_t s = (hipStream_t)stream;
+    char* img = (char*)packed;
+    for (int sg = 0; sg < P.nseg; ++sg) {
+        const WeSegSrc& f = P.from[sg];
+        const int kind = P.seg[sg].kind;
+        const int nq = (kind == WE_K128_C128 || kind == WE_K256_C128) ? 8 : 4;
+        for (int i = 0; i < we_kind_images(kind); ++i, img += WC_STAGE)
+            hipLaunchKernelGGL(we_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w[f.layer], (int64_t)f.ldw, f.c0, P.layer_c[f.layer], f.k0 + 16 * nq * i, nq, img);
+    }
+    PCD_CHECK_LAUNCH();
+    float* bias = (float*)img;
+    for (int i = 0; i < P.nlayer; ++i)
+        PCD_CHECK_HIP(hipMemcpyAsync(bias + P.layer_bias[i], b[i], (size_t)P.layer_c[i] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return PCD_OK;
+}
+
+extern "C" int pcd_pw_wide_ends(int chain, int hilo, const void* in1, const void* in2, const void* in3, int64_t m, const void* packed, void* out, void* out2,
+                                void* stream) {
+    PCD_CHECK_ARG((chain == 0 || chain == 1) && in1 && packed && out && m > 0 && m % WC_TILE == 0 && m <= 0x7fffffff);
+    PCD_CHECK_ARG(chain == 0 ? out2 != nullptr : (in2 != nullptr && in3 != nullptr));
+    const WePlan P = we_plan(chain, hilo ? 1 : 0);
+    WeParams p{};
+    p.in1 = (const half_t*)in1; p.in2 = (const half_t*)in2; p.in3 = (const half_t*)in3; p.m = m;
+    p.wpacked = (const char*)packed;
+    p.bias = (const float*)((const char*)packed + (size_t)P.nstage * WC_STAGE);
+    p.out = (half_t*)out;
+    p.out2 = (half_t*)out2;
+    const size_t lds = (size_t)WC_RING * WC_STAGE + (size_t)P.nbias * sizeof(float);
+    const int64_t tiles = m / WC_TILE;
+    const dim3 grid((unsigned)(tiles < 256 ? tiles : 256));
+    hipStream_t s = (hipStream_t)stream;
+    const bool split = g_wc_split != 0;
+    hipError_t e;
+    if (chain == 0) e = hilo ? we_launch<0, true>(split, grid, lds, s, p) : we_launch<0, false>(split, grid, lds, s, p);
+    else e = hilo ? we_launch<1, true>(split, grid, lds, s, p) : we_launch<1, false>(split, grid, lds, s, p);
+    PCD_CHECK_HIP(e);
     return PCD_OK;
 }

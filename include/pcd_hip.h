@@ -297,6 +297,19 @@ int pcd_pw_wide_chain(int chain, const void* in1, const void* in2, int64_t m, co
 /* A/B hook (TEST / BENCHMARK ONLY, process-global): which waves request the weight images of the wide-chain launches (1, default: one wave per SIMD,
  * alternating groups per image; 0: every wave; 2: the split form in the LN + Linear launches too).  Same bits either way. */
 int pcd_pw_wide_config(int split);
+/* The narrow ends of the same network on the same engine, with a shape per segment (K, C in {128, 256}; a stage image is 256 channels x 64 k or
+ * 128 channels x 128 k), one launch each:
+ *   chain 0 (E23): in1 = x1 [M][128] -> enc2.conv1 -> conv2 -> conv3 -> enc3.conv1 -> conv2 -> conv3; out = x3 [M][512], out2 = x2 [M][256] (stored for
+ *                  the decoder's skip, never read back); w[0..5] / b[0..5] = the six layers; in2, in3 unused;
+ *   chain 1 (D21): [in1 [M][256] | in2 = x2 [M][256]] -> dec2.conv1 -> conv2 -> conv3 -> dec1.conv1 on [that (128, in registers) | in3 = x1 [M][128]];
+ *                  out [M][128]; w[0..3] / b[0..3]; out2 unused.
+ * hilo != 0: the chain's narrow layer (enc2.conv3 / dec1.conv1) has [c][2 k] hi | lo weights: all hi K passes, then all lo passes onto the same
+ * accumulators, as in pcd_gemm_f16_hilo.  packed: pcd_pw_wide_ends_packed_bytes(chain, hilo) bytes, built once by pcd_pw_wide_ends_pack.  M % 256 == 0.
+ * pcd_pw_wide_config chooses the request form of the weight ring here too. */
+size_t pcd_pw_wide_ends_packed_bytes(int chain, int hilo);
+int pcd_pw_wide_ends_pack(int chain, int hilo, const void* const* w, const float* const* b, void* packed, void* stream);
+int pcd_pw_wide_ends(int chain, int hilo, const void* in1, const void* in2, const void* in3, int64_t m, const void* packed, void* out, void* out2,
+                     void* stream);
 /* LayerNorm(256) + Linear(256, 256 passes) [+ ReLU] as one launch of the wide-chain kernel (csrc/widechain.hip): the B fragments are normalised as they
  * are loaded (two-pass fp32 statistics, eps 1e-5, fp16 result as pcd_layernorm_f16's), so the LayerNorm launch and its tensor disappear: attention in_proj
  * (passes 3, relu 0) and ff.0 (passes 4, relu 1) of the C = 256 SetAttentionBlocks (networks.py:61-66, 81-82).  w fp16 [256 passes][256], b fp32;
@@ -364,6 +377,9 @@ int pcd_groupnorm_relu_f16(const float* x, int rows, int c, int groups, const fl
 int pcd_skinny_slabs(int k, int c);
 int pcd_skinny_gemm_f16(const void* a1, int k1, const void* a2, int k2, const void* w, int64_t ldw,
                         int m, int c, float* slabs, void* stream);
+/* the same with one fp32 activation matrix a [m][k], rounded to fp16 (saturating, as pcd_f32_to_f16) as it is loaded: the same slabs bit for bit
+ * as pcd_f32_to_f16 followed by pcd_skinny_gemm_f16 (the pooled maxima of pcd_unet_forward) */
+int pcd_skinny_gemm_f32in(const float* a, int k, const void* w, int64_t ldw, int m, int c, float* slabs, void* stream);
 int pcd_skinny_finish(const float* slabs, int nslabs, int m, int c, const float* bias, const float* row_bias,
                       int mode, int groups, const float* gamma, const float* beta,
                       void* out16, float* out32, void* stream);
