@@ -61,6 +61,24 @@ static inline hipError_t pcd_allow_lds(PcdLdsOnce& once, const void* kernel, int
     return e;
 }
 
+// Device copy of packed weights, made when a handle is created.  `src` points into the source weights: the copy is allocated on the CURRENT
+// device, and only if that is where they live (one process per GPU sets it so).  `pack(buf)` enqueues the packer on the null stream and returns a
+// PCD_* code; the copy is finished before this returns.  Any failure frees the buffer, clears the sticky HIP error and returns null: the caller
+// keeps the kernel that reads the unpacked weights.
+template <class Pack>
+static inline void* pcd_packed_copy(const void* src, size_t bytes, Pack pack) {
+    hipPointerAttribute_t at;
+    int cur = -1;
+    void* buf = nullptr;
+    if (bytes == 0) return nullptr;
+    if (hipGetDevice(&cur) == hipSuccess && hipPointerGetAttributes(&at, src) == hipSuccess && at.device == cur &&
+        hipMalloc(&buf, bytes) == hipSuccess && pack(buf) == PCD_OK && hipStreamSynchronize(nullptr) == hipSuccess)
+        return buf;
+    (void)hipGetLastError();
+    if (buf != nullptr) (void)hipFree(buf);
+    return nullptr;
+}
+
 }  // namespace pcd
 
 #include "device_prims.h"

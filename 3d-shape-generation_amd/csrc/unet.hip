@@ -124,50 +124,28 @@ extern "C" int pcd_unet_create(const pcd_unet_desc_t* desc, pcd_unet_t** out) {
         if (rc == PCD_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = PCD_ERR_HIP;
         if (rc != PCD_OK) {
             if (e != hipSuccess) set_error("pcd_unet_create: %s", hipGetErrorString(e));
-            for (int k = 0; k < 2; ++k) if (h->wide[k]) (void)hipFree(h->wide[k]);
-            delete h;
+            pcd_unet_destroy(h);
             return rc;
         }
     }
-    // global_feat.3 (2048 -> 4096): a fragment-order copy of its weights (16.8 MB) for the kernel that reads them straight from global memory;
-    // a failed allocation only means the LDS-staged kernel keeps running
-    hipPointerAttribute_t at;
-    int cur = -1;
-    const bool here = hipGetDevice(&cur) == hipSuccess && hipPointerGetAttributes(&at, desc->lin[12].w) == hipSuccess && at.device == cur;
-    if (!here) (void)hipGetLastError();
-    if (here && hipMalloc(&h->gf3_frag, (size_t)4096 * 2048 * 2) == hipSuccess) {
-        if (pcd_gemm_pack_wfrag(desc->lin[12].w, 2048, 2048, 4096, h->gf3_frag, nullptr) != PCD_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(h->gf3_frag);
-            h->gf3_frag = nullptr;
-        }
-    } else {
-        (void)hipGetLastError();
-        h->gf3_frag = nullptr;
-    }
-    // the ten store GEMMs that run as 256 x 256 tiles (K >= 512): fragment-order copies (29 MB in all) for gemm_xs_kernel; hi / lo layers keep pcd_gemm_f16_hilo
-    for (int i = 8; here && i <= 18; ++i) {
+    // Copies that only make a faster kernel available (pcd_packed_copy: a failed one leaves the kernel that runs without it; each is made only if ITS
+    // source weights live on the current device): global_feat.3's weights in
+    // fragment order (2048 -> 4096, 16.8 MB), for the kernel that reads them straight from global memory instead of staging them in LDS
+    h->gf3_frag = pcd_packed_copy(desc->lin[12].w, (size_t)4096 * 2048 * 2,
+                                  [&](void* buf) { return pcd_gemm_pack_wfrag(desc->lin[12].w, 2048, 2048, 4096, buf, nullptr); });
+    // the ten store GEMMs that run as 256 x 256 tiles (K >= 512): 29 MB in all, for gemm_xs_kernel; hi / lo layers keep pcd_gemm_f16_hilo
+    for (int i = 8; i <= 18; ++i) {
         if (i == 12 || ((desc->hilo_mask >> i) & 1u) || kLinK[i] < 384 || kLinC[i] % 256 != 0) continue;
-        if (hipMalloc(&h->lin_frag[i], (size_t)kLinK[i] * kLinC[i] * 2) != hipSuccess ||
-            pcd_gemm_pack_wfrag(desc->lin[i].w, kLinK[i], kLinK[i], kLinC[i], h->lin_frag[i], nullptr) != PCD_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h->lin_frag[i]) (void)hipFree(h->lin_frag[i]);
-            h->lin_frag[i] = nullptr;
-        }
+        h->lin_frag[i] = pcd_packed_copy(desc->lin[i].w, (size_t)kLinK[i] * kLinC[i] * 2,
+                                         [&](void* buf) { return pcd_gemm_pack_wfrag(desc->lin[i].w, kLinK[i], kLinK[i], kLinC[i], buf, nullptr); });
     }
-    // E23 = lin 2 .. 7, D21 = lin 19 .. 22: packed like the two above; a failed allocation only means E3 / D2 and the launches around them keep running
+    // E23 = lin 2 .. 7, D21 = lin 19 .. 22: packed like the two chains above; without them E3 / D2 and the launches around them keep running
     for (int c = 0; c < 2; ++c) {
         const int first = c == 0 ? 2 : 19, nl = c == 0 ? 6 : 4;
         const int hilo = (int)((desc->hilo_mask >> (c == 0 ? 4 : 22)) & 1u);
-        const void* w[6];
-        const float* b[6];
+        const void* w[6]; const float* b[6];
         for (int i = 0; i < nl; ++i) { w[i] = desc->lin[first + i].w; b[i] = desc->lin[first + i].b; }
-        if (!here || hipMalloc(&h->ends[c], pcd_pw_wide_ends_packed_bytes(c, hilo)) != hipSuccess ||
-            pcd_pw_wide_ends_pack(c, hilo, w, b, h->ends[c], nullptr) != PCD_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h->ends[c]) (void)hipFree(h->ends[c]);
-            h->ends[c] = nullptr;
-        }
+        h->ends[c] = pcd_packed_copy(w[0], pcd_pw_wide_ends_packed_bytes(c, hilo), [&](void* buf) { return pcd_pw_wide_ends_pack(c, hilo, w, b, buf, nullptr); });
     }
     *out = h;
     return PCD_OK;

@@ -6,28 +6,24 @@
 // launch and split-K for the small-grid layers, fp16 GEMMs for the Linear layers).  Activations NDHWC fp16, eval-mode
 // BatchNorm3d folded into the weights by the host packer.
 #include <new>
+#include <utility>
 #include "common.h"
 
 struct pcd_vae {
     pcd_vae_desc_t d;
-    // fragment-order copies of the k3 layers with C_in = 64 (pcd_conv3d_pack_wfrag), made at create: encoder.5.conv1, decoder.8.conv1 / conv2
-    void* wf_enc2c1 = nullptr;
-    void* wf_enc2c2 = nullptr;          // (with its fused projection shortcut's columns as "tap 27")
-    void* wf_dec9 = nullptr;
-    void* wf_dec11c1 = nullptr;
-    void* wf_dec11c2 = nullptr;
-    void* wf_enc5c1 = nullptr;
-    void* wf_enc5c2 = nullptr;          // (128 -> 128 with its 64-channel shortcut)
-    void* wf_dec5c1 = nullptr;
-    void* wf_dec5c2 = nullptr;
-    void* wf_dec8c1 = nullptr;
-    void* wf_dec8c2 = nullptr;
+    // Fragment-order copies of the k3 layers' weights (pcd_conv3d_pack_wfrag), made at create and keyed by the layer of `d` they belong to;
+    // a conv2 with a fused projection shortcut carries the shortcut's columns as "tap 27".  wf == null: that layer keeps the LDS-ring kernel.
+    struct Frag { const pcd_vae_conv_t* L; void* wf; };
+    Frag frag[11] = {};
     void* wf_last = nullptr;            // decoder.12's weights as MFMA A operands (pcd_conv3d_last_pack)
+
+    const void* wfrag(const pcd_vae_conv_t& L) const {
+        for (const Frag& f : frag) if (f.L == &L) return f.wf;
+        return nullptr;
+    }
 };
 
 namespace pcd {
-
-static inline size_t vae_align(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 // three rotating activation buffers (the largest activation is 32^3 x 64 channels), the split-K scratch of the
 // convolution launches, and the small GEMM operands
@@ -35,73 +31,83 @@ struct VaeWs { size_t a, b, c, scratch, scratch_bytes, small, total; };
 static constexpr size_t kConvScratchPerSample = (size_t)8 << 20;     // >= the split-K slabs of any layer (checked per launch)
 static VaeWs vae_carve(int batch) {
     VaeWs w{};
-    const size_t act = vae_align((size_t)batch * 32768 * 64 * 2);
+    const size_t act = align_up((size_t)batch * 32768 * 64 * 2);
     size_t o = 0;
     w.a = o; o += act;
     w.b = o; o += act;
     w.c = o; o += act;
     w.scratch = o;
-    w.scratch_bytes = vae_align(kConvScratchPerSample * (size_t)(batch < 4 ? 4 : batch));
+    w.scratch_bytes = align_up(kConvScratchPerSample * (size_t)(batch < 4 ? 4 : batch));
     o += w.scratch_bytes;
-    w.small = o; o += vae_align((size_t)batch * 1024 * 4);
+    w.small = o; o += align_up((size_t)batch * 1024 * 4);
     w.total = o;
     return w;
 }
 
-// pcd_vae_config: bit mask of the round-4 kernels in use (A/B, tests, bisecting): 2 = decoder.6 from one LDS halo, 4 = encoder.3 from sub-grid halos,
-// 8 = k3 layers with weights in registers; 0 = none (implicit-GEMM / LDS-ring forms), 1 = all
-static int g_convt_halo = 14;
+// pcd_vae_config, decoded: the LDS-halo / weights-in-registers forms in use (the table of codes is in include/pcd_hip.h).  TEST / BENCHMARK ONLY, process-global.
 enum { kCfgConvT = 2, kCfgK4S2 = 4, kCfgWreg = 8 };
+static int g_vae_forms = kCfgConvT | kCfgK4S2 | kCfgWreg;
+
+struct ConvGeom { int din, stride; const int* taps; int dout; };    // input grid, stride, tap table and output grid of a layer (cubes)
 
 struct Runner {
+    const pcd_vae& h;
     const pcd_vae_desc_t& d;
     int batch;
     char* scratch;
     size_t scratch_bytes;
     hipStream_t s;
+    void *x, *hb, *r;                 // x: the current activation (a layer or block leaves its output there, whichever buffer that is); hb, r: the other two
 
-    void fill(pcd_conv3d_desc_t& c, const pcd_vae_conv_t& L, const void* in, int din, int stride, const int* taps, int ntaps,
-              int dout, int relu, const void* resid, void* out, const void* in2 = nullptr, int cin2 = 0) const {
-        c = pcd_conv3d_desc_t{};
-        c.in = in; c.batch = batch; c.in_d = c.in_h = c.in_w = din; c.cin = L.cin;
-        c.rows_d = c.rows_h = c.rows_w = dout; c.stride = stride;
-        c.taps = taps; c.ntaps = ntaps; c.kpad = L.kpad;
-        c.w = L.w; c.bias = L.b; c.resid = resid; c.relu = relu;
-        c.out = out; c.cout = L.cout;
-        c.out_d = c.out_h = c.out_w = dout; c.out_scale = 1;
-        c.zero_page = d.zero_page;
-        c.in2 = in2; c.cin2 = in2 ? cin2 : 0;
-    }
+    ConvGeom k3(int dim) const { return {dim, 1, d.taps3, dim}; }           // k3 s1 p1
+    ConvGeom k1(int dim) const { return {dim, 1, d.taps1, dim}; }           // 1x1x1
+    ConvGeom down(int din) const { return {din, 2, d.taps4s2, din / 2}; }   // k4 s2 p1
+    ConvGeom flat(int din) const { return {din, 1, d.taps4p0, 1}; }         // k4 p0 over the whole grid
+
     int launch(const pcd_conv3d_desc_t* descs, int n) const {
         size_t need = pcd_conv3d_workspace_bytes(descs, n);
         if (need > scratch_bytes) need = 0;                           // too small: the launch simply runs unsplit
         return pcd_conv3d_f16_multi(descs, n, need ? scratch : nullptr, need, s);
     }
-    // Conv3d(k, stride, pad) [+ residual] [+ ReLU]
-    int conv(const pcd_vae_conv_t& L, const void* in, int din, int stride, const int* taps, int dout, int relu,
-             const void* resid, void* out, const void* in2 = nullptr, int cin2 = 0, const void* wfrag = nullptr) const {
-        pcd_conv3d_desc_t c;
-        fill(c, L, in, din, stride, taps, L.k * L.k * L.k, dout, relu, resid, out, in2, cin2);
-        // k3 layers with C_in = 64: weights in registers (fragment-order copy made at create), 256-row workgroups, no barrier in the tap loop
-        if (wfrag != nullptr && (g_convt_halo & kCfgWreg) && pcd_conv3d_k3s1_wreg_supported(&c)) return pcd_conv3d_k3s1_wreg_f16(&c, wfrag, s);
-        if (L.k == 3 && stride == 1 && pcd_conv3d_k3s1_supported(&c)) return pcd_conv3d_k3s1_f16(&c, s);   // LDS-resident halo
+    pcd_conv3d_desc_t desc(const pcd_vae_conv_t& L, int ntaps, const void* in, ConvGeom g, void* out, int relu, const void* resid, const void* in2, int cin2) const {
+        pcd_conv3d_desc_t c{};
+        c.in = in; c.batch = batch; c.in_d = c.in_h = c.in_w = g.din; c.cin = L.cin;
+        c.rows_d = c.rows_h = c.rows_w = g.dout; c.stride = g.stride;
+        c.taps = g.taps; c.ntaps = ntaps; c.kpad = L.kpad;
+        c.w = L.w; c.bias = L.b; c.resid = resid; c.relu = relu;
+        c.out = out; c.cout = L.cout;
+        c.out_d = c.out_h = c.out_w = g.dout; c.out_scale = 1;
+        c.zero_page = d.zero_page;
+        c.in2 = in2; c.cin2 = in2 ? cin2 : 0;
+        return c;
+    }
+    // Conv3d(k, stride, pad) [+ residual | + a second source behind the taps] [+ ReLU]
+    int conv(const pcd_vae_conv_t& L, const void* in, ConvGeom g, void* out, int relu = 1, const void* resid = nullptr, const void* in2 = nullptr,
+             int cin2 = 0) const {
+        const pcd_conv3d_desc_t c = desc(L, L.k * L.k * L.k, in, g, out, relu, resid, in2, cin2);
+        // k3 layers with a fragment-order copy: weights in registers, 256-row workgroups, no barrier in the tap loop
+        const void* wfrag = h.wfrag(L);
+        if (wfrag != nullptr && (g_vae_forms & kCfgWreg) && pcd_conv3d_k3s1_wreg_supported(&c)) return pcd_conv3d_k3s1_wreg_f16(&c, wfrag, s);
+        if (L.k == 3 && g.stride == 1 && pcd_conv3d_k3s1_supported(&c)) return pcd_conv3d_k3s1_f16(&c, s);   // LDS-resident halo
         // encoder.3 (k4 s2, 64 -> 64, 32^3 -> 16^3): the eight input-parity classes from LDS-resident sub-grid halos
-        if ((g_convt_halo & kCfgK4S2) && L.k == 4 && stride == 2 && resid == nullptr && in2 == nullptr && dout * 2 == din &&
-            pcd_conv3d_k4s2_halo_supported(batch, din, din, din, L.cin, L.cout, L.kpad))
-            return pcd_conv3d_k4s2_halo_f16(in, batch, din, din, din, L.cin, L.w, L.kpad, L.b, relu, L.cout, out, s);
+        if ((g_vae_forms & kCfgK4S2) && L.k == 4 && g.stride == 2 && resid == nullptr && in2 == nullptr && g.dout * 2 == g.din &&
+            pcd_conv3d_k4s2_halo_supported(batch, g.din, g.din, g.din, L.cin, L.cout, L.kpad))
+            return pcd_conv3d_k4s2_halo_f16(in, batch, g.din, g.din, g.din, L.cin, L.w, L.kpad, L.b, relu, L.cout, out, s);
         return launch(&c, 1);
     }
-    // ResidualBlock3D: relu(bn2(conv2(relu(bn1(conv1 x)))) + (downsample(x) | x)).  x <- the block's output; h, r: scratch buffers.
-    int res(const pcd_vae_res_t& R, void*& x, int dim, void*& h, void*& r, const void* wf1 = nullptr, const void* wf2 = nullptr) const {
-        int rc = conv(R.c1, x, dim, 1, d.taps3, dim, 1, nullptr, h, nullptr, 0, wf1);
+    // one layer from x into hb, which becomes x
+    int step(const pcd_vae_conv_t& L, ConvGeom g) { const int rc = conv(L, x, g, hb); std::swap(x, hb); return rc; }
+    int up(const pcd_vae_convT_t& T, int din) { const int rc = convT(T, x, din, hb); std::swap(x, hb); return rc; }
+    // ResidualBlock3D: relu(bn2(conv2(relu(bn1(conv1 x)))) + (downsample(x) | x))
+    int res(const pcd_vae_res_t& R, int dim) {
+        int rc = conv(R.c1, x, k3(dim), hb);
         if (rc) return rc;
         const void* resid = x;
-        void* out = x;                                                // in place: conv2 reads h and the residual row it overwrites
         if (R.has_ds && R.fused_ds) {
             // projection shortcut inside conv2's launch: its weights are K columns behind the 27 taps, x the second source.  NOT in
             // place: rows of x (ds.cin channels) and rows of the output (c2.cout channels) have different strides
-            rc = conv(R.c2, h, dim, 1, d.taps3, dim, 1, nullptr, r, x, R.ds.cin, wf2);
-            void* t = x; x = r; r = t;
+            rc = conv(R.c2, hb, k3(dim), r, 1, nullptr, x, R.ds.cin);
+            std::swap(x, r);
             return rc;
         }
         if (R.has_ds) {
@@ -109,28 +115,24 @@ struct Runner {
             if (pcd_conv1x1_supported(R.ds.cin, R.ds.cout))
                 rc = pcd_conv1x1_f16(x, (int64_t)batch * dim * dim * dim, R.ds.cin, R.ds.w, R.ds.kpad, R.ds.b, 0, R.ds.cout, r, s);
             else
-                rc = conv(R.ds, x, dim, 1, d.taps1, dim, 0, nullptr, r);
+                rc = conv(R.ds, x, k1(dim), r, 0);
             if (rc) return rc;
             resid = r;
         }
-        return conv(R.c2, h, dim, 1, d.taps3, dim, 1, resid, out, nullptr, 0, wf2);
+        return conv(R.c2, hb, k3(dim), x, 1, resid);                  // in place: conv2 reads hb and the residual row it overwrites
     }
     // ConvTranspose3d(k4, s2, p1) + ReLU: the 8 output-parity classes (2x2x2 taps each) in one launch
     int convT(const pcd_vae_convT_t& T, const void* in, int din, void* out) const {
         // decoder.6 (128 -> 64, 16^3 -> 32^3): all eight classes from one LDS-resident input halo
-        if ((g_convt_halo & kCfgConvT) && pcd_convt3d_k4s2_halo_supported(batch, din, din, din, T.cin, T.cout))
+        if ((g_vae_forms & kCfgConvT) && pcd_convt3d_k4s2_halo_supported(batch, din, din, din, T.cin, T.cout))
             return pcd_convt3d_k4s2_halo_f16(in, batch, din, din, din, T.cin, T.w, T.b, T.cout, out, s);
         pcd_conv3d_desc_t c[8];
-        for (int k = 0; k < 8; ++k) {
-            c[k] = pcd_conv3d_desc_t{};
-            c[k].in = in; c[k].batch = batch; c[k].in_d = c[k].in_h = c[k].in_w = din; c[k].cin = T.cin;
-            c[k].rows_d = c[k].rows_h = c[k].rows_w = din; c[k].stride = 1;
-            c[k].taps = T.taps[k]; c[k].ntaps = 8; c[k].kpad = 8 * T.cin;
-            c[k].w = T.w[k]; c[k].bias = T.b; c[k].resid = nullptr; c[k].relu = 1;
-            c[k].out = out; c[k].cout = T.cout;
+        for (int k = 0; k < 8; ++k) {              // a stride-1 layer of 2 x 2 x 2 taps on the input grid, written to every other voxel of the output grid
+            pcd_vae_conv_t L{};
+            L.w = T.w[k]; L.b = T.b; L.kpad = 8 * T.cin; L.cin = T.cin; L.cout = T.cout; L.k = 2;
+            c[k] = desc(L, 8, in, {din, 1, T.taps[k], din}, out, 1, nullptr, nullptr, 0);
             c[k].out_d = c[k].out_h = c[k].out_w = 2 * din; c[k].out_scale = 2;
             c[k].out_off_z = (k >> 2) & 1; c[k].out_off_y = (k >> 1) & 1; c[k].out_off_x = k & 1;
-            c[k].zero_page = d.zero_page;
         }
         return launch(c, 8);
     }
@@ -149,9 +151,9 @@ static bool res_ok(const pcd_vae_res_t& R) {
 
 using namespace pcd;
 
-extern "C" int pcd_vae_config(int convt_halo) {
-    PCD_CHECK_ARG(convt_halo >= 0 && convt_halo <= 15);
-    g_convt_halo = convt_halo == 1 ? 14 : (convt_halo & 14);
+extern "C" int pcd_vae_config(int v) {
+    PCD_CHECK_ARG(v >= 0 && v <= 15);
+    g_vae_forms = v == 1 ? 14 : (v & 14);
     return PCD_OK;
 }
 
@@ -172,45 +174,19 @@ extern "C" int pcd_vae_create(const pcd_vae_desc_t* desc, pcd_vae_t** out) {
     pcd_vae* h = new (std::nothrow) pcd_vae;
     PCD_CHECK_ARG(h != nullptr);
     h->d = *desc;
-    // fragment-order weight copies (one-time device work on the null stream, finished before the handle is returned); a failed allocation only
-    // means those layers keep the LDS-ring kernel
-    struct { const pcd_vae_conv_t* L; void** dst; } packs[] = {{&h->d.enc_res[1].c1, &h->wf_enc5c1}, {&h->d.dec_res[2].c1, &h->wf_dec8c1},
-                                                                {&h->d.dec_res[2].c2, &h->wf_dec8c2}, {&h->d.enc_res[0].c2, &h->wf_enc2c2},
-                                                                {&h->d.enc_res[0].c1, &h->wf_enc2c1}, {&h->d.dec_res[3].c1, &h->wf_dec11c1},
-                                                                {&h->d.dec_res[3].c2, &h->wf_dec11c2}, {&h->d.dec_conv9, &h->wf_dec9},
-                                                                {&h->d.enc_res[1].c2, &h->wf_enc5c2}, {&h->d.dec_res[1].c1, &h->wf_dec5c1},
-                                                                {&h->d.dec_res[1].c2, &h->wf_dec5c2}};
-    for (auto& pk : packs) {
-        const pcd_vae_conv_t& L = *pk.L;
+    // fragment-order weight copies (one-time device work on the null stream, finished before the handle is returned); a failed copy only
+    // means that layer keeps the LDS-ring kernel
+    const pcd_vae_conv_t* const layers[11] = {&h->d.enc_res[1].c1, &h->d.dec_res[2].c1, &h->d.dec_res[2].c2, &h->d.enc_res[0].c2, &h->d.enc_res[0].c1, &h->d.dec_res[3].c1,
+                                              &h->d.dec_res[3].c2, &h->d.dec_conv9,     &h->d.enc_res[1].c2, &h->d.dec_res[1].c1, &h->d.dec_res[1].c2};
+    for (int i = 0; i < 11; ++i) {
+        const pcd_vae_conv_t& L = *layers[i];
         const size_t bytes = L.k == 3 && L.kpad >= 27 * L.cin ? pcd_conv3d_wfrag_bytes(L.cin, L.cout) : 0;
-        if (bytes == 0) continue;
         // a fused projection shortcut's columns sit behind the 27 taps: up to kpad - 27 cin of them (the packer pads K to a multiple of 64 with zeros)
         const int extra = L.kpad - 27 * L.cin, cin2 = L.cin >= 64 ? (extra >= 64 ? 64 : (extra >= 32 ? 32 : 0)) : 0;
-        // (the copy is allocated on the CURRENT device: only if that is where the weights live -- one process per GPU sets it so)
-        hipPointerAttribute_t at;
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || hipPointerGetAttributes(&at, L.w) != hipSuccess || at.device != cur) { (void)hipGetLastError(); continue; }
-        void* buf = nullptr;
-        if (hipMalloc(&buf, bytes) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (pcd_conv3d_pack_wfrag(L.w, L.kpad, L.cin, L.cout, cin2, buf, nullptr) != PCD_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(buf);
-            continue;
-        }
-        *pk.dst = buf;
+        h->frag[i] = {&L, pcd_packed_copy(L.w, bytes, [&](void* buf) { return pcd_conv3d_pack_wfrag(L.w, L.kpad, L.cin, L.cout, cin2, buf, nullptr); })};
     }
-    {   // decoder.12's weights as MFMA A operands (27 KB); a failure leaves the VALU form
-        hipPointerAttribute_t at;
-        int cur = -1;
-        void* buf = nullptr;
-        if (hipGetDevice(&cur) == hipSuccess && hipPointerGetAttributes(&at, desc->last_w) == hipSuccess && at.device == cur &&
-            hipMalloc(&buf, pcd_conv3d_last_packed_bytes()) == hipSuccess) {
-            if (pcd_conv3d_last_pack(desc->last_w, buf, nullptr) == PCD_OK && hipStreamSynchronize(nullptr) == hipSuccess) h->wf_last = buf;
-            else { (void)hipGetLastError(); (void)hipFree(buf); }
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    // decoder.12's weights as MFMA A operands (27 KB); a failure leaves the VALU form
+    h->wf_last = pcd_packed_copy(desc->last_w, pcd_conv3d_last_packed_bytes(), [&](void* buf) { return pcd_conv3d_last_pack(desc->last_w, buf, nullptr); });
     *out = h;
     return PCD_OK;
 }
@@ -218,8 +194,8 @@ extern "C" int pcd_vae_create(const pcd_vae_desc_t* desc, pcd_vae_t** out) {
 extern "C" void pcd_vae_destroy(pcd_vae_t* h) {
     if (h == nullptr) return;
     if (h->wf_last) (void)hipFree(h->wf_last);
-    for (void* b : {h->wf_enc2c1, h->wf_enc2c2, h->wf_enc5c1, h->wf_enc5c2, h->wf_dec5c1, h->wf_dec5c2, h->wf_dec8c1, h->wf_dec8c2, h->wf_dec9, h->wf_dec11c1, h->wf_dec11c2})
-        if (b != nullptr) (void)hipFree(b);
+    for (const pcd_vae::Frag& f : h->frag)
+        if (f.wf != nullptr) (void)hipFree(f.wf);
     delete h;
 }
 
@@ -235,32 +211,25 @@ extern "C" size_t pcd_vae_workspace_bytes(int batch) {
         return PCD_ERR_WORKSPACE;                                                             \
     }                                                                                         \
     char* ws = (char*)workspace;                                                              \
-    void *x = ws + w.a, *hb = ws + w.b, *r = ws + w.c, *t_;  /* x: current activation; hb, r: the other two */ \
     const pcd_vae_desc_t& d = h->d;                                                           \
     hipStream_t s = (hipStream_t)stream;                                                      \
-    const Runner R{d, batch, ws + w.scratch, w.scratch_bytes, s};                             \
+    Runner R{*h, d, batch, ws + w.scratch, w.scratch_bytes, s, ws + w.a, ws + w.b, ws + w.c};     \
     int rc
-#define SWAP(a, b) do { t_ = a; a = b; b = t_; } while (0)
 
 extern "C" int pcd_vae_encode(pcd_vae_t* h, const float* vox, int batch, float* mu_logvar, void* workspace,
                               size_t workspace_bytes, void* stream) {
     PCD_CHECK_ARG(h && vox && mu_logvar && workspace && batch > 0);
     VAE_PROLOGUE();
     // encoder.0/1: Conv3d(1, 32, k3, p1) + ReLU straight from the fp32 occupancy grid
-    // a residual block leaves its output in x, whichever buffer that is
-    PCD_RUN(pcd_conv3d_first(vox, batch, 32, 32, 32, 1, d.enc0_w, d.enc0_b, 32, x, s));
-    PCD_RUN(R.res(d.enc_res[0], x, 32, hb, r, h->wf_enc2c1, h->wf_enc2c2));           // encoder.2   32 -> 64 @ 32^3
-    PCD_RUN(R.conv(d.enc_down[0], x, 32, 2, d.taps4s2, 16, 1, nullptr, hb));          // encoder.3/4 k4 s2 -> 16^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.enc_res[1], x, 16, hb, r, h->wf_enc5c1, h->wf_enc5c2));           // encoder.5   64 -> 128
-    PCD_RUN(R.conv(d.enc_down[1], x, 16, 2, d.taps4s2, 8, 1, nullptr, hb));           // encoder.6/7 -> 8^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.enc_res[2], x, 8, hb, r));                                        // encoder.8   128 -> 256
-    PCD_RUN(R.conv(d.enc_down[2], x, 8, 2, d.taps4s2, 4, 1, nullptr, hb));            // encoder.9/10 -> 4^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.enc_res[3], x, 4, hb, r));                                        // encoder.11  256 -> 512
-    void* const B = x; void* const A = hb;                                       // below: B = encoder.11's output, A = scratch
-    (void)r;
+    PCD_RUN(pcd_conv3d_first(vox, batch, 32, 32, 32, 1, d.enc0_w, d.enc0_b, 32, R.x, s));
+    PCD_RUN(R.res(d.enc_res[0], 32));                       // encoder.2   32 -> 64 @ 32^3
+    PCD_RUN(R.step(d.enc_down[0], R.down(32)));             // encoder.3/4 k4 s2 -> 16^3
+    PCD_RUN(R.res(d.enc_res[1], 16));                       // encoder.5   64 -> 128
+    PCD_RUN(R.step(d.enc_down[1], R.down(16)));             // encoder.6/7 -> 8^3
+    PCD_RUN(R.res(d.enc_res[2], 8));                        // encoder.8   128 -> 256
+    PCD_RUN(R.step(d.enc_down[2], R.down(8)));              // encoder.9/10 -> 4^3
+    PCD_RUN(R.res(d.enc_res[3], 4));                        // encoder.11  256 -> 512
+    void* const B = R.x; void* const A = R.hb;                                   // below: B = encoder.11's output, A = scratch
     // encoder.12/13: k4 p0 on a 4^3 grid = one row of 32768 inputs per sample -> (B, 512).  With <= 256 samples that is the
     // weight-streaming GEMM of the latent denoiser (33.5 MB of weights against B rows), not a 128-row convolution tile
     const int k_last = d.enc_last.cin * 64;
@@ -271,7 +240,7 @@ extern "C" int pcd_vae_encode(pcd_vae_t* h, const float* vox, int batch, float* 
         PCD_RUN(pcd_skinny_finish(slabs, pcd_skinny_slabs(k_last, d.enc_last.cout), batch, d.enc_last.cout, d.enc_last.b, nullptr,
                               1, 0, nullptr, nullptr, A, nullptr, s));
     } else {
-        PCD_RUN(R.conv(d.enc_last, B, 4, 1, d.taps4p0, 1, 1, nullptr, A));
+        PCD_RUN(R.conv(d.enc_last, B, R.flat(4), A));
     }
     // [fc_mu ; fc_logvar]: 512 -> 2 * latent, fp32 out
     const int c_fc = 2 * d.latent_dim, s_fc = pcd_skinny_slabs(512, c_fc);
@@ -297,21 +266,16 @@ extern "C" int pcd_vae_decode(pcd_vae_t* h, const float* z, int batch, float* ou
     pcd_gemm_desc_t g{};                                                         // decoder_input, columns already in NDHWC order
     g.a1 = z16; g.k1 = d.latent_dim; g.lda1 = d.latent_dim; g.w = d.din_w; g.ldw = d.latent_dim; g.bias = d.din_b;
     g.relu = 0; g.m = batch; g.c = 512 * 64;
-    PCD_RUN(pcd_gemm_f16(&g, x, 512 * 64, s));                                       // (B, 4,4,4, 512)
-    PCD_RUN(R.convT(d.dec_up[0], x, 4, hb));                                          // decoder.0/1  512 -> 256 @ 8^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.dec_res[0], x, 8, hb, r));                                        // decoder.2
-    PCD_RUN(R.convT(d.dec_up[1], x, 8, hb));                                          // decoder.3/4  256 -> 128 @ 16^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.dec_res[1], x, 16, hb, r, h->wf_dec5c1, h->wf_dec5c2));           // decoder.5
-    PCD_RUN(R.convT(d.dec_up[2], x, 16, hb));                                         // decoder.6/7  128 -> 64 @ 32^3
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.dec_res[2], x, 32, hb, r, h->wf_dec8c1, h->wf_dec8c2));           // decoder.8
-    PCD_RUN(R.conv(d.dec_conv9, x, 32, 1, d.taps3, 32, 1, nullptr, hb, nullptr, 0, h->wf_dec9));   // decoder.9/10  64 -> 32
-    SWAP(x, hb);
-    PCD_RUN(R.res(d.dec_res[3], x, 32, hb, r, h->wf_dec11c1, h->wf_dec11c2));         // decoder.11
-    PCD_RUN(pcd_conv3d_last_sigmoid_packed(x, batch, 32, 32, 32, 32, d.last_w, h->wf_last, d.last_b, out, s));   // decoder.12/13
+    PCD_RUN(pcd_gemm_f16(&g, R.x, 512 * 64, s));                                     // (B, 4,4,4, 512)
+    PCD_RUN(R.up(d.dec_up[0], 4));                          // decoder.0/1  512 -> 256 @ 8^3
+    PCD_RUN(R.res(d.dec_res[0], 8));                        // decoder.2
+    PCD_RUN(R.up(d.dec_up[1], 8));                          // decoder.3/4  256 -> 128 @ 16^3
+    PCD_RUN(R.res(d.dec_res[1], 16));                       // decoder.5
+    PCD_RUN(R.up(d.dec_up[2], 16));                         // decoder.6/7  128 -> 64 @ 32^3
+    PCD_RUN(R.res(d.dec_res[2], 32));                       // decoder.8
+    PCD_RUN(R.step(d.dec_conv9, R.k3(32)));                 // decoder.9/10  64 -> 32
+    PCD_RUN(R.res(d.dec_res[3], 32));                       // decoder.11
+    PCD_RUN(pcd_conv3d_last_sigmoid_packed(R.x, batch, 32, 32, 32, 32, d.last_w, h->wf_last, d.last_b, out, s));   // decoder.12/13
     return PCD_OK;
 }
-#undef SWAP
 #undef VAE_PROLOGUE

@@ -12,7 +12,7 @@ decoder_input, reparameterisation, KL) is a handful of few-row fp32 products.
 
 This is the straightforward formulation, not a tuned one: the row matrices are materialised (tens of GB of traffic per
 step at batch 16).  It exists so that `train_point_ldm.py` can
-run end to end on an MI355X; the sampler's implicit-GEMM convolutions (`csrc/conv3d.hip`) are the fast path.
+run end to end on an MI355X; the sampler's implicit-GEMM convolutions (`csrc/conv3d_igemm.hip`) are the fast path.
 """
 from __future__ import annotations
 

@@ -86,7 +86,7 @@ class VAE3DLarge(_HipModule):
             raise ValueError("VAE3DLarge's encoder reduces 32^3 to 1^3; other input shapes fail in the reference too")
         self.latent_dim = latent_dim
         self._build_from_spec(specs.vae3d_large_spec(latent_dim))
-        # the residual blocks' 1x1x1 projection shortcuts inside their conv2 launches (csrc/conv3d.hip, second source);
+        # the residual blocks' 1x1x1 projection shortcuts inside their conv2 launches (csrc/conv3d_igemm.hip and conv3d_halo.hip, second source);
         # PCD_VAE_FUSE_SHORTCUT=0 / set_fuse_shortcut(False): a pointwise launch + a residual read per block, as before round 4
         self.fuse_shortcut = os.environ.get("PCD_VAE_FUSE_SHORTCUT", "1") != "0"
         # reference init_weights (networks.py:2281-2283): xavier-normal(gain 0.01) for the latent heads
@@ -428,21 +428,25 @@ class VAE3D(_HipModule):
         self._packed = pk
         return pk
 
-    def _conv_s2(self, L, x, b, din):
-        lib = _lib.load()
-        dout = din // 2
-        out = torch.empty(b * dout ** 3, L["cout"], dtype=torch.float16, device=x.device)
+    def _desc(self, L, x, b, din, out, *, w, taps, kpad, rows, stride, out_dim, out_scale=1, out_off=(0, 0, 0)):
+        """One implicit-GEMM launch descriptor of layer L (+ folded BN, ReLU) over the cubic grid `din`, writing into `out`."""
         d = _lib.Conv3dDesc()
         d.inp, d.batch, d.in_d, d.in_h, d.in_w, d.cin = x.data_ptr(), b, din, din, din, L["cin"]
-        d.rows_d = d.rows_h = d.rows_w = dout
-        d.stride = 2
-        taps = self._packed["taps3"]
-        d.taps, d.ntaps, d.kpad = taps.data_ptr(), 27, L["kpad"]
-        d.w, d.bias, d.resid, d.relu = L["w"].data_ptr(), L["b"].data_ptr(), 0, 1
+        d.rows_d = d.rows_h = d.rows_w = rows
+        d.stride = stride
+        d.taps, d.ntaps, d.kpad = taps.data_ptr(), taps.numel(), kpad
+        d.w, d.bias, d.resid, d.relu = w.data_ptr(), L["b"].data_ptr(), 0, 1
         d.out, d.cout = out.data_ptr(), L["cout"]
-        d.out_d = d.out_h = d.out_w = dout
-        d.out_scale = 1
+        d.out_d = d.out_h = d.out_w = out_dim
+        d.out_scale = out_scale
+        d.out_off_z, d.out_off_y, d.out_off_x = out_off
         d.zero_page = self._packed["zero"].data_ptr()
+        return d
+
+    def _conv_s2(self, L, x, b, din):
+        dout = din // 2
+        out = torch.empty(b * dout ** 3, L["cout"], dtype=torch.float16, device=x.device)
+        d = self._desc(L, x, b, din, out, w=L["w"], taps=self._packed["taps3"], kpad=L["kpad"], rows=dout, stride=2, out_dim=dout)
         _launch_convs([d], x.device, "conv3d")
         return out
 
@@ -451,17 +455,8 @@ class VAE3D(_HipModule):
         out = torch.empty(b * dout ** 3, L["cout"], dtype=torch.float16, device=x.device)
         groups: Dict[int, list] = {}                                # classes with the same tap count share a launch
         for cls in L["classes"]:
-            d = _lib.Conv3dDesc()
-            d.inp, d.batch, d.in_d, d.in_h, d.in_w, d.cin = x.data_ptr(), b, din, din, din, L["cin"]
-            d.rows_d = d.rows_h = d.rows_w = din
-            d.stride = 1
-            d.taps, d.ntaps, d.kpad = cls["taps"].data_ptr(), cls["taps"].numel(), cls["kpad"]
-            d.w, d.bias, d.resid, d.relu = cls["w"].data_ptr(), L["b"].data_ptr(), 0, 1
-            d.out, d.cout = out.data_ptr(), L["cout"]
-            d.out_d = d.out_h = d.out_w = dout
-            d.out_scale = 2
-            d.out_off_z, d.out_off_y, d.out_off_x = cls["p"]
-            d.zero_page = self._packed["zero"].data_ptr()
+            d = self._desc(L, x, b, din, out, w=cls["w"], taps=cls["taps"], kpad=cls["kpad"], rows=din, stride=1, out_dim=dout,
+                           out_scale=2, out_off=cls["p"])
             groups.setdefault(cls["kpad"] * 64 + int(cls["taps"].numel()), []).append(d)
         for descs in groups.values():
             _launch_convs(descs, x.device, "conv3d(T)")

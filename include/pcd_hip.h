@@ -508,14 +508,27 @@ int pcd_conv3d_f16(const pcd_conv3d_desc_t* d, void* stream);
 size_t pcd_conv3d_workspace_bytes(const pcd_conv3d_desc_t* descs, int n);
 int pcd_conv3d_f16_multi(const pcd_conv3d_desc_t* descs, int n, void* workspace, size_t workspace_bytes,
                          void* stream);
-/* testing / tuning hook for pcd_conv3d_k3s1_f16 at C_in = 32, C_out <= 32: 0 = 128-row workgroups, 1 (default) = 256-row workgroups
- * (4 x 8 x 8 voxels, eight waves) where the grid has at least 512 of them, 2 = wherever H % 8 == 0 (tests).  Same bits.
- * pcd_conv3d_last_sigmoid_packed: default = per-tap partial products on the matrix pipe (a wave per four 8 x 8 output slices, every input slice read once; the fp32
- * weights as fp16 hi + lo + lo2 parts); + 16384: a wave per output slice; + 24: 8 x 8 x 8 output blocks with one MFMA per tap and 16 voxels (from the packed copy); + 16: the same blocks on the VALU (fp32 weights); + 8:
- * 4 x 4 x 8 blocks on the VALU.  The five forms agree to 1e-6.  + 64 / + 32 / + 96: split-K aims at 384 / 768 / 1024 workgroups
- * instead of 512 (all measured slower on VAE3DLarge); + 512: pcd_conv3d_first on 4 x 4 x 8 tiles where 8 x 8 x 8 would fit (same bits); + 128 / + 256: timing
- * ablations of the last layer's kernel, + 1024 x bits: of the 128 x 128 implicit GEMM (1 / 2 operand staging, 4 fragment reads, 8 MFMAs) (OUTPUTS WRONG).  TEST / BENCHMARK ONLY: process-global. */
-int pcd_conv3d_config(int tall_halo_tiles);
+/* Which of the convolution kernels run.  TEST / BENCHMARK ONLY: process-global, not synchronised with launches in flight.
+ * code = the sum of one value per field; 1 is the library's default; PCD_ERR_ARG unless 0 <= code < 262144 and (code & 7) <= 2.
+ *
+ *   bits    value        effect
+ *   0-2     0            pcd_conv3d_k3s1_f16 at C_in = 32, C_out <= 32: 128-row workgroups
+ *           1 (default)  256-row workgroups (4 x 8 x 8 voxels, eight waves) where the grid has at least 512 of them
+ *           2            256-row workgroups wherever H % 8 == 0 (tests).  Same bits in all three.
+ *   3-4     0 (default)  pcd_conv3d_last_sigmoid_packed: per-tap partial products on the matrix pipe (the fp32 weights as fp16 hi + lo + lo2 parts)
+ *           + 8          4 x 4 x 8 blocks on the VALU (fp32 weights)
+ *           + 16         8 x 8 x 8 blocks on the VALU (fp32 weights)
+ *           + 24         8 x 8 x 8 blocks with one MFMA per tap and 16 voxels (from the packed copy).  The forms agree to 1e-6.
+ *   5-6     0 (default)  split-K aims at 512 workgroups
+ *           + 32 / + 64 / + 96   at 768 / 384 / 1024 (all measured slower on VAE3DLarge)
+ *   7-8     + 128, + 256 timing ablations 1, 2 of the per-tap last-layer kernel (OUTPUTS WRONG); + 384 runs the real kernel
+ *   9       + 512        pcd_conv3d_first on 4 x 4 x 8 tiles where 8 x 8 x 8 would fit (same bits)
+ *   10-13   + 1024 x a   timing ablation a of the 128 x 128 implicit GEMM: 1 / 2 operand staging, 4 fragment reads, 8 MFMAs; the sums 3, 7, 15 of
+ *                        them are built too, any other a runs the real kernel (OUTPUTS WRONG)
+ *   14      + 16384      per-tap last layer with a wave per output slice instead of a wave per four 8 x 8 slices that reads every input slice once
+ *   15-17   + 32768 x a  timing ablation a of conv3d_halo_wreg_kernel<64, 2>: 1 halo not loaded, 2 no halo staging, 4 no taps; 6 is built too, any
+ *                        other a runs the real kernel (OUTPUTS WRONG) */
+int pcd_conv3d_config(int code);
 /* Conv3d(k3, stride 1, pad 1) (+ folded BN, residual, ReLU) with the input halo of a 4x4x8 output block held in
  * LDS and reused by all 27 taps -- the 32^3 layers of VAE3DLarge (encoder.2, decoder.8-11; networks.py:2227,
  * 2256-2259), whose gather traffic bounds the generic kernel.  Same descriptor; the tap table is implied
@@ -523,7 +536,7 @@ int pcd_conv3d_config(int tall_halo_tiles);
  * dims multiples of (4, 4, 8), out_scale 1; pcd_conv3d_k3s1_supported() tells (1/0), unsupported -> PCD_ERR_ARG. */
 int pcd_conv3d_k3s1_supported(const pcd_conv3d_desc_t* d);
 int pcd_conv3d_k3s1_f16(const pcd_conv3d_desc_t* d, void* stream);
-/* Conv3d(k3, stride 1, pad 1), C_in = 128, 64 or 32, with the weights in registers (csrc/conv3d.hip: conv3d_halo_wreg_kernel): the same function and descriptor as
+/* Conv3d(k3, stride 1, pad 1), C_in = 128, 64 or 32, with the weights in registers (csrc/conv3d_halo.hip: conv3d_halo_wreg_kernel): the same function and descriptor as
  * pcd_conv3d_k3s1_f16 (bias, residual, ReLU; d->w / d->kpad / d->taps are not read), the weights given in MFMA-fragment order -- wfrag, made once per
  * layer by pcd_conv3d_pack_wfrag from the [cout][kpad] matrix (pcd_conv3d_wfrag_bytes(cin, cout) bytes).  A workgroup owns 4 x 8 x 8 output voxels with their
  * halo in LDS; weight fragments are coalesced 1-KB global loads straight into MFMA operand registers; no barrier in the tap loop.  Supported: cin 128 (eight
@@ -535,7 +548,7 @@ size_t pcd_conv3d_wfrag_bytes(int cin, int cout);
 int pcd_conv3d_pack_wfrag(const void* w, int kpad, int cin, int cout, int cin2, void* wfrag, void* stream);
 int pcd_conv3d_k3s1_wreg_supported(const pcd_conv3d_desc_t* d);
 int pcd_conv3d_k3s1_wreg_f16(const pcd_conv3d_desc_t* d, const void* wfrag, void* stream);
-/* Conv3d(k4, s2, p1) (+ folded BN) (+ ReLU) with LDS-resident input (encoder.3/4, networks.py:2229-2230; csrc/conv3d.hip: conv3d_k4s2_halo_kernel):
+/* Conv3d(k4, s2, p1) (+ folded BN) (+ ReLU) with LDS-resident input (encoder.3/4, networks.py:2229-2230; csrc/conv3d_halo.hip: conv3d_k4s2_halo_kernel):
  * in fp16 [B][d][h][w][cin], w fp16 [cout][kpad] in the tap-major layout of pcd_conv3d_f16 (k = ((kz * 4 + ky) * 4 + kx) * cin + c), out fp16
  * [B][d/2][h/2][w/2][cout].  The kernel walks the eight input-parity classes (each a 2 x 2 x 2 stride-1 convolution of one sub-sampled grid) of a
  * 4 x 4 x 8 output block with that class's sub-grid halo in LDS.  Supported: cin 64, cout 64, d, h, w multiples of (8, 8, 16) and <= 64;
@@ -544,7 +557,7 @@ int pcd_conv3d_k4s2_halo_supported(int batch, int d, int h, int w, int cin, int 
 int pcd_conv3d_k4s2_halo_f16(const void* in, int batch, int d, int h, int w, int cin, const void* wgt, int kpad, const float* bias, int relu,
                              int cout, void* out, void* stream);
 /* ConvTranspose3d(k4, s2, p1) + ReLU (decoder.6/7, networks.py:2253-2254) with the 6 x 6 x 10 input halo of a 4 x 4 x 8 block of INPUT
- * voxels in LDS and all eight output-parity classes computed from it (csrc/conv3d.hip: convT3d_halo_kernel): in fp16 [B][d][h][w][cin],
+ * voxels in LDS and all eight output-parity classes computed from it (csrc/conv3d_halo.hip: convT3d_halo_kernel): in fp16 [B][d][h][w][cin],
  * out fp16 [B][2d][2h][2w][cout].  w8[4 pz + 2 py + px] = that class's fp16 [cout][8 * cin] matrix, K column (tz * 2 + tz... tap t) * cin + c
  * with t = (tz * 2 + ty) * 2 + tx, tap t_axis of parity p_axis reading input offset p - t (kernel index 1 + 2 t - p ... i.e. o = 2 i - 1 + k:
  * parity 0 -> k = 1, 3 at offsets 0, -1; parity 1 -> k = 0, 2 at offsets +1, 0) -- the layout pcd_vae_convT_t carries.  Supported:
@@ -600,9 +613,17 @@ typedef struct {
 } pcd_vae_desc_t;
 typedef struct pcd_vae pcd_vae_t;
 int pcd_vae_create(const pcd_vae_desc_t* desc, pcd_vae_t** out);
-/* testing / tuning hook, a bit mask of the round-4 kernels in use: 2 = decoder.6 through pcd_convt3d_k4s2_halo_f16, 4 = encoder.3 through
- * pcd_conv3d_k4s2_halo_f16, 8 = the k3 layers through pcd_conv3d_k3s1_wreg_f16; 1 (default) = all of them, 0 = none (implicit GEMM / LDS-ring forms) */
-int pcd_vae_config(int convt_halo);
+/* Which layers of pcd_vae_encode / pcd_vae_decode leave the implicit GEMM / LDS-ring forms.  TEST / BENCHMARK ONLY: process-global.
+ * PCD_ERR_ARG unless 0 <= code <= 15.
+ *
+ *   code         effect
+ *   0            none of the three below
+ *   1 (default)  all three (the same as 14)
+ *   bit 1 (+ 2)  decoder.6 through pcd_convt3d_k4s2_halo_f16
+ *   bit 2 (+ 4)  encoder.3 through pcd_conv3d_k4s2_halo_f16
+ *   bit 3 (+ 8)  the k3 layers that have a fragment-order copy through pcd_conv3d_k3s1_wreg_f16
+ *   bit 0 next to other bits is ignored */
+int pcd_vae_config(int code);
 void pcd_vae_destroy(pcd_vae_t* h);
 size_t pcd_vae_workspace_bytes(int batch);
 /* vox fp32 [B][1][32][32][32] in [0,1] -> mu_logvar fp32 [B][2*latent] = [mu | logvar] */

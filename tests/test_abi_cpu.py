@@ -234,3 +234,82 @@ def test_pair_metrics_workspace_layout_without_gpu():
             assert lay[k] % 256 == 0 and lay[nxt] - lay[k] >= need[k], (P, na, nb, k)
     off = (C.c_size_t * len(_lib.PCD_PAIR_WS))()
     assert lib.pcd_pair_metrics_workspace_layout(0, 4, 4, off) == -1 and lib.pcd_pair_metrics_workspace_layout(1, 4, 4, None) == -1
+
+
+def _conv_desc(_lib, B, dims, cin, cout, k, stride, cin2):
+    """A descriptor as the VAE runner builds it: rows = dims // stride (k4 / stride 1 / pad 0: one row), out = rows."""
+    dims = (dims,) * 3 if isinstance(dims, int) else dims
+    rows = (1, 1, 1) if (k == 4 and stride == 1) else tuple(d // stride for d in dims)
+    c = _lib.Conv3dDesc()
+    c.inp = c.w = c.out = c.taps = c.zero_page = 64                       # never dereferenced on the host
+    c.batch, (c.in_d, c.in_h, c.in_w), c.cin, c.cout = B, dims, cin, cout
+    c.rows_d, c.rows_h, c.rows_w = c.out_d, c.out_h, c.out_w = rows
+    c.stride, c.out_scale, c.ntaps = stride, 1, k ** 3
+    c.kpad = (k ** 3 * cin + cin2 + 63) // 64 * 64
+    c.in2, c.cin2 = (64 if cin2 > 0 else None), cin2
+    return c
+
+
+def test_conv3d_and_vae_host_plan_is_the_recorded_one():
+    """What the convolution and VAE entry points decide on the host, for the layers of VAE3DLarge and some awkward shapes, as recorded from
+    the library before the convolution code was split by kernel family (no GPU): which forms support a layer, the split-K scratch a launch asks for under each
+    split target, which configuration codes are valid, and the sizes of the packed copies and of the VAE workspace."""
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    # (B, dims, cin, cout, k, stride, cin2) -> k3s1_supported, wreg_supported, workspace_bytes(n = 1), workspace_bytes(n = 8)
+    plan = [((32, 32, 32, 64, 3, 1, 0), (1, 1, 0, 0)),
+            ((32, 32, 64, 64, 3, 1, 32), (1, 1, 0, 0)),
+            ((32, 32, 64, 64, 4, 2, 0), (0, 0, 0, 0)),
+            ((32, 16, 64, 128, 3, 1, 0), (1, 1, 0, 0)),
+            ((32, 16, 128, 128, 3, 1, 64), (0, 1, 0, 0)),
+            ((32, 16, 128, 128, 4, 2, 0), (0, 0, 33554432, 0)),
+            ((32, 8, 128, 256, 3, 1, 0), (0, 1, 33554432, 0)),
+            ((4, 8, 256, 256, 3, 1, 128), (0, 0, 33554432, 33554432)),
+            ((4, 8, 256, 256, 4, 2, 0), (0, 0, 16777216, 33554432)),
+            ((1, 4, 256, 512, 3, 1, 0), (0, 0, 3538944, 16777216)),
+            ((32, 4, 512, 512, 3, 1, 0), (0, 0, 33554432, 0)),
+            ((32, 4, 512, 512, 4, 1, 0), (0, 0, 4194304, 8388608)),
+            ((2, 32, 64, 32, 3, 1, 0), (1, 1, 0, 0)),
+            ((2, 32, 32, 32, 3, 1, 0), (1, 1, 0, 0)),
+            ((3, (5, 3, 7), 64, 72, 3, 1, 0), (0, 0, 544320, 4354560)),
+            ((2, (4, 12, 8), 32, 32, 3, 1, 0), (1, 0, 294912, 2359296)),
+            ((2, (4, 8, 4), 64, 64, 3, 1, 0), (0, 0, 393216, 3145728))]
+    for layer, want in plan:
+        c = _conv_desc(_lib, *layer)
+        got = (lib.pcd_conv3d_k3s1_supported(c), lib.pcd_conv3d_k3s1_wreg_supported(c),
+               lib.pcd_conv3d_workspace_bytes(c, 1), lib.pcd_conv3d_workspace_bytes(c, 8))
+        assert got == want, (layer, got, want)
+    # the configuration code is decoded field by field: the split-K target, seen through the scratch of encoder.11
+    c = _conv_desc(_lib, 32, 4, 512, 512, 3, 1, 0)
+    try:
+        for code, want in ((1, 33554432), (65, 25165824), (33, 50331648), (97, 67108864)):
+            assert lib.pcd_conv3d_config(code) == 0
+            assert lib.pcd_conv3d_workspace_bytes(c, 1) == want, code
+    finally:
+        assert lib.pcd_conv3d_config(1) == 0
+    try:
+        for code in (0, 1, 2, 8, 9, 25, 513, 16385):
+            assert lib.pcd_conv3d_config(code) == 0, code
+        for code in (-1, 3, 4, 7, 11, 262143, 262144, 262145):
+            assert lib.pcd_conv3d_config(code) == -1, code
+    finally:
+        assert lib.pcd_conv3d_config(1) == 0
+    try:
+        for code in (0, 1, 2, 14, 15):
+            assert lib.pcd_vae_config(code) == 0, code
+        for code in (-1, 16):
+            assert lib.pcd_vae_config(code) == -1, code
+    finally:
+        assert lib.pcd_vae_config(1) == 0
+    wfrag = {(32, 32): 57344, (32, 64): 114688, (64, 32): 114688, (64, 64): 229376, (64, 192): 688128, (128, 128): 901120,
+             (128, 256): 1802240, (64, 72): 0, (128, 192): 0, (256, 256): 0, (16, 32): 0}
+    for (cin, cout), want in wfrag.items():
+        assert lib.pcd_conv3d_wfrag_bytes(cin, cout) == want, (cin, cout)
+    for args, want in (((32, 32, 32, 32, 64, 64, 4096), 1), ((1, 8, 8, 16, 64, 64, 4096), 1), ((1, 8, 8, 8, 64, 64, 4096), 0),
+                       ((1, 16, 16, 16, 128, 128, 8192), 0), ((1, 8, 8, 16, 64, 64, 4032), 0)):
+        assert lib.pcd_conv3d_k4s2_halo_supported(*args) == want, args
+    for args, want in (((32, 16, 16, 16, 128, 64), 1), ((1, 4, 4, 8, 128, 64), 1), ((1, 4, 4, 4, 128, 64), 0), ((1, 8, 8, 8, 256, 128), 0)):
+        assert lib.pcd_convt3d_k4s2_halo_supported(*args) == want, args
+    assert lib.pcd_conv3d_last_packed_bytes() == 27648
+    for batch, want in ((0, 0), (1, 46141440), (4, 83902464), (5, 104878080), (32, 671219712)):
+        assert lib.pcd_vae_workspace_bytes(batch) == want, batch

@@ -283,11 +283,12 @@ def test_conv1x1_pointwise_exact_integers(k, c, ldw, m, relu):
     assert lib.pcd_conv1x1_f16(x.data_ptr(), m, 48, w.data_ptr(), ldw, b.data_ptr(), relu, c, out.data_ptr(), 0) != 0
 
 
-@pytest.mark.parametrize("dims,stride", [((8, 8, 8), 1), ((16, 8, 24), 1), ((4, 8, 16), 1), ((6, 5, 7), 1), ((8, 8, 8), 2)])
+@pytest.mark.parametrize("dims,stride", [((8, 8, 8), 1), ((16, 8, 24), 1), ((4, 8, 16), 1), ((6, 5, 7), 1), ((8, 8, 8), 2), ((4, 4, 8), 1)])
 def test_conv3d_first_and_last_layers(dims, stride):
     """encoder.0 (Cin = 1, ReLU, fp16 NDHWC out) and decoder.12/13 (Cout = 1, sigmoid) against F.conv3d in fp64:
     the LDS-halo last-layer path (dims multiples of 4, 4, 8), its direct fallback (6, 5, 7), and the cout = 32
-    first-layer path at both strides."""
+    first-layer path at both strides.  (4, 4, 8) is one 4 x 4 x 8 block that no 8-row form divides: with a packed copy
+    present the packed entry still has to land on the 4 x 4 x 8 halo form, the first layer on its 4 x 4 x 8 tiles."""
     from shapegen_amd import _lib
     lib = _lib.load()
     b = 2
@@ -360,6 +361,32 @@ def test_conv3d_first_and_last_layers(dims, stride):
             finally:
                 _lib.check(lib.pcd_conv3d_config(1))           # the library's default
             assert (o3.cpu().double() - want2).abs().max() <= 2e-6, cfg
+        if dims == (8, 8, 8):                                                        # the packed entry without a packed copy: the forms that read the fp32 weights
+            o8 = torch.empty_like(o2)
+            _lib.check(lib.pcd_conv3d_last_sigmoid_packed(h.data_ptr(), b, dims[0], dims[1], dims[2], 32, dwl.data_ptr(), None, bl,
+                                                          o8.data_ptr(), _lib.stream_ptr()))
+            assert (o8.cpu().double() - want2).abs().max() <= 2e-6
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_conv3d_first_layer_generic_width(stride):
+    """pcd_conv3d_first at a width other than 32 (cout = 16): the generic kernel, weights and bias in dynamic LDS, on a grid that no
+    tile divides, against F.conv3d in fp64."""
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    b, dims, cout = 2, (6, 5, 7), 16
+    g = torch.Generator().manual_seed(6)
+    x = torch.rand((b, 1) + dims, generator=g)
+    w0, b0 = torch.randn(cout, 1, 3, 3, 3, generator=g) * 0.3, torch.randn(cout, generator=g) * 0.1
+    want = F.conv3d(x.double(), w0.double(), b0.double(), stride=stride, padding=1).clamp_min(0)
+    od = tuple((d - 1) // stride + 1 for d in dims)
+    out = torch.empty(b * od[0] * od[1] * od[2], cout, dtype=torch.float16, device="cuda")
+    dx, dw, db = x.cuda().contiguous(), w0.reshape(cout, 27).contiguous().cuda(), b0.cuda()
+    _lib.check(lib.pcd_conv3d_first(dx.data_ptr(), b, dims[0], dims[1], dims[2], stride, dw.data_ptr(), db.data_ptr(), cout,
+                                    out.data_ptr(), _lib.stream_ptr()))
+    got = out.float().cpu().reshape((b,) + od + (cout,)).permute(0, 4, 1, 2, 3).double()
+    assert float(want.max()) > 0.5                                                   # the ReLU leaves something to compare
+    assert (got - want).abs().max() <= 2e-3 * max(1.0, float(want.abs().max()))       # one fp16 rounding
 
 
 def test_conv_transpose3d_classes_exact():
