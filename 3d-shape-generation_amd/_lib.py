@@ -30,6 +30,13 @@ class GemmDesc(C.Structure):
                 ("relu", i32), ("m", i32), ("c", i32)]
 
 
+class GemmPlan(C.Structure):
+    """pcd_gemm_plan_t: what a GEMM entry point would launch (tests and tools only)."""
+    _fields_ = [("family", i32), ("instance", i32), ("grid", C.c_uint), ("block", C.c_uint), ("tiles_m", i32), ("tiles_n", i32),
+                ("patch_pn", i32), ("patch_xn", i32), ("xp_depth", i32), ("xs_ablation", i32), ("zero_bias", i32), ("zero_shape_bias", i32),
+                ("no_zero_row", i32)]
+
+
 class LinearDesc(C.Structure):
     _fields_ = [("w", vp), ("b", vp), ("k", i32), ("c", i32)]
 
@@ -133,6 +140,7 @@ _SIGS = {
     "pcd_gemm_store_wfrag_enabled": (i32, []),
     "pcd_gemm_wfrag_stamps": (i32, [vp]),
     "pcd_gemm_set_config": (i32, [i32]),
+    "pcd_gemm_plan": (i32, [C.POINTER(GemmDesc), i32, i32, i32, i32, C.POINTER(GemmPlan)]),
     "pcd_fill_zero": (i32, [vp, sz, vp]),
     "pcd_f32_to_f16": (i32, [vp, vp, i64, vp]),
     "pcd_f16_to_f32": (i32, [vp, vp, i64, vp]),

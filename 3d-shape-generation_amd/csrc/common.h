@@ -79,6 +79,10 @@ static inline void* pcd_packed_copy(const void* src, size_t bytes, Pack pack) {
     return nullptr;
 }
 
+// gemm_f16.hip: would pcd_gemm_f16_colmax_wfrag take this column-max product (a fragment-order copy held, the path switched on, a shape of gemm_xw_kernel)?
+// It refuses the others, and the caller then goes to pcd_gemm_f16_colmax.
+bool gemm_colmax_takes_wfrag(const pcd_gemm_desc_t* d, int rows_per_shape, const void* wfrag);
+
 }  // namespace pcd
 
 #include "device_prims.h"

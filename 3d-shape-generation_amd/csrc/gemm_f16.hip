@@ -24,7 +24,7 @@ struct GemmParams {
     const half_t* w; int64_t ldw;
     const float* bias; const float* shape_bias; int rows_per_shape;
     int relu; int m; int c;
-    half_t* out16; float* out32; int64_t ldo;
+    half_t* out16; float* out32; int64_t ldo;   // out32, BORROWED by gemm_xw_kernel (whose epilogue has no fp32 output): the stamp buffer of pcd_gemm_wfrag_stamps, or null
     const half_t* resid; int64_t ldr;
     float* colmax; int cm_rps;
     int tiles_m; int tiles_n;
@@ -32,7 +32,8 @@ struct GemmParams {
     // split-K (EPI_F32 only): `splits` independent products over consecutive k1-deep slices of the reduction;
     // slice s reads A and W at column offset s*k1 and writes the fp32 slab out32 + s*split_out
     int splits; int64_t split_out;
-    int xp_depth;             // gemm_xp_kernel: K tiles of the next tile requested before the epilogue's stores (1 or 2)
+    int xp_depth;             // gemm_xp_kernel: K tiles of the next tile requested before the epilogue's stores (1 or 2).  BORROWED by gemm_xs_kernel: the
+                              // ablation bits of its ABL instance.  Both borrowed fields, like the tile and patch fields, are set in launch_plan and nowhere else.
     int krep;                 // 2 = hi / lo weights (pcd_gemm_f16_hilo): the sources are walked TWICE, first against columns [0, K) of W (the fp16
                               // weights), then against [K, 2K) (fp16 of the rounding residuals): ~22-bit weights on the fp16 matrix cores; 0 / 1 = once
 };
@@ -80,6 +81,71 @@ __device__ __forceinline__ void wait_vmcnt_rt(int n) {
         default: wait_vmcnt<0>(); break;          // (never reached with the counts of this file; waiting for everything is always safe)
     }
 }
+
+// tile index -> (row panel, column tile).  Default: n fastest.  XCD-aware variant (T1; speed only; `patched`: plan_gemm chose a patch shape): a
+// persistent grid of 256 blocks is dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2);
+// within each round of 256 tiles XCD x owns a pm x pn patch (pm*pn = 32), so its L2 streams pm + pn
+// operand panels instead of up to 32 + 1.
+__device__ __forceinline__ void patch_tile_coords(const GemmParams& p, bool patched, int tile, int& tm, int& tn) {
+    if (patched) {
+        const int pn = p.patch_pn, pm = 32 / pn, xn = p.patch_xn, xm = 8 / xn;
+        const int round = tile >> 8, b = tile & 255;
+        const int xcd = b & 7, slot = b >> 3;
+        const int sbn = p.tiles_n / (xn * pn);                   // super-blocks per row of super-blocks
+        const int sb_m = round / sbn, sb_n = round - sb_m * sbn;
+        tm = (sb_m * xm + xcd / xn) * pm + slot / pn;
+        tn = (sb_n * xn + xcd % xn) * pn + slot % pn;
+    } else {
+        tm = tile / p.tiles_n;
+        tn = tile - tm * p.tiles_n;
+    }
+}
+
+// a wave-uniform address, said so (where the divergence analysis loses it, an asm "s" operand would be handed a VGPR pair)
+__device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
+    const uint64_t v = (uint64_t)q;
+    return (const half_t*)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v));
+}
+
+// the tile's bias and per-shape bias columns of this wave's column quarter -> bias_lds[par] by LDS-DMA, 2 pieces (waves with the same wn write the same 256
+// bytes: benign).  A macro, not a function: it is the kernels' own text (lane, wn, WN, BN, p in scope), so their streams stay what they were.
+#define PCD_GEMM_STAGE_BIAS(DST)                                                                                                    \
+    auto stage_bias = [&](int m0, int n0, int par) __attribute__((always_inline)) {                                                 \
+        const unsigned dst = (DST);                                                                                                  \
+        glds4_s((unsigned)(lane * 4), p.bias + n0 + wn * WN, dst);                                                                   \
+        glds4_s((unsigned)(lane * 4), p.shape_bias + (int64_t)(m0 / p.rows_per_shape) * p.c + n0 + wn * WN, dst + BN * 4);           \
+    }
+
+// four fp32 values V clamped to [LO, 65504] -> two packed fp16 pairs PK[0], PK[1] (channels +0, +1 and +2, +3).  A macro for the same reason: as a function,
+// by value or by reference, it changes the streams of gemm_xp_kernel and gemm_xs_kernel (profiles/gemm_plan_isa.md).
+#define PCD_GEMM_CLAMP_PACK(V, LO, PK)                                      \
+    do {                                                                    \
+        half2_ lo2, hi2;                                                    \
+        lo2[0] = (half_t)__builtin_amdgcn_fmed3f((V)[0], LO, 65504.f);      \
+        lo2[1] = (half_t)__builtin_amdgcn_fmed3f((V)[1], LO, 65504.f);      \
+        hi2[0] = (half_t)__builtin_amdgcn_fmed3f((V)[2], LO, 65504.f);      \
+        hi2[1] = (half_t)__builtin_amdgcn_fmed3f((V)[3], LO, 65504.f);      \
+        (PK)[0] = __builtin_bit_cast(unsigned, lo2);                        \
+        (PK)[1] = __builtin_bit_cast(unsigned, hi2);                        \
+    } while (0)
+
+// column-max epilogue of the kernels that hold the tile's bias rows in bias_lds[par]: the maximum over the wave's rows of relu(acc + bias), one atomic per
+// column (acc, MI, NI, m0, n0, wm, wn, WM, WN, lane, q, par, p in scope).  A macro for the same reason.
+#define PCD_GEMM_COLMAX_FROM_LDS_BIAS()                                                             \
+    do {                                                                                            \
+        unsigned* cm = reinterpret_cast<unsigned*>(p.colmax);                                       \
+        const int shape = (m0 + wm * WM) / p.cm_rps, colq = lane & 15;                              \
+        _Pragma("unroll") for (int j = 0; j < NI; ++j) {                                            \
+            const int cl = wn * WN + j * 16 + colq;                                                 \
+            const float b = bias_lds[par][0][cl] + bias_lds[par][1][cl];                            \
+            float mx = 0.f;                                                                         \
+            _Pragma("unroll") for (int i = 0; i < MI; ++i)                                          \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r] + b);     \
+            mx = fmaxf(mx, __shfl_xor(mx, 16));                                                     \
+            mx = fmaxf(mx, __shfl_xor(mx, 32));                                                     \
+            if (q == 0) atomicMax(cm + (int64_t)shape * p.c + n0 + cl, __float_as_uint(mx));        \
+        }                                                                                           \
+    } while (0)
 
 // BM x BN x 64 tile, WGM x WGN waves (each wave (BM/WGM) x (BN/WGN)), STAGES LDS buffers.
 // STAGES == 2: one tile prefetched, plain barrier.  STAGES >= 3: STAGES-1 tiles prefetched, the
@@ -157,25 +223,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f16_kernel(GemmParams p) 
         }
     };
 
-    // tile index -> (row panel, column tile).  Default: n fastest.  XCD-aware variant (T1; speed only): a
-    // persistent grid of 256 blocks is dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2);
-    // within each round of 256 tiles XCD x owns a pm x pn patch (pm*pn = 32), so its L2 streams pm + pn
-    // operand panels instead of up to 32 + 1.
     auto tile_coords = [&](int tile, int& tm, int& tn, int& split) {
         split = 0;
         if (p.splits > 1) { split = tile / tiles_mn; tile -= split * tiles_mn; }
-        if (gridDim.x == 256 && p.patch_pn > 0) {
-            const int pn = p.patch_pn, pm = 32 / pn, xn = p.patch_xn, xm = 8 / xn;
-            const int round = tile >> 8, b = tile & 255;
-            const int xcd = b & 7, slot = b >> 3;
-            const int sbn = p.tiles_n / (xn * pn);                   // super-blocks per row of super-blocks
-            const int sb_m = round / sbn, sb_n = round - sb_m * sbn;
-            tm = (sb_m * xm + xcd / xn) * pm + slot / pn;
-            tn = (sb_n * xn + xcd % xn) * pn + slot % pn;
-        } else {
-            tm = tile / p.tiles_n;
-            tn = tile - tm * p.tiles_n;
-        }
+        patch_tile_coords(p, gridDim.x == 256 && p.patch_pn > 0, tile, tm, tn);       // (the generic grid need not be 256 blocks)
     };
 
     int it = 0;                      // K tiles consumed so far by this block (LDS ring position)
@@ -279,13 +330,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f16_kernel(GemmParams p) 
                         const int col = n0 + wn * WN + (j + t) * 16 + q4;
                         f32x4 v = acc[i][j + t] + bv[j + t];
                         if (!FULL && sbrow != nullptr && col < p.c) v += *(const f32x4*)(sbrow + col);
-                        half2_ lo2, hi2;
-                        lo2[0] = (half_t)__builtin_amdgcn_fmed3f(v[0], lo, 65504.f);
-                        lo2[1] = (half_t)__builtin_amdgcn_fmed3f(v[1], lo, 65504.f);
-                        hi2[0] = (half_t)__builtin_amdgcn_fmed3f(v[2], lo, 65504.f);
-                        hi2[1] = (half_t)__builtin_amdgcn_fmed3f(v[3], lo, 65504.f);
-                        pk[t][0] = __builtin_bit_cast(unsigned, lo2);
-                        pk[t][1] = __builtin_bit_cast(unsigned, hi2);
+                        PCD_GEMM_CLAMP_PACK(v, lo, pk[t]);
                     }
                     const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
@@ -448,25 +493,8 @@ __global__ __launch_bounds__(512) void gemm_xp_kernel(GemmParams p) {
     };
     // the tile's bias columns of this wave's column quarter (waves with the same wn write the same 256 bytes: benign) -> LDS, 2 pieces
     const unsigned lds_b = (unsigned)(size_t)&bias_lds[0][0][0];
-    auto stage_bias = [&](int m0, int n0, int par) __attribute__((always_inline)) {
-        const unsigned dst = lds_b + par * (2 * BN * 4) + wn * WN * 4;
-        glds4_s((unsigned)(lane * 4), p.bias + n0 + wn * WN, dst);
-        glds4_s((unsigned)(lane * 4), p.shape_bias + (int64_t)(m0 / p.rows_per_shape) * p.c + n0 + wn * WN, dst + BN * 4);
-    };
-    auto tile_coords = [&](int tile, int& tm, int& tn) {
-        if (p.patch_pn > 0) {
-            const int pn = p.patch_pn, pm = 32 / pn, xn = p.patch_xn, xm = 8 / xn;
-            const int round = tile >> 8, b = tile & 255;
-            const int xcd = b & 7, slot = b >> 3;
-            const int sbn = p.tiles_n / (xn * pn);
-            const int sb_m = round / sbn, sb_n = round - sb_m * sbn;
-            tm = (sb_m * xm + xcd / xn) * pm + slot / pn;
-            tn = (sb_n * xn + xcd % xn) * pn + slot % pn;
-        } else {
-            tm = tile / p.tiles_n;
-            tn = tile - tm * p.tiles_n;
-        }
-    };
+    PCD_GEMM_STAGE_BIAS(lds_b + par * (2 * BN * 4) + wn * WN * 4);
+    auto tile_coords = [&](int tile, int& tm, int& tn) { patch_tile_coords(p, p.patch_pn > 0, tile, tm, tn); };
 
     // fragment read offsets (as in gemm_f16_kernel)
     const int ra = wm * WM + (lane & 15), rb = wn * WN + (lane & 15), q = lane >> 4;
@@ -541,21 +569,7 @@ __global__ __launch_bounds__(512) void gemm_xp_kernel(GemmParams p) {
         }
         if constexpr (EPI == EPI_COLMAX) {
             // values are post-ReLU (>= 0): float bits order like unsigned ints, colmax pre-zeroed; the wave's 128 rows lie in one shape
-            unsigned* cm = reinterpret_cast<unsigned*>(p.colmax);
-            const int shape = (m0 + wm * WM) / p.cm_rps, colq = lane & 15;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int cl = wn * WN + j * 16 + colq;
-                const float b = bias_lds[par][0][cl] + bias_lds[par][1][cl];
-                float mx = 0.f;
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r] + b);
-                mx = fmaxf(mx, __shfl_xor(mx, 16));
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                if (q == 0) atomicMax(cm + (int64_t)shape * p.c + n0 + cl, __float_as_uint(mx));
-            }
+            PCD_GEMM_COLMAX_FROM_LDS_BIAS();
         } else {
         // ---- store epilogue (whole tile): accumulator element (i, j, r) = point row wm*WM + i*16 + (lane & 15), channel wn*WN + j*16 + 4 (lane >> 4) + r
         {
@@ -574,13 +588,7 @@ __global__ __launch_bounds__(512) void gemm_xp_kernel(GemmParams p) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
                         const f32x4 v = acc[i][j + t] + bv[j + t];
-                        half2_ lo2, hi2;
-                        lo2[0] = (half_t)__builtin_amdgcn_fmed3f(v[0], lo, 65504.f);
-                        lo2[1] = (half_t)__builtin_amdgcn_fmed3f(v[1], lo, 65504.f);
-                        hi2[0] = (half_t)__builtin_amdgcn_fmed3f(v[2], lo, 65504.f);
-                        hi2[1] = (half_t)__builtin_amdgcn_fmed3f(v[3], lo, 65504.f);
-                        pk[t][0] = __builtin_bit_cast(unsigned, lo2);
-                        pk[t][1] = __builtin_bit_cast(unsigned, hi2);
+                        PCD_GEMM_CLAMP_PACK(v, lo, pk[t]);
                     }
                     const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
@@ -657,32 +665,13 @@ __global__ __launch_bounds__(512) void gemm_xw_kernel(GemmParams p, const half_t
         const half_t* ab = kt < nk1 ? p.a1 + (int64_t)m0 * p.lda1 + kt * BKT : p.a2 + (int64_t)m0 * p.lda2 + (kt - nk1) * BKT;
         const unsigned la = lds0 + buf * STAGE_BYTES + (SPLIT ? (wave & 3) : wave) * 8 * ROWB;
         // (the base is wave-uniform; say so: the divergence analysis loses it through the tile walk below and would hand the asm a VGPR pair)
-        const uint64_t av = (uint64_t)ab;
-        const half_t* abu = (const half_t*)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(av >> 32)) << 32) |
-                                            (unsigned)__builtin_amdgcn_readfirstlane((int)av));
+        const half_t* abu = uniform_ptr(ab);
 #pragma unroll
         for (int r = 0; r < NPIECE; ++r) glds16_s(voa, abu + (int64_t)(r * RSTEP) * p.lda1, la + r * RSTEP * ROWB);
     };
     const unsigned lds_b = (unsigned)(size_t)&bias_lds[0][0][0];
-    auto stage_bias = [&](int m0, int n0, int par) __attribute__((always_inline)) {
-        const unsigned dst = lds_b + par * (2 * BN * 4) + wn * WN * 4;
-        glds4_s((unsigned)(lane * 4), p.bias + n0 + wn * WN, dst);
-        glds4_s((unsigned)(lane * 4), p.shape_bias + (int64_t)(m0 / p.rows_per_shape) * p.c + n0 + wn * WN, dst + BN * 4);
-    };
-    auto tile_coords = [&](int tile, int& tm, int& tn) {
-        if (p.patch_pn > 0) {
-            const int pn = p.patch_pn, pm = 32 / pn, xn = p.patch_xn, xm = 8 / xn;
-            const int round = tile >> 8, b = tile & 255;
-            const int xcd = b & 7, slot = b >> 3;
-            const int sbn = p.tiles_n / (xn * pn);
-            const int sb_m = round / sbn, sb_n = round - sb_m * sbn;
-            tm = (sb_m * xm + xcd / xn) * pm + slot / pn;
-            tn = (sb_n * xn + xcd % xn) * pn + slot % pn;
-        } else {
-            tm = tile / p.tiles_n;
-            tn = tile - tm * p.tiles_n;
-        }
-    };
+    PCD_GEMM_STAGE_BIAS(lds_b + par * (2 * BN * 4) + wn * WN * 4);
+    auto tile_coords = [&](int tile, int& tm, int& tn) { patch_tile_coords(p, p.patch_pn > 0, tile, tm, tn); };
     // this wave's weight fragments of K tile kt of column tile tn: 8 KB at wfrag + ((tn * nk + kt) * 4 + wn) * 4096 halfs: [ks][j][lane][8]
     auto wbase = [&](int tn_, int kt) __attribute__((always_inline)) {
         return wfrag + ((int64_t)(tn_ * nk + kt) * 4 + wn) * 4096 + lane * 8;
@@ -789,21 +778,7 @@ __global__ __launch_bounds__(512) void gemm_xw_kernel(GemmParams p, const half_t
             ++it;
         }
         {
-            unsigned* cm = reinterpret_cast<unsigned*>(p.colmax);
-            const int shape = (m0 + wm * WM) / p.cm_rps, colq = lane & 15;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int cl = wn * WN + j * 16 + colq;
-                const float b = bias_lds[par][0][cl] + bias_lds[par][1][cl];
-                float mx = 0.f;
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r] + b);
-                mx = fmaxf(mx, __shfl_xor(mx, 16));
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                if (q == 0) atomicMax(cm + (int64_t)shape * p.c + n0 + cl, __float_as_uint(mx));
-            }
+            PCD_GEMM_COLMAX_FROM_LDS_BIAS();
         }
         if (!has_next) break;
         behind_atomics = true;
@@ -841,11 +816,6 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void gstore16_s(unsigned voff, u32x4_t data, const half_t* sbase) {
     // (s_nop: a VALU write of the data registers needs one wait state behind a > 8-byte store; the compiler does not look into the asm)
     asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 0" ::"v"(voff), "v"(data), "s"(sbase) : "memory");
-}
-
-__device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
-    const uint64_t v = (uint64_t)q;
-    return (const half_t*)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v));
 }
 
 template <int R, bool ABL = false, bool MID = false, bool SPLIT = true>
@@ -890,24 +860,9 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
         for (int r = 0; r < NPIECE; ++r) glds16_s(voa, ab + (int64_t)(r * RSTEP) * lda, la + r * RSTEP * ROWB);
     };
     const unsigned lds_b = (unsigned)(size_t)&bias_lds[0][0][0] + wn * WN * 4;
-    auto stage_bias = [&](int m0, int n0, int par) __attribute__((always_inline)) {
-        const unsigned dst = lds_b + par * (2 * BN * 4);
-        glds4_s((unsigned)(lane * 4), p.bias + n0 + wn * WN, dst);
-        glds4_s((unsigned)(lane * 4), p.shape_bias + (int64_t)(m0 / p.rows_per_shape) * p.c + n0 + wn * WN, dst + BN * 4);
-    };
+    PCD_GEMM_STAGE_BIAS(lds_b + par * (2 * BN * 4));
     auto tile_coords = [&](int tile, int& tm, int& tn) {
-        if (p.patch_pn > 0) {
-            const int pn = p.patch_pn, pm = 32 / pn, xn = p.patch_xn, xm = 8 / xn;
-            const int round = tile >> 8, b = tile & 255;
-            const int xcd = b & 7, slot = b >> 3;
-            const int sbn = p.tiles_n / (xn * pn);
-            const int sb_m = round / sbn, sb_n = round - sb_m * sbn;
-            tm = (sb_m * xm + xcd / xn) * pm + slot / pn;
-            tn = (sb_n * xn + xcd % xn) * pn + slot % pn;
-        } else {
-            tm = tile / p.tiles_n;
-            tn = tile - tm * p.tiles_n;
-        }
+        patch_tile_coords(p, p.patch_pn > 0, tile, tm, tn);
         // (wave-uniform by construction; say so -- the divergence analysis loses it through the tile walk and would keep every tile-derived base in VGPRs)
         tm = __builtin_amdgcn_readfirstlane(tm);
         tn = __builtin_amdgcn_readfirstlane(tn);
@@ -1066,13 +1021,7 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
                         const f32x4 v = acc[i][j + t] + bv[j + t];
-                        half2_ lo2, hi2;
-                        lo2[0] = (half_t)__builtin_amdgcn_fmed3f(v[0], lo, 65504.f);
-                        lo2[1] = (half_t)__builtin_amdgcn_fmed3f(v[1], lo, 65504.f);
-                        hi2[0] = (half_t)__builtin_amdgcn_fmed3f(v[2], lo, 65504.f);
-                        hi2[1] = (half_t)__builtin_amdgcn_fmed3f(v[3], lo, 65504.f);
-                        pk[t][0] = __builtin_bit_cast(unsigned, lo2);
-                        pk[t][1] = __builtin_bit_cast(unsigned, hi2);
+                        PCD_GEMM_CLAMP_PACK(v, lo, pk[t]);
                     }
                     const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
@@ -1114,13 +1063,23 @@ __global__ __launch_bounds__(256) void gemm_pack_wfrag_kernel(const half_t* __re
     *(half8*)(out + idx * 8) = *(const half8*)(w + (int64_t)col * ldw + kt * 64 + ks * 32 + (lane >> 4) * 8);
 }
 
-static int g_split = 1;         // pcd_gemm_set_config(14) / (15): the fragment-order kernels' LDS-DMA pieces requested by every wave / by one wave per SIMD (default)
-static int g_xs_mid = 0;        // pcd_gemm_set_config(12) / (13): gemm_xs_kernel / gemm_xw_kernel request the next K tile's activation pieces at the top of a K tile / behind k step 0's MFMAs
+// ------------------------------------------------------------------------------------------------------------------------------ host side
+// Every entry point is: fill (the descriptor's checks), its own argument checks, plan_gemm (which kernel, which instance, which grid -- no device is
+// touched), launch_plan (the zero row, the kernel arguments the plan decides, the one switch with the launches).
+
+// The process's GEMM configuration: pcd_gemm_set_config decodes one code into one field (include/pcd_hip.h tabulates the codes).
+struct GemmConfig {
+    int tile = -1;             // generic tile 0 .. 4 forced for every launch; -1 = the shape heuristic
+    int xp_depth = 1;          // gemm_xp_kernel (cross-tile prefetching store kernel): 0 off, else K tiles of the next tile requested ahead (2: store epilogue only)
+    int xw = 1;                // callers that hold a fragment-order weight copy use gemm_xw_kernel (they ask pcd_gemm_wfrag_enabled)
+    int xs = 1;                // pcd_gemm_f16_wfrag uses gemm_xs_kernel (output dripped through LDS)
+    int request_pos = 0;       // gemm_xw / gemm_xs request the next K tile's activation pieces 0 at the top of a K tile, 1 behind k step 0's MFMAs; 2 (diagnostic):
+                               // gemm_xw reloads k step 0's weights late -- gemm_xs has no such form and runs its instance of 1
+    int split_requests = 1;    // those LDS-DMA pieces are requested 1 by one wave per SIMD, 0 by every wave
+    int xs_ablation = 0;       // timing ablations of gemm_xs_kernel (bits, see the kernel); outputs are wrong while set
+};
+static GemmConfig g_cfg;
 static void* g_wfrag_stamps = nullptr;
-static int g_xw = 1;            // tuning hook (pcd_gemm_set_config(8) / (9)): callers that hold a fragment-order weight copy use gemm_xw_kernel: off / on
-static int g_xs_abl = 0;        // timing ablations of gemm_xs_kernel (pcd_gemm_set_config(16 + bits)): see the kernel; outputs are wrong while set
-static int g_xs = 1;            // tuning hook (pcd_gemm_set_config(10) / (11)): pcd_gemm_f16_wfrag uses gemm_xs_kernel (output dripped through LDS): off / on
-static int g_xp = 1;            // tuning hook (pcd_gemm_set_config(5) / (6) / (7)): the cross-tile prefetching store kernel off / 2 K tiles ahead / 1
 
 static int num_cus() {
     static int n = 0;
@@ -1153,78 +1112,124 @@ static float* zero_row(int cols, hipStream_t s) {
     return zeros_of[dev];
 }
 
-template <int BM, int BN, int WGM, int WGN, int STAGES, int EPI, int BKT = 64>
-static int launch(const GemmParams& p0, hipStream_t s, int blocks_per_cu) {
-    GemmParams p = p0;
-    p.tiles_m = (int)ceil_div(p.m, BM);
-    p.tiles_n = (int)ceil_div(p.c, BN);
-    if (p.splits < 1) p.splits = 1;
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * p.splits;
+// The kernels by plan index.  Generic tiles (LDS per block: 48, 64, 144, 128, 96 KB).  256x256, 8 waves (2x4, 128x64 per wave): half the L2->LDS bytes per
+// FLOP of the 128x128 tile.  Measured and rejected: K tile 32 with 256x128 / 128x256 tiles (48 KB LDS, two blocks per CU, so one block's store tail hides
+// behind the other's MFMAs): 733-753 TFLOP/s on the dominant GEMM vs 1195-1260 for the 256x256 tile, and slower on every mid-size layer
+// (profiles/r01_c_gemm_tile_sweep.txt).
+struct TileShape { int bm, bn, threads, blocks_per_cu; };
+constexpr TileShape kTile[5] = {{128, 64, 256, 3}, {128, 128, 256, 2}, {256, 128, 512, 1}, {256, 256, 512, 1}, {128, 128, 256, 1}};
+using TileKernel = void (*)(GemmParams);
+using FragKernel = void (*)(GemmParams, const half_t*);
+#define PCD_TILE_ROW(EPI) {gemm_f16_kernel<128, 64, 2, 2, 2, EPI>, gemm_f16_kernel<128, 128, 2, 2, 2, EPI>, gemm_f16_kernel<256, 128, 4, 2, 3, EPI>, \
+                           gemm_f16_kernel<256, 256, 2, 4, 2, EPI>, gemm_f16_kernel<128, 128, 2, 2, 3, EPI>}
+constexpr TileKernel kTileKernel[4][5] = {PCD_TILE_ROW(EPI_F16), PCD_TILE_ROW(EPI_F32), PCD_TILE_ROW(EPI_COLMAX), PCD_TILE_ROW(EPI_RESID)};
+#undef PCD_TILE_ROW
+constexpr TileKernel kXpKernel[4] = {gemm_xp_kernel<EPI_F16>, nullptr, gemm_xp_kernel<EPI_COLMAX>, gemm_xp_kernel<EPI_RESID>};
+// variant 0 default, 1 every wave requests, 2 requests behind k step 0; 3: gemm_xw late weights, gemm_xs ablations
+constexpr FragKernel kXwKernel[4] = {gemm_xw_kernel<false, true>, gemm_xw_kernel<false, false>, gemm_xw_kernel<true, false>, gemm_xw_kernel<false, true, true>};
+#define PCD_XS_ROW(R) gemm_xs_kernel<R, false>, gemm_xs_kernel<R, false, false, false>, gemm_xs_kernel<R, false, true, false>, gemm_xs_kernel<R, true, false, false>
+constexpr FragKernel kXsKernel[8] = {PCD_XS_ROW(1), PCD_XS_ROW(2)};       // [4 * (R - 1) + variant]
+#undef PCD_XS_ROW
+
+typedef pcd_gemm_plan_t GemmPlan;
+enum { NO_ZERO_GENERIC = 0, NO_ZERO_DISPATCH = 1, NO_ZERO_ERROR = 2 };     // GemmPlan::no_zero_row
+
+// Does a 256 x 256 kernel family take the problem?  Common to the three: whole tiles, one pass over K (no hi / lo weights, no split-K), one A layout, a
+// per-shape bias only if a tile lies in one shape, column-max shapes of whole 128-row wave tiles.  What differs:
+//
+//                                  gemm_xp_kernel        gemm_xw_kernel               gemm_xs_kernel
+//   reached from                   tile 3 of any entry   pcd_gemm_f16_colmax_wfrag    pcd_gemm_f16_wfrag
+//   smallest number of K tiles     2                     2                            6
+//   a multiple of 256 tiles (>= 1) no                    yes                          yes
+//   256 CUs                        no                    no (grid fixed at 256)       yes
+//   32-bit byte offsets checked    A rows, W rows        none                         A rows, output rows
+//   bias / per-shape bias          any (zero row)        bias required, no per-shape  any (zero row)
+//   switched by the config         xp_depth              (the caller asks xw)         xs
+struct Tile256Rule { int min_nk; bool whole_rounds, cus_256, range_a, range_w, range_out; };
+constexpr Tile256Rule kXpRule = {2, false, false, true, true, false}, kXwRule = {2, true, false, false, false, false}, kXsRule = {6, true, true, true, false, true};
+
+static bool tile256_ok(const GemmParams& p, int epi, const Tile256Rule& r) {
+    const int64_t tiles = (int64_t)(p.m / 256) * (p.c / 256);
+    return p.m % 256 == 0 && p.c % 256 == 0 && p.krep != 2 && p.splits <= 1 && (p.k1 + p.k2) / BK >= r.min_nk && (p.k2 == 0 || p.lda2 == p.lda1) &&
+           (p.shape_bias == nullptr || p.rows_per_shape % 256 == 0) && (epi != EPI_COLMAX || p.cm_rps % 128 == 0) &&
+           (!r.whole_rounds || (tiles >= 256 && tiles % 256 == 0)) && (!r.cus_256 || num_cus() == 256) &&
+           (!r.range_a || (int64_t)255 * p.lda1 * 2 + 128 < 0x7fffffffLL) && (!r.range_w || (int64_t)255 * p.ldw * 2 + 128 < 0x7fffffffLL) &&
+           (!r.range_out || ((int64_t)255 * p.ldo + 256) * 2 < 0x7fffffffLL);
+}
+static bool xw_ok(const GemmParams& p) { return p.bias != nullptr && p.shape_bias == nullptr && tile256_ok(p, EPI_COLMAX, kXwRule); }
+
+// What `entry` launches for the filled p (its borrowed and launch fields still unset): reads p, the configuration and the CU count, nothing else.
+// zero_row = false: the plan for a process that cannot have the zero row (launch_plan asks when it finds that out).
+static int plan_gemm(const GemmParams& p, int epi, int entry, bool has_wfrag, GemmPlan& pl, bool zero_row = true) {
+    const GemmConfig& g = g_cfg;
+    const int nk = (p.k1 + p.k2) / BK, splits = p.splits < 1 ? 1 : p.splits;
+    const int variant = g.request_pos ? 2 : (g.split_requests ? 0 : 1);
+    const bool zeros_ok = zero_row || (p.bias != nullptr && p.shape_bias != nullptr);       // no kernel that would need the missing zero row
+    pl = GemmPlan{};
+    if (entry == PCD_GEMM_ENTRY_COLMAX_WFRAG) {
+        if (!has_wfrag || !xw_ok(p)) {
+            set_error("pcd_gemm_f16_colmax_wfrag: bad argument: no fragment-order copy, or not a shape of gemm_xw_kernel (whole 256 x 256 tiles, a multiple of 256 "
+                      "of them, 2 or more K tiles, one A layout, rows_per_shape %% 128 == 0, a bias and no per-shape bias)");
+            return PCD_ERR_ARG;
+        }
+        pl.family = PCD_GEMM_FAMILY_XW;
+        pl.instance = g.request_pos == 2 ? 3 : variant;
+        pl.zero_shape_bias = 1; pl.no_zero_row = NO_ZERO_ERROR;       // (the kernel stages a fixed number of bias pieces per tile)
+    } else if (entry == PCD_GEMM_ENTRY_WFRAG && has_wfrag && g.xs && zeros_ok && tile256_ok(p, epi, kXsRule)) {
+        pl.family = PCD_GEMM_FAMILY_XS;
+        pl.instance = (nk >= 12 ? 0 : 4) + (g.xs_ablation ? 3 : variant);
+        pl.xs_ablation = g.xs_ablation; pl.no_zero_row = NO_ZERO_DISPATCH;
+    } else {
+        // narrow outputs (C <= 64): 128x64 tile so no MFMA work is spent on masked columns.  Large problems: the 256x256 tile, measured 1223 vs 1074 TFLOP/s
+        // on 131072x2048x4096 and faster for every layer with K, C >= 256 (tools/bench_gemm.py, profiles/r01_c_gemm_tile_sweep.txt).
+        pl.family = g.tile >= 0 ? g.tile : (p.c <= 64 ? 0 : ((p.m >= 16384 && p.c >= 256 && (p.k1 + p.k2) >= 256) ? 3 : 1));
+        // the variant that refills both LDS stages for the next tile before the epilogue's stores
+        if (pl.family == 3 && epi != EPI_F32 && g.xp_depth && zeros_ok && tile256_ok(p, epi, kXpRule)) {
+            pl.family = PCD_GEMM_FAMILY_XP;
+            pl.xp_depth = epi == EPI_F16 ? g.xp_depth : 1; pl.no_zero_row = NO_ZERO_GENERIC;
+        }
+    }
+    const bool generic = pl.family < PCD_GEMM_FAMILY_XP;
+    if (!generic && pl.family != PCD_GEMM_FAMILY_XW) { pl.zero_bias = p.bias == nullptr; pl.zero_shape_bias = p.shape_bias == nullptr; }
+    const TileShape& t = kTile[generic ? pl.family : 3];
+    pl.tiles_m = (int)ceil_div(p.m, t.bm); pl.tiles_n = (int)ceil_div(p.c, t.bn);
+    const int64_t tiles = (int64_t)pl.tiles_m * pl.tiles_n * splits;
     if (tiles <= 0 || tiles > 0x7fffffff) { set_error("gemm: grid out of range"); return PCD_ERR_ARG; }
-    // persistent grid: as many blocks as are resident at once, each walking tiles b, b + grid, ...
-    const int64_t resident = (int64_t)num_cus() * blocks_per_cu;
-    const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
-    p.patch_pn = p.patch_xn = 0;
-    if (grid == 256 && tiles % 256 == 0 && p.splits == 1) {
-        const int pn = p.tiles_n >= 8 ? 8 : p.tiles_n;               // 8, 4, 2 or 1 column tiles per patch
-        const int xn = p.tiles_n >= 16 ? 2 : 1;
-        if ((pn & (pn - 1)) == 0 && p.tiles_n % (xn * pn) == 0 && p.tiles_m % ((8 / xn) * (32 / pn)) == 0) {
-            p.patch_pn = pn; p.patch_xn = xn;
-        }
+    // persistent grid: as many blocks as are resident at once, each walking tiles b, b + grid, ... (the fragment-order kernels: 256, whole rounds)
+    const int64_t resident = pl.family >= PCD_GEMM_FAMILY_XW ? 256 : (int64_t)num_cus() * t.blocks_per_cu;
+    pl.grid = (unsigned)(tiles < resident ? tiles : resident); pl.block = (unsigned)t.threads;
+    if (pl.grid == 256 && tiles % 256 == 0 && splits == 1) {          // the XCD patch map (patch_tile_coords)
+        const int pn = pl.tiles_n >= 8 ? 8 : pl.tiles_n, xn = pl.tiles_n >= 16 ? 2 : 1;             // 8, 4, 2 or 1 column tiles per patch; XCDs per patch row
+        if ((pn & (pn - 1)) == 0 && pl.tiles_n % (xn * pn) == 0 && pl.tiles_m % ((8 / xn) * (32 / pn)) == 0) { pl.patch_pn = pn; pl.patch_xn = xn; }
     }
-    if constexpr (BM == 256 && BN == 256 && (EPI == EPI_F16 || EPI == EPI_COLMAX || EPI == EPI_RESID) && STAGES == 2 && BKT == 64) {
-        // whole tiles, one A layout, per-shape bias only if a tile lies in one shape: the variant that refills both LDS stages for
-        // the next tile before the epilogue's stores (gemm_xp_kernel)
-        const bool ok = g_xp && p.krep != 2 && p.m % 256 == 0 && p.c % 256 == 0 && p.splits == 1 && (p.k1 + p.k2) >= 128 &&
-                        (p.k2 == 0 || p.lda2 == p.lda1) && (p.shape_bias == nullptr || p.rows_per_shape % 256 == 0) &&
-                        (EPI != EPI_COLMAX || p.cm_rps % 128 == 0) &&
-                        (int64_t)255 * p.lda1 * 2 + 128 < 0x7fffffffLL && (int64_t)255 * p.ldw * 2 + 128 < 0x7fffffffLL;
-        if (ok && (p.bias == nullptr || p.shape_bias == nullptr)) {
-            // a zero row stands in for a missing bias (fixed number of LDS-DMA pieces per tile: the waits are counted)
-            float* zeros = zero_row(p.c, s);
-            if (zeros != nullptr) {
-                if (p.bias == nullptr) p.bias = zeros;
-                if (p.shape_bias == nullptr) { p.shape_bias = zeros; p.rows_per_shape = p.m; }       // shape 0 for every tile
-            }
-        }
-        if (ok && p.bias != nullptr && p.shape_bias != nullptr) {
-            p.xp_depth = EPI == EPI_F16 ? g_xp : 1;
-            hipLaunchKernelGGL(gemm_xp_kernel<EPI>, dim3(grid), dim3(512), 0, s, p);
-            PCD_CHECK_LAUNCH();
-            return PCD_OK;
-        }
-    }
-    hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, WGM, WGN, STAGES, EPI, BKT>), dim3(grid), dim3(64 * WGM * WGN), 0, s, p);
-    PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
 
-static int g_force_cfg = -1;   // tuning hook (pcd_gemm_set_config): -1 = heuristic
-
-template <int EPI>
-static int dispatch(const GemmParams& p, hipStream_t s) {
-    int cfg = g_force_cfg;
-    if (cfg < 0) {
-        // narrow outputs (C <= 64): 128x64 tile so no MFMA work is spent on masked columns.
-        // large problems: 256x256 tile, 8 waves (2x4, 128x64 per wave): half the L2->LDS bytes per FLOP
-        // of the 128x128 tile; measured 1223 vs 1074 TFLOP/s on 131072x2048x4096 and faster for every
-        // layer with K, C >= 256 (tools/bench_gemm.py, profiles/r01_c_gemm_tile_sweep.txt).
-        if (p.c <= 64) cfg = 0;
-        else if (p.m >= 16384 && p.c >= 256 && (p.k1 + p.k2) >= 256) cfg = 3;
-        else cfg = 1;
+static int launch_plan(const GemmPlan& pl, int epi, GemmParams p, const half_t* wfrag, hipStream_t s) {
+    int rc;
+    if (pl.zero_bias || pl.zero_shape_bias) {
+        // a zero row stands in for a missing bias (fixed number of LDS-DMA pieces per tile: the waits are counted)
+        float* zeros = zero_row(p.c, s);
+        if (zeros == nullptr) {
+            if (pl.no_zero_row == NO_ZERO_ERROR) { set_error("pcd_gemm_f16_colmax_wfrag: no zero row (stream capture before the first eager call, or c > 16384)"); return PCD_ERR_ARG; }
+            GemmPlan alt;       // NO_ZERO_GENERIC, NO_ZERO_DISPATCH: pcd_gemm_f16's choice among the kernels that need no zero row -- the generic kernel of its tile
+            PCD_RUN(plan_gemm(p, epi, PCD_GEMM_ENTRY_F16, false, alt, false));
+            return launch_plan(alt, epi, p, nullptr, s);
+        }
+        if (pl.zero_bias) p.bias = zeros;
+        if (pl.zero_shape_bias) { p.shape_bias = zeros; p.rows_per_shape = p.m; }       // shape 0 for every tile
     }
-    GemmParams q = p;
-    switch (cfg) {
-        case 0: return launch<128, 64, 2, 2, 2, EPI>(q, s, 3);      // 48 KB LDS
-        case 1: return launch<128, 128, 2, 2, 2, EPI>(q, s, 2);     // 64 KB LDS
-        case 2: return launch<256, 128, 4, 2, 3, EPI>(q, s, 1);     // 144 KB LDS
-        case 3: return launch<256, 256, 2, 4, 2, EPI>(q, s, 1);     // 128 KB LDS
-        case 4: return launch<128, 128, 2, 2, 3, EPI>(q, s, 1);     // 96 KB LDS
-        // measured and rejected: K tile 32 with 256x128 / 128x256 tiles (48 KB LDS, two blocks per CU, so one
-        // block's store tail hides behind the other's MFMAs): 733-753 TFLOP/s on the dominant GEMM vs 1195-1260
-        // for the 256x256 tile, and slower on every mid-size layer (profiles/r01_c_gemm_tile_sweep.txt).
-        default: set_error("gemm: unknown config %d", cfg); return PCD_ERR_ARG;
+    p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.patch_pn = pl.patch_pn; p.patch_xn = pl.patch_xn;
+    if (p.splits < 1) p.splits = 1;
+    const dim3 grid(pl.grid), block(pl.block);
+    switch (pl.family) {
+        case PCD_GEMM_FAMILY_XP: p.xp_depth = pl.xp_depth; hipLaunchKernelGGL(kXpKernel[epi], grid, block, 0, s, p); break;
+        case PCD_GEMM_FAMILY_XW: p.out32 = (float*)g_wfrag_stamps; hipLaunchKernelGGL(kXwKernel[pl.instance], grid, block, 0, s, p, wfrag); break;
+        case PCD_GEMM_FAMILY_XS: p.xp_depth = pl.xs_ablation; hipLaunchKernelGGL(kXsKernel[pl.instance], grid, block, 0, s, p, wfrag); break;
+        default: hipLaunchKernelGGL(kTileKernel[epi][pl.family], grid, block, 0, s, p);
     }
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
 }
 
 static int fill(const pcd_gemm_desc_t* d, GemmParams& p) {
@@ -1249,49 +1254,84 @@ static int fill(const pcd_gemm_desc_t* d, GemmParams& p) {
     return PCD_OK;
 }
 
+// does global_feat.3 (or any column-max product) go to pcd_gemm_f16_colmax_wfrag?  Otherwise the caller takes pcd_gemm_f16_colmax.
+bool gemm_colmax_takes_wfrag(const pcd_gemm_desc_t* d, int rows_per_shape, const void* wfrag) {
+    GemmParams p;
+    if (wfrag == nullptr || !g_cfg.xw || fill(d, p) != PCD_OK) return false;
+    p.cm_rps = rows_per_shape;
+    return xw_ok(p);
+}
+
+// What an entry point takes besides the descriptor; `out` is its output of whatever type (fp16 rows, fp32 rows, slabs, column maxima).
+struct GemmArgs { void* out; int64_t ldo; const void* wfrag; int rows_per_shape; int splits; const void* resid; int64_t ldr; };
+
+// Every entry point: fill, its own argument checks and fields, plan_gemm, launch_plan -- or, for pcd_gemm_plan, the plan handed back and nothing launched.
+static int gemm_entry(const pcd_gemm_desc_t* d, int entry, const GemmArgs& a, void* stream, GemmPlan* plan_only = nullptr) {
+    GemmParams p; GemmPlan pl; int rc, epi = EPI_F16;
+    // (the checks keep the entry points' argument names: their text is the error message)
+    void* const out = a.out; const int64_t ldo = a.ldo, ldr = a.ldr; const void* const resid = a.resid; const int splits = a.splits, rows_per_shape = a.rows_per_shape;
+    PCD_RUN(fill(d, p));
+    p.ldo = ldo;
+    switch (entry) {
+        case PCD_GEMM_ENTRY_F16: case PCD_GEMM_ENTRY_HILO: case PCD_GEMM_ENTRY_WFRAG:
+            PCD_CHECK_ARG(out != nullptr && ldo >= d->c && ldo % 8 == 0 && d->c % 8 == 0);
+            if (entry == PCD_GEMM_ENTRY_HILO) { PCD_CHECK_ARG(d->ldw >= 2 * (int64_t)(d->k1 + d->k2)); p.krep = 2; }
+            p.out16 = (half_t*)out;
+            break;
+        case PCD_GEMM_ENTRY_OUT32:
+            PCD_CHECK_ARG(out != nullptr && ldo >= d->c);
+            p.out32 = (float*)out; epi = EPI_F32;
+            break;
+        case PCD_GEMM_ENTRY_SPLITK:      // slabs[s][m][c] = A[:, s*K/S : (s+1)*K/S] W[:, same]^T ; pcd_sum_slabs_f32 adds them in a fixed order
+            PCD_CHECK_ARG(out != nullptr && splits >= 1 && d->k2 == 0 && d->bias == nullptr && d->shape_bias == nullptr && d->relu == 0);
+            PCD_CHECK_ARG(d->k1 % splits == 0 && (d->k1 / splits) % BK == 0);
+            p.k1 = d->k1 / splits; p.splits = splits;
+            p.out32 = (float*)out; p.ldo = d->c; p.split_out = (int64_t)d->m * d->c; epi = EPI_F32;
+            break;
+        case PCD_GEMM_ENTRY_RESIDUAL:
+            PCD_CHECK_ARG(out != nullptr && resid != nullptr);
+            PCD_CHECK_ARG(ldo >= d->c && ldo % 8 == 0 && ldr >= d->c && ldr % 8 == 0 && d->c % 8 == 0);
+            p.out16 = (half_t*)out; p.resid = (const half_t*)resid; p.ldr = ldr; epi = EPI_RESID;
+            break;
+        case PCD_GEMM_ENTRY_COLMAX: case PCD_GEMM_ENTRY_COLMAX_WFRAG:     // (with a fragment-order copy: gemm_xw_kernel or PCD_ERR_ARG, see plan_gemm)
+            PCD_CHECK_ARG(out != nullptr && rows_per_shape > 0 && d->relu == 1);
+            p.colmax = (float*)out; p.cm_rps = rows_per_shape; epi = EPI_COLMAX;
+            break;
+        default: set_error("gemm: unknown entry point %d", entry); return PCD_ERR_ARG;
+    }
+    PCD_RUN(plan_gemm(p, epi, entry, a.wfrag != nullptr, pl));
+    if (plan_only != nullptr) { *plan_only = pl; return PCD_OK; }
+    return launch_plan(pl, epi, p, (const half_t*)a.wfrag, (hipStream_t)stream);
+}
+
 }  // namespace pcd
 
 using namespace pcd;
 
-extern "C" int pcd_gemm_f16(const pcd_gemm_desc_t* d, void* out, int64_t ldo, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(out != nullptr && ldo >= d->c && ldo % 8 == 0 && d->c % 8 == 0);
-    p.out16 = (half_t*)out; p.ldo = ldo;
-    return dispatch<EPI_F16>(p, (hipStream_t)stream);
-}
-
-extern "C" int pcd_gemm_f16_hilo(const pcd_gemm_desc_t* d, void* out, int64_t ldo, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(out != nullptr && ldo >= d->c && ldo % 8 == 0 && d->c % 8 == 0);
-    PCD_CHECK_ARG(d->ldw >= 2 * (int64_t)(d->k1 + d->k2));
-    p.out16 = (half_t*)out; p.ldo = ldo; p.krep = 2;
-    return dispatch<EPI_F16>(p, (hipStream_t)stream);
-}
-
-extern "C" int pcd_gemm_f16_out32(const pcd_gemm_desc_t* d, float* out, int64_t ldo, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(out != nullptr && ldo >= d->c);
-    p.out32 = out; p.ldo = ldo;
-    return dispatch<EPI_F32>(p, (hipStream_t)stream);
-}
-
-// split-K: slabs[s][m][c] = A[:, s*K/S : (s+1)*K/S] W[:, same]^T ; pcd_sum_slabs_f32 adds them in a fixed order
+extern "C" int pcd_gemm_f16(const pcd_gemm_desc_t* d, void* out, int64_t ldo, void* stream) { return gemm_entry(d, PCD_GEMM_ENTRY_F16, {out, ldo}, stream); }
+extern "C" int pcd_gemm_f16_hilo(const pcd_gemm_desc_t* d, void* out, int64_t ldo, void* stream) { return gemm_entry(d, PCD_GEMM_ENTRY_HILO, {out, ldo}, stream); }
+extern "C" int pcd_gemm_f16_out32(const pcd_gemm_desc_t* d, float* out, int64_t ldo, void* stream) { return gemm_entry(d, PCD_GEMM_ENTRY_OUT32, {out, ldo}, stream); }
 extern "C" int pcd_gemm_f16_splitk(const pcd_gemm_desc_t* d, int splits, float* slabs, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(slabs != nullptr && splits >= 1 && d->k2 == 0 && d->bias == nullptr && d->shape_bias == nullptr && d->relu == 0);
-    PCD_CHECK_ARG(d->k1 % splits == 0 && (d->k1 / splits) % BK == 0);
-    p.k1 = d->k1 / splits;
-    p.splits = splits;
-    p.out32 = slabs; p.ldo = d->c; p.split_out = (int64_t)d->m * d->c;
-    return dispatch<EPI_F32>(p, (hipStream_t)stream);
+    return gemm_entry(d, PCD_GEMM_ENTRY_SPLITK, {slabs, 0, nullptr, 0, splits}, stream);
+}
+extern "C" int pcd_gemm_f16_residual(const pcd_gemm_desc_t* d, const void* resid, int64_t ldr, void* out, int64_t ldo, void* stream) {
+    return gemm_entry(d, PCD_GEMM_ENTRY_RESIDUAL, {out, ldo, nullptr, 0, 0, resid, ldr}, stream);
+}
+extern "C" int pcd_gemm_f16_colmax(const pcd_gemm_desc_t* d, float* colmax, int rows_per_shape, void* stream) {
+    return gemm_entry(d, PCD_GEMM_ENTRY_COLMAX, {colmax, 0, nullptr, rows_per_shape}, stream);
+}
+extern "C" int pcd_gemm_f16_colmax_wfrag(const pcd_gemm_desc_t* d, const void* wfrag, float* colmax, int rows_per_shape, void* stream) {
+    return gemm_entry(d, PCD_GEMM_ENTRY_COLMAX_WFRAG, {colmax, 0, wfrag, rows_per_shape}, stream);
+}
+// (wfrag = pcd_gemm_pack_wfrag of the SAME weights as d->w): gemm_xs_kernel where its launch shape holds (whole 256 x 256 tiles, a multiple of 256 of them, 6 or
+// more K tiles, one A layout), pcd_gemm_f16's choice otherwise -- same bits either way
+extern "C" int pcd_gemm_f16_wfrag(const pcd_gemm_desc_t* d, const void* wfrag, void* out, int64_t ldo, void* stream) {
+    return gemm_entry(d, PCD_GEMM_ENTRY_WFRAG, {out, ldo, wfrag}, stream);
+}
+// tests and tools: the plan of an entry point with dense output rows; the addresses handed in are compared with null and never used
+extern "C" int pcd_gemm_plan(const pcd_gemm_desc_t* d, int entry, int rows_per_shape, int splits, int has_wfrag, pcd_gemm_plan_t* plan) {
+    PCD_CHECK_ARG(d != nullptr && plan != nullptr);
+    return gemm_entry(d, entry, {plan, d->c, has_wfrag ? plan : nullptr, rows_per_shape, splits, plan, d->c}, nullptr, plan);
 }
 
 namespace pcd {
@@ -1314,27 +1354,6 @@ extern "C" int pcd_sum_slabs_f32(const float* slabs, int nslabs, int64_t rows, i
     return PCD_OK;
 }
 
-extern "C" int pcd_gemm_f16_residual(const pcd_gemm_desc_t* d, const void* resid, int64_t ldr,
-                                     void* out, int64_t ldo, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(out != nullptr && resid != nullptr);
-    PCD_CHECK_ARG(ldo >= d->c && ldo % 8 == 0 && ldr >= d->c && ldr % 8 == 0 && d->c % 8 == 0);
-    p.out16 = (half_t*)out; p.ldo = ldo; p.resid = (const half_t*)resid; p.ldr = ldr;
-    return dispatch<EPI_RESID>(p, (hipStream_t)stream);
-}
-
-extern "C" int pcd_gemm_f16_colmax(const pcd_gemm_desc_t* d, float* colmax, int rows_per_shape, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(colmax != nullptr && rows_per_shape > 0 && d->relu == 1);
-    p.colmax = colmax; p.cm_rps = rows_per_shape;
-    return dispatch<EPI_COLMAX>(p, (hipStream_t)stream);
-}
-
-
 extern "C" int pcd_gemm_pack_wfrag(const void* w, int64_t ldw, int k, int c, void* wfrag, void* stream) {
     PCD_CHECK_ARG(w && wfrag && k > 0 && k % 64 == 0 && c > 0 && c % 256 == 0 && ldw >= k && ldw % 8 == 0);
     const int64_t total = (int64_t)(c / 256) * (k / 64) * 4 * 2 * 4 * 64;
@@ -1344,89 +1363,21 @@ extern "C" int pcd_gemm_pack_wfrag(const void* w, int64_t ldw, int k, int c, voi
     return PCD_OK;
 }
 
-extern "C" int pcd_gemm_f16_colmax_wfrag(const pcd_gemm_desc_t* d, const void* wfrag, float* colmax, int rows_per_shape, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(wfrag != nullptr && colmax != nullptr && rows_per_shape > 0 && d->relu == 1);
-    PCD_CHECK_ARG(p.m % 256 == 0 && p.c % 256 == 0 && (p.k1 + p.k2) >= 128 && (p.k2 == 0 || p.lda2 == p.lda1) && rows_per_shape % 128 == 0 &&
-                  p.bias != nullptr && (p.shape_bias == nullptr || p.rows_per_shape % 256 == 0));
-    p.colmax = colmax; p.cm_rps = rows_per_shape;
-    p.tiles_m = p.m / 256; p.tiles_n = p.c / 256;
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
-    PCD_CHECK_ARG(tiles >= 256 && tiles % 256 == 0 && p.shape_bias == nullptr);
-    float* zeros = zero_row(p.c, (hipStream_t)stream);
-    if (zeros == nullptr) { set_error("pcd_gemm_f16_colmax_wfrag: no zero row (stream capture before the first eager call, or c > 16384)"); return PCD_ERR_ARG; }
-    p.shape_bias = zeros; p.rows_per_shape = p.m;
-    p.patch_pn = p.patch_xn = 0;
-    const int pn = p.tiles_n >= 8 ? 8 : p.tiles_n, xn = p.tiles_n >= 16 ? 2 : 1;
-    if ((pn & (pn - 1)) == 0 && p.tiles_n % (xn * pn) == 0 && p.tiles_m % ((8 / xn) * (32 / pn)) == 0) { p.patch_pn = pn; p.patch_xn = xn; }
-    p.out32 = (float*)g_wfrag_stamps;
-    if (g_xs_mid == 2) hipLaunchKernelGGL((gemm_xw_kernel<false, true, true>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    else if (g_xs_mid) hipLaunchKernelGGL((gemm_xw_kernel<true, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    else if (g_split) hipLaunchKernelGGL((gemm_xw_kernel<false, true>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    else hipLaunchKernelGGL((gemm_xw_kernel<false, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    PCD_CHECK_LAUNCH();
-    return PCD_OK;
-}
-
-// Store GEMM with a fragment-order weight copy (pcd_gemm_pack_wfrag of the SAME weights as d->w): gemm_xs_kernel where its launch shape holds
-// (whole 256 x 256 tiles, a multiple of 256 of them, 6 or more K tiles, one A layout), pcd_gemm_f16's dispatch otherwise -- same bits either way.
-extern "C" int pcd_gemm_f16_wfrag(const pcd_gemm_desc_t* d, const void* wfrag, void* out, int64_t ldo, void* stream) {
-    GemmParams p;
-    int rc = fill(d, p);
-    if (rc) return rc;
-    PCD_CHECK_ARG(out != nullptr && ldo >= d->c && ldo % 8 == 0 && d->c % 8 == 0);
-    p.out16 = (half_t*)out; p.ldo = ldo;
-    const int nk = (p.k1 + p.k2) / 64;
-    const int64_t tiles = (int64_t)(p.m / 256) * (p.c / 256);
-    bool ok = g_xs && wfrag != nullptr && p.m % 256 == 0 && p.c % 256 == 0 && nk >= 6 && (p.k2 == 0 || p.lda2 == p.lda1) &&
-              (p.shape_bias == nullptr || p.rows_per_shape % 256 == 0) && tiles >= 256 && tiles % 256 == 0 && num_cus() == 256 &&
-              (int64_t)255 * p.lda1 * 2 + 128 < 0x7fffffffLL && ((int64_t)255 * p.ldo + 256) * 2 < 0x7fffffffLL;
-    if (ok && (p.bias == nullptr || p.shape_bias == nullptr)) {
-        float* zeros = zero_row(p.c, (hipStream_t)stream);
-        if (zeros == nullptr) ok = false;
-        else {
-            if (p.bias == nullptr) p.bias = zeros;
-            if (p.shape_bias == nullptr) { p.shape_bias = zeros; p.rows_per_shape = p.m; }
-        }
-    }
-    if (!ok) return dispatch<EPI_F16>(p, (hipStream_t)stream);
-    p.tiles_m = p.m / 256; p.tiles_n = p.c / 256;
-    p.patch_pn = p.patch_xn = 0;
-    const int pn = p.tiles_n >= 8 ? 8 : p.tiles_n, xn = p.tiles_n >= 16 ? 2 : 1;
-    if ((pn & (pn - 1)) == 0 && p.tiles_n % (xn * pn) == 0 && p.tiles_m % ((8 / xn) * (32 / pn)) == 0) { p.patch_pn = pn; p.patch_xn = xn; }
-    p.xp_depth = g_xs_abl;
-    if (g_xs_abl) {
-        if (nk >= 12) hipLaunchKernelGGL((gemm_xs_kernel<1, true, false, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-        else hipLaunchKernelGGL((gemm_xs_kernel<2, true, false, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    } else if (g_xs_mid) {
-        if (nk >= 12) hipLaunchKernelGGL((gemm_xs_kernel<1, false, true, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-        else hipLaunchKernelGGL((gemm_xs_kernel<2, false, true, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    } else if (g_split == 0) {
-        if (nk >= 12) hipLaunchKernelGGL((gemm_xs_kernel<1, false, false, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-        else hipLaunchKernelGGL((gemm_xs_kernel<2, false, false, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    } else if (nk >= 12) hipLaunchKernelGGL((gemm_xs_kernel<1, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    else hipLaunchKernelGGL((gemm_xs_kernel<2, false>), dim3(256), dim3(512), 0, (hipStream_t)stream, p, (const half_t*)wfrag);
-    PCD_CHECK_LAUNCH();
-    return PCD_OK;
-}
-
 // diagnostic: the next pcd_gemm_f16_colmax_wfrag launches write (shader cycles, 100-MHz ticks) of each workgroup's tile walk to stamps[256][2] (u64); NULL = off
 extern "C" int pcd_gemm_wfrag_stamps(void* stamps) { g_wfrag_stamps = stamps; return PCD_OK; }
-extern "C" int pcd_gemm_wfrag_enabled(void) { return g_xw; }
-extern "C" int pcd_gemm_store_wfrag_enabled(void) { return g_xs; }
+extern "C" int pcd_gemm_wfrag_enabled(void) { return g_cfg.xw; }
+extern "C" int pcd_gemm_store_wfrag_enabled(void) { return g_cfg.xs; }
 
 extern "C" int pcd_gemm_set_config(int cfg) {
-    if (cfg == 33) { g_xs_mid = 2; return PCD_OK; }                                 // diagnostic: gemm_xw_kernel reloads k step 0's weights late (see the kernel)
-    PCD_CHECK_ARG(cfg >= -1 && cfg <= 31);
-    if (cfg >= 16) { g_xs_abl = cfg - 16; return PCD_OK; }                          // timing ablations of gemm_xs_kernel (dev tools only)
-    if (cfg == 14 || cfg == 15) { g_split = cfg - 14; return PCD_OK; }              // gemm_xw / gemm_xs: every wave requests 4 activation pieces / one wave per SIMD 8 (default)
-    PCD_CHECK_ARG(cfg <= 13);
-    if (cfg >= 12) { g_xs_mid = cfg - 12; return PCD_OK; }
-    if (cfg >= 10) { g_xs = cfg - 10; return PCD_OK; }                              // A/B switch of gemm_xs_kernel (pcd_gemm_f16_wfrag)
-    if (cfg >= 8) { g_xw = cfg - 8; return PCD_OK; }                                // A/B switch of gemm_xw_kernel (pcd_gemm_wfrag_enabled)
-    if (cfg >= 5) { g_xp = cfg == 5 ? 0 : (cfg == 6 ? 2 : 1); return PCD_OK; }      // A/B switch of gemm_xp_kernel; the tile choice is left as it is
-    g_force_cfg = cfg;
+    GemmConfig& g = g_cfg;
+    PCD_CHECK_ARG((cfg >= -1 && cfg <= 31) || cfg == 33);
+    if (cfg <= 4) g.tile = cfg;
+    else if (cfg <= 7) g.xp_depth = cfg == 5 ? 0 : (cfg == 6 ? 2 : 1);
+    else if (cfg <= 9) g.xw = cfg - 8;
+    else if (cfg <= 11) g.xs = cfg - 10;
+    else if (cfg <= 13) g.request_pos = cfg - 12;
+    else if (cfg <= 15) g.split_requests = cfg - 14;
+    else if (cfg <= 31) g.xs_ablation = cfg - 16;
+    else g.request_pos = 2;
     return PCD_OK;
 }

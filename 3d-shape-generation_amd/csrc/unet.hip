@@ -288,9 +288,8 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
             }
             PCD_CHECK_HIP(hipEventRecord(h->ev0[h->prof_n], s));
         }
-        // whole 256 x 256 tiles, a multiple of 256 of them, shapes of whole 128-row wave tiles: the weights-from-global kernel; else the LDS-staged one
-        const int64_t tiles = (m / 256) * 16;
-        if (h->gf3_frag != nullptr && pcd_gemm_wfrag_enabled() && m % 256 == 0 && tiles >= 256 && tiles % 256 == 0 && n_points % 128 == 0)
+        // the weights-from-global kernel where the GEMM takes it (whole rounds of 256 x 256 tiles, shapes of whole 128-row wave tiles); else the LDS-staged one
+        if (gemm_colmax_takes_wfrag(&g, n_points, h->gf3_frag))
             PCD_RUN(pcd_gemm_f16_colmax_wfrag(&g, h->gf3_frag, pooled, n_points, s));
         else
             PCD_RUN(pcd_gemm_f16_colmax(&g, pooled, n_points, s));

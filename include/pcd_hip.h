@@ -100,15 +100,45 @@ int pcd_gemm_store_wfrag_enabled(void);
 /* diagnostic (dev tools): the following pcd_gemm_f16_colmax_wfrag launches write, per workgroup, (shader-clock cycles, 100-MHz ticks) of its whole tile walk to
  * stamps[256][2] (uint64, device memory); NULL switches it off.  In-kernel clock = cycles / ticks x 100 MHz (MI355X_MICROARCH.md, DVFS item 6). */
 int pcd_gemm_wfrag_stamps(void* stamps);
-/* tuning/benchmark hook: force a tile configuration for every following GEMM launch of this
- * process (-1 = shape heuristic; 0: 128x64, 1: 128x128, 2: 256x128 3-stage, 3: 256x256, 4: 128x128 3-stage).
- * 5 / 7 / 6 leave the tile choice alone and switch the 256x256 store / column-max kernel that requests the next tile's first
- * K tile(s) before the epilogue's stores (whole tiles only): off / one K tile ahead (default) / two (store epilogue only).
- * 8 / 9: pcd_gemm_wfrag_enabled() off / on (default on).  10 / 11: pcd_gemm_store_wfrag_enabled() off / on (default on).
- * 12 / 13: the fragment-order kernels request a K tile's LDS-DMA pieces at its top (default) / behind its first 32 MFMAs (measured: 14 % slower; kept as the
- * experiment that shows the K loop waits on those pieces).  16 + bits: timing ablations of gemm_xs_kernel.
- * TEST / BENCHMARK ONLY: process-global, read by every handle at every launch -- not for use while another thread is launching. */
+/* Which of the GEMM kernels run: one code sets one field of the process's GEMM configuration (csrc/gemm_f16.hip: GemmConfig) and leaves the others.
+ * TEST / BENCHMARK ONLY: process-global, read by every handle at every launch -- not for use while another thread is launching.
+ * PCD_ERR_ARG unless -1 <= code <= 31 or code == 33.
+ *
+ *   code       field            effect
+ *   -1         tile             (default) the shape heuristic picks the generic tile
+ *   0 .. 4     tile             every following launch uses 0: 128x64, 1: 128x128, 2: 256x128 3-stage, 3: 256x256, 4: 128x128 3-stage
+ *   5 / 7 / 6  xp_depth         the 256x256 store / column-max / residual kernel that requests the next tile's first K tile(s) before the epilogue's
+ *                               stores (gemm_xp_kernel, whole tiles only): off / one K tile ahead (default) / two (store epilogue only; the others stay at one)
+ *   8 / 9      xw               pcd_gemm_wfrag_enabled() off / on (default): read by callers that hold a fragment-order copy, not by pcd_gemm_f16_colmax_wfrag
+ *   10 / 11    xs               pcd_gemm_f16_wfrag runs gemm_xs_kernel: off / on (default); pcd_gemm_store_wfrag_enabled() reads it
+ *   12 / 13    request_pos      the fragment-order kernels (gemm_xw_kernel, gemm_xs_kernel) request a K tile's LDS-DMA pieces at its top (default) / behind its
+ *                               first 32 MFMAs (measured: 14 % slower; kept as the experiment that shows the K loop waits on those pieces).  Same bits.
+ *   14 / 15    split_requests   those pieces are requested by every wave (4 each) / by one wave per SIMD (8 each, default).  Same bits.
+ *   16 + bits  xs_ablation      timing ablations of gemm_xs_kernel (1: no direct stores, 2: no drip; 16 clears).  OUTPUTS WRONG while set.
+ *   33         request_pos = 2  diagnostic: gemm_xw_kernel reloads k step 0's weights late.  The store kernel has no such form: while this is set,
+ *                               gemm_xs_kernel runs its request_pos = 1 instance (the one of code 13).  Outputs not promised; 12 clears. */
 int pcd_gemm_set_config(int cfg);
+/* What a GEMM entry point would launch for `d` under the current configuration, without launching and without touching a device (csrc/gemm_f16.hip:
+ * plan_gemm, the function the entry points themselves launch from).  TESTS AND TOOLS ONLY -- no product code needs it.  `entry` names the entry
+ * point; rows_per_shape is the column-max entries' argument, splits pcd_gemm_f16_splitk's (both ignored elsewhere), has_wfrag whether a fragment-order
+ * copy would be passed.  The descriptor's pointers are compared with NULL and never read.  PCD_ERR_ARG where the entry point would refuse. */
+enum { PCD_GEMM_ENTRY_F16 = 0, PCD_GEMM_ENTRY_HILO, PCD_GEMM_ENTRY_OUT32, PCD_GEMM_ENTRY_SPLITK, PCD_GEMM_ENTRY_RESIDUAL, PCD_GEMM_ENTRY_COLMAX,
+       PCD_GEMM_ENTRY_COLMAX_WFRAG, PCD_GEMM_ENTRY_WFRAG };
+enum { PCD_GEMM_FAMILY_XP = 5, PCD_GEMM_FAMILY_XW = 6, PCD_GEMM_FAMILY_XS = 7 };   /* 0 .. 4: gemm_f16_kernel at that tile */
+typedef struct {
+    int family;                      /* 0 .. 4 or PCD_GEMM_FAMILY_*: gemm_xp_kernel, gemm_xw_kernel, gemm_xs_kernel */
+    int instance;                    /* xw: 0 default, 1 every wave requests, 2 requests behind k step 0, 3 late weights.  xs: 4 * (R - 1) + the same 0, 1, 2,
+                                      * or 3 = the ablation instance (R = 1: 12 or more K tiles, parked output chunks leave one per K tile; R = 2: two).  Else 0 */
+    unsigned grid, block;
+    int tiles_m, tiles_n;
+    int patch_pn, patch_xn;          /* XCD patch map: column tiles per patch, XCDs per patch row; 0, 0 = linear tile order */
+    int xp_depth;                    /* gemm_xp_kernel: K tiles of the next tile requested ahead (1 or 2), else 0 */
+    int xs_ablation;                 /* gemm_xs_kernel's ablation instance: the bits, else 0 */
+    int zero_bias, zero_shape_bias;  /* the launch puts the library's row of zeros in place of the missing bias / per-shape bias */
+    int no_zero_row;                 /* if that row cannot be had (stream capture before the first eager call, or c > 16384): 0 the generic kernel of the
+                                      * same tile runs, 1 pcd_gemm_f16's choice runs, 2 the entry point returns PCD_ERR_ARG */
+} pcd_gemm_plan_t;
+int pcd_gemm_plan(const pcd_gemm_desc_t* d, int entry, int rows_per_shape, int splits, int has_wfrag, pcd_gemm_plan_t* plan);
 
 int pcd_fill_zero(void* p, size_t bytes, void* stream);
 int pcd_f32_to_f16(const float* src, void* dst, int64_t n, void* stream);

@@ -26,6 +26,7 @@ def test_library_builds_and_exports_header_symbols():
         assert hasattr(lib, n), f"{n} declared in include/pcd_hip.h but not exported"
         assert n in _lib._SIGS, f"{n} has no ctypes prototype"
     assert set(_lib._SIGS) == set(names)
+    assert "pcd_gemm_plan" in names and "pcd_gemm_set_config" in names
     assert lib.pcd_abi_version() == _lib.ABI_VERSION == 2
 
 
@@ -313,3 +314,147 @@ def test_conv3d_and_vae_host_plan_is_the_recorded_one():
     assert lib.pcd_conv3d_last_packed_bytes() == 27648
     for batch, want in ((0, 0), (1, 46141440), (4, 83902464), (5, 104878080), (32, 671219712)):
         assert lib.pcd_vae_workspace_bytes(batch) == want, batch
+
+
+def test_gemm_host_plan():
+    """What the GEMM entry points decide on the host (`pcd_gemm_plan`: the plan the entry point itself launches from, no GPU), row by row against
+    expectations worked out by hand from the conditions of the code before it had one planner: the generic tile, the three 256 x 256 kernel families and
+    each conjunct that refuses them, the template instance, grid and block, the XCD patch map, the zero-row needs, and every configuration code."""
+    import ctypes as C
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    F16, HILO, OUT32, SPLITK, RESID, COLMAX, CMW, WFRAG = range(8)
+    XP, XW, XS = 5, 6, 7
+    DEFAULTS = (-1, 7, 9, 11, 12, 15, 16)
+
+    def P(family, instance, grid, block, tiles_m, tiles_n, pn=0, xn=0, xp_depth=0, abl=0, zb=0, zsb=0, nz=0):
+        return (family, instance, grid, block, tiles_m, tiles_n, pn, xn, xp_depth, abl, zb, zsb, nz)
+
+    def plan(entry, m, k1, k2, c, same_lda=True, bias=True, sb_rows=0, rps=0, splits=0, wfrag=False):
+        d = _lib.GemmDesc()
+        d.a1 = d.w = 64                                                       # never dereferenced on the host
+        d.a2 = 64 if k2 else None
+        d.k1, d.k2, d.lda1, d.lda2 = k1, k2, k1, (k1 if same_lda else k1 + k2) if k2 else 0
+        d.ldw = (k1 + k2) * (2 if entry == HILO else 1)
+        d.bias = 64 if bias else None
+        d.shape_bias, d.rows_per_shape = (64 if sb_rows else None), sb_rows
+        d.relu, d.m, d.c = (0 if entry == SPLITK else 1), m, c
+        out = _lib.GemmPlan()
+        if lib.pcd_gemm_plan(d, entry, rps, splits, int(wfrag), C.byref(out)) != 0:
+            return None
+        return tuple(getattr(out, f) for f, _ in _lib.GemmPlan._fields_)
+
+    xp512 = P(XP, 0, 256, 512, 256, 2, 2, 1, xp_depth=1, zsb=1)               # 65536 x 256 x 512: 512 tiles, two per workgroup, patches of 16 x 2 tiles
+    g512 = P(3, 0, 256, 512, 256, 2, 2, 1)                                    # the same launch shape on the generic 256 x 256 kernel
+    xp1 = lambda tiles_m, grid, patched: P(XP, 0, grid, 512, tiles_m, 1, int(patched), int(patched), xp_depth=1, zsb=1)
+    rows = [
+        # the heuristic's generic tiles
+        ((F16, 1000, 256, 0, 64), {}, P(0, 0, 8, 256, 8, 1)),                                  # c <= 64: 128 x 64
+        ((F16, 16128, 256, 0, 512), {}, P(1, 0, 504, 256, 126, 4)),                            # m < 16384: 128 x 128, 504 tiles under the 512 resident
+        ((F16, 65536, 128, 0, 512), {}, P(1, 0, 512, 256, 512, 4)),                            # k < 256: 128 x 128, 2048 tiles capped at 2 per CU
+        ((OUT32, 65536, 256, 0, 512), {}, g512),                                               # the 256 x 256 tile; the fp32 epilogue has no xp form
+        # gemm_xp_kernel taken, and refused by each conjunct in turn
+        ((F16, 65536, 256, 0, 512), {}, xp512),                                                # taken; the missing per-shape bias is the zero row
+        ((F16, 65536, 256, 0, 512), dict(bias=False, sb_rows=2048), P(XP, 0, 256, 512, 256, 2, 2, 1, xp_depth=1, zb=1)),   # ... the missing bias
+        ((RESID, 65536, 256, 0, 512), {}, xp512),                                              # residual epilogue: taken
+        ((COLMAX, 65536, 256, 0, 512), dict(rps=2048), xp512),                                 # column max: taken
+        ((F16, 65536, 128, 128, 512), {}, xp512),                                              # two sources with one row stride: taken
+        ((HILO, 65536, 256, 0, 512), {}, g512),                                                # krep == 2
+        ((F16, 65544, 256, 0, 512), {}, P(3, 0, 256, 512, 257, 2)),                            # ragged m (514 tiles: no patch map either)
+        ((F16, 65536, 256, 0, 520), {}, P(3, 0, 256, 512, 256, 3)),                            # ragged c (3 column tiles: no patch map)
+        ((F16, 65536, 64, 0, 512), dict(code=3), g512),                                        # nk = 1 (tile 3 forced: the heuristic would not pick it)
+        ((F16, 65536, 128, 128, 512), dict(same_lda=False), g512),                             # lda2 != lda1
+        ((F16, 65536, 256, 0, 512), dict(sb_rows=128), g512),                                  # per-shape rows not a multiple of 256
+        ((COLMAX, 65536, 256, 0, 512), dict(rps=64), g512),                                    # cm_rps % 128
+        # gemm_xs_kernel (pcd_gemm_f16_wfrag): R = 1 from 12 K tiles, R = 2 for 6 .. 11, pcd_gemm_f16's choice otherwise
+        ((WFRAG, 65536, 768, 0, 256), dict(wfrag=True), P(XS, 0, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # nk 12: R = 1
+        ((WFRAG, 65536, 384, 0, 256), dict(wfrag=True), P(XS, 4, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # nk 6: R = 2
+        ((WFRAG, 65536, 704, 0, 256), dict(wfrag=True), P(XS, 4, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # nk 11: R = 2
+        ((WFRAG, 65536, 384, 0, 256), dict(wfrag=True, bias=False, sb_rows=2048), P(XS, 4, 256, 512, 256, 1, 1, 1, zb=1, nz=1)),   # zero row for the bias
+        ((WFRAG, 65536, 320, 0, 256), dict(wfrag=True), xp1(256, 256, True)),                  # nk 5: refused
+        ((WFRAG, 65280, 384, 0, 256), dict(wfrag=True), xp1(255, 255, False)),                 # 255 tiles: refused
+        ((WFRAG, 65792, 384, 0, 256), dict(wfrag=True), xp1(257, 256, False)),                 # 257 tiles: refused
+        ((WFRAG, 65536, 384, 0, 256), {}, xp1(256, 256, True)),                                # no fragment copy passed
+        ((WFRAG, 65536, 192, 192, 256), dict(wfrag=True, same_lda=False), P(3, 0, 256, 512, 256, 1, 1, 1)),      # lda2 != lda1: neither xs nor xp
+        # gemm_xw_kernel (pcd_gemm_f16_colmax_wfrag): taken, or the entry point refuses
+        ((CMW, 65536, 128, 0, 256), dict(wfrag=True, rps=2048), P(XW, 0, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),
+        ((CMW, 16384, 2048, 0, 4096), dict(wfrag=True, rps=2048), P(XW, 0, 256, 512, 64, 16, 8, 2, zsb=1, nz=2)),   # global_feat.3 at batch 8
+        ((CMW, 8192, 128, 0, 256), dict(wfrag=True, rps=2048), None),                          # 32 tiles
+        ((CMW, 65536, 64, 0, 256), dict(wfrag=True, rps=2048), None),                          # nk = 1
+        ((CMW, 65536, 128, 0, 256), dict(wfrag=True, rps=64), None),                           # shapes of half a wave tile
+        ((CMW, 65536, 128, 0, 256), dict(wfrag=True, rps=2048, bias=False), None),             # no bias
+        ((CMW, 65536, 128, 0, 256), dict(wfrag=True, rps=2048, sb_rows=2048), None),           # a per-shape bias
+        ((CMW, 65536, 128, 0, 256), dict(rps=2048), None),                                     # no fragment copy
+        # the XCD patch map: 1, 2, 4, 8, 16 column tiles, and a tiles_m that fails the divisibility although the tiles fill whole rounds
+        ((F16, 65536, 256, 0, 256), {}, xp1(256, 256, True)),
+        ((F16, 16384, 256, 0, 1024), {}, P(XP, 0, 256, 512, 64, 4, 4, 1, xp_depth=1, zsb=1)),
+        ((F16, 16384, 256, 0, 2048), {}, P(XP, 0, 256, 512, 64, 8, 8, 1, xp_depth=1, zsb=1)),
+        ((F16, 16384, 256, 0, 4096), {}, P(XP, 0, 256, 512, 64, 16, 8, 2, xp_depth=1, zsb=1)),
+        ((F16, 18432, 256, 0, 8192), {}, P(XP, 0, 256, 512, 72, 32, 0, 0, xp_depth=1, zsb=1)),                   # 2304 tiles = 9 rounds, 72 % 16 != 0
+        # split-K: tiles x splits, capped at the resident blocks; never a patch map, also at 256 blocks and whole rounds
+        ((SPLITK, 1024, 8192, 0, 512), dict(bias=False, splits=4), P(1, 0, 128, 256, 8, 4)),
+        ((SPLITK, 1024, 8192, 0, 512), dict(bias=False, splits=32), P(1, 0, 512, 256, 8, 4)),
+        ((SPLITK, 1024, 8192, 0, 1024), dict(bias=False, splits=4, code=3), P(3, 0, 64, 512, 4, 4)),
+        ((SPLITK, 2048, 8192, 0, 1024), dict(bias=False, splits=8, code=3), P(3, 0, 256, 512, 8, 4)),
+        ((SPLITK, 1024, 8192, 0, 512), dict(bias=False, splits=3), None),                      # K / splits not a multiple of 64
+        # configuration codes, one field each
+        ((F16, 65536, 256, 0, 512), dict(code=5), g512),                                       # 5: gemm_xp_kernel off
+        ((F16, 65536, 256, 0, 512), dict(code=6), P(XP, 0, 256, 512, 256, 2, 2, 1, xp_depth=2, zsb=1)),          # 6: two K tiles ahead
+        ((COLMAX, 65536, 256, 0, 512), dict(code=6, rps=2048), xp512),                         # ... store epilogue only
+        ((F16, 65536, 256, 0, 512), dict(code=7), xp512),                                      # 7: the default
+        ((CMW, 65536, 128, 0, 256), dict(code=8, wfrag=True, rps=2048), P(XW, 0, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),   # 8: asked by callers only
+        ((WFRAG, 65536, 768, 0, 256), dict(code=10, wfrag=True), xp1(256, 256, True)),         # 10: gemm_xs_kernel off
+        ((WFRAG, 65536, 768, 0, 256), dict(code=13, wfrag=True), P(XS, 2, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # 13: request position
+        ((WFRAG, 65536, 384, 0, 256), dict(code=13, wfrag=True), P(XS, 6, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),
+        ((CMW, 65536, 128, 0, 256), dict(code=13, wfrag=True, rps=2048), P(XW, 2, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),
+        ((WFRAG, 65536, 768, 0, 256), dict(code=14, wfrag=True), P(XS, 1, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # 14: every wave requests
+        ((WFRAG, 65536, 384, 0, 256), dict(code=14, wfrag=True), P(XS, 5, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),
+        ((CMW, 65536, 128, 0, 256), dict(code=14, wfrag=True, rps=2048), P(XW, 1, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),
+        ((CMW, 65536, 128, 0, 256), dict(code=(14, 13), wfrag=True, rps=2048), P(XW, 2, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),   # the position wins
+        ((CMW, 65536, 128, 0, 256), dict(code=33, wfrag=True, rps=2048), P(XW, 3, 256, 512, 256, 1, 1, 1, zsb=1, nz=2)),  # 33: late weights ...
+        ((WFRAG, 65536, 768, 0, 256), dict(code=33, wfrag=True), P(XS, 2, 256, 512, 256, 1, 1, 1, zsb=1, nz=1)),          # ... and the store kernel as under 13
+        ((WFRAG, 65536, 768, 0, 256), dict(code=17, wfrag=True), P(XS, 3, 256, 512, 256, 1, 1, 1, abl=1, zsb=1, nz=1)),   # 16 + 1: ablation instance
+        ((WFRAG, 65536, 384, 0, 256), dict(code=(13, 14, 18), wfrag=True), P(XS, 7, 256, 512, 256, 1, 1, 1, abl=2, zsb=1, nz=1)),   # ... before the others
+        ((F16, 65536, 256, 0, 512), dict(code=17), xp512),                                     # ... and of that kernel alone
+        # forced tiles 0 .. 4 (blocks per CU 3, 2, 1, 1, 1): a generic kernel at 256 blocks and whole rounds takes the patch map too
+        ((F16, 16384, 128, 0, 1024), dict(code=0), P(0, 0, 768, 256, 128, 16)),
+        ((F16, 16384, 128, 0, 1024), dict(code=1), P(1, 0, 512, 256, 128, 8)),
+        ((F16, 16384, 128, 0, 1024), dict(code=2), P(2, 0, 256, 512, 64, 8, 8, 1)),
+        ((F16, 16384, 128, 0, 1024), dict(code=3), P(XP, 0, 256, 512, 64, 4, 4, 1, xp_depth=1, zsb=1)),
+        ((F16, 16384, 128, 0, 1024), dict(code=4), P(4, 0, 256, 256, 128, 8, 8, 1)),
+        ((F16, 1000, 256, 0, 64), dict(code=3), P(3, 0, 4, 512, 4, 1)),
+    ]
+    for args, kw, want in rows:
+        kw = dict(kw)
+        code = kw.pop("code", ())
+        try:
+            for cfg in (code if isinstance(code, tuple) else (code,)):
+                assert lib.pcd_gemm_set_config(cfg) == 0, cfg
+            got = plan(*args, **kw)
+        finally:
+            for cfg in DEFAULTS:
+                assert lib.pcd_gemm_set_config(cfg) == 0
+        assert got == want, (args, kw, code, got, want)
+    # the two switches that callers read back
+    try:
+        assert lib.pcd_gemm_wfrag_enabled() == 1 and lib.pcd_gemm_store_wfrag_enabled() == 1
+        assert lib.pcd_gemm_set_config(8) == 0 and lib.pcd_gemm_wfrag_enabled() == 0 and lib.pcd_gemm_store_wfrag_enabled() == 1
+        assert lib.pcd_gemm_set_config(10) == 0 and lib.pcd_gemm_store_wfrag_enabled() == 0
+    finally:
+        assert lib.pcd_gemm_set_config(9) == 0 and lib.pcd_gemm_set_config(11) == 0
+    assert lib.pcd_gemm_wfrag_enabled() == 1 and lib.pcd_gemm_store_wfrag_enabled() == 1
+    # accepted and refused codes
+    try:
+        for cfg in list(range(-1, 32)) + [33]:
+            assert lib.pcd_gemm_set_config(cfg) == 0, cfg
+        for cfg in (-2, 32, 34):
+            assert lib.pcd_gemm_set_config(cfg) == -1, cfg
+    finally:
+        for cfg in DEFAULTS:
+            assert lib.pcd_gemm_set_config(cfg) == 0
+    assert plan(F16, 65536, 256, 0, 512) == xp512
+    # pcd_gemm_f16_colmax_wfrag itself refuses a shape gemm_xw_kernel does not take (nothing is launched, so no device is needed): 32 tiles
+    d = _lib.GemmDesc()
+    d.a1 = d.w = d.bias = 64
+    d.k1, d.lda1, d.ldw, d.relu, d.m, d.c = 128, 128, 128, 1, 8192, 256
+    assert lib.pcd_gemm_f16_colmax_wfrag(d, 64, 64, 2048, 0) == -1 and b"gemm_xw_kernel" in lib.pcd_last_error()

@@ -231,6 +231,46 @@ def test_gemm_store_with_fragment_order_weights_exact(ops):
     assert torch.equal(on, off)
 
 
+def test_gemm_fragment_order_request_position_and_split_instances_exact(ops):
+    """The instances of gemm_xw_kernel / gemm_xs_kernel behind pcd_gemm_set_config(13) (the next K tile's activation pieces requested behind k step
+    0's MFMAs) and (14) (every wave requests its own pieces), which the tools time and nothing else checked: at the smallest shapes the kernels take
+    (256 tiles; 2, 6 and 12 K tiles, so both drip rates of the store kernel) the output is exact on small integers and bitwise the default
+    instance's, every launch run twice."""
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(13)
+    for colmax, (m, k, c) in [(True, (65536, 128, 256)), (False, (65536, 384, 256)), (False, (65536, 768, 256))]:
+        a = torch.randint(-3, 4, (m, k), generator=g, device="cuda").half()
+        w = torch.randint(-2, 3, (c, k), generator=g, device="cuda").half()
+        bias = torch.randint(-3, 4, (c,), generator=g, device="cuda").float()
+        want = (a.float() @ w.float().t() + bias).clamp_min(0)              # exact: small integers
+        want = want.reshape(-1, 2048, c).max(1)[0] if colmax else want.half()
+        wfrag = torch.empty_like(w)
+        _lib.check(lib.pcd_gemm_pack_wfrag(w.data_ptr(), k, k, c, wfrag.data_ptr(), _lib.stream_ptr()))
+        d = ops._desc(a, w, bias, relu=True)
+
+        def run():
+            if colmax:
+                out = torch.zeros(m // 2048, c, dtype=torch.float32, device="cuda")
+                _lib.check(lib.pcd_gemm_f16_colmax_wfrag(d, wfrag.data_ptr(), out.data_ptr(), 2048, _lib.stream_ptr()), "gemm_f16_colmax_wfrag")
+            else:
+                out = torch.full((m, c), float("nan"), dtype=torch.float16, device="cuda")
+                _lib.check(lib.pcd_gemm_f16_wfrag(d, wfrag.data_ptr(), out.data_ptr(), c, _lib.stream_ptr()), "gemm_f16_wfrag")
+            return out
+
+        default = run()
+        assert torch.equal(default, want), (m, k, c, "default")
+        for code in (13, 14):
+            try:
+                assert lib.pcd_gemm_set_config(code) == 0
+                for rep in range(2):
+                    out = run()
+                    assert torch.equal(out, default) and torch.equal(out, want), (m, k, c, code, rep, int((out != default).sum()))
+            finally:
+                lib.pcd_gemm_set_config(12)
+                lib.pcd_gemm_set_config(15)
+
+
 def test_gemm_dual_source_shape_bias_residual(ops):
     m, k1, k2, c, rps = 384, 128, 64, 136, 96
     a1, a2, w = _int_mat(m, k1, 4), _int_mat(m, k2, 5), _int_mat(c, k1 + k2, 6)
