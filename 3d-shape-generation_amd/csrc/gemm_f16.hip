@@ -118,6 +118,9 @@ __device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
 
 // four fp32 values V clamped to [LO, 65504] -> two packed fp16 pairs PK[0], PK[1] (channels +0, +1 and +2, +3).  A macro for the same reason: as a function,
 // by value or by reference, it changes the streams of gemm_xp_kernel and gemm_xs_kernel (profiles/gemm_plan_isa.md).
+// Per PAIR of values the compiler emits 2 v_med3_f32 + ONE v_cvt_pk_f16_f32 (gfx950's packed round-to-nearest-even convert; there is no separate pack): 1.5
+// VALU per value.  Converting first and clamping the packed pair (v_cvt_pk_f16_f32 + v_pk_max_f16 + v_pk_min_f16) is 1.5 per value as well -- measured on
+// the assembly, 595 v. 596 VALU instructions in gemm_xs_kernel -- so the fp32 form stays: its handling of -0 and NaN needs no argument.
 #define PCD_GEMM_CLAMP_PACK(V, LO, PK)                                      \
     do {                                                                    \
         half2_ lo2, hi2;                                                    \
@@ -131,6 +134,9 @@ __device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
 
 // column-max epilogue of the kernels that hold the tile's bias rows in bias_lds[par]: the maximum over the wave's rows of relu(acc + bias), one atomic per
 // column (acc, MI, NI, m0, n0, wm, wn, WM, WN, lane, q, par, p in scope).  A macro for the same reason.
+// The bias comes AFTER the maximum: fl(x + b) is monotone in x, so max_i fl(acc_i + b) = fl(max_i acc_i + b) bit for bit -- one add per column where
+// there were 32, and the maximum against 0 is taken last, as the zero start took it.  NaN as before (fmaxf returns the operand that is a number): a NaN
+// accumulator is passed over, and a column whose every sum is NaN gives 0.
 #define PCD_GEMM_COLMAX_FROM_LDS_BIAS()                                                             \
     do {                                                                                            \
         unsigned* cm = reinterpret_cast<unsigned*>(p.colmax);                                       \
@@ -138,11 +144,12 @@ __device__ __forceinline__ const half_t* uniform_ptr(const half_t* q) {
         _Pragma("unroll") for (int j = 0; j < NI; ++j) {                                            \
             const int cl = wn * WN + j * 16 + colq;                                                 \
             const float b = bias_lds[par][0][cl] + bias_lds[par][1][cl];                            \
-            float mx = 0.f;                                                                         \
+            float mx = -__builtin_inff();                                                           \
             _Pragma("unroll") for (int i = 0; i < MI; ++i)                                          \
-                _Pragma("unroll") for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r] + b);     \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r]);         \
             mx = fmaxf(mx, __shfl_xor(mx, 16));                                                     \
             mx = fmaxf(mx, __shfl_xor(mx, 32));                                                     \
+            mx = fmaxf(0.f, mx + b);                                                                \
             if (q == 0) atomicMax(cm + (int64_t)shape * p.c + n0 + cl, __float_as_uint(mx));        \
         }                                                                                           \
     } while (0)
@@ -803,9 +810,9 @@ __global__ __launch_bounds__(512) void gemm_xw_kernel(GemmParams p, const half_t
 // computes -- gemm_xp_kernel hides two K tiles of the next tile under it and still pays ~4 us per tile at K = 1024 (514 us against 399 us for
 // the same K loop without stores); dripping the converted tile from REGISTERS needs 64 registers nobody has.  With the weights out of LDS
 // (fragment-order copy, straight into the MFMA operand registers as in gemm_xw_kernel) the activation ring is 64 KB and 88 KB of LDS are
-// free: the epilogue stores ND = 5 (6) of a wave's sixteen 1-KB chunks at once and parks NDRIP = 11 (10) in the wave's own LDS slots; the
+// free: the epilogue stores ND = 6 of a wave's sixteen 1-KB chunks at once and parks NDRIP = 10 in the wave's own LDS slots; the
 // next tile's K tiles read R = 1 (2) chunks back per K tile (ds_read_b128, 4 transient registers) and store them from there -- one 1-KB store
-// per wave every 1.5 us instead of sixteen at once.  The waves keep their vmcnt waits counted: the drip stores sit at a fixed place of the
+// per wave every 1.5 us instead of sixteen at once, and each of those a run of eight whole output rows of the wave's tile (the parking layout below).  The waves keep their vmcnt waits counted: the drip stores sit at a fixed place of the
 // K tile's issue order ([activation pieces x 4 (+ bias x 2)] [weights of k step 0 x 4] [drip x R] [weights of k step 1 x 4]) and each wait names
 // the operations younger than the ones it needs.  A store must have completed one K tile after its issue (vmcnt retires in order).
 // Output addresses: SGPR base (tile, chunk) + one tile-invariant 32-bit lane offset (global_store_dwordx4 v, v[4], s[2]): no per-row pointers.
@@ -821,7 +828,7 @@ __device__ __forceinline__ void gstore16_s(unsigned voff, u32x4_t data, const ha
 template <int R, bool ABL = false, bool MID = false, bool SPLIT = true>
 __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t* __restrict__ wfrag) {
     constexpr int NCH = 16;                                // 1-KB output chunks of a wave's 128 x 64 tile: chunk c = rows i = c / 2 (16 each), column pair c % 2
-    constexpr int NDRIP = R == 1 ? 11 : 10;                // chunks parked in LDS, R of them stored per K tile of the next tile
+    constexpr int NDRIP = 10;                              // chunks parked in LDS (five pairs: both column halves of sixteen rows), R of them stored per K tile of the next tile
     constexpr int ND = NCH - NDRIP;                        // chunks stored straight from the epilogue (they count in vmcnt)
     constexpr int BM = 256, BN = 256, BKT = 64, ROWB = 128, WGN = 4;
     constexpr int WM = 128, WN = 64, MI = 8, NI = 4;
@@ -840,7 +847,11 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
     // formed once, and the K loop's address arithmetic kept dependent on an opaque copy of its counter so that it is not hoisted into more live values.
     const int lda = (int)p.lda1, ldo = (int)p.ldo;
     const int abl = ABL ? p.xp_depth : 0;                  // timing ablations (a separate instance: the product kernel carries none of it) (pcd_gemm_set_config(16 + bits); outputs are then WRONG): 1 no direct stores, 2 no drip
-                                                           // stores, 4 no LDS parking, 8 no epilogue arithmetic
+                                                           // stores, 4 no LDS parking, 8 no epilogue arithmetic; (pcd_gemm_set_config(35 .. 37): 16, 32, both) the other store
+                                                           // SHAPE, same bytes, count and vmcnt accounting, WRONG places in the same tile: 16 the drip stores as 16 rows x 64
+                                                           // bytes (half lines, as the direct ones), 32 the direct stores as 8 rows x 128 bytes (whole lines, as the drip: chunk
+                                                           // (i, jp) to rows i * 16 + jp * 8 + lane / 8) -- what whole lines are worth, profiles/gemm_store_lines.md; 64 (code 38)
+                                                           // nothing: this instance with the product's stores, the control of those
 
     // staging: a piece = 8 rows x 128 bytes; 16-byte chunk swz(row, lane % 8), and the swizzle does not see the r term below.  SPLIT (default): the 32 pieces of a K
     // tile are requested by ONE wave of each SIMD -- waves 0-3 for even K tiles of the workgroup's run, 4-7 for odd ones, rows r * 32 + (wave & 3) * 8 + lane / 8, r < 8 --
@@ -890,7 +901,26 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
     // output: accumulator element (i, j, r) = point row wm*WM + i*16 + (lane & 15), channel wn*WN + j*16 + 4 (lane >> 4) + r; after the half swap a lane
     // holds 8 consecutive channels: chunk (i, jp) goes to row i*16 + (lane & 15), column (2 jp + (q & 1)) * 16 + (q >> 1) * 8 of the wave's tile
     const unsigned vout = (unsigned)((((wm * WM + (lane & 15)) * ldo) + wn * WN + (q & 1) * 16 + (q >> 1) * 8) * 2);
-    char* const my_drip = drip + (wave * NDRIP * 64 + lane) * 16;
+    // the parked chunks leave as WHOLE rows of the wave's tile: a drip store covers 8 rows x 128 bytes, lane L writing 16-byte segment L % 8 of row L / 8 -- whole
+    // 128-byte lines where the output rows are line-aligned, as every operand fill is (a direct store covers 16 rows x 64 bytes, sixteen half lines; measured
+    // with the stores misplaced, profiles/gemm_store_lines.md: the whole-line shape of the ten dripped chunks is worth 2.5-3 % of the kernel, that of the six
+    // direct ones nothing, so those keep the registers' own order).  For that the chunk PAIR (i, 0), (i, 1) -- the two 64-byte halves of the same sixteen rows --
+    // is parked as two 1-KB slots by ROWS, slot h = rows 8 h .. 8 h + 7: the lane that holds row pr, segment s = 4 jp + 2 (q & 1) + (q >> 1) writes
+    //     slot pr / 8, byte (pr % 8) * 128 + (s ^ (pr % 8)) * 16                                                       (park_off below, ^ 64 for jp = 1)
+    // and lane L of the drip reads slot h, byte (L / 8) * 128 + ((L % 8) ^ (L / 8)) * 16 (drip_rd): row L / 8, segment L % 8.  Bank conflicts: none either way.
+    // ds_write_b128 goes in groups of 8 consecutive lanes over 8 16-byte slots (banks (a / 4) % 32): such a group has one q and pr % 8 = 0 .. 7, so its slot
+    // indices s ^ (pr % 8) are all different.  ds_read_b128 goes in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32 for the other two) over 16
+    // slots (banks (a / 4) % 64), slot index (8 (L / 8) + ((L % 8) ^ (L / 8))) % 16: in each group the two even rows supply one run of four segments each and so
+    // do the two odd rows, the runs of a parity being opposite halves (0-3 / 4-7), and the XOR with the row permutes inside a half or swaps the halves of both
+    // alike -- 16 different slots.  Without the XOR the write would be 8-way conflicted (a group's lanes differ in the row only: same slot index).
+    // (the drip stores' lane offset: formed where it is used, per dripping K tile, from an opaque copy of the lane's slot -- carried across the K loop it would
+    // cost the one register that the every-wave-requests instances do not have; ldo * 2 < 2^24 by the host's range check, so the multiply is a 24-bit one)
+    auto vout_line = [&]() __attribute__((always_inline)) {
+        unsigned l16 = vlane16;
+        asm volatile("" : "+v"(l16));
+        return __umul24((unsigned)(wm * WM) + (l16 >> 7), (unsigned)ldo * 2u) + (unsigned)(wn * WN * 2) + (l16 & 0x70u);
+    };
+    char* const drip_rd = drip + wave * NDRIP * 1024 + (lane >> 3) * 128 + (((lane & 7) ^ (lane >> 3)) << 4);
     f32x4 acc[MI][NI];
     half8 wq[2][NI];
 
@@ -954,7 +984,7 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
             const char* base = smem + (it & 1) * STAGE_BYTES;
             const bool dripping = dnext < NDRIP;
             u32x4_t dv;                                    // (R = 2: the second chunk is read once the first has been stored -- the same four registers)
-            if (dripping) dv = *(const u32x4_t*)(my_drip + dnext * 1024);
+            if (dripping) dv = *(const u32x4_t*)(drip_rd + dnext * 1024);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 half8 af[MI];
@@ -982,12 +1012,14 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
                 if constexpr (MID) { if (ks == 0) request_next(); }
                 wload4(wq[ks], wnext + ks * 2048);         // this k step's registers take the next K tile's fragments (the MFMAs that read them have been issued)
                 if (ks == 0 && dripping) {
+                    const unsigned vline = vout_line();
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const int c = ND + dnext + r;
-                        if (r > 0) dv = *(const u32x4_t*)(my_drip + (dnext + r) * 1024);
+                        if (r > 0) dv = *(const u32x4_t*)(drip_rd + (dnext + r) * 1024);
                         if (abl & 2) { asm volatile("global_load_dword %0, %1, %2" : "=v"(dv[0]) : "v"(vlane16), "s"(wnext) : "memory"); continue; }   // (same vmcnt count)
-                        gstore16_s(vout, dv, uniform_ptr(prev_out + (int64_t)((c >> 1) * 16) * ldo + (c & 1) * 32));
+                        if (abl & 16) { gstore16_s(vout, dv, uniform_ptr(prev_out + (int64_t)((c >> 1) * 16) * ldo + (c & 1) * 32)); continue; }
+                        gstore16_s(vline, dv, uniform_ptr(prev_out + (int64_t)((c >> 1) * 16 + (c & 1) * 8) * ldo));      // slot c - ND: rows 8 (c & 1) .. + 7 of pair c / 2
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1008,6 +1040,11 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
             for (int c = 0; c < (has_next ? ND : NCH); ++c) { unsigned junk; asm volatile("global_load_dword %0, %1, %2" : "=v"(junk) : "v"(vlane16), "s"(tile_out) : "memory"); }
         } else {
             const int q4 = q * 4;
+            // (formed here, per tile, from an opaque copy of the lane's slot: a value carried across the K loop would cost a register there)
+            unsigned l16 = vlane16;
+            asm volatile("" : "+v"(l16));
+            const unsigned pr7 = (l16 >> 4) & 7;              // lane = 16 q + pr: row in its half, the half, and the segment's low bits 2 (q & 1) + (q >> 1)
+            const unsigned park_off = wave * NDRIP * 1024 + ((l16 >> 7) & 1) * 1024 + pr7 * 128 + (((((l16 >> 8) & 1) * 2 + ((l16 >> 9) & 1)) ^ pr7) << 4);
             f32x4 bv[NI];
 #pragma unroll
             for (int j = 0; j < NI; ++j)
@@ -1029,8 +1066,9 @@ __global__ __launch_bounds__(512) void gemm_xs_kernel(GemmParams p, const half_t
                     const int c = i * 2 + (j >> 1);
                     if (c < ND || !has_next) {
                         if (abl & 1) { unsigned junk; asm volatile("global_load_dword %0, %1, %2" : "=v"(junk) : "v"(vlane16), "s"(tile_out), "v"(o) : "memory"); }
+                        else if (abl & 32) gstore16_s(vout_line(), o, tile_out + (int64_t)(i * 16 + (j >> 1) * 8) * ldo);
                         else gstore16_s(vout, o, tile_out + (int64_t)(i * 16) * ldo + (j >> 1) * 32);
-                    } else if (!(abl & 4)) *(u32x4_t*)(my_drip + (c - ND) * 1024) = o;
+                    } else if (!(abl & 4)) *(u32x4_t*)(drip + ((park_off ^ ((j >> 1) * 64)) + (i - ND / 2) * 2048)) = o;
                     else asm volatile("" ::"v"(o));
                 }
             }
@@ -1370,7 +1408,7 @@ extern "C" int pcd_gemm_store_wfrag_enabled(void) { return g_cfg.xs; }
 
 extern "C" int pcd_gemm_set_config(int cfg) {
     GemmConfig& g = g_cfg;
-    PCD_CHECK_ARG((cfg >= -1 && cfg <= 31) || cfg == 33);
+    PCD_CHECK_ARG((cfg >= -1 && cfg <= 31) || cfg == 33 || (cfg >= 35 && cfg <= 38));
     if (cfg <= 4) g.tile = cfg;
     else if (cfg <= 7) g.xp_depth = cfg == 5 ? 0 : (cfg == 6 ? 2 : 1);
     else if (cfg <= 9) g.xw = cfg - 8;
@@ -1378,6 +1416,7 @@ extern "C" int pcd_gemm_set_config(int cfg) {
     else if (cfg <= 13) g.request_pos = cfg - 12;
     else if (cfg <= 15) g.split_requests = cfg - 14;
     else if (cfg <= 31) g.xs_ablation = cfg - 16;
-    else g.request_pos = 2;
+    else if (cfg == 33) g.request_pos = 2;
+    else g.xs_ablation = (cfg - 34) * 16;      // 35 .. 38: bits 16, 32, both, 64
     return PCD_OK;
 }

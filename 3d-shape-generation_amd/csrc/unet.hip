@@ -69,7 +69,10 @@ static UnetWs carve(int64_t batch, int64_t n) {
     w.x3 = o; o += align_up(m * 512 * 2);
     w.x4 = o; o += align_up(m * 1024 * 2);
     w.s0 = o; o += align_up(m * 2048 * 2);
-    w.s1 = o; o += align_up(m * 1024 * 2);
+    // s1 also takes the split-K slabs of the pooled product (pcd_unet_forward, batch <= 256: slabs x batch x 1024 floats = 32 KB per shape), which are
+    // larger than its widest activation (2 KB per point) for shapes of fewer than 16 points
+    const size_t slabs = batch <= 256 ? (size_t)pcd_skinny_slabs(4096, 1024) * (size_t)batch * 1024 * 4 : 0;
+    w.s1 = o; o += align_up(m * 1024 * 2 > slabs ? m * 1024 * 2 : slabs);
     w.pooled = o; o += align_up((size_t)batch * 4096 * 4);
     w.pooled16 = o; if (batch > 256) o += align_up((size_t)batch * 4096 * 2);
     w.gbias = o; o += align_up((size_t)batch * 1024 * 4);

@@ -102,7 +102,7 @@ int pcd_gemm_store_wfrag_enabled(void);
 int pcd_gemm_wfrag_stamps(void* stamps);
 /* Which of the GEMM kernels run: one code sets one field of the process's GEMM configuration (csrc/gemm_f16.hip: GemmConfig) and leaves the others.
  * TEST / BENCHMARK ONLY: process-global, read by every handle at every launch -- not for use while another thread is launching.
- * PCD_ERR_ARG unless -1 <= code <= 31 or code == 33.
+ * PCD_ERR_ARG unless -1 <= code <= 31, code == 33 or 35 <= code <= 38.
  *
  *   code       field            effect
  *   -1         tile             (default) the shape heuristic picks the generic tile
@@ -116,7 +116,11 @@ int pcd_gemm_wfrag_stamps(void* stamps);
  *   14 / 15    split_requests   those pieces are requested by every wave (4 each) / by one wave per SIMD (8 each, default).  Same bits.
  *   16 + bits  xs_ablation      timing ablations of gemm_xs_kernel (1: no direct stores, 2: no drip; 16 clears).  OUTPUTS WRONG while set.
  *   33         request_pos = 2  diagnostic: gemm_xw_kernel reloads k step 0's weights late.  The store kernel has no such form: while this is set,
- *                               gemm_xs_kernel runs its request_pos = 1 instance (the one of code 13).  Outputs not promised; 12 clears. */
+ *                               gemm_xs_kernel runs its request_pos = 1 instance (the one of code 13).  Outputs not promised; 12 clears.
+ *   35/36/37   xs_ablation      = 16 / 32 / 48: the ablation instance sends its drip stores out in the direct stores' shape (16: 16 rows x 64 bytes, half
+ *                               lines) / its direct stores in the drip's (32: 8 rows x 128 bytes, whole lines), to the wrong places of the same output
+ *                               tile (profiles/gemm_store_lines.md).  OUTPUTS WRONG while set; 16 clears.
+ *   38         xs_ablation      = 64: the ablation instance with nothing ablated (the control of 35 .. 37; outputs right).  16 clears. */
 int pcd_gemm_set_config(int cfg);
 /* What a GEMM entry point would launch for `d` under the current configuration, without launching and without touching a device (csrc/gemm_f16.hip:
  * plan_gemm, the function the entry points themselves launch from).  TESTS AND TOOLS ONLY -- no product code needs it.  `entry` names the entry
