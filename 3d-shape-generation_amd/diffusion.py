@@ -895,40 +895,52 @@ class LatentDiffusion(_DiffusionBase):
             return self._randn_like(torch.empty(num_samples, self.hparams.latent_dim, device=self.device))
         return z_T.to(self.device, torch.float32).contiguous().clone()
 
-    def _finish(self, z_0, threshold, return_latent=False):
-        from .utils import voxel_tensor_to_point_clouds
+    @staticmethod
+    def _check_output(output):
+        if output not in ("points", "mesh"):
+            raise ValueError(f"output must be 'points' or 'mesh', got {output!r}")
+
+    def _finish(self, z_0, threshold, return_latent=False, output="points"):
+        from .utils import voxel_tensor_to_meshes, voxel_tensor_to_point_clouds
         x_0 = self.vae.decode(z_0)
         if self.hparams.is_voxel_based:
-            pcs = voxel_tensor_to_point_clouds(x_0, threshold=threshold)
+            convert = voxel_tensor_to_meshes if output == "mesh" else voxel_tensor_to_point_clouds
+            pcs = convert(x_0, threshold=threshold)
             return (pcs, z_0) if return_latent else pcs
         # the reference's sample()/sample3() leave `point_clouds` unbound here (diffusion.py:650-653)
         raise UnboundLocalError("local variable 'point_clouds' referenced before assignment "
                                 "(is_voxel_based=False is not supported by the reference's samplers either)")
 
     @torch.no_grad()
-    def sample(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, return_latent=False):
-        """DDIM in latent space, VAE decode, voxel -> points (diffusion.py:619-653)."""
+    def sample(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, return_latent=False, output="points"):
+        """DDIM in latent space, VAE decode, voxel -> points (diffusion.py:619-653).  `output="mesh"` (here and in `sample2`, `sample3`,
+        `sample_dpm`): the decoded grids leave as `utils.Mesh` surfaces of the same threshold (`utils.voxel_tensor_to_meshes`) instead."""
+        self._check_output(output)
         z = self._start(num_samples, z_T)
-        return self._finish(self._run_table(z, self.ddim_table(num_steps, num_samples), "ddim"), threshold, return_latent)
+        return self._finish(self._run_table(z, self.ddim_table(num_steps, num_samples), "ddim"), threshold, return_latent, output)
 
     @torch.no_grad()
     def sample_dpm(self, num_samples, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, threshold=0.4, z_T=None,
-                   return_latent=False):
+                   return_latent=False, output="points"):
         """`PointCloudDiffusion.sample_dpm` in latent space, then VAE decode and voxel -> points like `sample`.  Runs on the per-layer
         launches (the persistent kernel implements the DDIM update only)."""
+        self._check_output(output)
         if z_T is not None and tuple(z_T.shape) != (num_samples, self.hparams.latent_dim):
             raise ValueError(f"z_T must be {(num_samples, self.hparams.latent_dim)}, got {tuple(z_T.shape)}")
         tab = self.dpm_table(num_steps, order, spacing, t_last)
-        return self._finish(self._run_table(self._start(num_samples, z_T), tab, "dpm"), threshold, return_latent)
+        return self._finish(self._run_table(self._start(num_samples, z_T), tab, "dpm"), threshold, return_latent, output)
 
     @torch.no_grad()
-    def sample2(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, noises=None, return_latent=False):
+    def sample2(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, noises=None, return_latent=False, output="points"):
         """DDPM in latent space (diffusion.py:575-616)."""
+        self._check_output(output)
         z = self._start(num_samples, z_T)
-        return self._finish(self._run_table(z, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises), threshold, return_latent)
+        return self._finish(self._run_table(z, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises), threshold, return_latent,
+                            output)
 
     @torch.no_grad()
-    def sample3(self, num_samples, z=None, start_t=None, num_steps=1000, threshold=0.4, return_latent=False):
+    def sample3(self, num_samples, z=None, start_t=None, num_steps=1000, threshold=0.4, return_latent=False, output="points"):
         """DDIM from a given latent/time (diffusion.py:655-707)."""
+        self._check_output(output)
         z0 = self._run_from_state(num_samples, lambda: self._start(num_samples, None), z, start_t, num_steps)
-        return self._finish(z0, threshold, return_latent)
+        return self._finish(z0, threshold, return_latent, output)

@@ -845,6 +845,33 @@ int pcd_voxels_to_points(const float* vox, int batch, int d, int h, int w, float
 /* mean BCE(x, target) with torch's log clamp at -100 (metrics.py:181); out fp32 [1]. */
 int pcd_binary_bce_mean(const float* x, const float* target, int64_t n, float* out, void* stream);
 
+/* ---- Surface-nets meshes of occupancy grids (csrc/mesh.hip; definition in DESIGN.md "Mesh output") ----
+ * vox fp32 [B][D][H][W] as pcd_voxels_to_points reads it, any d, h, w > 1; a node is inside iff v > threshold, 0 < threshold < inf.
+ * The field is surrounded by one layer of nodes of value 0, so every mesh is closed.  Cell (cz, cy, cx), 0 <= cz <= D (likewise cy, cx),
+ * has the padded nodes (cz + a, cy + b, cx + c), a, b, c in {0, 1}; a cell whose corners are not all on one side owns one vertex, the mean
+ * of the crossing points A + (threshold - v_A) / (v_B - v_A) (B - A) of its edges whose ends differ in side.  Vertices are numbered in row-major
+ * (cz, cy, cx) order and leave as [x, y, z] rows under the affine map of pcd_voxels_to_points (index i of an axis of n nodes -> 2 i / (n - 1) - 1;
+ * surfaces that close in the padding reach up to one pitch 2 / (n - 1) outside [-1, 1]).  Faces: per padded node in row-major order and per axis
+ * z, y, x, the edge to the +1 neighbour, where its ends differ in side, gives one quad of the four cells round it, as two triangles
+ * (q0, q1, q2), (q0, q2, q3), wound so that normals point outward.  One workgroup per grid, ballot + block-scan compaction, no atomics: bitwise
+ * repeatable and independent of the rest of the batch.
+ *
+ * Two calls with one host read of `counts` between them to size the packed outputs:
+ *   pcd_mesh_count  leaves in `workspace` each cell's vertex number or -1 -- int32 [B][D+1][H+1][W+1], pcd_mesh_workspace_bytes() bytes (host
+ *                   arithmetic; 0 for arguments the other two refuse) -- and counts int32 [B][2] = (vertices, triangles) of each grid.
+ *   pcd_mesh_emit   with the same vox, extents, threshold and workspace: offsets int64 [B][2] = first vertex row, first face row of each grid
+ *                   (the exclusive running sums of counts); vertices fp32 [sum V][3]; faces int32 [sum F][3], indices local to the grid.
+ * V <= (D+1)(H+1)(W+1), F <= 2 ((W+1)HD + (H+1)DW + (D+1)HW).  PCD_ERR_ARG (before any device work) for a null pointer, batch <= 0, an extent
+ * <= 1, a threshold <= 0 or not finite, or more than (2^31 - 1) / 6 cells per grid. */
+size_t pcd_mesh_workspace_bytes(int batch, int d, int h, int w);
+int pcd_mesh_count(const float* vox, int batch, int d, int h, int w, float threshold, void* workspace, int32_t* counts, void* stream);
+int pcd_mesh_emit(const float* vox, int batch, int d, int h, int w, float threshold, const void* workspace, const int64_t* offsets,
+                  float* vertices, int32_t* faces, void* stream);
+/* Which form the two mesh kernels take.  TEST / BENCHMARK ONLY: process-global.  1 (default): a grid of at most 144 KB is staged in LDS once
+ * per workgroup and the corner reads are served from there; 0: every grid is read through the vector cache, as larger grids always are.
+ * Same bits either way.  PCD_ERR_ARG for any other code. */
+int pcd_mesh_config(int code);
+
 /* ---- Sinkhorn EMD (metrics.py:94-158, `earth_mover_distance_gpu`), cost matrix never stored ----
  * out_max[0] = max over (b,i,j) of |x_i - y_j|   (the global C.max() of metrics.py:123) */
 int pcd_pairwise_max_dist(const float* x, const float* y, int batch, int n, int m, float* out_max, void* stream);
