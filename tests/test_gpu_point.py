@@ -332,6 +332,79 @@ def test_full_size_forward_next_to_the_oracle(model):
     assert rel_l2(eps[62:64], want) < EPS_TOL
 
 
+def _forward_with_taps(model, x, t, shapes):
+    """eps of the whole batch, and the x3 / x4 / d4 / d2 / pooled taps of `shapes`, on the host."""
+    b, n = x.shape[:2]
+    model.model.capture_decoder(b, n)
+    try:
+        eps = model.model(x.cuda(), t.cuda()).cpu()
+        taps = {k: model.model.tap(k, b, n)[shapes].float().cpu() for k in ("x3", "x4", "d4", "d2")}
+        taps["pooled"] = model.model.tap("pooled", b, n)[shapes].cpu()
+    finally:
+        model.model.capture_decoder(b, n, on=False)
+    return eps, taps
+
+
+def _assert_next_to_the_oracle(eps, taps_hip, x, t, shapes):
+    from oracle import torch_oracle as O
+    taps = {}
+    want = O.unet_pointnet_large(point_sd(), "model.", x[shapes], t[shapes], taps=taps)      # shapes are independent (SURVEY 8(e))
+    assert rel_l2(eps[shapes], want) < EPS_TOL
+    assert rel_l2(taps_hip["pooled"], taps["pooled"]) < 2e-3
+    for k in ("x3", "x4", "d4", "d2"):
+        assert rel_l2(taps_hip[k].transpose(1, 2), taps[k]) < 2.5e-3, k
+
+
+def test_ragged_batch_forward_next_to_the_oracle(model):
+    """B = 9, N = 2000: m = 18000 rows is past the 256 x 256 tile's threshold and no multiple of 256, so the wide chains are dropped and enc3, enc4,
+    global_feat, dec4 and dec3 run on the ragged generic 256 x 256 tile -- the column max with 2000-row shapes (every maximum an atomic), dec4.conv1
+    with a per-row per-shape bias.  Shapes 0, 1 and 8 (the last one owns the ragged rows) against the oracle; and the same three shapes as their own
+    small batches (m <= 4000: 128 x 128 tiles), which must give what the big batch gave -- the bound is test_full_size_properties' for a batch slice."""
+    gen = torch.Generator().manual_seed(9)
+    x = torch.randn(9, 2000, 3, generator=gen)
+    t = torch.rand(9, generator=gen)
+    shapes = [0, 1, 8]
+    eps, taps = _forward_with_taps(model, x, t, shapes)
+    assert torch.isfinite(eps).all()
+    _assert_next_to_the_oracle(eps, taps, x, t, shapes)
+    for sl in (slice(0, 2), slice(8, 9)):
+        sub = model.model(x[sl].contiguous().cuda(), t[sl].contiguous().cuda()).cpu()
+        print(f"B=9 N=2000, shapes {sl.start}..{sl.stop - 1} alone: rel-L2 to the big batch {rel_l2(sub, eps[sl]):.3e}, bitwise {torch.equal(sub, eps[sl])}")
+        assert rel_l2(sub, eps[sl]) < 1e-6, sl
+
+
+def test_straddling_batch_forward_next_to_the_oracle(model):
+    """B = 32, N = 640: m = 20480 rows is whole 256-row tiles, but a shape is 2.5 of them, so tiles straddle shapes: global_feat.3 goes to
+    gemm_xw_kernel (80 x 16 tiles, patches of 8 x 2) with the two wave tiles of one output tile in different shapes, the per-shape biases take the
+    per-row path.  Shapes 0, 1, 30 and 31 against the oracle; then the forward with gemm_xw_kernel off and with gemm_xp_kernel off (checked at
+    N = 2048 elsewhere), each bitwise the default."""
+    from shapegen_amd import _lib
+    lib = _lib.load()
+    d = _lib.GemmDesc()                                                     # global_feat.3 at this batch: the plan reads no address
+    d.a1 = d.w = d.bias = 64
+    d.k1, d.lda1, d.ldw, d.relu, d.m, d.c = 2048, 2048, 2048, 1, 32 * 640, 4096
+    plan = _lib.GemmPlan()
+    _lib.check(lib.pcd_gemm_plan(d, 6, 640, 0, 1, plan), "gemm_plan")
+    assert (plan.family, plan.tiles_m, plan.tiles_n, plan.patch_pn, plan.patch_xn) == (6, 80, 16, 8, 2)
+    gen = torch.Generator().manual_seed(32)
+    x = torch.randn(32, 640, 3, generator=gen)
+    t = torch.rand(32, generator=gen)
+    shapes = [0, 1, 30, 31]
+    eps, taps = _forward_with_taps(model, x, t, shapes)
+    assert torch.isfinite(eps).all()
+    _assert_next_to_the_oracle(eps, taps, x, t, shapes)
+    xd, td = x.cuda(), t.cuda()
+    for off, on, name in ((8, 9, "gemm_xw_kernel"), (5, 7, "gemm_xp_kernel")):
+        try:
+            assert lib.pcd_gemm_set_config(off) == 0
+            other = model.model(xd, td).cpu()
+            pooled = model.model.tap("pooled", 32, 640)[shapes].cpu()
+        finally:
+            assert lib.pcd_gemm_set_config(on) == 0
+        assert torch.equal(pooled, taps["pooled"]), name
+        assert torch.equal(other, eps), name
+
+
 def test_cpu_module_fails_loudly():
     from shapegen_amd.diffusion import PointCloudDiffusion
     m = PointCloudDiffusion(num_points=16)
