@@ -307,6 +307,10 @@ _SIGS = {
     "pcd_mesh_count": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp]),
     "pcd_mesh_emit": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "pcd_mesh_config": (i32, [i32]),
+    "pcd_mesh_voxelize_workspace_bytes": (sz, [i32, i32]),
+    "pcd_mesh_voxelize": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "pcd_mesh_sample_workspace_bytes": (sz, [i32, i64]),
+    "pcd_mesh_sample_points": (i32, [vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]),
     "pcd_pairwise_max_dist": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "pcd_sinkhorn_dual_update": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp]),
     "pcd_sinkhorn_cost": (i32, [vp, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),

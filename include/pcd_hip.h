@@ -872,6 +872,57 @@ int pcd_mesh_emit(const float* vox, int batch, int d, int h, int w, float thresh
  * Same bits either way.  PCD_ERR_ARG for any other code. */
 int pcd_mesh_config(int code);
 
+/* ---- Triangle meshes in: voxelizer and surface sampler (csrc/mesh_in.hip; DESIGN.md "Mesh input") ----
+ * A batch of meshes is packed as pcd_mesh_emit packs its outputs: vertices fp32 [sum V][3] rows [x, y, z]; faces int32 [sum F][3], indices
+ * local to the mesh; offsets int64 [B + 1][2] = first vertex row, first face row of each mesh, the totals in the last row.  A face with an
+ * index outside its mesh's rows is skipped (it marks nothing, has area 0).
+ *
+ * Voxelizer.  All index work is done in index coordinates p = (x - lo) * inv_pitch per component, inv_pitch = (R - 1) / (hi - lo) computed by the
+ * caller in double and passed as fp32: node i of an axis sits at p = i, which for bounds (-1, 1) inverts the 2 i / (R - 1) - 1 map of
+ * pcd_voxels_to_points / pcd_mesh_emit.  vox fp32 [B][R][R][R] indexed [z][y][x], values 0 or 1.
+ *   Surface   node (z, y, x) is 1 iff some triangle of the mesh intersects the closed cube of side 1 centred on the node: triangle / box overlap by
+ *             the 13 separating axes -- the 3 box normals, the triangle normal n = (b - a) x (c - a), and e x X, e x Y, e x Z for the edges
+ *             e = b - a, c - b, a - c.  With the vertices taken relative to the node, an axis separates iff the least projection of the three
+ *             vertices exceeds the cube's radius 1/2 (|l_x| + |l_y| + |l_z|) on that axis l, or the greatest is below its negative; touching
+ *             counts as intersecting.  A triangle of zero area is tested as the segment or point it is (its zero axes separate nothing).
+ *   Interior  for node (z, y, x) take every triangle whose projection on the xy plane covers the point (y, x): exact edge functions
+ *             E(p, q) = p_x q_y - p_y q_x of the vertices relative to the point, after orienting the projection counter-clockwise (b and c are
+ *             swapped when n_z < 0), covered iff all three are > 0 or, where one is 0, its edge is a top-left one: d_y < 0, or d_y = 0 and
+ *             d_x > 0, for d = q - p (the point is sampled at (x + eps, y + eps^2)).  Triangles with n_z = 0 contribute nothing.  With z* the
+ *             height of the triangle's plane over (y, x), the winding of the node is the sum of sign(n_z) over those triangles with z* > z
+ *             (strictly), decided without division as sign(n_z) n . (a - p) > 0, p the node.  The node is 1 iff the winding is not 0 (nonzero
+ *             winding, not parity: overlapping closed components fill as one solid, an inside-out one fills too).
+ *   Solid     the union of the two.
+ * The predicates are fp32 without contraction: on inputs whose intermediate values are exactly representable they decide ties as this statement
+ * does.  Integer atomics only, one workgroup per mesh, no host synchronisation: bitwise repeatable and independent of the rest of the batch.  A
+ * mesh without faces gives an all-zero grid.  workspace: pcd_mesh_voxelize_workspace_bytes() bytes (host arithmetic, 0 for arguments
+ * pcd_mesh_voxelize refuses), any contents; the accumulators of a grid with R > 32 live there, smaller ones in LDS.
+ * PCD_ERR_ARG (before any device work) for a null pointer, batch <= 0, r < 2 or r > 64, an unknown mode, a non-finite lo or inv_pitch, or
+ * inv_pitch <= 0. */
+#define PCD_MESH_FILL_SURFACE 0
+#define PCD_MESH_FILL_INTERIOR 1
+#define PCD_MESH_FILL_SOLID 2
+size_t pcd_mesh_voxelize_workspace_bytes(int batch, int r);
+int pcd_mesh_voxelize(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, int r, float lo, float inv_pitch,
+                      int mode, void* workspace, float* vox, void* stream);
+/* Sampler: points fp32 [B][N][3] uniform by area on each mesh's surface, in the vertices' own coordinates.  Two launches:
+ *   1. triangle areas |e0 x e1| / 2 in fp32 and, per mesh, their inclusive running sum, left in the workspace (fp32 [sum F],
+ *      pcd_mesh_sample_workspace_bytes() bytes); added in a fixed tree (lanes of a wave, the 16 waves, then chunks of 1024 faces in order), so the
+ *      same input gives the same bits.  A face whose area is not finite counts as 0.
+ *   2. per output point i of mesh b three uniforms u0, u1, u2 in [0, 1): u[b][i][0..2] when u (fp32 [B][N][3]) is not null, otherwise from
+ *      Philox4x32-10 as in pcd_randn -- counter words {lo(ctr), hi(ctr), 0, 0}, key {lo(seed), hi(seed)} -- with ctr = philox_offset + i and
+ *      u_k = (word k >> 8) / 2^24 (word 3 is not used).  The counter does not depend on b: a mesh gets in a batch the bits it gets alone, and
+ *      a call consumes the counters [philox_offset, philox_offset + N).  Triangle f is the first whose running sum exceeds u0 * total (the
+ *      last one at most); the point is (1 - s) A + s (1 - u2) B + s u2 C with s = sqrt(u1).
+ * normals (optional, fp32 [B][N][3]): the unit face normal (b - a) x (c - a) / |.|, zero for a zero-area face.  face_index (optional, int32
+ * [B][N]): f, local to the mesh.  A mesh whose total area is 0 puts every point on the first vertex of its first face; a mesh without faces
+ * gives zero rows (callers refuse them on the host, where offsets is built).  PCD_ERR_ARG for a null vertices, faces, offsets, workspace or
+ * points, batch <= 0 or > 65535, n_points <= 0. */
+size_t pcd_mesh_sample_workspace_bytes(int batch, int64_t total_faces);
+int pcd_mesh_sample_points(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, int n_points, uint64_t seed,
+                           uint64_t philox_offset, const float* u, void* workspace, float* points, float* normals, int32_t* face_index,
+                           void* stream);
+
 /* ---- Sinkhorn EMD (metrics.py:94-158, `earth_mover_distance_gpu`), cost matrix never stored ----
  * out_max[0] = max over (b,i,j) of |x_i - y_j|   (the global C.max() of metrics.py:123) */
 int pcd_pairwise_max_dist(const float* x, const float* y, int batch, int n, int m, float* out_max, void* stream);
