@@ -18,7 +18,9 @@
 // sab_head_kernel below does the block's first half in the same form (LN1 + in_proj).  Rows must be a multiple of 256 (otherwise the caller keeps the
 // separate launches).  Arithmetic: fp16 operands, fp32 accumulation; x1 and the
 // LayerNorm in fp32 (the four-launch form rounds x1 and LN2(x1) to fp16 in between: this form is the closer one to the reference's fp32).
+// Host side: the block's packed buffer is st_layout below; stage_images.h has the packer (stage_pack) and the launch (ring_launch).
 #include "common.h"
+#include "stage_images.h"
 
 namespace pcd {
 
@@ -40,8 +42,6 @@ struct StCfg {
     static constexpr int HSTAGE = NT * KS * 1024;      // one pass of W_in: C x C fp16
     static constexpr int HPPW = HSTAGE / 1024 / ST_WAVES;
     static constexpr int HB = 0, HGA = 3 * C, HBE = 4 * C, HNPAR = 5 * C;
-    static constexpr size_t TAIL_BYTES = (size_t)NSTG * STAGE + NPAR * sizeof(float);
-    static constexpr size_t HEAD_BYTES = (size_t)3 * HSTAGE + HNPAR * sizeof(float);
     static_assert(C == 64 || C == 128, "the tail kernel is built for C = 64 and C = 128");
     static_assert((2 * KS + 4 * NT) * 1024 == STAGE && NT * KS * 1024 <= STAGE, "stage image layout");
 };
@@ -339,85 +339,64 @@ __global__ __launch_bounds__(ST_THREADS, 2) void sab_head_kernel(SabHeadParams p
     }
 }
 
-// W [.][ldw] fp16 -> fragment-order pieces: piece (t * nq + q) * 64 + lane = the 8 halfs W[c0 + 32 t + (lane & 31)][k0 + 16 q + 8 (lane >> 5) .. + 7]
-__global__ __launch_bounds__(256) void st_pack_kernel(const half_t* __restrict__ w, int64_t ldw, int c0, int k0, int ntile, int nq, char* __restrict__ img) {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= ntile * nq * 64) return;
-    const int lane = id & 63, tq = id >> 6, t = tq / nq, q = tq - t * nq;
-    const int ch = c0 + 32 * t + (lane & 31);
-    *(half8*)(img + (size_t)id * 16) = *(const half8*)(w + (int64_t)ch * ldw + k0 + 16 * q + 8 * (lane >> 5));
-}
-
 static int g_sab_split = 1;     // pcd_sab_tail_config + 2 switches it off: one wave per SIMD requests a stage's LDS-DMA pieces
 static int g_sab_tail = 1;      // pcd_sab_tail_config: 0 = pcd_sab_forward keeps the four launches even where the descriptor carries a packed tail
 
-template <int C>
-static int tail_pack(const pcd_sab_desc_t& d, char* packed, hipStream_t s) {
-    using K = StCfg<C>;
-    PCD_CHECK_HIP(hipMemsetAsync(packed, 0, (size_t)K::NSTG * K::STAGE, s));
-    auto pack = [&](const void* w, int ldw, int c0, int k0, int ntile, int nq, char* img) {
-        const int n = ntile * nq * 64;
-        hipLaunchKernelGGL(st_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const half_t*)w, (int64_t)ldw, c0, k0, ntile, nq, img);
-    };
-    pack(d.w_out, C, 0, 0, K::NT, K::KS, packed);
-    for (int ch = 0; ch < K::NCH; ++ch) {
-        char* img = packed + (size_t)(1 + ch) * K::STAGE;
-        pack(d.w_ff1, C, 64 * ch, 0, 2, K::KS, img);
-        pack(d.w_ff2, 4 * C, 0, 64 * ch, K::NT, 4, img + K::W2OFF);
+// The block's buffer = the tail's part, then the head's; each is images | parameters, in the order StCfg gives the kernels.  Weights and parameters by index:
+enum { ST_W_OUT, ST_W_FF1, ST_W_FF2, ST_W_IN };
+enum { ST_B_OUT, ST_LN2_G, ST_LN2_B, ST_B_FF2, ST_B_FF1, ST_B_IN, ST_LN1_G, ST_LN1_B };
+constexpr StageLayout st_layout(int C, bool head) {
+    const int nt = C / 32, ks = C / 16;
+    StageLayout L{};
+    if (head) {                                                // W_in as three C-wide passes | b_in [3C] | ln1 gamma | ln1 beta
+        for (int i = 0; i < 3; ++i) sl_frag(L, ST_W_IN, C, i * C, 3 * C, 0, nt, ks);
+        sl_row(L, ST_B_IN, 0, 3 * C, 3 * C);
+        for (int i = ST_LN1_G; i <= ST_LN1_B; ++i) sl_row(L, i, 0, C, C);
+        return L;
     }
-    PCD_CHECK_LAUNCH();
-    float* par = (float*)(packed + (size_t)K::NSTG * K::STAGE);
-    PCD_CHECK_HIP(hipMemcpyAsync(par + K::BO, d.b_out, C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(par + K::GA, d.ln2_g, C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(par + K::BE, d.ln2_b, C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(par + K::B2, d.b_ff2, C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(par + K::B1, d.b_ff1, 4 * C * 4, hipMemcpyDeviceToDevice, s));
-    // the head's part: W_in as three passes, b_in, LN1 affine
-    char* head = packed + K::TAIL_BYTES;
-    for (int i = 0; i < 3; ++i) pack(d.w_in, C, i * C, 0, K::NT, K::KS, head + (size_t)i * K::HSTAGE);
-    PCD_CHECK_LAUNCH();
-    float* hpar = (float*)(head + (size_t)3 * K::HSTAGE);
-    PCD_CHECK_HIP(hipMemcpyAsync(hpar + K::HB, d.b_in, 3 * C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(hpar + K::HGA, d.ln1_g, C * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(hpar + K::HBE, d.ln1_b, C * 4, hipMemcpyDeviceToDevice, s));
-    return PCD_OK;
+    sl_frag(L, ST_W_OUT, C, 0, C, 0, nt, ks);
+    L.bytes = L.par = (2 * ks + 4 * nt) * 1024;                // a whole stage image: at C = 64 W_out fills half of it, the rest stays zero
+    for (int ch = 0; ch < C / 16; ++ch) {                      // per 64-wide chunk of the hidden channels [W1 chunk | W2 chunk]
+        sl_frag(L, ST_W_FF1, C, 64 * ch, 4 * C, 0, 2, ks);
+        sl_frag(L, ST_W_FF2, 4 * C, 0, C, 64 * ch, nt, 4);
+    }
+    for (int i = ST_B_OUT; i <= ST_B_FF2; ++i) sl_row(L, i, 0, C, C);
+    sl_row(L, ST_B_FF1, 0, 4 * C, 4 * C);
+    return L;
 }
+template <int C>
+constexpr bool st_layout_ok() {
+    using K = StCfg<C>;
+    constexpr StageLayout T = st_layout(C, false), H = st_layout(C, true);
+    return T.par == (size_t)K::NSTG * K::STAGE && T.bytes - T.par == K::NPAR * sizeof(float) && T.block[1].off == (size_t)K::STAGE &&
+           T.block[2].off == (size_t)K::STAGE + K::W2OFF && T.row[0].off == K::BO && T.row[1].off == K::GA && T.row[2].off == K::BE &&
+           T.row[3].off == K::B2 && T.row[4].off == K::B1 && H.par == (size_t)3 * K::HSTAGE && H.bytes - H.par == K::HNPAR * sizeof(float) &&
+           H.row[0].off == K::HB && H.row[1].off == K::HGA && H.row[2].off == K::HBE;
+}
+static_assert(st_layout_ok<64>() && st_layout_ok<128>(), "StCfg (what the kernels read) and the packed layout disagree");
 
 template <int C>
 static int head_launch(const void* packed, const void* x, int64_t m, void* qkv, const float* pre_e, int64_t estride, int rps, hipStream_t s) {
-    using K = StCfg<C>;
+    constexpr StageLayout T = st_layout(C, false), H = st_layout(C, true);
     SabHeadParams p{};
-    p.x = (const half_t*)x; p.packed = (const char*)packed + K::TAIL_BYTES; p.qkv = (half_t*)qkv; p.m = m;
+    p.x = (const half_t*)x; p.packed = (const char*)packed + T.bytes; p.qkv = (half_t*)qkv; p.m = m;
     p.pre_e = pre_e; p.estride = estride; p.rps = rps > 0 ? rps : 1;
     p.split = g_sab_split;
-    static PcdLdsOnce once;
-    const size_t lds = (size_t)ST_RING * K::HSTAGE + K::HNPAR * sizeof(float);
-    PCD_CHECK_HIP(pcd_allow_lds(once, (const void*)sab_head_kernel<C>, (int)lds));
-    const int64_t tiles = m / ST_TILE;
-    const int64_t cap = C == 64 ? 768 : 256;                   // C = 64: 74 registers, 26 KB of LDS: three workgroups per CU (HBM-bound: 67 MB per launch at cfg2)
-    const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
-    hipLaunchKernelGGL(sab_head_kernel<C>, dim3(grid), dim3(ST_THREADS), lds, s, p);
-    PCD_CHECK_LAUNCH();
+    PCD_CHECK_HIP((ring_launch<sab_head_kernel<C>, sab_head_kernel<C>>(m / ST_TILE, C == 64 ? RING_CAP_HEAD64 : RING_CAP_CU, ST_THREADS,
+                                                                      ST_RING * StCfg<C>::HSTAGE + H.bytes - H.par, false, s, p)));
     return PCD_OK;
 }
 
 template <int C>
 static int tail_launch(const void* packed, const void* a, const void* x, int64_t m, void* y, const float* pre_e, const float* post_e, int64_t estride, int rps,
                        hipStream_t s) {
-    using K = StCfg<C>;
+    constexpr StageLayout T = st_layout(C, false);
     SabTailParams p{};
     p.a = (const half_t*)a; p.x = (const half_t*)x; p.packed = (const char*)packed; p.y = (half_t*)y; p.m = m;
     p.pre_e = pre_e; p.post_e = post_e; p.estride = estride; p.rps = rps > 0 ? rps : 1;
     p.split = g_sab_split;
-    static PcdLdsOnce once;
-    const size_t lds = (size_t)ST_RING * K::STAGE + K::NPAR * sizeof(float);
-    PCD_CHECK_HIP(pcd_allow_lds(once, (const void*)sab_tail_kernel<C>, (int)lds));
-    const int64_t tiles = m / ST_TILE;
-    // C = 64: 128 registers and 50 KB of LDS let two workgroups share a CU, and the kernel is closer to its HBM bound than to the matrix pipe's
-    const int64_t cap = C == 64 ? 512 : 256;
-    const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
-    hipLaunchKernelGGL(sab_tail_kernel<C>, dim3(grid), dim3(ST_THREADS), lds, s, p);
-    PCD_CHECK_LAUNCH();
+    PCD_CHECK_HIP((ring_launch<sab_tail_kernel<C>, sab_tail_kernel<C>>(m / ST_TILE, C == 64 ? RING_CAP_TAIL64 : RING_CAP_CU, ST_THREADS,
+                                                                      ST_RING * StCfg<C>::STAGE + T.bytes - T.par, false, s, p)));
     return PCD_OK;
 }
 
@@ -426,9 +405,7 @@ static int tail_launch(const void* packed, const void* a, const void* x, int64_t
 using namespace pcd;
 
 extern "C" size_t pcd_sab_tail_packed_bytes(int dim) {
-    if (dim == 128) return StCfg<128>::TAIL_BYTES + StCfg<128>::HEAD_BYTES;
-    if (dim == 64) return StCfg<64>::TAIL_BYTES + StCfg<64>::HEAD_BYTES;
-    return 0;
+    return (dim == 64 || dim == 128) ? st_layout(dim, false).bytes + st_layout(dim, true).bytes : 0;
 }
 
 extern "C" int pcd_sab_tail_supported(int dim, int64_t rows) {
@@ -448,7 +425,12 @@ extern "C" int pcd_sab_tail_pack(const pcd_sab_desc_t* d, void* packed, void* st
     PCD_CHECK_ARG(d && packed && (d->dim == 64 || d->dim == 128));
     PCD_CHECK_ARG(d->w_out && d->b_out && d->ln2_g && d->ln2_b && d->w_ff1 && d->b_ff1 && d->w_ff2 && d->b_ff2);
     PCD_CHECK_ARG(d->w_in && d->b_in && d->ln1_g && d->ln1_b);
-    return d->dim == 128 ? tail_pack<128>(*d, (char*)packed, (hipStream_t)stream) : tail_pack<64>(*d, (char*)packed, (hipStream_t)stream);
+    const void* const weights[] = {d->w_out, d->w_ff1, d->w_ff2, d->w_in};                                     // ST_W_*
+    const float* const params[] = {d->b_out, d->ln2_g, d->ln2_b, d->b_ff2, d->b_ff1, d->b_in, d->ln1_g, d->ln1_b};     // ST_B_OUT ..
+    const StageLayout tail = st_layout(d->dim, false);
+    int rc = stage_pack(tail, weights, params, packed, (hipStream_t)stream);
+    if (rc == PCD_OK) rc = stage_pack(st_layout(d->dim, true), weights, params, (char*)packed + tail.bytes, (hipStream_t)stream);
+    return rc;
 }
 
 extern "C" int pcd_sab_tail_bias_f16(int dim, const void* packed, const void* a, const void* x, int64_t rows, int rows_per_shape, const float* pre_e,

@@ -14,7 +14,9 @@
 //     (256 points) of a workgroup; a 256 x 256 tile of work per 32 KB of LDS fill = 256 FLOP per filled byte, twice the GEMM's.
 // Output rows leave as 16-byte pieces (8 consecutive channels per lane after the same swap).  M must be a multiple of 256.
 // Further down, the same engine with a shape per segment takes the narrow layers next to these chains along (pw_wide_ends_kernel: E23, D21).
+// Host side: each packed buffer is one StageLayout (wc_layout, wl_layout, we_layout); stage_images.h has the packer (stage_pack) and the launch (ring_launch).
 #include "common.h"
+#include "stage_images.h"
 
 namespace pcd {
 
@@ -130,30 +132,30 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_chain_kernel(WcParams p
     }
 }
 
-// the largest dynamic LDS either launch form asks for (ring + bias rows of WC_MAXSEG passes + LayerNorm affine): set once, for both
+// the LN + Linear launches' dynamic LDS: the ring, then ln_lds where the kernel puts it (behind the bias rows of WC_MAXSEG passes)
 constexpr size_t WC_LDS_MAX = (size_t)WC_RING * WC_STAGE + (size_t)(WC_MAXSEG * 256 + 512) * sizeof(float);
-static hipError_t wc_allow_lds() {
-    static PcdLdsOnce once[4];
-    hipError_t e = pcd_allow_lds(once[0], (const void*)pw_wide_chain_kernel<false, false>, (int)WC_LDS_MAX);
-    if (e == hipSuccess) e = pcd_allow_lds(once[1], (const void*)pw_wide_chain_kernel<true, false>, (int)WC_LDS_MAX);
-    if (e == hipSuccess) e = pcd_allow_lds(once[2], (const void*)pw_wide_chain_kernel<false, true>, (int)WC_LDS_MAX);
-    if (e == hipSuccess) e = pcd_allow_lds(once[3], (const void*)pw_wide_chain_kernel<true, true>, (int)WC_LDS_MAX);
-    return e;
-}
 
-// W [C][ldw] fp16 (columns k0 .. k0 + 63 of channels c0 .. c0 + 255, rows >= c_limit read as zero) -> one stage image
-__global__ __launch_bounds__(256) void wc_pack_kernel(const half_t* __restrict__ w, int64_t ldw, int c0, int c_limit, int k0, char* __restrict__ img) {
-    // piece id = (t * 4 + q) * 64 + lane: 8 halfs W[c0 + 32 t + (lane & 31)][k0 + 16 q + 8 (lane >> 5) .. + 7]
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= 8 * 4 * 64) return;
-    const int lane = id & 63, tq = id >> 6, t = tq >> 2, q = tq & 3;
-    const int ch = c0 + 32 * t + (lane & 31);
-    half8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (half_t)0.f;
-    if (ch < c_limit) v = *(const half8*)(w + (int64_t)ch * ldw + k0 + 16 * q + 8 * (lane >> 5));
-    *(half8*)(img + (size_t)id * 16) = v;
+// E3 / D2: w[0..2] / b[0..2] as four 256-channel passes of four images (256 channels x 64 k each), then one bias row of 256 floats per pass
+constexpr StageLayout wc_layout(int chain) {
+    // per pass: layer, ldw, first channel, channel limit, first k, channels with a bias (0: the pass has no epilogue)
+    constexpr int pass[2][4][6] = {{{0, 256, 0, 256, 0, 256}, {1, 256, 0, 256, 0, 256}, {2, 256, 0, 512, 0, 256}, {2, 256, 256, 512, 0, 256}},
+                                   {{0, 512, 0, 256, 0, 0}, {0, 512, 0, 256, 256, 256}, {1, 256, 0, 256, 0, 256}, {2, 256, 0, 128, 0, 128}}};
+    StageLayout L{};
+    for (const auto& p : pass[chain]) sl_frag(L, p[0], p[1], p[2], p[3], p[4], 8, 4, 4);
+    for (const auto& p : pass[chain]) sl_row(L, p[0], p[2], p[5], 256);
+    return L;
 }
+constexpr StageLayout WC_LAYOUT[2] = {wc_layout(0), wc_layout(1)};
+
+// LN + Linear: w [256 P][256] as P passes | b [256 P] | gamma [256] | beta [256]
+constexpr StageLayout wl_layout(int passes) {
+    StageLayout L{};
+    for (int i = 0; i < passes; ++i) sl_frag(L, 0, 256, 256 * i, 256 * passes, 0, 8, 4, 4);
+    sl_row(L, 0, 0, 256 * passes, 256 * passes);
+    for (int i = 1; i < 3; ++i) sl_row(L, i, 0, 256, 256);
+    return L;
+}
+constexpr StageLayout WL_LAYOUT[4] = {wl_layout(1), wl_layout(2), wl_layout(3), wl_layout(4)};
 
 // ------------------------------------------------------------------------------------------------ the narrow ends: enc2 + enc3 and dec2 + dec1.conv1
 // The same engine with a shape per segment: K in {128, 256} input channels (K / 16 B fragments) x C in {128, 256} output channels (C / 32 accumulator
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(256) void wc_pack_kernel(const half_t* __restrict__
 //   E23: x1 [M][128] -> enc2.conv1 -> conv2 -> conv3 (x2 [M][256] stored AND kept as fragments) -> enc3.conv1 -> conv2 -> conv3 -> x3 [M][512]
 //   D21: [dec3 out [M][256] | x2 [M][256]] -> dec2.conv1 -> conv2 -> conv3 -> dec1.conv1 on [registers 128 | x1 [M][128]] -> [M][128]
 // A hi / lo layer is two segments on the same accumulators and the same B fragments: all hi K passes, then all lo passes (the order of pcd_gemm_f16_hilo).
-constexpr int WE_MAXSEG = 8, WE_MAXBIAS = 1536;
+constexpr int WE_MAXSEG = 8;
 enum { WE_K128_C128 = 0, WE_K128_C256 = 1, WE_K256_C128 = 2, WE_K256_C256 = 3 };
 
 struct WeSeg {
@@ -340,29 +342,33 @@ __global__ __launch_bounds__(WC_THREADS, 2) void pw_wide_ends_kernel(WeParams p)
     }
 }
 
-constexpr size_t WE_LDS = (size_t)WC_RING * WC_STAGE + (size_t)WE_MAXBIAS * sizeof(float);
-template <int CHAIN, bool HILO>
-static hipError_t we_launch(bool split, dim3 grid, size_t lds, hipStream_t s, const WeParams& p) {
-    static PcdLdsOnce once[2];
-    hipError_t e = pcd_allow_lds(once[0], (const void*)pw_wide_ends_kernel<CHAIN, HILO, false>, (int)WE_LDS);
-    if (e == hipSuccess) e = pcd_allow_lds(once[1], (const void*)pw_wide_ends_kernel<CHAIN, HILO, true>, (int)WE_LDS);
-    if (e != hipSuccess) return e;
-    if (split) hipLaunchKernelGGL((pw_wide_ends_kernel<CHAIN, HILO, true>), grid, dim3(WC_THREADS), lds, s, p);
-    else hipLaunchKernelGGL((pw_wide_ends_kernel<CHAIN, HILO, false>), grid, dim3(WC_THREADS), lds, s, p);
-    return hipGetLastError();
+// the ends' buffer from the plan: every segment's images in execution order (32 pieces each: 8 channel tiles x 4 k-steps or 4 x 8), then the layers' biases
+constexpr StageLayout we_layout(const WePlan& P) {
+    StageLayout L{};
+    for (int sg = 0; sg < P.nseg; ++sg) {
+        const WeSegSrc& f = P.from[sg];
+        const int kind = P.seg[sg].kind, nt = (kind == WE_K128_C128 || kind == WE_K256_C128) ? 4 : 8;
+        sl_frag(L, f.layer, f.ldw, f.c0, P.layer_c[f.layer], f.k0, nt, 32 / nt, we_kind_images(kind));
+    }
+    for (int i = 0; i < P.nlayer; ++i) sl_row(L, i, 0, P.layer_c[i], P.layer_c[i]);
+    return L;
 }
+// ... holds what the kernel takes from the plan itself: the stage count in front of the biases, and every layer's bias offset
+constexpr bool we_layout_ok(int chain, int hilo) {
+    const WePlan P = we_plan(chain, hilo);
+    const StageLayout L = we_layout(P);
+    bool ok = L.par == (size_t)P.nstage * WC_STAGE && L.bytes - L.par == P.nbias * sizeof(float);
+    for (int i = 0; i < P.nlayer; ++i) ok = ok && L.row[i].off == P.layer_bias[i];
+    return ok;
+}
+static_assert(we_layout_ok(0, 0) && we_layout_ok(0, 1) && we_layout_ok(1, 0) && we_layout_ok(1, 1), "ends: plan and packed layout disagree");
 
-// wc_pack_kernel for either image shape: nq = 4 (256 channels x 64 k, the same image) or 8 (128 channels x 128 k); piece id = (t * nq + q) * 64 + lane
-__global__ __launch_bounds__(256) void we_pack_kernel(const half_t* __restrict__ w, int64_t ldw, int c0, int c_limit, int k0, int nq, char* __restrict__ img) {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= 32 * 64) return;
-    const int lane = id & 63, tq = id >> 6, t = tq / nq, q = tq % nq;
-    const int ch = c0 + 32 * t + (lane & 31);
-    half8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (half_t)0.f;
-    if (ch < c_limit) v = *(const half8*)(w + (int64_t)ch * ldw + k0 + 16 * q + 8 * (lane >> 5));
-    *(half8*)(img + (size_t)id * 16) = v;
+template <int CHAIN, bool HILO>
+static hipError_t we_launch(bool split, hipStream_t s, WeParams& p) {
+    constexpr StageLayout L = we_layout(we_plan(CHAIN, HILO));
+    p.bias = (const float*)(p.wpacked + L.par);
+    return ring_launch<pw_wide_ends_kernel<CHAIN, HILO, false>, pw_wide_ends_kernel<CHAIN, HILO, true>>(p.m / WC_TILE, RING_CAP_CU, WC_THREADS,
+                                                                                                        WC_RING * WC_STAGE + L.bytes - L.par, split, s, p);
 }
 
 }  // namespace pcd
@@ -373,167 +379,99 @@ static int g_wc_split = 1;         // pcd_pw_wide_config: which waves request th
                                     // 2: in the LN + Linear launches too)
 extern "C" int pcd_pw_wide_config(int split) { g_wc_split = split < 0 ? 0 : (split > 2 ? 2 : split); return PCD_OK; }
 
-extern "C" size_t pcd_pw_wide_packed_bytes(int chain) {
-    return (chain == 0 || chain == 1) ? (size_t)16 * WC_STAGE + (size_t)4 * 256 * sizeof(float) : 0;
-}
+extern "C" size_t pcd_pw_wide_packed_bytes(int chain) { return (chain == 0 || chain == 1) ? WC_LAYOUT[chain].bytes : 0; }
 
 // chain 0 (E3): w[0..2] = enc3.conv1 [256][256], conv2 [256][256], conv3 [512][256]; chain 1 (D2): dec2.conv1 [256][512], conv2 [256][256],
-// conv3 [128][256].  Writes the stage images followed by the per-pass bias rows (4 x 256 fp32) into `packed`.
+// conv3 [128][256].  Writes the stage images followed by the per-pass bias rows (4 x 256 fp32) into `packed` (wc_layout).
 extern "C" int pcd_pw_wide_pack(int chain, const void* const* w, const float* const* b, void* packed, void* stream) {
     PCD_CHECK_ARG((chain == 0 || chain == 1) && w && b && packed && w[0] && w[1] && w[2] && b[0] && b[1] && b[2]);
-    hipStream_t s = (hipStream_t)stream;
-    char* img = (char*)packed;
-    float* bias = (float*)(img + (size_t)16 * WC_STAGE);
-    // passes in execution order: (weights, ldw, first channel, channel limit, first k, bias source, bias channels)
-    struct Pass { int layer; int ldw; int c0; int climit; int k0; };
-    const Pass e3[4] = {{0, 256, 0, 256, 0}, {1, 256, 0, 256, 0}, {2, 256, 0, 512, 0}, {2, 256, 256, 512, 0}};
-    const Pass d2[4] = {{0, 512, 0, 256, 0}, {0, 512, 0, 256, 256}, {1, 256, 0, 256, 0}, {2, 256, 0, 128, 0}};
-    const Pass* ps = chain == 0 ? e3 : d2;
-    for (int i = 0; i < 4; ++i)
-        for (int kt = 0; kt < 4; ++kt)
-            hipLaunchKernelGGL(wc_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w[ps[i].layer], (int64_t)ps[i].ldw, ps[i].c0, ps[i].climit,
-                               ps[i].k0 + 64 * kt, img + (size_t)(4 * i + kt) * WC_STAGE);
-    PCD_CHECK_LAUNCH();
-    PCD_CHECK_HIP(hipMemsetAsync(bias, 0, 4 * 256 * sizeof(float), s));
-    if (chain == 0) {
-        PCD_CHECK_HIP(hipMemcpyAsync(bias, b[0], 256 * 4, hipMemcpyDeviceToDevice, s));
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + 256, b[1], 256 * 4, hipMemcpyDeviceToDevice, s));
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + 512, b[2], 512 * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + 256, b[0], 256 * 4, hipMemcpyDeviceToDevice, s));      // pass 1 finishes dec2.conv1 (pass 0 has no epilogue)
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + 512, b[1], 256 * 4, hipMemcpyDeviceToDevice, s));
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + 768, b[2], 128 * 4, hipMemcpyDeviceToDevice, s));
-    }
-    return PCD_OK;
+    return stage_pack(WC_LAYOUT[chain], w, b, packed, (hipStream_t)stream);
 }
 
 extern "C" int pcd_pw_wide_chain(int chain, const void* in1, const void* in2, int64_t m, const void* packed, void* out, void* stream) {
     PCD_CHECK_ARG((chain == 0 || chain == 1) && in1 && packed && out && m > 0 && m % WC_TILE == 0);
     PCD_CHECK_ARG(chain == 0 || in2 != nullptr);
+    const StageLayout& L = WC_LAYOUT[chain];
     WcParams p{};
     p.in1 = (const half_t*)in1; p.in2 = (const half_t*)in2; p.m = m;
     p.wpacked = (const char*)packed;
-    p.bias = (const float*)((const char*)packed + (size_t)16 * WC_STAGE);
+    p.bias = (const float*)(p.wpacked + L.par);
     p.out = (half_t*)out;
     p.nseg = 4;
-    if (chain == 0) {
-        p.ldo = 512;
-        p.seg[0] = WcSeg{1, 0, 1, 0, 256, 0, 0, 0};
-        p.seg[1] = WcSeg{0, 0, 1, 0, 256, 256, 0, 0};
-        p.seg[2] = WcSeg{0, 0, 2, 0, 256, 512, 1, 0};
-        p.seg[3] = WcSeg{0, 0, 2, 256, 256, 768, 0, 0};
-    } else {
-        p.ldo = 128;
-        p.seg[0] = WcSeg{1, 0, 0, 0, 256, 0, 0, 0};
-        p.seg[1] = WcSeg{2, 1, 1, 0, 256, 256, 0, 0};
-        p.seg[2] = WcSeg{0, 0, 1, 0, 256, 512, 0, 0};
-        p.seg[3] = WcSeg{0, 0, 2, 0, 128, 768, 0, 0};
+    p.ldo = chain == 0 ? 512 : 128;
+    // how the kernel walks wc_layout's passes: {src, cont, finish, keep_b}; a pass's channels and bias row come from the layout
+    static const int walk[2][4][4] = {{{1, 0, 1, 0}, {0, 0, 1, 0}, {0, 0, 2, 1}, {0, 0, 2, 0}}, {{1, 0, 0, 0}, {2, 1, 1, 0}, {0, 0, 1, 0}, {0, 0, 2, 0}}};
+    for (int i = 0; i < 4; ++i) {
+        const FragBlock& b = L.block[i];
+        const int* w = walk[chain][i];
+        const int valid = b.row_limit - b.row0;
+        p.seg[i] = WcSeg{w[0], w[1], w[2], b.row0, valid < 256 ? valid : 256, L.row[i].off, w[3], 0};
     }
-    const size_t lds = (size_t)WC_RING * WC_STAGE + 4 * 256 * sizeof(float);
-    PCD_CHECK_HIP(wc_allow_lds());
-    const int64_t tiles = m / WC_TILE;
-    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    if (g_wc_split) hipLaunchKernelGGL((pw_wide_chain_kernel<false, true>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((pw_wide_chain_kernel<false, false>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
-    PCD_CHECK_LAUNCH();
+    PCD_CHECK_HIP((ring_launch<pw_wide_chain_kernel<false, false>, pw_wide_chain_kernel<false, true>>(
+        m / WC_TILE, RING_CAP_CU, WC_THREADS, WC_RING * WC_STAGE + L.bytes - L.par, g_wc_split != 0, (hipStream_t)stream, p)));
     return PCD_OK;
 }
 
 // ---- LayerNorm(256) + Linear(256, 256 P) [+ ReLU] as one launch of the same kernel (P <= 4 output passes over B fragments that are normalised as they are
 // loaded): the in_proj and the first FFN layer of the C = 256 attention blocks (reference networks.py:61-66, 81-82) without the LayerNorm launch and its
-// 67 + 67 MB.  packed = P x 4 stage images | bias [P][256] fp32 | gamma [256] | beta [256].
-extern "C" size_t pcd_pw_wide_ln_linear_packed_bytes(int passes) {
-    return (passes >= 1 && passes <= 4) ? (size_t)passes * 4 * WC_STAGE + (size_t)(passes * 256 + 512) * sizeof(float) : 0;
-}
+// 67 + 67 MB.  packed = P x 4 stage images | bias [P][256] fp32 | gamma [256] | beta [256] (wl_layout).
+extern "C" size_t pcd_pw_wide_ln_linear_packed_bytes(int passes) { return (passes >= 1 && passes <= 4) ? WL_LAYOUT[passes - 1].bytes : 0; }
 
 extern "C" int pcd_pw_wide_ln_linear_pack(const void* w, const float* b, int passes, const float* ln_g, const float* ln_b, void* packed, void* stream) {
     PCD_CHECK_ARG(w && b && ln_g && ln_b && packed && passes >= 1 && passes <= 4);
-    hipStream_t s = (hipStream_t)stream;
-    char* img = (char*)packed;
-    for (int i = 0; i < passes; ++i)
-        for (int kt = 0; kt < 4; ++kt)
-            hipLaunchKernelGGL(wc_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w, (int64_t)256, 256 * i, 256 * passes, 64 * kt,
-                               img + (size_t)(4 * i + kt) * WC_STAGE);
-    PCD_CHECK_LAUNCH();
-    float* f = (float*)(img + (size_t)passes * 4 * WC_STAGE);
-    PCD_CHECK_HIP(hipMemcpyAsync(f, b, (size_t)passes * 256 * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(f + passes * 256, ln_g, 256 * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(f + passes * 256 + 256, ln_b, 256 * 4, hipMemcpyDeviceToDevice, s));
-    return PCD_OK;
+    const float* const params[3] = {b, ln_g, ln_b};
+    return stage_pack(WL_LAYOUT[passes - 1], &w, params, packed, (hipStream_t)stream);
 }
 
 extern "C" int pcd_pw_wide_ln_linear_supported(int dim, int64_t rows) { return dim == 256 && rows > 0 && rows % WC_TILE == 0 ? 1 : 0; }
 
 extern "C" int pcd_pw_wide_ln_linear(const void* packed, int passes, int relu, const void* x, int64_t m, void* out, void* stream) {
     PCD_CHECK_ARG(packed && x && out && x != out && passes >= 1 && passes <= 4 && m > 0 && m % WC_TILE == 0);
+    const StageLayout& L = WL_LAYOUT[passes - 1];
     WcParams p{};
     p.in1 = (const half_t*)x; p.in2 = nullptr; p.m = m;
     p.wpacked = (const char*)packed;
-    p.bias = (const float*)((const char*)packed + (size_t)passes * 4 * WC_STAGE);
-    p.ln = p.bias + passes * 256;
+    p.bias = (const float*)(p.wpacked + L.par);
+    p.ln = p.bias + L.row[1].off;
     p.out = (half_t*)out; p.ldo = 256 * passes;
     p.nseg = passes;
-    for (int i = 0; i < passes; ++i) p.seg[i] = WcSeg{i == 0 ? 1 : 0, 0, 2, 256 * i, 256, 256 * i, i + 1 < passes ? 1 : 0, relu ? 0 : 1};
-    const size_t lds = WC_LDS_MAX;
-    PCD_CHECK_HIP(wc_allow_lds());
-    const int64_t tiles = m / WC_TILE;
-    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
+    for (int i = 0; i < passes; ++i) p.seg[i] = WcSeg{i == 0 ? 1 : 0, 0, 2, 256 * i, 256, L.row[0].off + 256 * i, i + 1 < passes ? 1 : 0, relu ? 0 : 1};
     // (the LN + Linear launches store a 256-wide output piece per pass: a requesting wave's vmcnt(0) would wait for those stores at every stage -- measured neutral to
     // slightly slower in the attention U-Net's forward, so they keep "every wave requests" unless pcd_pw_wide_config(2) asks for the split form)
-    if (g_wc_split == 2) hipLaunchKernelGGL((pw_wide_chain_kernel<true, true>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((pw_wide_chain_kernel<true, false>), dim3(grid), dim3(WC_THREADS), lds, (hipStream_t)stream, p);
-    PCD_CHECK_LAUNCH();
+    PCD_CHECK_HIP((ring_launch<pw_wide_chain_kernel<true, false>, pw_wide_chain_kernel<true, true>>(m / WC_TILE, RING_CAP_CU, WC_THREADS, WC_LDS_MAX, g_wc_split == 2,
+                                                                                                    (hipStream_t)stream, p)));
     return PCD_OK;
 }
 
 // ---- the narrow ends of UNetPointNetLarge as one launch each (pw_wide_ends_kernel): chain 0 = E23, enc2.conv1-3 + enc3.conv1-3 (w[0..5], b[0..5]: x1 [M][128] ->
 // x2 [M][256] and x3 [M][512]); chain 1 = D21, dec2.conv1-3 + dec1.conv1 (w[0..3]: [in1 [M][256] | in2 [M][256]] -> ... -> [. | in3 [M][128]] -> out [M][128]).
-// hilo: the chain's narrow layer (enc2.conv3 / dec1.conv1) carries [c][2 k] hi | lo weights.  packed = the stage images in execution order | the layers' biases.
+// hilo: the chain's narrow layer (enc2.conv3 / dec1.conv1) carries [c][2 k] hi | lo weights.  packed = the stage images in execution order | the layers' biases
+// (we_layout).
 extern "C" size_t pcd_pw_wide_ends_packed_bytes(int chain, int hilo) {
-    if (chain != 0 && chain != 1) return 0;
-    const WePlan P = we_plan(chain, hilo ? 1 : 0);
-    return (size_t)P.nstage * WC_STAGE + (size_t)P.nbias * sizeof(float);
+    return (chain == 0 || chain == 1) ? we_layout(we_plan(chain, hilo ? 1 : 0)).bytes : 0;
 }
 
 extern "C" int pcd_pw_wide_ends_pack(int chain, int hilo, const void* const* w, const float* const* b, void* packed, void* stream) {
     PCD_CHECK_ARG((chain == 0 || chain == 1) && w && b && packed);
     const WePlan P = we_plan(chain, hilo ? 1 : 0);
     for (int i = 0; i < P.nlayer; ++i) PCD_CHECK_ARG(w[i] != nullptr && b[i] != nullptr);
-    hipStream_t s = (hipStream_t)stream;
-    char* img = (char*)packed;
-    for (int sg = 0; sg < P.nseg; ++sg) {
-        const WeSegSrc& f = P.from[sg];
-        const int kind = P.seg[sg].kind;
-        const int nq = (kind == WE_K128_C128 || kind == WE_K256_C128) ? 8 : 4;
-        for (int i = 0; i < we_kind_images(kind); ++i, img += WC_STAGE)
-            hipLaunchKernelGGL(we_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w[f.layer], (int64_t)f.ldw, f.c0, P.layer_c[f.layer], f.k0 + 16 * nq * i, nq, img);
-    }
-    PCD_CHECK_LAUNCH();
-    float* bias = (float*)img;
-    for (int i = 0; i < P.nlayer; ++i)
-        PCD_CHECK_HIP(hipMemcpyAsync(bias + P.layer_bias[i], b[i], (size_t)P.layer_c[i] * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return PCD_OK;
+    return stage_pack(we_layout(P), w, b, packed, (hipStream_t)stream);
 }
 
 extern "C" int pcd_pw_wide_ends(int chain, int hilo, const void* in1, const void* in2, const void* in3, int64_t m, const void* packed, void* out, void* out2,
                                 void* stream) {
     PCD_CHECK_ARG((chain == 0 || chain == 1) && in1 && packed && out && m > 0 && m % WC_TILE == 0 && m <= 0x7fffffff);
     PCD_CHECK_ARG(chain == 0 ? out2 != nullptr : (in2 != nullptr && in3 != nullptr));
-    const WePlan P = we_plan(chain, hilo ? 1 : 0);
     WeParams p{};
     p.in1 = (const half_t*)in1; p.in2 = (const half_t*)in2; p.in3 = (const half_t*)in3; p.m = m;
     p.wpacked = (const char*)packed;
-    p.bias = (const float*)((const char*)packed + (size_t)P.nstage * WC_STAGE);
     p.out = (half_t*)out;
     p.out2 = (half_t*)out2;
-    const size_t lds = (size_t)WC_RING * WC_STAGE + (size_t)P.nbias * sizeof(float);
-    const int64_t tiles = m / WC_TILE;
-    const dim3 grid((unsigned)(tiles < 256 ? tiles : 256));
     hipStream_t s = (hipStream_t)stream;
     const bool split = g_wc_split != 0;
     hipError_t e;
-    if (chain == 0) e = hilo ? we_launch<0, true>(split, grid, lds, s, p) : we_launch<0, false>(split, grid, lds, s, p);
-    else e = hilo ? we_launch<1, true>(split, grid, lds, s, p) : we_launch<1, false>(split, grid, lds, s, p);
+    if (chain == 0) e = hilo ? we_launch<0, true>(split, s, p) : we_launch<0, false>(split, s, p);
+    else e = hilo ? we_launch<1, true>(split, s, p) : we_launch<1, false>(split, s, p);
     PCD_CHECK_HIP(e);
     return PCD_OK;
 }

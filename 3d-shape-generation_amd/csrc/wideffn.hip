@@ -14,7 +14,9 @@
 //   * epilogue: + b2 + x1 (re-read, 16 bytes per lane and piece), fp16, 16-byte stores.
 // Registers: 64 (input) + 64 (output accumulators) + 32 + 16 + 16 + weight fragments: two waves per SIMD.  LDS: 96 KB ring + 32 KB exchange + 7 KB constants.
 // 128 FLOP per filled byte (a 128-point tile re-streams the 1 MB of weights); the 268-MB hidden tensor never exists.  rows % 128 == 0.
+// Host side: the packed buffer is wf_layout below; stage_images.h has the packer (stage_pack) and the launch (ring_launch).
 #include "common.h"
+#include "stage_images.h"
 
 namespace pcd {
 
@@ -211,13 +213,21 @@ __global__ __launch_bounds__(WF_THREADS, 2) void wide_ffn_kernel(WfParams p) {
     }
 }
 
-// W [rows][ldw] fp16 -> one stage image of nblk x nq fragments: fragment (blk, qq) = rows row0 + 32 blk .. + 31, columns k0 + 16 qq .. + 15
-__global__ __launch_bounds__(256) void wf_pack_kernel(const half_t* __restrict__ w, int64_t ldw, int row0, int nblk, int k0, int nq, char* __restrict__ img) {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= nblk * nq * 64) return;
-    const int lane = id & 63, fr = id >> 6, blk = fr / nq, qq = fr - blk * nq;
-    *(half8*)(img + (size_t)id * 16) = *(const half8*)(w + (int64_t)(row0 + 32 * blk + (lane & 31)) * ldw + k0 + 16 * qq + 8 * (lane >> 5));
+// weights {w1 [1024][256], w2 [256][1024]}, params {b1, b2, gamma, beta}.  Per slab: W1's 128 rows as two images of [4 tiles][8 k-steps] (128 k each), then W2's 256
+// rows x the slab's 128 k as two images of [8 tiles][4 k-steps] (64 k each); the constants in the order the kernel reads them
+constexpr StageLayout wf_layout() {
+    StageLayout L{};
+    for (int slab = 0; slab < WF_SLABS; ++slab) {
+        sl_frag(L, 0, 256, 128 * slab, 1024, 0, 4, 8, 2);
+        sl_frag(L, 1, 1024, 0, 256, 128 * slab, 8, 4, 2);
+    }
+    sl_row(L, 0, 0, 1024, 1024);
+    for (int i = 1; i < 4; ++i) sl_row(L, i, 0, 256, 256);
+    return L;
 }
+constexpr StageLayout WF_LAYOUT = wf_layout();
+static_assert(WF_LAYOUT.par == WF_IMG_BYTES && WF_LAYOUT.bytes == WF_IMG_BYTES + WF_NCONST * sizeof(float), "wide_ffn_kernel's constants and the packed layout disagree");
+static_assert(WF_LAYOUT.row[1].off == 1024 && WF_LAYOUT.row[2].off == 1280 && WF_LAYOUT.row[3].off == 1536, "b2 | gamma | beta where wide_ffn_kernel reads them");
 
 }  // namespace pcd
 
@@ -232,7 +242,7 @@ extern "C" int pcd_wide_ffn_config(int split) {
     return PCD_OK;
 }
 
-extern "C" size_t pcd_wide_ffn_packed_bytes(void) { return WF_IMG_BYTES + (size_t)WF_NCONST * sizeof(float); }
+extern "C" size_t pcd_wide_ffn_packed_bytes(void) { return WF_LAYOUT.bytes; }
 
 extern "C" int pcd_wide_ffn_supported(int dim, int64_t rows) { return dim == 256 && rows > 0 && rows % WF_TILE == 0 ? 1 : 0; }
 
@@ -240,22 +250,9 @@ extern "C" int pcd_wide_ffn_supported(int dim, int64_t rows) { return dim == 256
 extern "C" int pcd_wide_ffn_pack(const void* w1, const float* b1, const void* w2, const float* b2, const float* ln_g, const float* ln_b, void* packed,
                                  void* stream) {
     PCD_CHECK_ARG(w1 && b1 && w2 && b2 && ln_g && ln_b && packed);
-    hipStream_t s = (hipStream_t)stream;
-    char* img = (char*)packed;
-    for (int slab = 0; slab < WF_SLABS; ++slab)
-        for (int j = 0; j < 2; ++j) {
-            hipLaunchKernelGGL(wf_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w1, (int64_t)256, slab * 128, 4, 128 * j, 8,
-                               img + (size_t)(4 * slab + j) * WF_STAGE);
-            hipLaunchKernelGGL(wf_pack_kernel, dim3(8), dim3(256), 0, s, (const half_t*)w2, (int64_t)1024, 0, 8, slab * 128 + 64 * j, 4,
-                               img + (size_t)(4 * slab + 2 + j) * WF_STAGE);
-        }
-    PCD_CHECK_LAUNCH();
-    float* f = (float*)(img + WF_IMG_BYTES);
-    PCD_CHECK_HIP(hipMemcpyAsync(f, b1, 1024 * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(f + 1024, b2, 256 * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(f + 1280, ln_g, 256 * 4, hipMemcpyDeviceToDevice, s));
-    PCD_CHECK_HIP(hipMemcpyAsync(f + 1536, ln_b, 256 * 4, hipMemcpyDeviceToDevice, s));
-    return PCD_OK;
+    const void* const weights[2] = {w1, w2};
+    const float* const params[4] = {b1, b2, ln_g, ln_b};
+    return stage_pack(WF_LAYOUT, weights, params, packed, (hipStream_t)stream);
 }
 
 extern "C" int pcd_wide_ffn_f16(const void* packed, const void* x, int64_t rows, void* y, void* stream) {
@@ -266,26 +263,17 @@ extern "C" int pcd_wide_ffn_f16(const void* packed, const void* x, int64_t rows,
 extern "C" int pcd_wide_ffn_bias_f16(const void* packed, const void* x, int64_t rows, int rows_per_shape, const float* post_e, int64_t e_stride, void* y, void* stream) {
     PCD_CHECK_ARG(packed && x && y && rows > 0 && rows % WF_TILE == 0);
     PCD_CHECK_ARG(post_e == nullptr || (rows_per_shape > 0 && e_stride >= 0 && e_stride % 4 == 0 && ((uintptr_t)post_e & 15) == 0));
-    static PcdLdsOnce once, once_split;
-    PCD_CHECK_HIP(pcd_allow_lds(once, (const void*)wide_ffn_kernel<false>, (int)WF_LDS));
-    PCD_CHECK_HIP(pcd_allow_lds(once_split, (const void*)wide_ffn_kernel<true>, (int)WF_LDS));
     WfParams p{};
     p.x = (const half_t*)x; p.wpacked = (const char*)packed; p.y = (half_t*)y; p.m = rows;
     p.post_e = post_e; p.estride = e_stride; p.rps = rows_per_shape > 0 ? rows_per_shape : 1;
-    const int64_t tiles = rows / WF_TILE;
-    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-#define PCD_WF_ABL(A)                                                                                                  \
-    if (g_wf_abl == A) {                                                                                                \
-        static PcdLdsOnce once_a;                                                                                       \
-        PCD_CHECK_HIP(pcd_allow_lds(once_a, (const void*)wide_ffn_kernel<true, A>, (int)WF_LDS));                       \
-        hipLaunchKernelGGL((wide_ffn_kernel<true, A>), dim3(grid), dim3(WF_THREADS), WF_LDS, (hipStream_t)stream, p);   \
-        PCD_CHECK_LAUNCH();                                                                                             \
-        return PCD_OK;                                                                                                  \
-    }
+    // (an ablation is an instantiation of the split form, whatever pcd_wide_ffn_config chose)
+#define PCD_WF_LAUNCH(EVERY, SPLIT) \
+    PCD_CHECK_HIP((ring_launch<EVERY, SPLIT>(rows / WF_TILE, RING_CAP_CU, WF_THREADS, WF_LDS, g_wf_split != 0, (hipStream_t)stream, p)))
+#define PCD_WF_ABL(A) \
+    if (g_wf_abl == A) { PCD_WF_LAUNCH((wide_ffn_kernel<true, A>), (wide_ffn_kernel<true, A>)); return PCD_OK; }
     PCD_WF_ABL(1) PCD_WF_ABL(2) PCD_WF_ABL(3) PCD_WF_ABL(4) PCD_WF_ABL(5) PCD_WF_ABL(8) PCD_WF_ABL(9) PCD_WF_ABL(10) PCD_WF_ABL(7) PCD_WF_ABL(11)
 #undef PCD_WF_ABL
-    if (g_wf_split) hipLaunchKernelGGL(wide_ffn_kernel<true>, dim3(grid), dim3(WF_THREADS), WF_LDS, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(wide_ffn_kernel<false>, dim3(grid), dim3(WF_THREADS), WF_LDS, (hipStream_t)stream, p);
-    PCD_CHECK_LAUNCH();
+    PCD_WF_LAUNCH(wide_ffn_kernel<false>, wide_ffn_kernel<true>);
+#undef PCD_WF_LAUNCH
     return PCD_OK;
 }

@@ -384,46 +384,41 @@ class _PackedSAB:
         self.ln2_g, self.ln2_b = _dev32(g("ln2.weight"), dev), _dev32(g("ln2.bias"), dev)
         self.w_ff1, self.b_ff1 = devw(g("ff.0.weight"), dev), _dev32(g("ff.0.bias"), dev)
         self.w_ff2, self.b_ff2 = devw(g("ff.2.weight"), dev), _dev32(g("ff.2.bias"), dev)
-        self.tail = None
-        self.lnlin = None
-        self.ffn = None
+        self.packed = {}                                                   # descriptor field -> the packed buffer it points to
         self.f32 = f32
 
     def fill(self, d: "_lib.SabDesc") -> "_lib.SabDesc":
         d.dim = self.dim
         for k in ("w_in", "b_in", "w_out", "b_out", "ln1_g", "ln1_b", "ln2_g", "ln2_b", "w_ff1", "b_ff1", "w_ff2", "b_ff2"):
             setattr(d, k, getattr(self, k).data_ptr())
-        d.tail_packed = None
-        d.ln_in_packed = d.ln_ff1_packed = d.ffn_packed = None
-        packed_now = False
-        # C <= 128, fp16: the block's tail (out_proj + residual + LN2 + FFN + residual) as one launch needs its weights in fragment-order stage images
         lib = _lib.load()
-        nbytes = 0 if self.f32 else lib.pcd_sab_tail_packed_bytes(self.dim)
-        if nbytes:
-            if self.tail is None:
-                self.tail = torch.empty(nbytes, dtype=torch.uint8, device=self.w_out.device)
-                _lib.check(lib.pcd_sab_tail_pack(C.byref(d), self.tail.data_ptr(), _lib.stream_ptr()), "sab_tail_pack")
-                packed_now = True
-            d.tail_packed = self.tail.data_ptr()
-        # C = 256, fp16: LN1 + in_proj and LN2 + ff.0 as one launch each (wide-chain kernel with a LayerNorm prologue)
+        p = lambda *names: [getattr(self, n).data_ptr() for n in names]
+        # fp16 only: (descriptor field, bytes, packer(destination, stream)) of the fragment-order stage images a fused launch reads
+        fused = []
+        if not self.f32:
+            # C <= 128 (0 bytes otherwise): the block's head (LN1 + in_proj) and tail (out_proj + residual + LN2 + FFN + residual) as one launch each
+            fused.append(("tail_packed", lib.pcd_sab_tail_packed_bytes(self.dim), lambda dst, st: lib.pcd_sab_tail_pack(C.byref(d), dst, st)))
         if self.dim == 256 and not self.f32:
-            if self.lnlin is None:
-                bufs = []
-                for w, b, passes, g_, b_ in ((self.w_in, self.b_in, 3, self.ln1_g, self.ln1_b), (self.w_ff1, self.b_ff1, 4, self.ln2_g, self.ln2_b)):
-                    buf = torch.empty(lib.pcd_pw_wide_ln_linear_packed_bytes(passes), dtype=torch.uint8, device=self.w_out.device)
-                    _lib.check(lib.pcd_pw_wide_ln_linear_pack(w.data_ptr(), b.data_ptr(), passes, g_.data_ptr(), b_.data_ptr(), buf.data_ptr(),
-                                                              _lib.stream_ptr()), "pw_wide_ln_linear_pack")
-                    bufs.append(buf)
-                self.lnlin = bufs
-                packed_now = True
-            d.ln_in_packed, d.ln_ff1_packed = self.lnlin[0].data_ptr(), self.lnlin[1].data_ptr()
+            # LN1 + in_proj and LN2 + ff.0 as one launch each (wide-chain kernel with a LayerNorm prologue) ...
+            ln_linear = lambda passes, *names: (lib.pcd_pw_wide_ln_linear_packed_bytes(passes),
+                                                lambda dst, st: lib.pcd_pw_wide_ln_linear_pack(*p(*names[:2]), passes, *p(*names[2:]), dst, st))
+            fused.append(("ln_in_packed", *ln_linear(3, "w_in", "b_in", "ln1_g", "ln1_b")))
+            fused.append(("ln_ff1_packed", *ln_linear(4, "w_ff1", "b_ff1", "ln2_g", "ln2_b")))
             # ... and LN2 + ff.0 + ReLU + ff.2 + residual as ONE launch (csrc/wideffn.hip): the 4C-wide hidden tensor is never written
-            if self.ffn is None:
-                self.ffn = torch.empty(lib.pcd_wide_ffn_packed_bytes(), dtype=torch.uint8, device=self.w_out.device)
-                _lib.check(lib.pcd_wide_ffn_pack(self.w_ff1.data_ptr(), self.b_ff1.data_ptr(), self.w_ff2.data_ptr(), self.b_ff2.data_ptr(),
-                                                 self.ln2_g.data_ptr(), self.ln2_b.data_ptr(), self.ffn.data_ptr(), _lib.stream_ptr()), "wide_ffn_pack")
+            fused.append(("ffn_packed", lib.pcd_wide_ffn_packed_bytes(),
+                          lambda dst, st: lib.pcd_wide_ffn_pack(*p("w_ff1", "b_ff1", "w_ff2", "b_ff2", "ln2_g", "ln2_b"), dst, st)))
+        packed_now = False
+        for field in ("tail_packed", "ln_in_packed", "ln_ff1_packed", "ffn_packed"):
+            setattr(d, field, None)
+        for field, nbytes, pack in fused:
+            if not nbytes:
+                continue
+            if field not in self.packed:
+                buf = torch.empty(nbytes, dtype=torch.uint8, device=self.w_out.device)
+                _lib.check(pack(buf.data_ptr(), _lib.stream_ptr()), field)
+                self.packed[field] = buf
                 packed_now = True
-            d.ffn_packed = self.ffn.data_ptr()
+            setattr(d, field, self.packed[field].data_ptr())
         if packed_now:
             # the images were written by pack kernels on the CURRENT stream; a forward enqueued on another stream (a side stream, a capture) must find them
             # complete: one synchronisation per model packing
