@@ -110,6 +110,11 @@ class VaeDesc(C.Structure):
                 ("taps3", vp), ("taps4s2", vp), ("taps4p0", vp), ("taps1", vp), ("zero_page", vp)]
 
 
+class RenderStyle(C.Structure):
+    """pcd_render_style_t"""
+    _fields_ = [("colors", vp), ("light", f32 * 3), ("ambient", f32), ("background", f32 * 3)]
+
+
 # offsets[] of pcd_pair_metrics_workspace_layout, in the order of the header's PCD_PAIR_WS_* enum
 PCD_PAIR_WS = ("an", "bn", "mins", "alpha", "beta", "rowc", "cmax", "err", "bits", "total")
 
@@ -311,6 +316,9 @@ _SIGS = {
     "pcd_mesh_voxelize": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
     "pcd_mesh_sample_workspace_bytes": (sz, [i32, i64]),
     "pcd_mesh_sample_points": (i32, [vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "pcd_render_points": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, f32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
+    "pcd_render_meshes": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
+    "pcd_render_config": (i32, [i32]),
     "pcd_pairwise_max_dist": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "pcd_sinkhorn_dual_update": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp]),
     "pcd_sinkhorn_cost": (i32, [vp, vp, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),

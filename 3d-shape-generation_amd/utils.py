@@ -364,6 +364,192 @@ def sample_mesh_points(meshes, num_points: int, seed: Optional[int] = None, retu
     return out[0] if len(out) == 1 else out
 
 
+# ------------------------------------------------------------------ images out (csrc/render.hip)
+DEFAULT_LIGHT = (-0.4, -0.6, -0.7)                               # normalised by the caller; view space, towards the surfaces that face the eye
+DEFAULT_COLOR = (0.27, 0.51, 0.71)
+RENDER_MAX_SIDE, RENDER_MAX_RADIUS = 2048, 64.0
+
+
+def orbit_view(azim: float, elev: float, height: int, width: int, half_extent: float = 1.0, center=(0.0, 0.0, 0.0)) -> torch.Tensor:
+    """(3, 4) float32 view [M | t] (DESIGN.md "Render"): an orthographic camera on a sphere round `center`, world z up, angles in degrees in
+    matplotlib's convention, `half_extent` world units from the centre to the nearer image border.  Host arithmetic in float64."""
+    if not (half_extent > 0.0 and np.isfinite(half_extent)):
+        raise ValueError(f"half_extent must be positive and finite, got {half_extent!r}")
+    a, e = np.deg2rad(float(azim)), np.deg2rad(float(elev))
+    s = min(int(height), int(width)) / (2.0 * float(half_extent))
+    right = np.array([-np.sin(a), np.cos(a), 0.0])
+    up = np.array([-np.cos(a) * np.sin(e), -np.sin(a) * np.sin(e), np.cos(e)])
+    toward = np.array([np.cos(a) * np.cos(e), np.sin(a) * np.cos(e), np.sin(e)])
+    m = np.stack([s * right, -s * up, -s * toward])
+    t = np.array([width / 2.0, height / 2.0, 0.0]) - m @ np.asarray(center, np.float64).reshape(3)
+    return torch.from_numpy(np.concatenate([m, t[:, None]], axis=1).astype(np.float32))
+
+
+def orbit_views(n: int, elev: float, height: int, width: int, half_extent: float = 1.0, center=(0.0, 0.0, 0.0),
+                azim0: float = -60.0) -> torch.Tensor:
+    """(n, 3, 4) float32: a turntable of `n` views at azimuths azim0 + 360 i / n."""
+    if int(n) < 1:
+        raise ValueError(f"orbit_views needs n >= 1, got {n!r}")
+    return torch.stack([orbit_view(azim0 + 360.0 * i / int(n), elev, height, width, half_extent, center) for i in range(int(n))])
+
+
+def _render_args(what, batch, views, height, width, radius, color, background, light, ambient, device):
+    """Validate on the host and build (views tensor, view_sets, V, RenderStyle, the tensors it points to)."""
+    h, w = int(height), int(width)
+    if h != height or w != width or not (1 <= h <= RENDER_MAX_SIDE and 1 <= w <= RENDER_MAX_SIDE):
+        raise ValueError(f"{what}: height and width must be integers in 1..{RENDER_MAX_SIDE}, got {height!r} x {width!r}")
+    if not (0.0 < float(radius) <= RENDER_MAX_RADIUS):
+        raise ValueError(f"{what}: radius must be in (0, {RENDER_MAX_RADIUS:g}] pixels, got {radius!r}")
+    if not (0.0 <= float(ambient) <= 1.0):
+        raise ValueError(f"{what}: ambient must be in [0, 1], got {ambient!r}")
+    v = torch.as_tensor(views, dtype=torch.float32)
+    if v.dim() == 2:
+        v = v.unsqueeze(0)
+    if v.dim() not in (3, 4) or tuple(v.shape[-2:]) != (3, 4) or v.shape[-3] < 1 or (v.dim() == 4 and v.shape[0] != batch):
+        raise ValueError(f"{what}: views must be (3, 4), (V, 3, 4) or ({batch}, V, 3, 4), got {tuple(v.shape)}")
+    view_sets = batch if v.dim() == 4 else 1
+    n_views = int(v.shape[-3])
+    v = v.to(device).contiguous()
+    light = np.asarray(DEFAULT_LIGHT if light is None else light, np.float64).reshape(-1)
+    if light.shape != (3,) or not np.isfinite(light).all() or not np.linalg.norm(light) > 0.0:
+        raise ValueError(f"{what}: light must be a non-zero 3-vector")
+    light = light / np.linalg.norm(light)
+    bg = np.asarray(background, np.float64).reshape(-1)
+    if bg.shape != (3,) or not ((bg >= 0.0) & (bg <= 1.0)).all():
+        raise ValueError(f"{what}: background must be an RGB in [0, 1]")
+    col = np.asarray(DEFAULT_COLOR if color is None else color, np.float64)
+    if col.shape == (3,):
+        col = np.broadcast_to(col, (batch, 3))
+    if col.shape != (batch, 3) or not ((col >= 0.0) & (col <= 1.0)).all():
+        raise ValueError(f"{what}: color must be an RGB in [0, 1] or one per shape ({batch}, 3)")
+    colors = torch.from_numpy(np.ascontiguousarray(col, dtype=np.float32)).to(device)
+    style = _lib.RenderStyle(colors.data_ptr(), (_lib.f32 * 3)(*light), float(ambient), (_lib.f32 * 3)(*bg))
+    return v, view_sets, n_views, style, colors
+
+
+def _render_outputs(batch, n_views, h, w, device, return_buffers):
+    rgb = torch.empty(batch, n_views, h, w, 3, dtype=torch.uint8, device=device)
+    ids = torch.empty(batch, n_views, h, w, dtype=torch.int32, device=device) if return_buffers else None
+    depth = torch.empty(batch, n_views, h, w, dtype=torch.float32, device=device) if return_buffers else None
+    return rgb, ids, depth
+
+
+def render_point_clouds(clouds, views, height: int = 256, width: int = 256, radius: float = 1.5, color=None, background=(1.0, 1.0, 1.0),
+                        light=None, ambient: float = 0.3, return_buffers: bool = False):
+    """Depth-buffered discs (sphere impostors) of `radius` pixels (DESIGN.md "Render").  `clouds`: a (B, N, 3) tensor or a list of (n_i, 3)
+    tensors on the device (the ragged output of `voxel_tensor_to_point_clouds`); an empty cloud gives a background image.  `views`: (3, 4),
+    (V, 3, 4) shared by the shapes, or (B, V, 3, 4) (`orbit_view`, `orbit_views`).  -> uint8 (B, V, H, W, 3) on the device; with `return_buffers`
+    also ids int32 (B, V, H, W) (the winning row of the cloud, -1 for background) and depth float32 (+inf for background).  One launch, integer
+    atomics only: bitwise repeatable and independent of the rest of the batch."""
+    what = "render_point_clouds"
+    if torch.is_tensor(clouds):
+        if clouds.dim() != 3 or clouds.shape[2] != 3:
+            raise ValueError(f"{what}: a cloud tensor must be (B, N, 3), got {tuple(clouds.shape)}")
+        clouds = list(clouds)
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError(f"{what}: no clouds")
+    rows = [0]
+    for i, c in enumerate(clouds):
+        if c.dim() != 2 or c.shape[1] != 3:
+            raise ValueError(f"{what}: cloud {i} is not (n, 3)")
+        if c.device.type != "cuda":
+            raise RuntimeError(f"{what} runs only on an MI355X device (no CPU path)")
+        rows.append(rows[-1] + c.shape[0])
+    dev, b = clouds[0].device, len(clouds)
+    v, view_sets, n_views, style, keep = _render_args(what, b, views, height, width, radius, color, background, light, ambient, dev)
+    pts = torch.cat([c.to(torch.float32) for c in clouds]).contiguous() if rows[-1] else torch.zeros(1, 3, dtype=torch.float32, device=dev)
+    offsets = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)
+    rgb, ids, depth = _render_outputs(b, n_views, int(height), int(width), dev, return_buffers)
+    _lib.check(_lib.load().pcd_render_points(pts.data_ptr(), offsets.data_ptr(), b, v.data_ptr(), view_sets, n_views, int(height), int(width),
+                                             float(radius), style, _lib.ptr(ids), _lib.ptr(depth), rgb.data_ptr(), _lib.stream_ptr()),
+               "render_points")
+    return (rgb, ids, depth) if return_buffers else rgb
+
+
+def render_meshes(meshes, views, height: int = 256, width: int = 256, color=None, background=(1.0, 1.0, 1.0), light=None,
+                  ambient: float = 0.3, return_buffers: bool = False):
+    """Depth-buffered flat-shaded triangles, both faces drawn, watertight along shared edges (DESIGN.md "Render").  `meshes`: a list of `Mesh` /
+    (vertices, faces) pairs on the device; a mesh without faces gives a background image.  Views and outputs as `render_point_clouds`; ids
+    are face rows."""
+    what = "render_meshes"
+    verts, faces, offsets, rows = _pack_meshes(meshes, what)
+    b = len(rows) - 1
+    v, view_sets, n_views, style, keep = _render_args(what, b, views, height, width, 1.0, color, background, light, ambient, verts.device)
+    rgb, ids, depth = _render_outputs(b, n_views, int(height), int(width), verts.device, return_buffers)
+    _lib.check(_lib.load().pcd_render_meshes(verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(), b, v.data_ptr(), view_sets, n_views,
+                                             int(height), int(width), style, _lib.ptr(ids), _lib.ptr(depth), rgb.data_ptr(),
+                                             _lib.stream_ptr()), "render_meshes")
+    return (rgb, ids, depth) if return_buffers else rgb
+
+
+def render_voxels(grid: torch.Tensor, views, threshold: float = 0.5, **kwargs):
+    """(B, 1, D, H, W) grid -> images of its surface-nets meshes: `render_meshes(voxel_tensor_to_meshes(grid, threshold), views, ...)`."""
+    return render_meshes(voxel_tensor_to_meshes(grid, threshold), views, **kwargs)
+
+
+def image_grid(images: torch.Tensor, cols: int, pad: int = 0, background=(1.0, 1.0, 1.0)) -> torch.Tensor:
+    """Contact sheet: (N, H, W, 3) uint8 (any leading shape, flattened; or one image) -> (rows (H + pad) - pad, cols (W + pad) - pad, 3), row-major, the
+    last row filled up with `background`.  torch ops on the images' device."""
+    if images.dim() < 3 or images.shape[-1] != 3 or images.dtype != torch.uint8:
+        raise ValueError(f"image_grid takes uint8 (..., H, W, 3) images, got {images.dtype} {tuple(images.shape)}")
+    cols = int(cols)
+    if cols < 1 or pad < 0:
+        raise ValueError(f"image_grid needs cols >= 1 and pad >= 0, got {cols!r}, {pad!r}")
+    im = images.reshape(-1, *images.shape[-3:])
+    n, h, w = im.shape[0], im.shape[1], im.shape[2]
+    if n < 1:
+        raise ValueError("image_grid: no images")
+    rows = (n + cols - 1) // cols
+    bg = torch.tensor([int(np.floor(255.0 * float(c) + 0.5)) for c in background], dtype=torch.uint8, device=im.device)
+    sheet = bg.expand(rows, h + pad, cols, w + pad, 3).clone()
+    full = bg.expand(rows * cols, h, w, 3).clone()
+    full[:n] = im
+    sheet[:, :h, :, :w] = full.reshape(rows, cols, h, w, 3).permute(0, 2, 1, 3, 4)
+    return sheet.reshape(rows * (h + pad), cols * (w + pad), 3)[:rows * (h + pad) - pad, :cols * (w + pad) - pad].contiguous()
+
+
+def save_png(path: str, image) -> None:
+    """Write an (H, W, 3) uint8 image (tensor on any device, or array) as an 8-bit RGB PNG: zlib + struct, filter 0 on every row.  Host only."""
+    import struct
+    import zlib
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"save_png writes uint8 (H, W, 3) images, got {a.dtype} {a.shape}")
+    h, w = a.shape[0], a.shape[1]
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), np.ascontiguousarray(a).reshape(h, w * 3)], axis=1).tobytes()
+
+    def chunk(kind: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                  chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def axis_views(height: int, width: int, half_extent: float = 1.0) -> torch.Tensor:
+    """(3, 3, 4) float32: the XY (from above), XZ (from the front) and YZ (from the side) orthographic views of the reference's 2-D panels."""
+    return torch.stack([orbit_view(-90.0, 90.0, height, width, half_extent), orbit_view(-90.0, 0.0, height, width, half_extent),
+                        orbit_view(0.0, 0.0, height, width, half_extent)])
+
+
+def save_shape_pngs(png_dir: str, index: int, result, original=None, size: int = 256, radius: float = 1.5) -> None:
+    """The reference's per-sample pictures (no text): `sample_{index}_3d.png` (one orbit view, azim -60, elev 30), `sample_{index}_2d.png`
+    (XY | XZ | YZ) and, with `original`, `comparison_{index}.png` (original | result).  `result` / `original`: an (n, 3) cloud or a `Mesh` on
+    the device."""
+    def draw(shape, views):
+        if isinstance(shape, (tuple, list)):
+            return render_meshes([shape], views, size, size)[0]
+        return render_point_clouds([shape], views, size, size, radius)[0]
+
+    orbit = orbit_view(-60.0, 30.0, size, size)
+    save_png(os.path.join(png_dir, f"sample_{index}_3d.png"), draw(result, orbit)[0])
+    save_png(os.path.join(png_dir, f"sample_{index}_2d.png"), image_grid(draw(result, axis_views(size, size)), 3))
+    if original is not None:
+        save_png(os.path.join(png_dir, f"comparison_{index}.png"), image_grid(torch.stack([draw(original, orbit)[0], draw(result, orbit)[0]]), 2))
+
+
 def setup_logger(name: str, log_file: str, level=logging.INFO) -> logging.Logger:
     """File + console logger (reference utils.py:354-385 behaviour)."""
     os.makedirs(os.path.dirname(log_file) or ".", exist_ok=True)

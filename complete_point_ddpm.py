@@ -2,12 +2,13 @@
 unconditional point DDPM (`PointCloudDiffusion.complete`, RePaint-style resampling) and score the result.
 
     python complete_point_ddpm.py [--ckpt-dir DIR] [--clouds FILE.npy] [--num-samples 16] [--num-points 2048]
-                                  [--steps 1000] [--resample 10] [--jump 10] [--cut 0.0]
+                                  [--steps 1000] [--resample 10] [--jump 10] [--cut 0.0] [--png-dir DIR]
 
 The points of each cloud with x < `--cut` are kept, moved to the front and handed over as the partial input, so the
 known counts are ragged.  Every `.ckpt` of `--ckpt-dir` is evaluated; without checkpoints (none ship with the reference)
 a model with deterministic synthetic weights runs, and without `--clouds` (a (B, N, 3) .npy of unit-sphere-scaled
 clouds) the synthetic ShapeNet-shaped clouds of test_point_ddpm.py are used, so the plumbing is exercised end to end.
+`--png-dir DIR` also writes `sample_<i>_3d.png`, `sample_<i>_2d.png` (the completion) and `comparison_<i>.png` (original | completion).
 Multi-GPU: launch with torch.distributed.run; shapes are sharded across ranks and metric rows are all-gathered.
 """
 from __future__ import annotations
@@ -24,7 +25,7 @@ import shapegen_amd  # noqa: F401
 from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import PointCloudDiffusion
-from shapegen_amd.utils import setup_logger
+from shapegen_amd.utils import save_shape_pngs, setup_logger
 from test_point_ddpm import synthetic_clouds
 
 LOG = "complete_logger_point_ddpm"
@@ -66,6 +67,7 @@ def main():
     ap.add_argument("--jump", type=int, default=10)
     ap.add_argument("--cut", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join("test", "outputs"))
+    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write the reference's pictures (sample_{i}_3d.png, sample_{i}_2d.png, comparison_{i}.png) here")
     args = ap.parse_args()
     torch.manual_seed(24)
     rank, world, local = D.init_from_env()
@@ -91,6 +93,9 @@ def main():
         done, rows = complete_and_score(model, name, val, partial, counts, args.steps, args.resample, args.jump)
         tag = "" if len(models) == 1 else "_" + name
         result["completion" + tag], result["metrics" + tag] = done.cpu().numpy(), rows.cpu().numpy()
+        if args.png_dir and rank == 0:
+            for i in range(done.shape[0]):
+                save_shape_pngs(os.path.join(args.png_dir, name) if len(models) > 1 else args.png_dir, i, done[i], val[i].to(device))
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         np.savez_compressed(os.path.join(args.out, "completions.npz"), **result)

@@ -2,7 +2,7 @@
 triangle mesh per shape.
 
     python generate_mesh_ldm.py [--vae-ckpt FILE] [--ldm-ckpt FILE] [--num-samples 16] [--sampler ddim|dpm] [--steps N]
-                                [--threshold 0.4] [--format obj|ply] [--out DIR]
+                                [--threshold 0.4] [--format obj|ply] [--out DIR] [--png-dir DIR]
 
 `--sampler dpm` (default, 20 steps) is `LatentDiffusion.sample_dpm`, `ddim` (default 1000 steps) is `sample`; both run with
 `output="mesh"`, so the decoded grids go through the surface-nets kernel (`utils.voxel_tensor_to_meshes`) at `--threshold`, the
@@ -10,7 +10,8 @@ predicate of the point conversion.  The latent-diffusion checkpoint carries the 
 a trained VAE under a denoiser with synthetic weights.  Without checkpoints (none ship with the reference) both run on deterministic
 synthetic weights, so the plumbing is exercised end to end.  One file `mesh_<i>.<format>` per shape goes to `--out`; vertices are in
 the [-1, 1] cube of the point clouds (a surface that reaches the grid's border closes up to one voxel pitch outside it).  Per shape
-the log gives the vertex and triangle counts and whether the mesh is closed.  One process, one GPU.
+the log gives the vertex and triangle counts and whether the mesh is closed.  `--png-dir DIR` also writes `sample_<i>_3d.png` and
+`sample_<i>_2d.png`, the meshes rendered on the device.  One process, one GPU.
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import shapegen_amd  # noqa: F401
 from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import LatentDiffusion
-from shapegen_amd.utils import mesh_is_closed, save_mesh, setup_logger
+from shapegen_amd.utils import mesh_is_closed, save_mesh, save_shape_pngs, setup_logger
 from shapegen_amd.vae import VAE3DLarge
 
 LOG = "generate_logger_mesh_ldm"
@@ -55,6 +56,7 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.4)
     ap.add_argument("--format", choices=("obj", "ply"), default="obj")
     ap.add_argument("--out", default=os.path.join("test", "outputs", "meshes"))
+    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write the reference's pictures (sample_{i}_3d.png, sample_{i}_2d.png) here")
     args = ap.parse_args()
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.sampler]
     torch.manual_seed(24)
@@ -77,6 +79,8 @@ def main():
         path = os.path.join(args.out, f"mesh_{i}.{args.format}")
         save_mesh(path, mesh)
         log.info(f"mesh {i}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles, closed {mesh_is_closed(mesh)} -> {path}")
+        if args.png_dir:
+            save_shape_pngs(args.png_dir, i, mesh)
 
 
 if __name__ == "__main__":

@@ -2,6 +2,7 @@
 
     python generate_point_ddpm.py [--ckpt-dir DIR] [--sampler dpm|ddim|ddpm] [--steps N] [--order 2] [--num-samples 16]
                                   [--num-points 2048] [--compare-steps 1000] [--out DIR] [--label K [--guidance W]]
+                                  [--png-dir DIR]
 
 `--sampler dpm` (default, 20 steps) is `PointCloudDiffusion.sample_dpm`, the second-order multistep solver on a log-SNR grid;
 `ddim` and `ddpm` are the reference's `sample` and `sample2` (default 1000 steps).  With `--compare-steps T` the start state is
@@ -11,7 +12,8 @@ synthetic weights runs, so the plumbing is exercised end to end.  `--label K` as
 (`train_point_ddpm.py --class-conditional`) for class K, with classifier-free guidance of scale `--guidance W` (1 = off, one
 forward per step; larger trades diversity for fidelity at two forwards per step); the synthetic-weights model then has K + 1
 classes.  Multi-GPU: launch with torch.distributed.run; clouds are
-sharded across ranks and all-gathered.
+sharded across ranks and all-gathered.  `--png-dir DIR` also writes the reference's pictures of every cloud, rendered on the device
+(`sample_{i}_3d.png`, `sample_{i}_2d.png`; with `--compare-steps` `comparison_{i}.png`, the long run beside the result).
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import PointCloudDiffusion
 from shapegen_amd.metrics import chamfer_per_sample
-from shapegen_amd.utils import setup_logger
+from shapegen_amd.utils import save_shape_pngs, setup_logger
 
 LOG = "generate_logger_point_ddpm"
 DEFAULT_STEPS = {"dpm": 20, "ddim": 1000, "ddpm": 1000}
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--out", default=os.path.join("test", "outputs"))
     ap.add_argument("--label", type=int, default=None, metavar="K", help="class to generate (class-conditional models)")
     ap.add_argument("--guidance", type=float, default=1.0, metavar="W", help="classifier-free guidance scale (needs --label)")
+    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write sample_{i}_3d.png / sample_{i}_2d.png (and comparison_{i}.png) here")
     args = ap.parse_args()
     if args.label is None and args.guidance != 1.0:
         ap.error("--guidance needs --label")
@@ -95,6 +98,7 @@ def main():
                  + ("" if args.label is None else f", class {args.label}, guidance {args.guidance}"))
         tag = "" if len(models) == 1 else "_" + name
         result["samples" + tag] = out.cpu().numpy()
+        ref = None
         if x_T is not None:
             ref = generate(model, "ddim", args.num_samples, args.num_points, args.compare_steps, 1, x_T, args.label, args.guidance)
             cd = chamfer_per_sample(out, ref)
@@ -102,6 +106,9 @@ def main():
                 log.info(f"{name} sample {i}: Chamfer Distance to sample at {args.compare_steps} steps {v:.3f}")
             log.info(f"{name}: Average Chamfer Distance to sample at {args.compare_steps} steps: {float(cd.mean()):.3f}")
             result["compare_chamfer" + tag] = cd.cpu().numpy()
+        if args.png_dir and rank == 0:
+            for i in range(out.shape[0]):
+                save_shape_pngs(os.path.join(args.png_dir, name) if len(models) > 1 else args.png_dir, i, out[i], None if ref is None else ref[i])
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         np.savez_compressed(os.path.join(args.out, "generated.npz"), **result)

@@ -923,6 +923,44 @@ int pcd_mesh_sample_points(const float* vertices, const int32_t* faces, const in
                            uint64_t philox_offset, const float* u, void* workspace, float* points, float* normals, int32_t* face_index,
                            void* stream);
 
+/* ---- Images out: depth-buffered renderer for point clouds and triangle meshes (csrc/render.hip; DESIGN.md "Render") ----
+ * View.  views fp32 [view_sets][V][12], a row-major 3 x 4 matrix [M | t] each; view_sets = 1 shares the V views among the shapes, view_sets = B
+ * gives every shape its own.  A world point p maps to q = M p + t = (x, y, z), each component evaluated in fp32 without contraction as
+ * ((m0 px + m1 py) + m2 pz) + t: x, y in pixels (x right, y down, the centre of pixel (i, j) at (j + 1/2, i + 1/2)), z the depth in pixel
+ * units, smaller = nearer.  Orthographic only.  A primitive with a projected coordinate that is not finite is skipped.
+ *   Points     pcd_render_points: points fp32 [sum n][3], offsets int64 [B + 1] = first row of each cloud, the total last.  Point k covers the
+ *              pixel centre c iff dx^2 + dy^2 <= r^2 with (dx, dy) = c - (qx, qy) (evaluated (dx dx + dy dy) <= r r); depth qz on the whole
+ *              disc; shading normal n = (dx, dy, -sqrt(r^2 - (dx^2 + dy^2))) / r, L = max(0, n . l).
+ *   Triangles  pcd_render_meshes: packed as for pcd_mesh_voxelize (offsets int64 [B + 1][2]); a face with an index outside its mesh's rows is
+ *              skipped; both faces are drawn.  With u = q1 - q0, v = q2 - q0 and n = u x v, a triangle with n_z = 0 (screen area 0) draws
+ *              nothing.  Every edge is evaluated from its canonical order -- the endpoint A with the lexicographically smaller (x, y) first,
+ *              d = B - A: e(c) = d_x (c_y - A_y) - d_y (c_x - A_x), and w = e(the third vertex) (w = 0: the triangle draws nothing).  With
+ *              s = sign(w) and the inward normal (nx, ny) = s (-d_y, d_x) the centre is inside the edge iff s e > 0, or e = 0 and
+ *              (nx > 0, or nx = 0 and ny > 0): the top-left rule.  Two triangles that share an edge evaluate the same e, so a closed mesh is
+ *              watertight in fp32.  Depth z0 - (n_x (c_x - x0) + n_y (c_y - y0)) / n_z (a pixel where it is not finite is not covered);
+ *              L = |n . l| / |n|.
+ * Visibility: per pixel the covering primitive with the least (depth, index) wins; depth compared as fp32 (-0 = +0), equal depth to the lower
+ * index; independent of the order of evaluation.  Outputs [B][V][H][W](,3), each optional (null: not written): ids int32 = the winner's row
+ * local to its shape, -1 for background; depth fp32, +inf for background; rgb uint8 = floor(min(max((255 color_k) (ambient + (1 - ambient) L),
+ * 0), 255) + 1/2), the background round(255 background_k).  One launch, one workgroup per (shape, view, tile of 128 x 64 or 128 x 128 pixels),
+ * visibility keys in LDS, integer atomics only: bitwise repeatable, independent of the rest of the batch and of the tile shape; no workspace.
+ * PCD_ERR_ARG (before any device work) for a null input or style, batch or n_views outside 1 .. 65535, view_sets not 1 or batch, height or
+ * width outside 1 .. 2048, radius outside (0, 64] or an ambient outside [0, 1]. */
+typedef struct {
+    const float* colors;      /* fp32 [B][3] RGB in [0, 1] per shape, or null: (0.27, 0.51, 0.71) for all */
+    float light[3];           /* l: unit vector in view space */
+    float ambient;
+    float background[3];      /* RGB in [0, 1] */
+} pcd_render_style_t;
+int pcd_render_points(const float* points, const int64_t* offsets, int batch, const float* views, int view_sets, int n_views, int height,
+                      int width, float radius, const pcd_render_style_t* style, int32_t* ids, float* depth, uint8_t* rgb, void* stream);
+int pcd_render_meshes(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, const float* views, int view_sets,
+                      int n_views, int height, int width, const pcd_render_style_t* style, int32_t* ids, float* depth, uint8_t* rgb,
+                      void* stream);
+/* The tile of a workgroup.  TEST / BENCHMARK ONLY: process-global.  0: 128 x 64 pixels (64 KB of keys); 1: 128 x 128 (128 KB); 2 (default): 128 x 64
+ * while that is at most one workgroup per CU, 128 x 128 for larger launches.  Same bits every way.  PCD_ERR_ARG for any other code. */
+int pcd_render_config(int code);
+
 /* ---- Sinkhorn EMD (metrics.py:94-158, `earth_mover_distance_gpu`), cost matrix never stored ----
  * out_max[0] = max over (b,i,j) of |x_i - y_j|   (the global C.max() of metrics.py:123) */
 int pcd_pairwise_max_dist(const float* x, const float* y, int batch, int n, int m, float* out_max, void* stream);
