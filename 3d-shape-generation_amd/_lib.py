@@ -360,6 +360,9 @@ _SIGS = {
     "pcd_embed_rows_backward": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "pcd_voxel_batch_clouds": (i32, [vp, i32, vp, i32, i32, u64, u64, i32, f32, f32, vp, vp, vp]),
     "pcd_voxel_batch_grids": (i32, [vp, i32, vp, i32, vp, vp]),
+    "pcd_mesh_area_sums": (i32, [vp, vp, vp, i32, vp, vp]),
+    "pcd_mesh_batch_clouds": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, u64, u64, i32, f32, f32, vp, vp, vp, vp]),
+    "pcd_mesh_data_config": (i32, [i32]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -11,6 +11,7 @@
 // The predicates are fp32 without contraction and without division: where every intermediate value is exactly representable they decide ties as
 // the float64 statement (tests/mesh_in_statement.py) does.
 #include "common.h"
+#include "mesh_tri.h"
 #include <cmath>
 
 namespace pcd {
@@ -21,28 +22,6 @@ constexpr int MIN_THREADS = 1024;
 constexpr int MIN_WAVES = MIN_THREADS / 64;
 constexpr int MIN_LDS_R = 32;                                  // accumulators of a grid up to this extent live in LDS
 constexpr int MIN_MAX_R = 64;
-
-struct MinTri {
-    float ax, ay, az, bx, by, bz, cx, cy, cz;                  // index coordinates p = (v - lo) * inv_pitch, per component
-    bool ok;                                                   // all three indices inside the mesh's vertex rows
-};
-
-__device__ __forceinline__ MinTri min_load_tri(const float* __restrict__ v, const int32_t* __restrict__ f, int t, int64_t nv, float lo, float ip) {
-    MinTri q;
-    const int i0 = f[(int64_t)t * 3], i1 = f[(int64_t)t * 3 + 1], i2 = f[(int64_t)t * 3 + 2];
-    q.ok = (unsigned long long)i0 < (unsigned long long)nv && (unsigned long long)i1 < (unsigned long long)nv &&
-           (unsigned long long)i2 < (unsigned long long)nv && i0 >= 0 && i1 >= 0 && i2 >= 0;
-    q.ax = q.ay = q.az = q.bx = q.by = q.bz = q.cx = q.cy = q.cz = 0.f;
-    if (q.ok) {
-        const float* a = v + (int64_t)i0 * 3;
-        const float* b = v + (int64_t)i1 * 3;
-        const float* c = v + (int64_t)i2 * 3;
-        q.ax = (a[0] - lo) * ip; q.ay = (a[1] - lo) * ip; q.az = (a[2] - lo) * ip;
-        q.bx = (b[0] - lo) * ip; q.by = (b[1] - lo) * ip; q.bz = (b[2] - lo) * ip;
-        q.cx = (c[0] - lo) * ip; q.cy = (c[1] - lo) * ip; q.cz = (c[2] - lo) * ip;
-    }
-    return q;
-}
 
 // nodes i of one axis whose closed unit interval [i - 1/2, i + 1/2] meets [mn, mx], cut to [0, r - 1]: first node and count (0 for none, also
 // for NaN: fmaxf / fminf drop it and the clamp bounds the conversion)
@@ -343,6 +322,12 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float* __restric
 
 static bool min_vox_args_ok(int batch, int r) { return batch > 0 && r >= 2 && r <= MIN_MAX_R; }
 
+int mesh_area_scan_launch(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, float* cdf, hipStream_t stream) {
+    hipLaunchKernelGGL(mesh_area_scan_kernel, dim3(batch), dim3(MIN_THREADS), 0, stream, vertices, faces, offsets, cdf);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
 }  // namespace pcd
 
 using namespace pcd;
@@ -381,8 +366,8 @@ extern "C" int pcd_mesh_sample_points(const float* vertices, const int32_t* face
                                       int32_t* face_index, void* stream) {
     PCD_CHECK_ARG(vertices && faces && offsets && workspace && points);
     PCD_CHECK_ARG(batch > 0 && batch <= 65535 && n_points > 0);
-    hipLaunchKernelGGL(mesh_area_scan_kernel, dim3(batch), dim3(MIN_THREADS), 0, (hipStream_t)stream, vertices, faces, offsets, (float*)workspace);
-    PCD_CHECK_LAUNCH();
+    int rc;
+    PCD_RUN(mesh_area_scan_launch(vertices, faces, offsets, batch, (float*)workspace, (hipStream_t)stream));
     hipLaunchKernelGGL(mesh_sample_kernel, dim3((unsigned)ceil_div(n_points, 256), batch), dim3(256), 0, (hipStream_t)stream, vertices, faces,
                        offsets, n_points, seed, philox_offset, u, (const float*)workspace, points, normals, face_index);
     PCD_CHECK_LAUNCH();

@@ -9,6 +9,8 @@ Differences, both deliberate:
     `setup()` / `train_dataloader()` / `val_dataloader()` surface;
   * `DeviceVoxelDataModule` (not in the reference): the same directory read once, the grids bit-packed on the GPU and each batch
     assembled by one kernel launch (csrc/dataset.hip); opt-in, the host modules are unchanged;
+  * `DeviceMeshDataModule` (not in the reference): triangle meshes resident on the GPU, every batch freshly drawn from their surfaces
+    by one kernel launch (csrc/mesh_data.hip); labels from the subdirectories;
   * file format: the reference stores each sample as a deepdish HDF5 file `*.dd` read with
     `dd.io.load(path)['data']` (data.py:176).  deepdish/h5py are not part of this image, so besides `.dd`
     (read through h5py when it is importable) the dataset accepts `.npz` (key `data`) and `.npy` files with
@@ -313,8 +315,9 @@ class _DeviceLoader:
     """One pass over `rows` in batches, every batch one kernel launch.  Shuffled: the permutation and a 63-bit Philox key are drawn from
     the global torch generator when the iteration starts (where DataLoader's RandomSampler draws its seed)."""
 
-    def __init__(self, module: "DeviceVoxelDataModule", rows: Sequence[int], shuffle: bool):
+    def __init__(self, module, rows: Sequence[int], shuffle: bool, ctr_span: int = VOXEL_CTR_SPAN):
         self.module, self.rows, self.shuffle = module, torch.as_tensor(list(rows), dtype=torch.int64), shuffle
+        self.ctr_span = ctr_span             # Philox counters one batch slot owns in the module's kernel
 
     def __len__(self):
         return (len(self.rows) + self.module.batch_size - 1) // self.module.batch_size
@@ -324,11 +327,14 @@ class _DeviceLoader:
         if self.shuffle:
             rows = rows[torch.randperm(len(rows))]
             key = int(torch.empty((), dtype=torch.int64).random_().item())
-        rows = rows.to(m.packed.device)
+        rows = rows.to(m.device)
         rows32 = rows.to(torch.int32)
         for i, lo in enumerate(range(0, len(rows), m.batch_size)):
-            item = m.batch(rows32[lo:lo + m.batch_size], seed=key, offset=i * m.batch_size * VOXEL_CTR_SPAN)
-            yield (item, m.labels_device[rows[lo:lo + m.batch_size]]) if m.return_labels else item
+            item = m.batch(rows32[lo:lo + m.batch_size], seed=key, offset=i * m.batch_size * self.ctr_span)
+            if m.return_labels:
+                labels = m.labels_device[rows[lo:lo + m.batch_size]]
+                item = (*item, labels) if isinstance(item, tuple) else (item, labels)
+            yield item
 
 
 class DeviceVoxelDataModule:
@@ -435,3 +441,136 @@ class DeviceVoxelDataModule:
 
     def val_dataloader(self):
         return _DeviceLoader(self, self.val_dataset.indices, shuffle=False)
+
+
+# ---------------------------------------------------------------------------------------------- device-resident mesh data
+MESH_CTR_SPAN = 1 << 26                  # Philox counters owned by one batch slot (PCD_MESH_CTR_SPAN)
+MESH_MAX_POINTS = 1 << 24                # PCD_MESH_MAX_POINTS
+_MESH_EXTS = (".obj", ".ply")
+
+
+def mesh_files(data_dir: str) -> List[str]:
+    """The `.obj` / `.ply` files under `data_dir`, as paths relative to it, sorted."""
+    found = []
+    for root, _, files in os.walk(data_dir):
+        found += [os.path.relpath(os.path.join(root, f), data_dir) for f in files if f.lower().endswith(_MESH_EXTS)]
+    return sorted(found)
+
+
+def mesh_category(relative_path: str) -> str:
+    """The category of a mesh file: the subdirectory of the data directory that holds it, "" for a file directly in it."""
+    parts = relative_path.split(os.sep)
+    return parts[0] if len(parts) > 1 else ""
+
+
+class DeviceMeshDataModule:
+    """Triangle meshes resident on the GPU, every batch a fresh draw from their surfaces: `setup()` reads every `.obj` / `.ply` file under
+    `data_dir` once (`utils.load_mesh`, sorted order), packs them into one table -- vertices, faces local to the mesh, offsets -- uploads
+    it and runs `pcd_mesh_area_sums` once; a batch is one launch of `pcd_mesh_batch_clouds` (csrc/mesh_data.hip): `num_points`
+    area-uniform surface points per mesh, new ones for every batch of every epoch, then the chain of `DeviceVoxelDataModule`
+    (`augmentations` = jitter, `rotate` opt-in, `normalization` = centroid and unit radius last).  A batch is `(B, num_points, 3)`; with
+    `return_normals` a pair (clouds, unit face normals, rotated with the points); with `return_labels` the int64 labels follow.  The
+    category of a file is the subdirectory of `data_dir` that holds it ("" for files directly in it), `categories` the sorted distinct
+    names, a label the index into them.  The split is `random_split` over the rows under the global torch generator; the per-epoch
+    Philox key comes from that generator too, the validation loader's is fixed.
+    `meshes=` (a list of `Mesh` / (vertices, faces) pairs) with optional integer `labels=` replaces `data_dir` (tests, synthetic runs);
+    `device="cpu"` keeps the table on the host, where `setup()` works and the loaders do not."""
+
+    def __init__(self, data_dir=None, num_points=2048, batch_size=32, train_val_split=0.8, augmentations=True, normalization=True,
+                 rotate=False, return_labels=False, return_normals=False, device="cuda", meshes=None, labels=None,
+                 jitter_sigma=0.01, jitter_clip=0.05):
+        if (data_dir is None) == (meshes is None):
+            raise ValueError("give either data_dir or meshes")
+        if return_labels and meshes is not None and labels is None:
+            raise ValueError("return_labels with meshes= needs labels=")
+        if not 0 < int(num_points) <= MESH_MAX_POINTS:
+            raise ValueError(f"num_points must be in 1..{MESH_MAX_POINTS}, got {num_points!r}")
+        self.data_dir, self.num_points, self.batch_size, self.train_val_split = data_dir, int(num_points), batch_size, train_val_split
+        self.augmentations, self.normalization, self.rotate = augmentations, normalization, bool(rotate)
+        self.return_labels, self.return_normals = return_labels, return_normals
+        self.device, self.meshes, self.labels = torch.device(device), meshes, labels
+        self.jitter_sigma, self.jitter_clip = float(jitter_sigma), float(jitter_clip)
+        self.flags = ((VOXEL_NORMALIZE if normalization else 0) | (VOXEL_JITTER if augmentations else 0)
+                      | (VOXEL_ROTATE if rotate else 0))
+        self.categories: List[str] = []
+
+    @staticmethod
+    def _checked(mesh, name: str):
+        """(vertices float32 (V, 3), faces int32 (F, 3)) of one mesh on the host, or ValueError naming it."""
+        v, f = mesh
+        v = np.ascontiguousarray(torch.as_tensor(v).detach().cpu().numpy(), dtype=np.float32)
+        f = np.ascontiguousarray(torch.as_tensor(f).detach().cpu().numpy())
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"{name}: not (V, 3) vertices and (F, 3) faces")
+        if f.shape[0] == 0:
+            raise ValueError(f"{name}: the mesh has no faces")
+        if f.min() < 0 or f.max() >= v.shape[0]:
+            raise ValueError(f"{name}: a face index is outside the mesh's {v.shape[0]} vertices")
+        t = v.astype(np.float64)[f.astype(np.int64)]
+        with np.errstate(all="ignore"):
+            area = 0.5 * np.linalg.norm(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]), axis=1).sum()
+        if not np.isfinite(area) or not area > 0.0 or not area <= 3.0e38:
+            raise ValueError(f"{name}: the total area of the mesh is {area}; a surface to draw from needs a positive finite area")
+        return v, f.astype(np.int32)
+
+    def setup(self, stage=None):
+        if self.meshes is not None:
+            names = [f"meshes[{i}]" for i in range(len(self.meshes))]
+            raw = iter(self.meshes)
+            labels = None if self.labels is None else [int(v) for v in self.labels]
+            if labels is not None and len(labels) != len(names):
+                raise ValueError(f"{len(labels)} labels for {len(names)} meshes")
+        else:
+            from .utils import load_mesh
+            self.file_list = mesh_files(self.data_dir)
+            names = [os.path.join(self.data_dir, f) for f in self.file_list]
+            raw = (load_mesh(p) for p in names)
+            self.categories = sorted({mesh_category(f) for f in self.file_list})
+            labels = [self.categories.index(mesh_category(f)) for f in self.file_list] if self.return_labels else None
+        if not names:
+            raise ValueError(f"{self.data_dir}: no .obj or .ply file" if self.meshes is None else "meshes is empty")
+        vs, fs, rows = [], [], [(0, 0)]
+        for name, mesh in zip(names, raw):
+            v, f = self._checked(mesh, name)
+            vs.append(v)
+            fs.append(f)
+            rows.append((rows[-1][0] + v.shape[0], rows[-1][1] + f.shape[0]))
+        self.offsets_host = np.asarray(rows, dtype=np.int64)
+        self.vertices = torch.from_numpy(np.concatenate(vs)).to(self.device)
+        self.faces = torch.from_numpy(np.concatenate(fs)).to(self.device)
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.area_sums = None
+        if self.device.type == "cuda":
+            from . import _lib
+            self.area_sums = torch.empty(self.faces.shape[0], dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().pcd_mesh_area_sums(_lib.ptr(self.vertices), _lib.ptr(self.faces), _lib.ptr(self.offsets), len(names),
+                                                          _lib.ptr(self.area_sums), _lib.stream_ptr()), "mesh_area_sums")
+        self.labels_device = None if labels is None else torch.as_tensor(labels, dtype=torch.int64, device=self.device)
+        table = _Rows(len(names))
+        train_size = int(self.train_val_split * len(table))
+        self.train_dataset, self.val_dataset = torch.utils.data.random_split(table, [train_size, len(table) - train_size])
+
+    def batch(self, index: torch.Tensor, seed: int, offset: int, return_faces: bool = False):
+        """The batch of the table's rows `index` (device int32) under Philox key `seed`, slot b's counters starting at
+        `offset + b * MESH_CTR_SPAN`: (B, num_points, 3) clouds; with `return_normals` (clouds, normals); `return_faces` (tests) appends
+        the (B, num_points) int32 face of every point."""
+        from . import _lib
+        if self.area_sums is None:
+            raise RuntimeError("DeviceMeshDataModule assembles batches on the GPU: construct it with device='cuda' (no CPU path)")
+        lib, b, dev = _lib.load(), int(index.numel()), self.vertices.device
+        out = torch.empty((b, self.num_points, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((b, self.num_points, 3), dtype=torch.float32, device=dev) if self.return_normals else None
+        faces = torch.empty((b, self.num_points), dtype=torch.int32, device=dev) if return_faces else None
+        _lib.check(lib.pcd_mesh_batch_clouds(_lib.ptr(self.vertices), _lib.ptr(self.faces), _lib.ptr(self.offsets), self.offsets.shape[0] - 1,
+                                             _lib.ptr(self.area_sums), _lib.ptr(index), b, self.num_points, seed & 0xFFFFFFFFFFFFFFFF,
+                                             offset & 0xFFFFFFFFFFFFFFFF, self.flags, self.jitter_sigma, self.jitter_clip, _lib.ptr(out),
+                                             _lib.ptr(normals), _lib.ptr(faces), _lib.stream_ptr()), "mesh_batch_clouds")
+        res = (out,) + ((normals,) if self.return_normals else ()) + ((faces,) if return_faces else ())
+        return res[0] if len(res) == 1 else res
+
+    def train_dataloader(self):
+        return _DeviceLoader(self, self.train_dataset.indices, shuffle=True, ctr_span=MESH_CTR_SPAN)
+
+    def val_dataloader(self):
+        return _DeviceLoader(self, self.val_dataset.indices, shuffle=False, ctr_span=MESH_CTR_SPAN)

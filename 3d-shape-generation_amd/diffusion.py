@@ -521,12 +521,23 @@ class Stepper:
     def capture(self, steps: int = 1):
         """Capture `steps` consecutive generic steps in one graph (must follow at least one eager step: kernels
         loaded, workspaces allocated).  Every step reads its constants through the device-side counter, so the same
-        graph is valid wherever it is replayed."""
+        graph is valid wherever it is replayed.
+        No garbage collection runs inside the capture: a dead module that a reference cycle kept alive (a model and its trainer) gives its C
+        handles back in `__del__`, and the library frees their device memory with hipFree, which is not allowed while a stream is
+        capturing (and torch.cuda.graph does not collect before it begins).  The collector stays off until the capture has ended; what
+        is dead waits for the next collection after it, which costs nothing here."""
+        import gc
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            for _ in range(steps):
-                self.step(-1, True)
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                for _ in range(steps):
+                    self.step(-1, True)
+        finally:
+            if was_enabled:
+                gc.enable()
 
     def replay(self):
         self.graph.replay()

@@ -1170,6 +1170,63 @@ int pcd_voxel_batch_clouds(const uint32_t* grids, int n_grids, const int* index,
 /* out[batch][1][32][32][32] = 0.f / 1.f, [z][y][x]: the indexed grids unpacked (an index outside the table gives zeros) */
 int pcd_voxel_batch_grids(const uint32_t* grids, int n_grids, const int* index, int batch, float* out, void* stream);
 
+/* ------------------------------------------------ device-resident mesh dataset (csrc/mesh_data.hip; DESIGN.md "Mesh dataset")
+ * The table: n_meshes meshes in the packing of pcd_mesh_sample_points -- vertices fp32 [sum V][3], faces int32 [sum F][3] local to
+ * the mesh, offsets int64 [n_meshes + 1][2] -- and area_sums fp32 [sum F], the per-mesh inclusive running sums of the triangle
+ * areas.  pcd_mesh_area_sums writes them: it IS launch 1 of pcd_mesh_sample_points (same kernel, same tree, a non-finite area
+ * counts as 0), so area_sums is bitwise that call's workspace.  Once per table.  PCD_ERR_ARG for a null pointer or n_meshes <= 0. */
+int pcd_mesh_area_sums(const float* vertices, const int32_t* faces, const int64_t* offsets, int n_meshes, float* area_sums, void* stream);
+/* out fp32 [batch][num_points][3]: slot b is a cloud of num_points points drawn uniformly by area from mesh index[b] (device int32),
+ * then sent through the chain of pcd_voxel_batch_clouds.  normals (optional, fp32 [batch][num_points][3]): the unit normal of each
+ * point's face; face_index (optional, int32 [batch][num_points]): that face, local to the mesh.  One workgroup per slot, one launch,
+ * no workspace, no host synchronisation, no float atomics: bitwise repeatable.
+ *
+ * Randomness is Philox4x32-10 as in pcd_randn: counter words {lo(ctr), hi(ctr), 0, 0}, key {lo(seed), hi(seed)}.  Batch slot b owns
+ * the PCD_MESH_CTR_SPAN counters from offset + b * PCD_MESH_CTR_SPAN; inside its span (counter numbers relative to it)
+ *   [PCD_MESH_CTR_POINT,  + num_points)  counter i gives point i its u0, u1, u2 as pcd_mesh_sample_points derives them:
+ *                                        u_k = (word k >> 8) / 2^24 (word 3 is not used)
+ *    PCD_MESH_CTR_ANGLE                  rotation: angle = 2 pi u, u = ((word 0 >> 8) + 0.5) / 2^24 (PCD_VOXEL_CTR_ANGLE's formula)
+ *   [PCD_MESH_CTR_JITTER, + num_points)  jitter: counter i gives point i its normals, pcd_randn's Box-Muller values 0, 1, 2 of the
+ *                                        counter for columns 0, 1, 2 (value 3 is not used), as PCD_VOXEL_CTR_JITTER does
+ * The ranges are 2^24 counters apart and num_points <= PCD_MESH_MAX_POINTS = 2^24, so they cannot meet.  Slot b's rows depend on
+ * (mesh, seed, offset, b, num_points, flags) only, not on the rest of the batch.
+ *
+ * Draw.  Triangle f is the first of the mesh whose running sum exceeds u0 * total (the last one at most), total the mesh's last
+ * running sum; the point is (1 - s) A + s (1 - u2) B + s u2 C with s = sqrt(u1), evaluated per coordinate as
+ * ((1 - s) a + (s (1 - u2)) b) + (s u2) c in fp32 without contraction.  With flags = 0 slot b is bitwise pcd_mesh_sample_points on
+ * mesh index[b] alone with philox_offset = offset + b * PCD_MESH_CTR_SPAN + PCD_MESH_CTR_POINT: points, normals and face_index.
+ *
+ * Chain.  flags are PCD_VOXEL_NORMALIZE, PCD_VOXEL_ROTATE, PCD_VOXEL_JITTER with the meaning and order of pcd_voxel_batch_clouds:
+ *   rotate     centre on the centroid and scale to unit radius (as below), then right-multiply by the rotation about column 1,
+ *              [[c, 0, s], [0, 1, 0], [-s, 0, c]]: p0' = p0 c - p2 s, p2' = p0 s + p2 c
+ *   jitter     add clip(sigma * normal, -clip, clip) to every coordinate
+ *   normalize  p = (p - mean) / radius, mean = sum / float(num_points), radius = sqrt(max((d0 d0 + d1 d1) + d2 d2)) over the points,
+ *              d = p - mean
+ * Every cloud has exactly num_points points: there is no resample stage.  All of it is fp32 without contraction, division and root
+ * correctly rounded.  The column sums of a centroid are added in this fixed order: lane t of the 1024 adds the points t, t + 1024,
+ * t + 2048, ... in ascending order to a partial that starts at 0; inside each wave (lanes 64 w .. 64 w + 63) the partials are
+ * combined by the butterfly x[l] = x[l] + x[l ^ o] for o = 32, 16, 8, 4, 2, 1; the 16 wave sums are then added in ascending w,
+ * starting from wave 0's.  The radius is a max and does not depend on the order.  tests/mesh_data_statement.py reproduces the sums:
+ * given the device's sine, cosine and normals the rows are bit-exact against the same numpy operations.  normals are rotated with
+ * the points; jitter and normalisation do not change them.
+ *
+ * An index outside [0, n_meshes), a mesh without vertices or faces, or one whose total area is not above 0 gives zero rows, zero
+ * normals and face_index -1.  A cloud of radius 0 under normalize or rotate (every point the same) gives NaN rows, 0 / 0 as in
+ * pcd_voxel_batch_clouds.  PCD_ERR_ARG (before any device work) for a null vertices, faces, offsets, area_sums, index or out,
+ * n_meshes <= 0, batch <= 0, num_points <= 0 or > PCD_MESH_MAX_POINTS, an unknown flag, or a non-finite sigma or clip. */
+#define PCD_MESH_CTR_POINT 0ull
+#define PCD_MESH_CTR_ANGLE (1ull << 24)
+#define PCD_MESH_CTR_JITTER (1ull << 25)
+#define PCD_MESH_CTR_SPAN (1ull << 26)
+#define PCD_MESH_MAX_POINTS (1 << 24)
+int pcd_mesh_batch_clouds(const float* vertices, const int32_t* faces, const int64_t* offsets, int n_meshes, const float* area_sums,
+                          const int* index, int batch, int num_points, uint64_t seed, uint64_t offset, int flags, float sigma, float clip,
+                          float* out, float* normals, int32_t* face_index, void* stream);
+/* Which form pcd_mesh_batch_clouds takes.  TEST / BENCHMARK ONLY: process-global.  1 (default): a slot's drawn cloud is kept in LDS
+ * between the passes of the chain when num_points <= 8192 (96 KB) and drawn again from the counters in every pass above that;
+ * 0: always drawn again.  Same bits either way.  PCD_ERR_ARG for any other code. */
+int pcd_mesh_data_config(int code);
+
 #ifdef __cplusplus
 }
 #endif

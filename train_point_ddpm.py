@@ -7,7 +7,7 @@ BatchNorm batch statistics, L1 loss, AdamW + ReduceLROnPlateau, top-k checkpoint
     python train_point_ddpm.py [--data-dir DIR] [--category chair] [--epochs 500] [--ckpt weights.ckpt] [--max-steps N]
                                [--backbone {pointnet,attention}] [--resume last.ckpt] [--save-last] [--ema-decay D]
                                [--grad-clip NORM] [--accumulate-grad-batches K] [--skip-nonfinite]
-                               [--class-conditional [--p-uncond 0.1]] [--device-data]
+                               [--class-conditional [--p-uncond 0.1]] [--device-data] [--mesh-data [DIR]]
 
 `--backbone attention` trains `UNetAttentionPointExperimental` (the reference reaches it by editing diffusion.py's
 import); `--ckpt` starts a new run from a checkpoint's weights (with the backbone stored in its hyper-parameters).
@@ -27,6 +27,11 @@ through the classes.
 `--device-data` feeds the trainer from `DeviceVoxelDataModule`: the directory is read once, the grids stay bit-packed on the GPU and
 every batch is one kernel launch (Philox draws, subsets in scan order; `shapegen_amd.data`).  Without it nothing changes.
 
+`--mesh-data DIR` feeds the trainer from `DeviceMeshDataModule`: every `.obj` / `.ply` file under DIR is read once, the triangles stay
+on the GPU and every batch of every epoch is a fresh area-uniform draw of `--num-points` surface points per mesh, jittered and
+normalised, in one kernel launch.  With `--class-conditional` the categories are DIR's subdirectories.  Without DIR (or when it does
+not exist) the run builds boxes and ellipsoids in memory, one class each.
+
 Without a data directory (none ships with the reference) it trains on synthetic ShapeNet-shaped clouds so the whole
 loop can be exercised.
 """
@@ -40,7 +45,7 @@ import numpy as np
 import torch
 
 import shapegen_amd  # noqa: F401
-from shapegen_amd.data import DeviceVoxelDataModule, PointCloudDataDirectoryModule, PointCloudDataModule
+from shapegen_amd.data import DeviceMeshDataModule, DeviceVoxelDataModule, PointCloudDataDirectoryModule, PointCloudDataModule
 from shapegen_amd.diffusion import PointCloudDiffusion
 from shapegen_amd.training import fit
 from shapegen_amd.utils import setup_logger
@@ -79,6 +84,37 @@ def synthetic_grids(count: int, seed: int = 24, families: int = 0):
         for j in range(blobs):
             grids[i][((zz - c[j, 0]) / r[j, 0]) ** 2 + ((yy - c[j, 1]) / r[j, 1]) ** 2 + ((xx - c[j, 2]) / r[j, 2]) ** 2 <= 1] = 1
     return grids, labels
+
+
+SYNTHETIC_MESH_FAMILIES = 2
+_BOX_FACES = ((0, 2, 1), (0, 3, 2), (4, 5, 6), (4, 6, 7), (0, 1, 5), (0, 5, 4), (2, 3, 7), (2, 7, 6), (1, 2, 6), (1, 6, 5), (0, 4, 7), (0, 7, 3))
+
+
+def synthetic_meshes(count: int, seed: int = 24, rings: int = 12, segments: int = 16):
+    """(meshes, labels) for --mesh-data without a directory: mesh i is a box of random extents (label 0, 12 triangles) for even i and a
+    latitude / longitude ellipsoid of random semi-axes (label 1) for odd i; (vertices float32 (V, 3), faces int32 (F, 3)) pairs."""
+    rng = np.random.default_rng(seed)
+    meshes, labels = [], np.arange(count, dtype=np.int64) % SYNTHETIC_MESH_FAMILIES
+    th = np.pi * np.arange(1, rings) / rings
+    ph = 2 * np.pi * np.arange(segments) / segments
+    sphere = np.concatenate([[(0.0, 0.0, 1.0)], np.stack([np.outer(np.sin(th), np.cos(ph)), np.outer(np.sin(th), np.sin(ph)),
+                                                          np.outer(np.cos(th), np.ones(segments))], axis=2).reshape(-1, 3), [(0.0, 0.0, -1.0)]])
+    at = lambda r, s: 1 + (r - 1) * segments + s % segments        # noqa: E731
+    faces = []
+    for s in range(segments):
+        faces += [(0, at(1, s), at(1, s + 1)), (len(sphere) - 1, at(rings - 1, s + 1), at(rings - 1, s))]
+        for r in range(1, rings - 1):
+            faces += [(at(r, s), at(r + 1, s), at(r + 1, s + 1)), (at(r, s), at(r + 1, s + 1), at(r, s + 1))]
+    for i in range(count):
+        half = rng.uniform(0.3, 1.0, 3)
+        if labels[i] == 0:
+            lo, hi = -half, half
+            v = [(lo[0], lo[1], lo[2]), (hi[0], lo[1], lo[2]), (hi[0], hi[1], lo[2]), (lo[0], hi[1], lo[2]),
+                 (lo[0], lo[1], hi[2]), (hi[0], lo[1], hi[2]), (hi[0], hi[1], hi[2]), (lo[0], hi[1], hi[2])]
+            meshes.append((np.asarray(v, np.float32), np.asarray(_BOX_FACES, np.int32)))
+        else:
+            meshes.append(((sphere * half).astype(np.float32), np.asarray(faces, np.int32)))
+    return meshes, labels
 
 
 def synthetic_labelled_clouds(count: int, num_points: int, seed: int = 24):
@@ -127,12 +163,31 @@ def main():
     ap.add_argument("--p-uncond", type=float, default=0.1, help="probability of replacing a training label by the null class")
     ap.add_argument("--device-data", action="store_true",
                     help="keep the voxel grids on the GPU and assemble every batch there in one launch (DeviceVoxelDataModule)")
+    ap.add_argument("--mesh-data", nargs="?", const="", default=None, metavar="DIR",
+                    help="train on fresh surface samples of the .obj / .ply meshes under DIR, kept on the GPU (DeviceMeshDataModule); "
+                         "categories are DIR's subdirectories; without DIR: boxes and ellipsoids built in memory")
     args = ap.parse_args()
+    if args.mesh_data is not None and args.device_data:
+        ap.error("--mesh-data and --device-data are two data sources: give one")
     torch.manual_seed(24)
     timestamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     logger = setup_logger("train_point_ddpm", os.path.join("train", "logs", f"train_point_ddpm_log_{timestamp}.log"))
     num_classes = 0
-    if os.path.isdir(args.data_dir):
+    if args.mesh_data is not None and os.path.isdir(args.mesh_data):
+        dm = DeviceMeshDataModule(args.mesh_data, num_points=args.num_points, batch_size=args.batch_size, return_labels=args.class_conditional)
+        if args.class_conditional:
+            from shapegen_amd.data import mesh_category, mesh_files
+            found = sorted({mesh_category(f) for f in mesh_files(args.mesh_data)})
+            num_classes = len(found)
+            logger.info(f"class-conditional over {num_classes} categories: {found}")
+    elif args.mesh_data is not None:
+        logger.info(f"no mesh directory{' ' + repr(args.mesh_data) if args.mesh_data else ''}: training on {args.synthetic_shapes} boxes and "
+                    "ellipsoids kept on the GPU")
+        meshes, labels = synthetic_meshes(args.synthetic_shapes)
+        dm = DeviceMeshDataModule(meshes=meshes, labels=labels, num_points=args.num_points, batch_size=args.batch_size,
+                                  return_labels=args.class_conditional)
+        num_classes = SYNTHETIC_MESH_FAMILIES if args.class_conditional else 0
+    elif os.path.isdir(args.data_dir):
         categories = args.category.split(",")
         module = DeviceVoxelDataModule if args.device_data else PointCloudDataDirectoryModule
         dm = module(args.data_dir, num_points=args.num_points, batch_size=args.batch_size, file_mode="voxels",
