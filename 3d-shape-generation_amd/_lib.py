@@ -126,6 +126,12 @@ def pair_metrics_workspace_layout(pairs: int, na_max: int, nb_max: int) -> dict:
     return dict(zip(PCD_PAIR_WS, (int(v) for v in off)))
 
 
+# columns of a pcd_surface_metrics row, in the order of the header's PCD_SURF_ROW_* enum; three more per threshold from PCD_SURF_ROW_BASE on
+PCD_SURF_ROW = ("ACC", "COMP", "CHAMFER_L1", "ACC2", "COMP2", "CHAMFER_L2", "HAUSDORFF", "NC_A", "NC_B", "NC")
+PCD_SURF_ROW_BASE = len(PCD_SURF_ROW)
+PCD_SURF_MAX_THRESHOLDS = 8
+
+
 # name -> (restype, argtypes).  Kept in the order of include/pcd_hip.h.
 _SIGS = {
     "pcd_last_error": (C.c_char_p, []),
@@ -325,6 +331,11 @@ _SIGS = {
     "pcd_pair_metrics_workspace_bytes": (sz, [i32, i32, i32]),
     "pcd_pair_metrics": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
     "pcd_pair_metrics_workspace_layout": (i32, [i32, i32, i32, C.POINTER(sz)]),
+    "pcd_nearest_workspace_bytes": (sz, [i32, i32, i32]),
+    "pcd_nearest_neighbors": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "pcd_surface_metrics_workspace_bytes": (sz, [i32, i32, i32]),
+    "pcd_surface_metrics": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, C.POINTER(f32), i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "pcd_voxel_iou": (i32, [vp, vp, i32, i32, f32, vp, vp]),
     "pcd_colsum_f16": (i32, [vp, i64, i32, i32, vp, vp]),
     "pcd_bn_batch_stats": (i32, [vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]),
     "pcd_bn_apply_f16": (i32, [vp, i64, i32, vp, vp, vp, vp, f32, i32, vp, vp]),

@@ -1002,6 +1002,50 @@ enum { PCD_PAIR_WS_AN = 0, PCD_PAIR_WS_BN, PCD_PAIR_WS_MINS, PCD_PAIR_WS_ALPHA, 
        PCD_PAIR_WS_CMAX, PCD_PAIR_WS_ERR, PCD_PAIR_WS_BITS, PCD_PAIR_WS_TOTAL, PCD_PAIR_WS_FIELDS };
 int pcd_pair_metrics_workspace_layout(int pairs, int na_max, int nb_max, size_t* offsets);
 
+/* ---- surface evaluation of a batch of independent cloud pairs (csrc/surface_metrics.hip; DESIGN.md "Surface metrics") ----
+ * The packing of pcd_pair_metrics: pair p = q[p][0..nq[p]) vs t[p][0..nt[p]) inside padded fp32 arrays [P][nq_max][3] / [P][nt_max][3], counts
+ * device int32 [P] (a count below 0 counts as 0, one above the padded size as that size); rows at or past a count are never read.  All distance
+ * and dot-product arithmetic is fp32 without contraction, so every stage below is an exact statement.
+ * Nearest neighbour.  For every query i < nq[p]: d2[p][i] = min_j ((dx dx + dy dy) + dz dz) over the targets j < nt[p] whose value is finite,
+ * from direct differences, and index[p][i] = the LOWEST j that attains it.  A query with no finite distance to any target -- a query or every
+ * target with a coordinate that is not finite, or no targets -- gets d2 = NaN, index = -1, as does every row at or past the count; a target that
+ * is not finite is never anyone's neighbour.  d2 fp32 [P][nq_max], index int32 [P][nq_max].  The target range is split over the grid; the
+ * partial results meet in a 64-bit unsigned atomic min on (bits of d2) << 32 | j, so the result is bitwise repeatable and independent of the
+ * split count and of the rest of the batch.  workspace: pcd_nearest_workspace_bytes() bytes (host arithmetic, 0 for arguments the call refuses),
+ * any contents.  One enqueue, no host synchronisation.  PCD_ERR_ARG (before any device work) for a null pointer, pairs <= 0 or > 65535, a
+ * padded size <= 0, or a workspace that is too small. */
+size_t pcd_nearest_workspace_bytes(int pairs, int nq_max, int nt_max);
+int pcd_nearest_neighbors(const float* q, const int* nq, int nq_max, const float* t, const int* nt, int nt_max, int pairs, float* d2,
+                          int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
+/* Rows.  Both directions of all pairs (a queries b, b queries a) through the nearest-neighbour kernel in one launch, then one workgroup per
+ * pair: rows fp32 [P][PCD_SURF_ROW_BASE + 3 n_thresholds].  With d = sqrtf(d2) per query:
+ *   ACC, COMP          the mean of d over a, over b            ACC2, COMP2   the means of d2
+ *   CHAMFER_L1         (ACC + COMP) / 2                        CHAMFER_L2    ACC2 + COMP2
+ *   HAUSDORFF          sqrtf of the largest d2 of both directions
+ *   NC_A, NC_B         the mean over a (over b) of |n . n'[index]| = fabsf((x x' + y y') + z z'), n the query's normal and n' the normal of its
+ *                      nearest neighbour; NC = (NC_A + NC_B) / 2.  The absolute value makes it blind to a flipped winding, on purpose.  NaN
+ *                      when normals_a or normals_b (fp32, packed as the clouds) is null.
+ *   BASE + 3k ..       threshold tau_k: PRECISION = |{i in a: d2 <= tau_k tau_k}| / na (one fp32 product, an integer count, one fp32 division),
+ *                      RECALL the same over b, FSCORE = (2 P R) / (P + R), 0 when P + R = 0.
+ * The means are accumulated in double in a fixed order (per-thread strided partials, a butterfly over each wave, the four waves in order) and
+ * rounded to fp32 once; the derived columns are fp32 operations on those.  A pair with a count of 0, or with a point that has no finite
+ * distance to the other cloud (any coordinate inside the counts that is not finite, on either side), gets an all-NaN row; the other pairs are
+ * not affected.  thresholds: HOST fp32 [n_thresholds], 0 <= n_thresholds <= PCD_SURF_MAX_THRESHOLDS.  Optional outputs (null: not written):
+ * d2_a / index_a [P][na_max] and d2_b / index_b [P][nb_max], the nearest-neighbour results of the two directions as pcd_nearest_neighbors
+ * defines them.  workspace: pcd_surface_metrics_workspace_bytes() bytes, any contents.  PCD_ERR_ARG (before any device work) for a null a, na,
+ * b, nb, rows or workspace, pairs <= 0 or 2 pairs > 65535, a padded size <= 0, n_thresholds outside 0 .. 8 (or > 0 with null thresholds), a
+ * threshold that is negative or not finite, or a workspace that is too small. */
+#define PCD_SURF_MAX_THRESHOLDS 8
+enum { PCD_SURF_ROW_ACC = 0, PCD_SURF_ROW_COMP, PCD_SURF_ROW_CHAMFER_L1, PCD_SURF_ROW_ACC2, PCD_SURF_ROW_COMP2, PCD_SURF_ROW_CHAMFER_L2,
+       PCD_SURF_ROW_HAUSDORFF, PCD_SURF_ROW_NC_A, PCD_SURF_ROW_NC_B, PCD_SURF_ROW_NC, PCD_SURF_ROW_BASE };
+size_t pcd_surface_metrics_workspace_bytes(int pairs, int na_max, int nb_max);
+int pcd_surface_metrics(const float* a, const float* normals_a, const int* na, int na_max, const float* b, const float* normals_b,
+                        const int* nb, int nb_max, int pairs, const float* thresholds, int n_thresholds, float* rows, float* d2_a,
+                        int32_t* index_a, float* d2_b, int32_t* index_b, void* workspace, size_t workspace_bytes, void* stream);
+/* out[p] = |A and B| / |A or B| of two fp32 grids [P][voxels] with occupancy value > threshold: integer counts, one fp32 division, NaN for an
+ * empty union.  PCD_ERR_ARG for a null pointer, pairs <= 0, voxels <= 0 or a threshold that is not finite. */
+int pcd_voxel_iou(const float* a, const float* b, int pairs, int voxels, float threshold, float* out, void* stream);
+
 /* ------------------------------------------------ training step of the point denoiser
  * diffusion.py:70-86,170-186 (add_noise -> model in train() mode -> F.l1_loss -> AdamW, diffusion.py:60).
  * The dense products (forward, backward-data, backward-weight) are pcd_gemm_f16* calls; these entry points
