@@ -57,9 +57,12 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const half_t* __rest
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float mean = s / (float)C;
-    float q = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { f[e] -= mean; q += f[e] * f[e]; }
+    for (int e = 0; e < 8; ++e) f[e] -= mean;
+    float q = f[1] * f[1];                           // f1^2 rounded, the others fused: the form `q += f[e] * f[e]` had been contracted to
+    q = __builtin_fmaf(f[0], f[0], q);
+#pragma unroll
+    for (int e = 2; e < 8; ++e) q = __builtin_fmaf(f[e], f[e], q);
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o);
     const float rstd = rsqrtf(q / (float)C + 1e-5f);
@@ -68,8 +71,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const half_t* __rest
     half8 o8;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        o8[e] = to_half_sat(f[e] * rstd * g0[e] + b0[e]);
-        o8[4 + e] = to_half_sat(f[4 + e] * rstd * g1[e] + b1[e]);
+        o8[e] = to_half_sat(__builtin_fmaf(f[e] * rstd, g0[e], b0[e]));
+        o8[4 + e] = to_half_sat(__builtin_fmaf(f[4 + e] * rstd, g1[e], b1[e]));
     }
     if (row < rows) *(half8*)(out + row * C + l * 8) = o8;
 }

@@ -278,7 +278,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const half_t* __restri
 }
 
 // ---------------------------------------------------------------- LayerNorm with saved statistics
-// C = 8 * LPR; the arithmetic of pcd_layernorm_f16's vector kernel (same values), plus mean / rstd per row
+// C = 8 * LPR; the arithmetic of pcd_layernorm_f16's vector kernel (same bits), plus mean / rstd per row.  The fused multiply-adds are spelled out in
+// both: left to contraction, the same source came out as a chain of v_fmac in one file and as v_pk_mul + v_add (every square rounded) in the other, rstd
+// differed in its last bit and a few outputs by an fp16 ulp (tests/test_gpu_layernorm_rows.py compares the two bit for bit).
 template <int LPR>
 __global__ __launch_bounds__(256) void layernorm_train_kernel(const half_t* __restrict__ x, int64_t rows,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -296,9 +298,12 @@ __global__ __launch_bounds__(256) void layernorm_train_kernel(const half_t* __re
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float mean = s / (float)C;
-    float q = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { f[e] -= mean; q += f[e] * f[e]; }
+    for (int e = 0; e < 8; ++e) f[e] -= mean;
+    float q = f[1] * f[1];                           // f1^2 rounded, the others fused: the form `q += f[e] * f[e]` had been contracted to
+    q = __builtin_fmaf(f[0], f[0], q);
+#pragma unroll
+    for (int e = 2; e < 8; ++e) q = __builtin_fmaf(f[e], f[e], q);
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o);
     const float rstd = rsqrtf(q / (float)C + 1e-5f);
@@ -307,8 +312,8 @@ __global__ __launch_bounds__(256) void layernorm_train_kernel(const half_t* __re
     half8 o8;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        o8[e] = to_half_sat(f[e] * rstd * g0[e] + b0[e]);
-        o8[4 + e] = to_half_sat(f[4 + e] * rstd * g1[e] + b1[e]);
+        o8[e] = to_half_sat(__builtin_fmaf(f[e] * rstd, g0[e], b0[e]));
+        o8[4 + e] = to_half_sat(__builtin_fmaf(f[4 + e] * rstd, g1[e], b1[e]));
     }
     if (row < rows) {
         *(half8*)(out + row * C + l * 8) = o8;

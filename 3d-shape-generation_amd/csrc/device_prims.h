@@ -149,10 +149,16 @@ __device__ __forceinline__ half8 regroup_bias_clamp(const f32x16& acc, int gp, c
 
 // LayerNorm (eps 1e-5) of a point's C channels held as B fragments: lane (point, hh = lane >> 5) holds the 8 channels 16 s + 8 hh .. + 7 of every k-step s, lane ^ 32
 // the others.  fp32 statistics, result in fp16 like pcd_layernorm_f16's.
-// Statistics straight from the packed fp16 pairs by v_dot2_f32_f16 with fp32 accumulation (a pass over converted values would keep C / 2 more registers
-// alive and spill at C = 256).  Two passes, the variance about the mean: sum(x^2) - C mean^2 cancels when |mean| >> std (post-ReLU rows near the fp16
-// range).  The second pass subtracts mh = fp16(mean) in packed fp16 (exact or 1 ulp of a small difference) and removes the shift exactly:
-// sum (x - mh)^2 = sum (x - mean)^2 + C (mean - mh)^2 because sum (x - mean) = 0.
+// Two passes, the variance about the mean: sum(x^2) - C mean^2 cancels when |mean| >> std (post-ReLU rows near the fp16 range).  The sum straight from the
+// packed fp16 pairs by v_dot2_f32_f16 with fp32 accumulation.  The second pass forms x - mean in fp32, element by element, the arithmetic of the plain kernels
+// (attention.hip, attn_bwd.hip): |x - mean| reaches 131008 on finite rows (all +65504, one -65504), so no fp16 holds it.  A packed x - fp16(mean) is inf from
+// 65520 on, which made sq inf, rstd 0 and the whole row beta (three quarters of a row near -30000, one quarter near +60000 did that); halved inside a packed
+// fma it stays finite but is rounded to 11 bits, and on a row that is one outlier above a flat bulk that rounding alone moves rstd by 2.4e-4 and the row of
+// a following Linear by 9.5e-4 (tests/test_gpu_layernorm_rows.py holds every row to 1e-3 of fp64).
+// The pass streams: each difference is used once, one v_fma_mix_f32 (x - sum / C, the conversion inside it; sum / C is exact) and one v_fmac_f32 per
+// element.  It reads the sum through `sum2`, an identity DPP move: the same bits, but not the same value to the compiler, which would otherwise keep the
+// differences for the third pass, where x - mean appears again: no converted copy of the fragments stays alive (C / 2 more registers, a spill at C = 256).
+// A move, not an empty asm: the timing ablations of wide_ffn_kernel that drop the MFMAs must still lose the whole LayerNorm as dead code.
 // A macro, not a function: a function is simplified on its own before it is inlined (with hh a parameter of unknown range, the 4 C / 16 reads of the affine
 // each get an address register: 92 more instructions at C = 256), and even with that mended the kernels' instruction streams come out reordered.
 // frag: half8 [C / 16], normalised in place; gamma + goff, beta + boff: const float* (LDS), C floats each, base and offset apart because the two
@@ -168,17 +174,14 @@ __device__ __forceinline__ half8 regroup_bias_clamp(const f32x16& acc, int gp, c
             }                                                                                                                                         \
         sum += __shfl_xor(sum, 32);                                                                                                                   \
         const float mean = sum * (1.f / (C));                                                                                                         \
-        const half_t mh = (half_t)__builtin_amdgcn_fmed3f(mean, -65504.f, 65504.f);                                                                   \
-        half2_ mh2; mh2.x = mh2.y = mh;                                                                                                               \
+        const float sum2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sum), 0xE4, 0xF, 0xF, false));                  \
         _Pragma("unroll") for (int s = 0; s < (C) / 16; ++s)                                                                                          \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                                                           \
-                half2_ v; v.x = (frag)[s][2 * e]; v.y = (frag)[s][2 * e + 1];                                                                         \
-                const half2_ d = v - mh2;                                                                                                             \
-                sq = __builtin_amdgcn_fdot2(d, d, sq, false);                                                                                         \
+            _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                                                           \
+                const float d = (float)(frag)[s][e] - sum2 * (1.f / (C));                                                                             \
+                sq = __builtin_fmaf(d, d, sq);                                                                                                        \
             }                                                                                                                                         \
         sq += __shfl_xor(sq, 32);                                                                                                                     \
-        const float shift = mean - (float)mh;                                                                                                         \
-        const float rstd = rsqrtf(fmaxf(sq - (C) * shift * shift, 0.f) * (1.f / (C)) + 1e-5f);                                                        \
+        const float rstd = rsqrtf(sq * (1.f / (C)) + 1e-5f);                                                                                          \
         _Pragma("unroll") for (int s = 0; s < (C) / 16; ++s) {                                                                                        \
             const f32x4 g0 = *(const f32x4*)&(gamma)[(goff) + 16 * s + 8 * (hh)], g1 = *(const f32x4*)&(gamma)[(goff) + 16 * s + 8 * (hh) + 4];                         \
             const f32x4 b0 = *(const f32x4*)&(beta)[(boff) + 16 * s + 8 * (hh)], b1 = *(const f32x4*)&(beta)[(boff) + 16 * s + 8 * (hh) + 4];                           \

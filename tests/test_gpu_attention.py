@@ -494,6 +494,10 @@ def test_fused_layernorm_rows_with_a_large_mean(C):
     err_ln = rel_l2(ops.layernorm_f16(xd, ga.cuda(), be.cuda()).cpu().double(), ln)          # the unfused kernel on the same rows
     print(f"C = {C}: fused LayerNorm + Linear on large-mean rows rel-L2 {err:.2e} (pcd_layernorm_f16 alone {err_ln:.2e})")
     assert err < 2e-3 and err_ln < 2e-3
+    # the two special rows on their own: inside the bound over 512 rows a row that is 3 % wrong adds 1.3e-3 and passes
+    for r in (7, 8):
+        row = float((got[r] - want[r]).norm() / want[r].norm())
+        assert row <= 1e-3, (C, r, row)
 
 
 @pytest.mark.parametrize("rows", [128, 128 * 7, 128 * 600])
