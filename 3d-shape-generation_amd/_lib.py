@@ -130,6 +130,9 @@ def pair_metrics_workspace_layout(pairs: int, na_max: int, nb_max: int) -> dict:
 PCD_SURF_ROW = ("ACC", "COMP", "CHAMFER_L1", "ACC2", "COMP2", "CHAMFER_L2", "HAUSDORFF", "NC_A", "NC_B", "NC")
 PCD_SURF_ROW_BASE = len(PCD_SURF_ROW)
 PCD_SURF_MAX_THRESHOLDS = 8
+PCD_KNN_MAX_K = 32
+PCD_NORMALS_UNORIENTED, PCD_NORMALS_OUTWARD, PCD_NORMALS_TOWARD_VIEW = 0, 1, 2
+PCD_OUTLIER_STATISTICAL, PCD_OUTLIER_RADIUS = 0, 1
 
 
 # name -> (restype, argtypes).  Kept in the order of include/pcd_hip.h.
@@ -336,6 +339,11 @@ _SIGS = {
     "pcd_surface_metrics_workspace_bytes": (sz, [i32, i32, i32]),
     "pcd_surface_metrics": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, C.POINTER(f32), i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "pcd_voxel_iou": (i32, [vp, vp, i32, i32, f32, vp, vp]),
+    "pcd_knn": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "pcd_cloud_normals_workspace_bytes": (sz, [i32]),
+    "pcd_cloud_normals": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "pcd_cloud_outlier_mask": (i32, [vp, vp, i32, i32, i32, i32, C.c_double, f32, i32, vp, vp, vp]),
+    "pcd_cloud_compact": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "pcd_colsum_f16": (i32, [vp, i64, i32, i32, vp, vp]),
     "pcd_bn_batch_stats": (i32, [vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]),
     "pcd_bn_apply_f16": (i32, [vp, i64, i32, vp, vp, vp, vp, f32, i32, vp, vp]),

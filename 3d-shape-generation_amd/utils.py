@@ -267,6 +267,100 @@ def load_mesh(path: str) -> Mesh:
     return Mesh(torch.from_numpy(v.astype(np.float32)), torch.from_numpy(f.astype(np.int32)))
 
 
+# ------------------------------------------------------------------ point-cloud files
+def save_point_cloud(path: str, points, normals=None, ascii: bool = False) -> None:
+    """Write a cloud (N, 3), CPU or device tensor, as a PLY file: element `vertex` with `float x y z` and, with `normals` (N, 3), `float nx ny
+    nz`; binary little-endian, or text with 9 significant digits (float32 round-trips) under `ascii=True`.  Host only."""
+    if os.path.splitext(path)[1].lower() != ".ply":
+        raise ValueError(f"save_point_cloud writes .ply, not {os.path.splitext(path)[1]!r} ({path})")
+    table = np.ascontiguousarray(torch.as_tensor(points).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+    names = ["x", "y", "z"]
+    if normals is not None:
+        nrm = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+        if nrm.shape != table.shape:
+            raise ValueError(f"normals {nrm.shape} must be shaped like the points {table.shape}")
+        table = np.ascontiguousarray(np.concatenate([table, nrm], axis=1))
+        names += ["nx", "ny", "nz"]
+    header = (f"ply\nformat {'ascii' if ascii else 'binary_little_endian'} 1.0\nelement vertex {table.shape[0]}\n"
+              + "".join(f"property float {n}\n" for n in names) + "end_header\n")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        if ascii:
+            out.write("".join(" ".join(f"{float(v):.9g}" for v in row) + "\n" for row in table).encode("ascii"))
+        else:
+            out.write(table.tobytes())
+
+
+def load_point_cloud(path: str):
+    """Read the vertex element of a PLY file, `ascii` or `binary_little_endian`, as a cloud: -> (points (N, 3) float32, normals (N, 3) float32
+    or None), CPU tensors.  `x y z` (and `nx ny nz`, all three or none) must be `float` or `double` properties; other scalar vertex
+    properties are skipped, and whatever follows the vertex element -- the faces of a mesh file -- is left unread.  `ValueError`, naming
+    the file, for a file that is not such a PLY or that ends inside the vertex element."""
+    if os.path.splitext(path)[1].lower() != ".ply":
+        raise ValueError(f"load_point_cloud reads .ply, not {os.path.splitext(path)[1]!r} ({path})")
+    with open(path, "rb") as src:
+        raw = src.read()
+    end = raw.find(b"end_header")
+    nl = raw.find(b"\n", end)
+    if not raw.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' ... 'end_header')")
+    fmt, count, props, element = None, None, [], None
+    for line in raw[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format" and len(tok) > 1:
+            fmt = tok[1]
+        elif tok[0] == "element" and len(tok) > 2:
+            element = tok[1]
+            if element == "vertex" and count is None:
+                try:
+                    count = int(tok[2])
+                except ValueError:
+                    raise ValueError(f"{path}: the vertex count {tok[2]!r} is not a number") from None
+            elif count is None:
+                raise ValueError(f"{path}: the first element must be 'vertex', found {element!r}")
+        elif tok[0] == "property" and element == "vertex" and len(tok) > 2:
+            if tok[1] == "list":
+                raise ValueError(f"{path}: a list property on the vertex element")
+            if tok[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: unknown property type {tok[1]!r}")
+            props.append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt == "binary_big_endian":
+        raise ValueError(f"{path}: binary_big_endian PLY files are not read (ascii and binary_little_endian are)")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+    if count is None or count < 0:
+        raise ValueError(f"{path}: no vertex element")
+    types = dict(props)
+    have_normals = [a in types for a in ("nx", "ny", "nz")]
+    if any(have_normals) and not all(have_normals):
+        raise ValueError(f"{path}: nx, ny, nz must come all three or not at all")
+    wanted = ["x", "y", "z"] + (["nx", "ny", "nz"] if all(have_normals) else [])
+    for a in wanted:
+        if types.get(a) not in ("f4", "f8"):
+            raise ValueError(f"{path}: vertex property {a!r} must be float or double")
+    body = raw[nl + 1:]
+    if fmt == "ascii":
+        lines = body.decode("ascii", "replace").split("\n")
+        cols = [p[0] for p in props]
+        ix = [cols.index(a) for a in wanted]
+        try:
+            table = np.asarray([[float(lines[i].split()[c]) for c in ix] for i in range(count)], np.float64).reshape(-1, len(wanted))
+        except (IndexError, ValueError) as e:
+            raise ValueError(f"{path}: the file ends inside the vertex element or a row is malformed ({e})") from None
+    else:
+        vdt = np.dtype([(n, "<" + t) for n, t in props])
+        if len(body) < count * vdt.itemsize:
+            raise ValueError(f"{path}: the file ends inside the vertex element")
+        rows = np.frombuffer(body, dtype=vdt, count=count)
+        table = np.stack([rows[a].astype(np.float64) for a in wanted], axis=1).reshape(-1, len(wanted))
+    points = torch.from_numpy(np.ascontiguousarray(table[:, :3], dtype=np.float32))
+    normals = torch.from_numpy(np.ascontiguousarray(table[:, 3:6], dtype=np.float32)) if all(have_normals) else None
+    return points, normals
+
+
 def normalize_mesh(mesh, margin: float = 0.0) -> Mesh:
     """Centre the bounding box of `mesh` on the origin and scale its largest half-extent to 1 - margin (fp32, on the tensors' device); a mesh
     without extent (or without vertices) is only centred.  What `preprocess_meshes.py` does before it voxelizes."""

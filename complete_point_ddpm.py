@@ -3,12 +3,17 @@ unconditional point DDPM (`PointCloudDiffusion.complete`, RePaint-style resampli
 
     python complete_point_ddpm.py [--ckpt-dir DIR] [--clouds FILE.npy] [--num-samples 16] [--num-points 2048]
                                   [--steps 1000] [--resample 10] [--jump 10] [--cut 0.0] [--png-dir DIR]
+                                  [--remove-outliers [--outlier-k 16] [--outlier-ratio 2.0]] [--ply-dir DIR]
 
 The points of each cloud with x < `--cut` are kept, moved to the front and handed over as the partial input, so the
 known counts are ragged.  Every `.ckpt` of `--ckpt-dir` is evaluated; without checkpoints (none ship with the reference)
 a model with deterministic synthetic weights runs, and without `--clouds` (a (B, N, 3) .npy of unit-sphere-scaled
 clouds) the synthetic ShapeNet-shaped clouds of test_point_ddpm.py are used, so the plumbing is exercised end to end.
 `--png-dir DIR` also writes `sample_<i>_3d.png`, `sample_<i>_2d.png` (the completion) and `comparison_<i>.png` (original | completion).
+`--remove-outliers` drops the stray points of every completion on the device (`geometry.remove_outliers`, `--outlier-k` neighbours,
+`--outlier-ratio` standard deviations) and stores `filtered` / `filtered_counts` next to the untouched `completion` (the metrics stay those
+of the completion as sampled); the pictures and PLY files then show the filtered clouds.  `--ply-dir DIR` writes one `sample_<i>.ply` per
+completion with estimated outward normals.
 Multi-GPU: launch with torch.distributed.run; shapes are sharded across ranks and metric rows are all-gathered.
 """
 from __future__ import annotations
@@ -25,6 +30,7 @@ import shapegen_amd  # noqa: F401
 from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import PointCloudDiffusion
+from shapegen_amd.geometry import remove_outliers, save_cloud_plys
 from shapegen_amd.utils import save_shape_pngs, setup_logger
 from test_point_ddpm import synthetic_clouds
 
@@ -68,6 +74,10 @@ def main():
     ap.add_argument("--cut", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join("test", "outputs"))
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write the reference's pictures (sample_{i}_3d.png, sample_{i}_2d.png, comparison_{i}.png) here")
+    ap.add_argument("--remove-outliers", action="store_true", help="drop stray points (statistical outlier removal) and store `filtered`")
+    ap.add_argument("--outlier-k", type=int, default=16, metavar="K", help="neighbours of the outlier rule and of the PLY normals")
+    ap.add_argument("--outlier-ratio", type=float, default=2.0, metavar="R", help="standard deviations above the mean neighbour distance")
+    ap.add_argument("--ply-dir", default=None, metavar="DIR", help="also write sample_{i}.ply with estimated outward normals here")
     args = ap.parse_args()
     torch.manual_seed(24)
     rank, world, local = D.init_from_env()
@@ -93,9 +103,18 @@ def main():
         done, rows = complete_and_score(model, name, val, partial, counts, args.steps, args.resample, args.jump)
         tag = "" if len(models) == 1 else "_" + name
         result["completion" + tag], result["metrics" + tag] = done.cpu().numpy(), rows.cpu().numpy()
+        shapes, kept_counts = done, [done.shape[1]] * done.shape[0]
+        if args.remove_outliers:
+            shapes, kept = remove_outliers(done.contiguous(), k=args.outlier_k, std_ratio=args.outlier_ratio)
+            kept_counts = kept.tolist()
+            result["filtered" + tag], result["filtered_counts" + tag] = shapes.cpu().numpy(), kept.cpu().numpy()
+            logging.getLogger(LOG).info(f"{name}: outlier removal (k {args.outlier_k}, ratio {args.outlier_ratio}) kept {sum(kept_counts)} of "
+                                        f"{done.shape[0] * done.shape[1]} points")
         if args.png_dir and rank == 0:
             for i in range(done.shape[0]):
-                save_shape_pngs(os.path.join(args.png_dir, name) if len(models) > 1 else args.png_dir, i, done[i], val[i].to(device))
+                save_shape_pngs(os.path.join(args.png_dir, name) if len(models) > 1 else args.png_dir, i, shapes[i, :kept_counts[i]], val[i].to(device))
+        if args.ply_dir and rank == 0:
+            save_cloud_plys(os.path.join(args.ply_dir, name) if len(models) > 1 else args.ply_dir, shapes, kept_counts, k=args.outlier_k)
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         np.savez_compressed(os.path.join(args.out, "completions.npz"), **result)

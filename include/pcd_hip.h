@@ -1046,6 +1046,52 @@ int pcd_surface_metrics(const float* a, const float* normals_a, const int* na, i
  * empty union.  PCD_ERR_ARG for a null pointer, pairs <= 0, voxels <= 0 or a threshold that is not finite. */
 int pcd_voxel_iou(const float* a, const float* b, int pairs, int voxels, float threshold, float* out, void* stream);
 
+/* ---- local geometry of a batch of independent clouds (csrc/cloud_geometry.hip; DESIGN.md "Cloud geometry") ----
+ * The packing of the surface evaluation above: cloud p = points[p][0..counts[p]) inside a padded fp32 array [P][n_max][3], counts device int32 [P]
+ * (below 0 counts as 0, above the padded size as that size); rows at or past a count are never read as data.  Every call is one enqueue with no
+ * host synchronisation, bitwise repeatable, and a cloud's result does not depend on the rest of the batch.  PCD_ERR_ARG (before any device work)
+ * for a null required pointer, clouds <= 0 or > 65535, a padded size <= 0, k outside 1 .. PCD_KNN_MAX_K, or what an entry point names below.
+ * k nearest.  For every query i < nq[p] the k nearest targets j < nt[p], sorted: d2 fp32 [P][nq_max][k], index int32 [P][nq_max][k].  d2 =
+ * (dx dx + dy dy) + dz dz in fp32 from direct differences without contraction (the arithmetic of pcd_nearest_neighbors); the candidates are
+ * ordered by the key (bits of d2) << 32 | j, so slot 0 is the nearest and equal distances go to the lower j.  A target whose d2 is not finite
+ * is nobody's neighbour.  With exclude_self the target j == i (the query's own row) is skipped and nothing else is -- the caller passes the
+ * same array as q and t; a duplicate of the point at another index is a neighbour at distance 0.  A query with fewer than k candidates has
+ * (NaN, -1) in the trailing slots; a query with a coordinate that is not finite, and every row at or past nq[p], has (NaN, -1) in every slot.
+ * Slot s does not depend on k. */
+#define PCD_KNN_MAX_K 32
+int pcd_knn(const float* q, const int* nq, int nq_max, const float* t, const int* nt, int nt_max, int clouds, int k, int exclude_self,
+            float* d2, int32_t* index, void* stream);
+/* Normals by principal component analysis of the neighbour lists index [P][n_max][k] (pcd_knn with exclude_self).  The neighbourhood of point i
+ * is the point itself and its neighbours 0 <= index < counts[p] (other entries are skipped).  With fewer than 3 members: normal (0, 0, 0),
+ * curvature NaN.  Otherwise the covariance about the neighbourhood's own mean, with eigenvalues l0 <= l1 <= l2: the normal is the unit
+ * eigenvector of l0 and the curvature l0 / (l0 + l1 + l2) (NaN for a trace of 0).  All of it is computed in double from the differences to
+ * point i and rounded to fp32 once, so |n| = 1 to an fp32 rounding; where l0 = l1 the direction is one of the plane's, still of unit length.
+ * mode: PCD_NORMALS_UNORIENTED (the sign is unspecified but repeatable), PCD_NORMALS_OUTWARD (n . (p - c) >= 0 with c the mean, accumulated
+ * in double, of the cloud's rows below the count whose coordinates are finite), PCD_NORMALS_TOWARD_VIEW (n . (v - p) >= 0 with v =
+ * viewpoints[p], fp32 [P][3]).  normals fp32 [P][n_max][3]; curvature fp32 [P][n_max] or null.  Rows at or past the count, and a neighbourhood
+ * with a coordinate that is not finite: zero normal, NaN curvature.  workspace: pcd_cloud_normals_workspace_bytes() bytes, any contents, read
+ * and written only under PCD_NORMALS_OUTWARD (null otherwise is fine).  PCD_ERR_ARG also for an unknown mode, PCD_NORMALS_TOWARD_VIEW with
+ * null viewpoints, PCD_NORMALS_OUTWARD with a workspace that is null or too small. */
+enum { PCD_NORMALS_UNORIENTED = 0, PCD_NORMALS_OUTWARD = 1, PCD_NORMALS_TOWARD_VIEW = 2 };
+size_t pcd_cloud_normals_workspace_bytes(int clouds);
+int pcd_cloud_normals(const float* points, const int* counts, int n_max, int clouds, const int32_t* index, int k, int mode,
+                      const float* viewpoints, float* normals, float* curvature, void* workspace, size_t workspace_bytes, void* stream);
+/* Outlier mask from the neighbour distances d2 [P][n_max][k] of pcd_knn (a NaN slot is not valid).  dbar_i = the mean over the valid slots of
+ * sqrtf(d2): correctly rounded fp32 roots, summed in slot order and divided in double.  PCD_OUTLIER_STATISTICAL: a point without a valid slot
+ * is dropped and takes no part in the statistics; mu and sigma (the population standard deviation, two passes) over the points that have a
+ * dbar, in double in a fixed order; the point is kept iff dbar_i <= mu + std_ratio sigma, compared in double.  PCD_OUTLIER_RADIUS: the point is
+ * kept iff at least min_neighbors slots have d2 <= radius * radius, one fp32 product.  mask uint8 [P][n_max], 1 = keep, 0 at and past the count;
+ * mean_distance fp32 [P][n_max] or null: dbar_i rounded to fp32, NaN without a valid slot and at and past the count.  PCD_ERR_ARG also for an
+ * unknown method, a std_ratio that is not finite, a radius that is negative or not finite, min_neighbors outside 1 .. k. */
+enum { PCD_OUTLIER_STATISTICAL = 0, PCD_OUTLIER_RADIUS = 1 };
+int pcd_cloud_outlier_mask(const float* d2, const int* counts, int n_max, int clouds, int k, int method, double std_ratio, float radius,
+                           int min_neighbors, uint8_t* mask, float* mean_distance, void* stream);
+/* Stable compaction: the rows i < counts[p] with mask[p][i] != 0 move, in their order, to the front of points_out[p] (and those of the
+ * optional second array attr [P][n_max][3], normals for instance, to attr_out), the rows behind them are set to zero and counts_out[p] is their
+ * number.  Nothing is read back.  PCD_ERR_ARG also for attr without attr_out (or the reverse) and for an output that is its input. */
+int pcd_cloud_compact(const float* points, const float* attr, const uint8_t* mask, const int* counts, int n_max, int clouds,
+                      float* points_out, float* attr_out, int* counts_out, void* stream);
+
 /* ------------------------------------------------ training step of the point denoiser
  * diffusion.py:70-86,170-186 (add_noise -> model in train() mode -> F.l1_loss -> AdamW, diffusion.py:60).
  * The dense products (forward, backward-data, backward-weight) are pcd_gemm_f16* calls; these entry points

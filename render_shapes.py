@@ -7,7 +7,8 @@ Inputs by extension.  `.npz`: every array of it that is a batch of clouds (B, N,
 `test_point_ddpm.py` writes it, `samples` of `generate_point_ddpm.py`, `sample_<i>` of `test_point_ldm.py` -- or of voxel grids (B, 1, D, H, W) /
 (B, D, H, W) / (D, H, W), which are drawn as their surface-nets meshes at `--threshold`; other arrays, and the `metrics*` rows the scripts
 store next to their shapes, are skipped (`--arrays NAME ...` picks arrays by name instead).  `.obj` / `.ply`: one mesh
-(`utils.load_mesh`), normalised to the unit cube.  Per shape one PNG `<input>_<array>_<i>.png` goes to `--out`: a turntable of `--views` views
+(`utils.load_mesh`), normalised to the unit cube; a `.ply` that holds no faces (`utils.save_point_cloud`, `--ply-dir` of the generation
+scripts) is drawn as the cloud it is, in its own coordinates like the clouds of an `.npz`.  Per shape one PNG `<input>_<array>_<i>.png` goes to `--out`: a turntable of `--views` views
 at elevation `--elev`, side by side.  `--grid COLS` writes one contact sheet `<input>_<array>.png` per array instead, the first view of every
 shape, COLS to a row.  No text and no axes in the pictures.  One process, one GPU.
 """
@@ -28,6 +29,8 @@ def shapes_of(path: str, threshold: float, arrays=None):
     ext = os.path.splitext(path)[1].lower()
     if ext in (".obj", ".ply"):
         mesh = utils.load_mesh(path)
+        if ext == ".ply" and mesh.faces.shape[0] == 0:
+            return [("cloud", "points", [mesh.vertices.cuda()])]
         return [("mesh", "meshes", [utils.normalize_mesh(utils.Mesh(mesh.vertices.cuda(), mesh.faces.cuda()))])]
     if ext != ".npz":
         raise ValueError(f"render_shapes reads .npz, .obj or .ply, not {ext!r} ({path})")
