@@ -344,6 +344,11 @@ _SIGS = {
     "pcd_cloud_normals": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
     "pcd_cloud_outlier_mask": (i32, [vp, vp, i32, i32, i32, i32, C.c_double, f32, i32, vp, vp, vp]),
     "pcd_cloud_compact": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "pcd_cloud_spacing": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, f32, vp, vp]),
+    "pcd_cloud_shell_fill": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "pcd_grid_fill_outside": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "pcd_grid_depth_field": (i32, [vp, i32, i32, f32, vp, f32, vp, vp, vp]),
+    "pcd_project_to_cloud": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, f32, f32, vp, vp]),
     "pcd_colsum_f16": (i32, [vp, i64, i32, i32, vp, vp]),
     "pcd_bn_batch_stats": (i32, [vp, i64, i32, f32, vp, vp, vp, vp, vp, vp]),
     "pcd_bn_apply_f16": (i32, [vp, i64, i32, vp, vp, vp, vp, f32, i32, vp, vp]),

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "geo_prims.h"
 
 namespace pcd {
 
@@ -25,11 +26,6 @@ constexpr int KNN_TILE = 512;      // targets per LDS tile
 constexpr int KNN_BLOCK = 256;     // queries per workgroup, one per thread
 constexpr int KNN_STEP = 4;        // targets per step of the inner loop: one group of LDS reads, one look at the queues
 constexpr int KNN_PEND = 8;        // parked candidates per thread; a queue is emptied before a step could overflow it
-
-__device__ __forceinline__ int geo_count(const int* n, int p, int cap) {
-    const int v = n[p];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
 
 // the sorted list takes (d, j) if d is below its last entry; entries equal to d stay in front of it (they came with a lower j)
 template <int K>
@@ -131,25 +127,6 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(const float* __restrict_
     }
 }
 
-// sums over the 256 threads in a fixed order: butterfly over each wave (every lane ends with the same bits), then the four waves in order
-__device__ __forceinline__ double geo_block_sum(double v, double* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
-
-__device__ __forceinline__ int geo_block_sum(int v, int* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
-}
-
 // grid (P): centroid[p][3] = the mean in double of the rows below the count whose three coordinates are finite (0 without one)
 __global__ __launch_bounds__(256) void geo_centroid_kernel(const float* __restrict__ points, const int* __restrict__ counts, int N,
                                                            double* __restrict__ centroid) {
@@ -174,27 +151,6 @@ __global__ __launch_bounds__(256) void geo_centroid_kernel(const float* __restri
         out[2] = c > 0 ? sz / (double)c : 0.0;
     }
 }
-
-// one Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix, r the third index: app, aqq, apq, arp, arq and the columns p, q of V
-__device__ __forceinline__ void geo_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v1p,
-                                           double& v2p, double& v0q, double& v1q, double& v2q) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double tt = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));      // 0 for a theta beyond the range of its square
-    const double tn = theta < 0.0 ? -tt : tt;
-    const double c = 1.0 / sqrt(tn * tn + 1.0), s = tn * c;
-    app = app - tn * apq;
-    aqq = aqq + tn * apq;
-    apq = 0.0;
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
-    const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
-    const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
-    const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
-    v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
-}
-
-constexpr int GEO_SWEEPS = 8;      // cyclic Jacobi on 3 x 3 converges quadratically; 5 sweeps reach double precision, the rest are free
 
 // grid (ceil(N / 256), P): normals [P][N][3], curvature [P][N] or null.  mode 0: no orientation, 1: away from centroid[p], 2: toward view[p].
 __global__ __launch_bounds__(256) void geo_normals_kernel(const float* __restrict__ points, const int* __restrict__ counts, int N,

@@ -1,9 +1,10 @@
 """Local geometry of generated clouds on the device (csrc/cloud_geometry.hip; DESIGN.md "Cloud geometry"): the k nearest neighbours of
-every point, PCA normals, and statistical / radius outlier removal.
+every point, PCA normals, and statistical / radius outlier removal; and closed triangle meshes from clouds by grid closing
+(csrc/cloud_mesh.hip; DESIGN.md "Cloud to mesh"): `cloud_to_meshes` and its stages.
 
 Clouds are packed as `metrics._pack_clouds` packs them: a (P, N, 3) device tensor with optional (P,) counts, or a list of ragged
 (n_i, 3) device clouds.  PyTorch allocates; every value comes from a kernel, nothing is read back and nothing synchronises with the
-host, so every function here can be captured in a graph.  A CPU tensor raises the usual RuntimeError; bad arguments raise ValueError
+host, so every function here can be captured in a graph (`cloud_to_meshes` reads the mesh sizes back once, as it says).  A CPU tensor raises the usual RuntimeError; bad arguments raise ValueError
 before the library is loaded.
 """
 from __future__ import annotations
@@ -15,7 +16,7 @@ import torch
 
 from . import _lib
 from .metrics import _pack_clouds
-from .utils import save_point_cloud
+from .utils import Mesh, save_mesh, save_point_cloud
 
 
 def _check_k(k) -> int:
@@ -150,3 +151,240 @@ def save_cloud_plys(ply_dir: str, clouds, counts=None, k: int = 16) -> None:
     host_points, host_normals, sizes = points.cpu(), normals.cpu(), cnt.tolist()
     for i, n in enumerate(sizes):
         save_point_cloud(os.path.join(ply_dir, f"sample_{i}.ply"), host_points[i, :n], host_normals[i, :n])
+
+
+# ------------------------------------------------------------------ cloud -> closed mesh (csrc/cloud_mesh.hip; DESIGN.md "Cloud to mesh")
+MESH_R_MIN, MESH_R_MAX = 8, 64
+
+
+def _check_grid(resolution, bounds, inset):
+    """-> (R, lo, hi, h): the validated grid of a cloud-to-mesh call, h = (hi - lo) / (R - 1) in double."""
+    if isinstance(resolution, bool) or not isinstance(resolution, int) or not MESH_R_MIN <= resolution <= MESH_R_MAX:
+        raise ValueError(f"resolution must be an integer in {MESH_R_MIN} .. {MESH_R_MAX} (one 64-bit word per grid row), got {resolution!r}")
+    try:
+        lo, hi = (float(b) for b in bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds must be a pair (lo, hi) of numbers, got {bounds!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError(f"bounds must be finite with lo < hi, got {bounds!r}")
+    if isinstance(inset, bool) or not isinstance(inset, (int, float)) or not -1.0 <= float(inset) <= 1.0:
+        raise ValueError(f"inset must be a number of pitches in [-1, 1], got {inset!r}")
+    return resolution, lo, hi, (hi - lo) / (resolution - 1)
+
+
+def _check_radius(radius, radius_scale, lo, hi):
+    if radius is None:
+        if isinstance(radius_scale, bool) or not isinstance(radius_scale, (int, float)) or not (math.isfinite(radius_scale) and radius_scale > 0):
+            raise ValueError(f"radius_scale must be a finite number > 0, got {radius_scale!r}")
+    elif isinstance(radius, torch.Tensor):
+        if radius.dim() != 1:
+            raise ValueError("a radius tensor must be shaped (P,), one radius per cloud")
+    elif isinstance(radius, bool) or not isinstance(radius, (int, float)) or not (math.isfinite(radius) and 0 < radius <= (hi - lo) / 2):
+        raise ValueError(f"radius must be None, a (P,) tensor or a number in (0, (hi - lo) / 2 = {(hi - lo) / 2}] -- the shell costs "
+                         f"N (r / h)^3 --, got {radius!r}")
+
+
+def _radii(points, cnt, radius, radius_scale, inset, h):
+    """The radius every cloud is closed with, (P,) float32: max(r_p, (2 - inset) h), r_p given or radius_scale * the cloud's spacing."""
+    P, N = points.shape[0], points.shape[1]
+    lib = _lib.load()
+    out = torch.empty(P, dtype=torch.float32, device=points.device)
+    if radius is None:
+        d2, _ = _knn(points, cnt, points, cnt, 8, True)
+        _lib.check(lib.pcd_cloud_spacing(d2.data_ptr(), cnt.data_ptr(), N, P, 8, None, float(radius_scale), h, float(inset), out.data_ptr(),
+                                         _lib.stream_ptr()), "cloud_spacing")
+        return out
+    if isinstance(radius, torch.Tensor):
+        if radius.device.type != "cuda":
+            raise RuntimeError("geometry runs only on an MI355X device: move the radii to 'cuda' (no CPU path)")
+        if radius.shape[0] != P:
+            raise ValueError("a radius tensor must hold one radius per cloud")
+        given = radius.to(device=points.device, dtype=torch.float32).contiguous()
+    else:
+        given = torch.full((P,), float(radius), dtype=torch.float32, device=points.device)
+    _lib.check(lib.pcd_cloud_spacing(None, None, 0, P, 0, given.data_ptr(), 1.0, h, float(inset), out.data_ptr(), _lib.stream_ptr()),
+               "cloud_spacing")
+    return out
+
+
+def _words(t, what):
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[1] != t.shape[2] or t.dtype != torch.int64:
+        raise ValueError(f"{what} must be a (P, R, R) int64 tensor of row words, bit x of word [z][y] = node (z, y, x)")
+    if not MESH_R_MIN <= t.shape[1] <= MESH_R_MAX:
+        raise ValueError(f"{what}: the resolution must lie in {MESH_R_MIN} .. {MESH_R_MAX}, got {t.shape[1]}")
+    if t.device.type != "cuda":
+        raise RuntimeError("geometry runs only on an MI355X device: move the grid words to 'cuda' (no CPU path)")
+    return t.contiguous()
+
+
+def cloud_radius(clouds, resolution=64, radius=None, radius_scale=1.5, inset=0.0, bounds=(-1.25, 1.25), counts=None):
+    """The ball radius `cloud_to_meshes` closes every cloud with, (P,) float32 on the device.  `radius=None`: radius_scale * s_p, s_p the mean
+    distance from a point to its 8th nearest neighbour over the points that have 8; a number or a (P,) tensor: that.  In every case at least
+    (2 - inset) pitches h = (hi - lo) / (resolution - 1), which is also what a cloud of fewer than 9 points gets."""
+    R, lo, hi, h = _check_grid(resolution, bounds, inset)
+    _check_radius(radius, radius_scale, lo, hi)
+    points, cnt = _pack_clouds(clouds, counts, "clouds")
+    return _radii(points, cnt, radius, radius_scale, inset, h)
+
+
+def _shell_fill(points, cnt, R, lo, h, radii):
+    P, N = points.shape[0], points.shape[1]
+    dev = points.device
+    shell = torch.empty(P, R, R, dtype=torch.int64, device=dev)
+    outside = torch.empty(P, R, R, dtype=torch.int64, device=dev)
+    info = torch.empty(P, 3, dtype=torch.int32, device=dev)
+    sweeps = torch.empty(P, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().pcd_cloud_shell_fill(points.data_ptr(), cnt.data_ptr(), N, P, R, lo, h, radii.data_ptr(), shell.data_ptr(),
+                                                outside.data_ptr(), info.data_ptr(), sweeps.data_ptr(), _lib.stream_ptr()), "cloud_shell_fill")
+    return shell, outside, info, sweeps
+
+
+def cloud_shell_grid(clouds, resolution=64, radius=None, radius_scale=1.5, inset=0.0, bounds=(-1.25, 1.25), counts=None):
+    """Stages 1 - 3 of `cloud_to_meshes`: -> (shell (P, R, R) int64, outside (P, R, R) int64, info (P, 3) int32, radius (P,) float32).  A word
+    [z][y] holds the nodes of one grid row, bit x = node x (read the int64 as unsigned).  Shell: the nodes within the radius of a finite point
+    of the cloud; outside: the free nodes that the grid's surroundings reach through free nodes, 6-connected; info = (shell nodes, enclosed
+    nodes, shell nodes on the six faces of the grid)."""
+    R, lo, hi, h = _check_grid(resolution, bounds, inset)
+    _check_radius(radius, radius_scale, lo, hi)
+    points, cnt = _pack_clouds(clouds, counts, "clouds")
+    radii = _radii(points, cnt, radius, radius_scale, inset, h)
+    shell, outside, info, _ = _shell_fill(points, cnt, R, lo, h, radii)
+    return shell, outside, info, radii
+
+
+def grid_outside(shell, return_sweeps=False):
+    """The fill alone: shell words (P, R, R) int64 -> (outside (P, R, R) int64, info (P, 3) int32 [, sweeps (P,) int32]); `sweeps` counts the
+    passes over the grid until one changed nothing (-1 would say the cap of R^3 was passed)."""
+    words = _words(shell, "shell")
+    P, R = words.shape[0], words.shape[1]
+    outside = torch.empty_like(words)
+    info = torch.empty(P, 3, dtype=torch.int32, device=words.device)
+    sweeps = torch.empty(P, dtype=torch.int32, device=words.device)
+    _lib.check(_lib.load().pcd_grid_fill_outside(words.data_ptr(), P, R, outside.data_ptr(), info.data_ptr(), sweeps.data_ptr(),
+                                                 _lib.stream_ptr()), "grid_fill_outside")
+    return (outside, info, sweeps) if return_sweeps else (outside, info)
+
+
+def _depth_field(outside, R, h, radii, inset, want_d2):
+    P = outside.shape[0]
+    v = torch.empty(P, R, R, R, dtype=torch.float32, device=outside.device)
+    d2 = torch.empty(P, R, R, R, dtype=torch.int32, device=outside.device) if want_d2 else None
+    _lib.check(_lib.load().pcd_grid_depth_field(outside.data_ptr(), P, R, h, radii.data_ptr(), float(inset), _lib.ptr(d2), v.data_ptr(),
+                                                _lib.stream_ptr()), "grid_depth_field")
+    return v, d2
+
+
+def grid_depth_field(outside, radius, inset=0.0, bounds=(-1.25, 1.25), return_d2=False):
+    """Stages 4 and 5: outside words (P, R, R) int64 and the radii (P,) float32 as `cloud_radius` returns them (used as they are, no clamp) ->
+    v (P, R, R, R) float32 [, D2 (P, R, R, R) int32].  D2 is the exact squared distance in pitches to the nearest outside node, the layer round
+    the grid included; v = 0 on outside nodes and 1 + ((sqrt(D2) h - r) - inset h) elsewhere, so the closed solid is v > 1."""
+    if not isinstance(radius, torch.Tensor) or not isinstance(outside, torch.Tensor) or radius.shape != outside.shape[:1]:
+        raise ValueError("radius must be a (P,) tensor, one radius per grid")
+    words = _words(outside, "outside")
+    R, lo, hi, h = _check_grid(int(words.shape[1]), bounds, inset)
+    if radius.device.type != "cuda":
+        raise RuntimeError("geometry runs only on an MI355X device: move the radii to 'cuda' (no CPU path)")
+    v, d2 = _depth_field(words, R, h, radius.to(torch.float32).contiguous(), inset, return_d2)
+    return (v, d2) if return_d2 else v
+
+
+def _project(verts, vcnt, points, cnt, index, k, scale, offset, out):
+    P, V = verts.shape[0], verts.shape[1]
+    _lib.check(_lib.load().pcd_project_to_cloud(verts.data_ptr(), vcnt.data_ptr(), V, _lib.ptr(points), _lib.ptr(cnt),
+                                                0 if points is None else points.shape[1], P, _lib.ptr(index), k, scale, offset,
+                                                out.data_ptr(), _lib.stream_ptr()), "project_to_cloud")
+    return out
+
+
+def project_to_cloud(vertices, clouds, k=8, vertex_counts=None, counts=None, index=None):
+    """Stage 7: move every vertex onto the plane fitted to its k nearest points of its own cloud: c their mean, n the unit eigenvector of the
+    least eigenvalue of their covariance, v' = v - ((v - c) . n) n, in double on the device, rounded to fp32 once.  `vertices` (P, V, 3) with
+    optional `vertex_counts`, packed like the clouds; -> (P, V, 3) float32, rows past a count zero.  A vertex with fewer than 3 neighbours stays
+    where it is.  `index` (P, V, k) int32: neighbour lists to use instead of searching."""
+    k = _check_k(k)
+    verts, vcnt = _pack_clouds(vertices, vertex_counts, "vertices")
+    points, cnt = _pack_clouds(clouds, counts, "clouds")
+    if verts.shape[0] != points.shape[0]:
+        raise ValueError("vertices and clouds must hold the same number of clouds")
+    if index is None:
+        _, index = _knn(verts, vcnt, points, cnt, k, False)
+    elif not isinstance(index, torch.Tensor) or index.shape != (verts.shape[0], verts.shape[1], k) or index.dtype != torch.int32:
+        raise ValueError("index must be a (P, V, k) int32 tensor")
+    elif index.device.type != "cuda":
+        raise RuntimeError("geometry runs only on an MI355X device: move the index lists to 'cuda' (no CPU path)")
+    return _project(verts, vcnt, points, cnt, index.contiguous(), k, 1.0, 0.0, torch.zeros_like(verts))
+
+
+def cloud_to_meshes(clouds, resolution=64, radius=None, radius_scale=1.5, inset=0.0, bounds=(-1.25, 1.25), counts=None, project=True, k=8,
+                    return_info=False):
+    """One closed triangle mesh per cloud, by morphological closing on a grid (DESIGN.md "Cloud to mesh"): -> list of `utils.Mesh`, views of one
+    padded (P, Vmax, 3) vertex tensor and one packed face tensor; with `return_info` also a dict of device tensors `radius` (P,) float32 and
+    `shell`, `enclosed`, `border` (P,) int32.
+
+    The grid has `resolution` nodes per axis over `bounds` = (lo, hi), pitch h = (hi - lo) / (resolution - 1).  (1) The radius r of a cloud is
+    `radius` (a number, or a (P,) tensor) or, for None, `radius_scale` times the cloud's spacing, the mean distance to the 8th nearest neighbour;
+    in every case at least (2 - inset) h.  (2) Shell: the nodes within r of a point.  (3) Outside: the free nodes reached from the grid's
+    surroundings through free nodes; the free nodes left are enclosed.  (4, 5) The solid (shell + enclosed) is eroded by r + inset h through the
+    exact distance to the outside: what remains is the closing of the point set by a ball of radius r with its cavities filled.  (6) Surface
+    nets (`utils.voxel_tensor_to_meshes`' kernels) on that field, mapped to `bounds`.  (7) `project`: every vertex moves onto the plane fitted
+    to its `k` nearest points of the cloud (`project_to_cloud`); the faces do not change, so the mesh stays closed and consistently oriented as
+    a complex, but self-intersection after the projection is not excluded.  No oriented normals are needed anywhere.  All integer and bit work,
+    or fp32 without contraction: bitwise repeatable, a cloud's mesh independent of the rest of the batch.  One host read (the mesh sizes), as in
+    `voxel_tensor_to_meshes`, and no other synchronisation.
+
+    Limits.  Gaps narrower than 2 r are bridged.  A part thinner than about (1 + inset) pitches, and any open sheet at inset >= 0, vanishes;
+    inset = -1 keeps it as a slab of two pitches that the projection flattens.  `bounds` must hold the cloud plus r + 2 h, or the solid is cut
+    at the border: `border` > 0 reports shell nodes on the faces of the grid.  A shell that does not seal (`enclosed` == 0 on a shape that has
+    an inside) gives an empty or fragmentary mesh: raise `radius_scale`.  Clouds of fewer than 9 points get the least radius; empty clouds and
+    clouds whose solid erodes away give empty meshes, no error."""
+    R, lo, hi, h = _check_grid(resolution, bounds, inset)
+    _check_radius(radius, radius_scale, lo, hi)
+    k = _check_k(k)
+    points, cnt = _pack_clouds(clouds, counts, "clouds")
+    P, dev = points.shape[0], points.device
+    lib = _lib.load()
+    radii = _radii(points, cnt, radius, radius_scale, inset, h)
+    _, outside, info, sweeps = _shell_fill(points, cnt, R, lo, h, radii)
+    v, _ = _depth_field(outside, R, h, radii, inset, False)
+    ws = torch.empty(max(lib.pcd_mesh_workspace_bytes(P, R, R, R), 4) // 4, dtype=torch.int32, device=dev)
+    sizes = torch.empty(P, 2, dtype=torch.int32, device=dev)
+    _lib.check(lib.pcd_mesh_count(v.data_ptr(), P, R, R, R, 1.0, ws.data_ptr(), sizes.data_ptr(), _lib.stream_ptr()), "mesh_count")
+    host = torch.cat([sizes.reshape(-1), sweeps]).cpu().tolist()          # the one host read: the outputs are sized on the host
+    nv, nf, done = host[0:2 * P:2], host[1:2 * P:2], host[2 * P:]
+    if min(done) < 0:
+        raise RuntimeError("cloud_to_meshes: the outside fill passed its cap of resolution^3 sweeps")
+    vmax = max(nv)
+    verts = torch.zeros(P, max(vmax, 1), 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(sum(nf), 3, dtype=torch.int32, device=dev)
+    if vmax > 0:
+        offsets = torch.stack([torch.arange(P, dtype=torch.int64, device=dev) * vmax,
+                               torch.cumsum(sizes[:, 1], dim=0, dtype=torch.int64) - sizes[:, 1]], dim=1).contiguous()
+        _lib.check(lib.pcd_mesh_emit(v.data_ptr(), P, R, R, R, 1.0, ws.data_ptr(), offsets.data_ptr(), verts.data_ptr(), faces.data_ptr(),
+                                     _lib.stream_ptr()), "mesh_emit")
+        vcnt = sizes[:, 0].contiguous()
+        _project(verts, vcnt, None, None, None, 0, (hi - lo) / 2, (lo + hi) / 2, verts)      # the nets' [-1, 1] -> bounds
+        if project:
+            _, index = _knn(verts, vcnt, points, cnt, k, False)
+            _project(verts, vcnt, points, cnt, index, k, 1.0, 0.0, verts)
+    meshes = [Mesh(verts[p, :nv[p]], f) for p, f in enumerate(torch.split(faces, nf))]
+    if return_info:
+        return meshes, {"radius": radii, "shell": info[:, 0], "enclosed": info[:, 1], "border": info[:, 2]}
+    return meshes
+
+
+def save_cloud_meshes(mesh_dir: str, clouds, counts=None, resolution: int = 64, radius_scale: float = 1.5, fmt: str = "obj", log=None):
+    """`cloud_to_meshes` on a batch and one `sample_{i}.{fmt}` per cloud in `mesh_dir`; per shape the vertices, faces and enclosed nodes go to
+    `log` (a logging.Logger), with a warning where the shell touches the border of the grid or the mesh is empty.  -> the meshes."""
+    if fmt not in ("obj", "ply"):
+        raise ValueError(f"fmt must be 'obj' or 'ply', got {fmt!r}")
+    meshes, info = cloud_to_meshes(clouds, resolution=resolution, radius_scale=radius_scale, counts=counts, return_info=True)
+    enclosed, border = info["enclosed"].tolist(), info["border"].tolist()
+    for i, mesh in enumerate(meshes):
+        save_mesh(os.path.join(mesh_dir, f"sample_{i}.{fmt}"), mesh)
+        if log is not None:
+            log.info(f"mesh {i}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces, {enclosed[i]} enclosed nodes")
+            if border[i] > 0:
+                log.warning(f"mesh {i}: {border[i]} shell nodes on the border of the grid: the solid is cut there (widen the bounds)")
+            if mesh.faces.shape[0] == 0:
+                log.warning(f"mesh {i} is empty: the shell did not seal or the solid eroded away (raise --mesh-radius-scale)")
+    return meshes

@@ -4,6 +4,7 @@ unconditional point DDPM (`PointCloudDiffusion.complete`, RePaint-style resampli
     python complete_point_ddpm.py [--ckpt-dir DIR] [--clouds FILE.npy] [--num-samples 16] [--num-points 2048]
                                   [--steps 1000] [--resample 10] [--jump 10] [--cut 0.0] [--png-dir DIR]
                                   [--remove-outliers [--outlier-k 16] [--outlier-ratio 2.0]] [--ply-dir DIR]
+                                  [--mesh-dir DIR [--mesh-resolution 64] [--mesh-format obj|ply] [--mesh-radius-scale 1.5]]
 
 The points of each cloud with x < `--cut` are kept, moved to the front and handed over as the partial input, so the
 known counts are ragged.  Every `.ckpt` of `--ckpt-dir` is evaluated; without checkpoints (none ship with the reference)
@@ -13,7 +14,9 @@ clouds) the synthetic ShapeNet-shaped clouds of test_point_ddpm.py are used, so 
 `--remove-outliers` drops the stray points of every completion on the device (`geometry.remove_outliers`, `--outlier-k` neighbours,
 `--outlier-ratio` standard deviations) and stores `filtered` / `filtered_counts` next to the untouched `completion` (the metrics stay those
 of the completion as sampled); the pictures and PLY files then show the filtered clouds.  `--ply-dir DIR` writes one `sample_<i>.ply` per
-completion with estimated outward normals.
+completion with estimated outward normals.  `--mesh-dir DIR` writes one closed triangle mesh `sample_<i>.obj` (or `.ply`) per completion, the
+filtered one under `--remove-outliers` (`geometry.cloud_to_meshes` on a grid of `--mesh-resolution` nodes per axis, closing radius
+`--mesh-radius-scale` point spacings), and logs vertices, faces and enclosed nodes per shape.
 Multi-GPU: launch with torch.distributed.run; shapes are sharded across ranks and metric rows are all-gathered.
 """
 from __future__ import annotations
@@ -30,7 +33,7 @@ import shapegen_amd  # noqa: F401
 from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import PointCloudDiffusion
-from shapegen_amd.geometry import remove_outliers, save_cloud_plys
+from shapegen_amd.geometry import remove_outliers, save_cloud_meshes, save_cloud_plys
 from shapegen_amd.utils import save_shape_pngs, setup_logger
 from test_point_ddpm import synthetic_clouds
 
@@ -78,7 +81,13 @@ def main():
     ap.add_argument("--outlier-k", type=int, default=16, metavar="K", help="neighbours of the outlier rule and of the PLY normals")
     ap.add_argument("--outlier-ratio", type=float, default=2.0, metavar="R", help="standard deviations above the mean neighbour distance")
     ap.add_argument("--ply-dir", default=None, metavar="DIR", help="also write sample_{i}.ply with estimated outward normals here")
+    ap.add_argument("--mesh-dir", default=None, metavar="DIR", help="also write one closed triangle mesh sample_{i}.obj|ply per cloud here")
+    ap.add_argument("--mesh-resolution", type=int, default=64, metavar="R", help="grid nodes per axis of the cloud-to-mesh closing, 8 .. 64")
+    ap.add_argument("--mesh-format", choices=("obj", "ply"), default="obj")
+    ap.add_argument("--mesh-radius-scale", type=float, default=1.5, metavar="S", help="closing radius in units of the cloud's point spacing")
     args = ap.parse_args()
+    if not 8 <= args.mesh_resolution <= 64:
+        ap.error("--mesh-resolution must lie in 8 .. 64")
     torch.manual_seed(24)
     rank, world, local = D.init_from_env()
     device = torch.device("cuda", local)
@@ -115,6 +124,9 @@ def main():
                 save_shape_pngs(os.path.join(args.png_dir, name) if len(models) > 1 else args.png_dir, i, shapes[i, :kept_counts[i]], val[i].to(device))
         if args.ply_dir and rank == 0:
             save_cloud_plys(os.path.join(args.ply_dir, name) if len(models) > 1 else args.ply_dir, shapes, kept_counts, k=args.outlier_k)
+        if args.mesh_dir and rank == 0:
+            save_cloud_meshes(os.path.join(args.mesh_dir, name) if len(models) > 1 else args.mesh_dir, shapes.contiguous(), kept_counts,
+                              resolution=args.mesh_resolution, radius_scale=args.mesh_radius_scale, fmt=args.mesh_format, log=logging.getLogger(LOG))
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         np.savez_compressed(os.path.join(args.out, "completions.npz"), **result)

@@ -3,6 +3,7 @@
     python generate_point_ddpm.py [--ckpt-dir DIR] [--sampler dpm|ddim|ddpm] [--steps N] [--order 2] [--num-samples 16]
                                   [--num-points 2048] [--compare-steps 1000] [--out DIR] [--label K [--guidance W]]
                                   [--png-dir DIR] [--remove-outliers [--outlier-k 16] [--outlier-ratio 2.0]] [--ply-dir DIR]
+                                  [--mesh-dir DIR [--mesh-resolution 64] [--mesh-format obj|ply] [--mesh-radius-scale 1.5]]
 
 `--sampler dpm` (default, 20 steps) is `PointCloudDiffusion.sample_dpm`, the second-order multistep solver on a log-SNR grid;
 `ddim` and `ddpm` are the reference's `sample` and `sample2` (default 1000 steps).  With `--compare-steps T` the start state is
@@ -18,6 +19,9 @@ sharded across ranks and all-gathered.  `--png-dir DIR` also writes the referenc
 its `--outlier-k` nearest neighbours exceeds the cloud's mean by `--outlier-ratio` standard deviations) and stores the result as `filtered`
 (zeros behind the kept points) and `filtered_counts` next to the untouched `samples`; the pictures and the PLY files then show the filtered
 clouds.  `--ply-dir DIR` writes one `sample_{i}.ply` per cloud with estimated outward normals (`geometry.estimate_normals`).
+`--mesh-dir DIR` writes one closed triangle mesh `sample_{i}.obj` (or `.ply`) per cloud, the filtered cloud under `--remove-outliers`
+(`geometry.cloud_to_meshes`: closing on a grid of `--mesh-resolution` nodes per axis with a ball of `--mesh-radius-scale` point spacings), and
+logs vertices, faces and enclosed nodes per shape, with a warning where the shell touches the grid's border or the mesh is empty.
 """
 from __future__ import annotations
 
@@ -33,7 +37,7 @@ import shapegen_amd  # noqa: F401
 from shapegen_amd import dist as D
 from shapegen_amd import specs
 from shapegen_amd.diffusion import PointCloudDiffusion
-from shapegen_amd.geometry import remove_outliers, save_cloud_plys
+from shapegen_amd.geometry import remove_outliers, save_cloud_meshes, save_cloud_plys
 from shapegen_amd.metrics import chamfer_per_sample
 from shapegen_amd.utils import save_shape_pngs, setup_logger
 
@@ -74,9 +78,15 @@ def main():
     ap.add_argument("--outlier-k", type=int, default=16, metavar="K", help="neighbours of the outlier rule and of the PLY normals")
     ap.add_argument("--outlier-ratio", type=float, default=2.0, metavar="R", help="standard deviations above the mean neighbour distance")
     ap.add_argument("--ply-dir", default=None, metavar="DIR", help="also write sample_{i}.ply with estimated outward normals here")
+    ap.add_argument("--mesh-dir", default=None, metavar="DIR", help="also write one closed triangle mesh sample_{i}.obj|ply per cloud here")
+    ap.add_argument("--mesh-resolution", type=int, default=64, metavar="R", help="grid nodes per axis of the cloud-to-mesh closing, 8 .. 64")
+    ap.add_argument("--mesh-format", choices=("obj", "ply"), default="obj")
+    ap.add_argument("--mesh-radius-scale", type=float, default=1.5, metavar="S", help="closing radius in units of the cloud's point spacing")
     args = ap.parse_args()
     if args.label is None and args.guidance != 1.0:
         ap.error("--guidance needs --label")
+    if not 8 <= args.mesh_resolution <= 64:
+        ap.error("--mesh-resolution must lie in 8 .. 64")
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.sampler]
     torch.manual_seed(24)
     rank, world, local = D.init_from_env()
@@ -127,6 +137,9 @@ def main():
                                 None if ref is None else ref[i])
         if args.ply_dir and rank == 0:
             save_cloud_plys(os.path.join(args.ply_dir, name) if len(models) > 1 else args.ply_dir, shapes, counts, k=args.outlier_k)
+        if args.mesh_dir and rank == 0:
+            save_cloud_meshes(os.path.join(args.mesh_dir, name) if len(models) > 1 else args.mesh_dir, shapes, counts, resolution=args.mesh_resolution,
+                              radius_scale=args.mesh_radius_scale, fmt=args.mesh_format, log=log)
     if rank == 0:
         os.makedirs(args.out, exist_ok=True)
         np.savez_compressed(os.path.join(args.out, "generated.npz"), **result)

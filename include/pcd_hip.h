@@ -1092,6 +1092,46 @@ int pcd_cloud_outlier_mask(const float* d2, const int* counts, int n_max, int cl
 int pcd_cloud_compact(const float* points, const float* attr, const uint8_t* mask, const int* counts, int n_max, int clouds,
                       float* points_out, float* attr_out, int* counts_out, void* stream);
 
+/* ---- closed meshes from clouds by grid closing (csrc/cloud_mesh.hip; definition in DESIGN.md "Cloud to mesh") ----
+ * The clouds are packed as above.  The grid has R nodes per axis, 8 <= R <= 64; node i of an axis sits at lo + (float)i * h in fp32, the
+ * product rounded, then the sum; h = (hi - lo) / (R - 1) is computed by the caller in double and passed as fp32.  Grids are indexed [z][y][x].
+ * A row (z, y) of node bits is one uint64 word, bit x = node x, bits at and past R are 0 on output and ignored on input.  Every call is one
+ * enqueue (pcd_grid_depth_field: two) with no host synchronisation, bitwise repeatable, a cloud's result independent of the rest of the batch.
+ * PCD_ERR_ARG (before any device work) for a null required pointer, clouds <= 0 or > 65535, R outside 8 .. 64, lo or h that is not finite,
+ * h <= 0, inset outside [-1, 1], or what an entry point names below.
+ *
+ * Radius.  With d2 [P][n_max][k] (pcd_knn with exclude_self; the issue's k = 8) and radii_in null: s_p = the mean, over the rows below the count
+ * whose slot k - 1 is valid, of sqrtf(d2[.][k - 1]) (correctly rounded fp32 roots, summed in double, rounded to fp32 once), r_p = radius_scale *
+ * s_p, 0 without such a row.  With radii_in fp32 [P] and d2 null: r_p = radii_in[p].  Either way radii[p] = max(r_p, (2 - inset) * h), the
+ * clamp in fp32 as written, which a NaN r_p takes too.  PCD_ERR_ARG also for both or neither of d2 and radii_in, and with d2 for null counts,
+ * n_max <= 0, k outside 1 .. PCD_KNN_MAX_K, a radius_scale that is not finite or <= 0. */
+int pcd_cloud_spacing(const float* d2, const int* counts, int n_max, int clouds, int k, const float* radii_in, float radius_scale, float h,
+                      float inset, float* radii, void* stream);
+/* Shell and outside in one launch, one workgroup per cloud with both masks in LDS.  Node (z, y, x) is shell iff some row i < counts[p] with three
+ * finite coordinates has (dx dx + dy dy) + dz dz <= radii[p] * radii[p], the differences from the node coordinates above, all fp32 without
+ * contraction.  Free = not shell; outside = the free nodes 6-connected through free nodes to the layer of free nodes that is thought round the
+ * grid.  shell, outside uint64 [P][R][R]; info int32 [P][3] = (shell nodes, enclosed nodes = free and not outside, shell nodes on the six faces
+ * of the grid); sweeps int32 [P] or null: the sweeps the fill took, -1 had it passed R^3 (it cannot: every sweep but the last gains a node).
+ * The radii must be finite; the cost grows with n (r / h)^2.  PCD_ERR_ARG also for n_max <= 0. */
+int pcd_cloud_shell_fill(const float* points, const int* counts, int n_max, int clouds, int resolution, float lo, float h, const float* radii,
+                         uint64_t* shell, uint64_t* outside, int32_t* info, int32_t* sweeps, void* stream);
+/* The fill alone, on the caller's shell words [P][R][R]; outputs as above.  PCD_ERR_ARG also for outside == shell. */
+int pcd_grid_fill_outside(const uint64_t* shell, int clouds, int resolution, uint64_t* outside, int32_t* info, int32_t* sweeps, void* stream);
+/* d2 int32 [P][R][R][R] or null: the squared Euclidean distance in pitches from every node to the nearest outside node, the layer round the grid
+ * counting as outside (the exact integer transform, 0 on outside nodes).  v fp32 [P][R][R][R]: 0 where d2 = 0, elsewhere
+ * 1.0f + ((sqrtf((float)d2) * h - radii[p]) - inset * h) in fp32 in that order without contraction; the closed solid is v > 1.  v holds
+ * intermediate integers between the two launches.  PCD_ERR_ARG also for d2 == v. */
+int pcd_grid_depth_field(const uint64_t* outside, int clouds, int resolution, float h, const float* radii, float inset, int32_t* d2, float* v,
+                         void* stream);
+/* out[p][i] = scale * vertices[p][i] + offset per component (fp32, product then sum) for i < vertex_counts[p], vertices and out fp32
+ * [P][v_max][3] (out may be vertices); rows at and past the count are not written.  With index int32 [P][v_max][k] (pcd_knn of the mapped vertices
+ * against the clouds) the mapped vertex v is then projected: over its neighbours 0 <= index < counts[p], their mean c and their covariance about
+ * c, n the unit eigenvector of the least eigenvalue, out = v - ((v - c) . n) n, all in double from the differences to v, rounded to fp32 once;
+ * with fewer than 3 neighbours, or a result that is not finite, out = v.  PCD_ERR_ARG also for v_max <= 0, a scale or offset that is not
+ * finite, and with index for null points or counts, n_max <= 0, k outside 1 .. PCD_KNN_MAX_K. */
+int pcd_project_to_cloud(const float* vertices, const int* vertex_counts, int v_max, const float* points, const int* counts, int n_max,
+                         int clouds, const int32_t* index, int k, float scale, float offset, float* out, void* stream);
+
 /* ------------------------------------------------ training step of the point denoiser
  * diffusion.py:70-86,170-186 (add_noise -> model in train() mode -> F.l1_loss -> AdamW, diffusion.py:60).
  * The dense products (forward, backward-data, backward-weight) are pcd_gemm_f16* calls; these entry points
