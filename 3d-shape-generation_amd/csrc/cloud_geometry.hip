@@ -1,7 +1,7 @@
 // Local geometry of P ragged clouds (DESIGN.md "Cloud geometry"): the k nearest neighbours of every point, PCA normals from the neighbour
 // lists, the statistical / radius outlier masks from the neighbour distances, and the stable compaction of a cloud by a mask.  Cloud p is
 // points[p][0..counts[p]) inside a padded [P][N][3] array, as in surface_metrics.hip; rows at or past a count are never read as data.
-//   * k nearest: the loop of surf_nn_kernel (targets in LDS as float4, read as a wave-wide broadcast, d2 = (dx dx + dy dy) + dz dz without
+//   * k nearest: a loop of its own next to nearest_scan of pair_scan.h (targets in LDS as float4, read as a wave-wide broadcast, d2 = (dx dx + dy dy) + dz dz without
 //     contraction), one query per thread.  A thread keeps its K best (d2, j) in registers, sorted, K a template constant >= k, so the
 //     insertion is a fully unrolled compare-and-shift and nothing is indexed at run time.  A target is a candidate while d2 < the thread's
 //     K-th best.  Candidates are rare after the first few hundred targets, but among the 64 lanes of a wave some lane has one at almost
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(const float* __restrict_
     __shared__ float4 tile[KNN_TILE];
     __shared__ uint2 pend[KNN_PEND][KNN_BLOCK];           // parked candidates: (bits of d2, j), one 8-byte write each
     const int p = blockIdx.y, tid = threadIdx.x;
-    const int nq = geo_count(nq_, p, NQ), nt = geo_count(nt_, p, NT);
+    const int nq = clamped_count(nq_, p, NQ), nt = clamped_count(nt_, p, NT);
     const int q0 = blockIdx.x * KNN_BLOCK, qi = q0 + tid;
     const float* q = q_ + (int64_t)p * NQ * 3;
     const float* t = t_ + (int64_t)p * NT * 3;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void geo_centroid_kernel(const float* __restri
                                                            double* __restrict__ centroid) {
     __shared__ double sd[4];
     __shared__ int si[4];
-    const int p = blockIdx.x, n = geo_count(counts, p, N);
+    const int p = blockIdx.x, n = clamped_count(counts, p, N);
     const float* pts = points + (int64_t)p * N * 3;
     double sx = 0.0, sy = 0.0, sz = 0.0;
     int c = 0;
@@ -140,10 +140,10 @@ __global__ __launch_bounds__(256) void geo_centroid_kernel(const float* __restri
         const float x = pts[(int64_t)i * 3], y = pts[(int64_t)i * 3 + 1], z = pts[(int64_t)i * 3 + 2];
         if (isfinite(x) && isfinite(y) && isfinite(z)) { sx += (double)x; sy += (double)y; sz += (double)z; c += 1; }
     }
-    sx = geo_block_sum(sx, sd);
-    sy = geo_block_sum(sy, sd);
-    sz = geo_block_sum(sz, sd);
-    c = geo_block_sum(c, si);
+    sx = block_reduce<4>(sx, SumOp(), sd);
+    sy = block_reduce<4>(sy, SumOp(), sd);
+    sz = block_reduce<4>(sz, SumOp(), sd);
+    c = block_reduce<4>(c, SumOp(), si);
     if (threadIdx.x == 0) {
         double* out = centroid + (int64_t)p * 3;
         out[0] = c > 0 ? sx / (double)c : 0.0;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void geo_normals_kernel(const float* __restric
                                                           float* __restrict__ normals, float* __restrict__ curvature) {
     const int p = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const int n = geo_count(counts, p, N);
+    const int n = clamped_count(counts, p, N);
     const int64_t row = (int64_t)p * N + i;
     float* out = normals + row * 3;
     float nx = 0.f, ny = 0.f, nz = 0.f, curv = __builtin_nanf("");
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void geo_outlier_kernel(const float* __restric
                                                           unsigned char* __restrict__ mask, float* __restrict__ mean_distance) {
     __shared__ double sd[4];
     __shared__ int si[4];
-    const int p = blockIdx.x, n = geo_count(counts, p, N);
+    const int p = blockIdx.x, n = clamped_count(counts, p, N);
     const float* rows = d2 + (int64_t)p * N * k;
     unsigned char* keep = mask + (int64_t)p * N;
     if (mean_distance) {
@@ -261,15 +261,15 @@ __global__ __launch_bounds__(256) void geo_outlier_kernel(const float* __restric
         const double dbar = geo_dbar(rows + (int64_t)i * k, k, slots);
         if (slots > 0) { s += dbar; c += 1; }
     }
-    const int have = geo_block_sum(c, si);
-    const double mu = geo_block_sum(s, sd) / (double)(have > 0 ? have : 1);
+    const int have = block_reduce<4>(c, SumOp(), si);
+    const double mu = block_reduce<4>(s, SumOp(), sd) / (double)(have > 0 ? have : 1);
     double v = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         int slots = 0;
         const double dbar = geo_dbar(rows + (int64_t)i * k, k, slots);
         if (slots > 0) v += (dbar - mu) * (dbar - mu);
     }
-    const double sigma = sqrt(geo_block_sum(v, sd) / (double)(have > 0 ? have : 1));
+    const double sigma = sqrt(block_reduce<4>(v, SumOp(), sd) / (double)(have > 0 ? have : 1));
     const double limit = mu + ratio * sigma;
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
         int slots = 0;
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void geo_compact_kernel(const float* __restric
                                                           float* __restrict__ points_out, float* __restrict__ attr_out,
                                                           int* __restrict__ counts_out) {
     __shared__ int wave_total[4];
-    const int p = blockIdx.x, n = geo_count(counts, p, N), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.x, n = clamped_count(counts, p, N), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t base = (int64_t)p * N;
     int kept = 0;                                            // the same in every thread
     for (int i0 = 0; i0 < n; i0 += 256) {

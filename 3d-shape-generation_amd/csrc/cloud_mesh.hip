@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void cm_spacing_kernel(const float* __restrict
     const int p = blockIdx.x;
     float r = 0.f;
     if (d2) {
-        const int n = geo_count(counts, p, N);
+        const int n = clamped_count(counts, p, N);
         const float* last = d2 + (int64_t)p * N * k + (k - 1);
         double s = 0.0;
         int c = 0;
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(256) void cm_spacing_kernel(const float* __restrict
             const float v = last[(int64_t)i * k];
             if (v == v) { s += (double)sqrtf(v); c += 1; }
         }
-        const int have = geo_block_sum(c, si);
-        const double total = geo_block_sum(s, sd);
+        const int have = block_reduce<4>(c, SumOp(), si);
+        const double total = block_reduce<4>(s, SumOp(), sd);
         if (have > 0) r = scale * (float)(total / (double)have);
     } else {
         r = radii_in[p];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_fill_kernel(const float* __rest
     if (FROM_CLOUD) {
         for (int row = threadIdx.x; row < rows; row += CM_THREADS) shell[row] = 0ull;
         __syncthreads();
-        cm_shell(points + (int64_t)p * N * 3, geo_count(counts, p, N), R, lo, h, radii[p], shell);
+        cm_shell(points + (int64_t)p * N * 3, clamped_count(counts, p, N), R, lo, h, radii[p], shell);
     } else {
         const u64 full = cm_full(R);
         for (int row = threadIdx.x; row < rows; row += CM_THREADS) shell[row] = shell_in[(int64_t)p * rows + row] & full;
@@ -289,12 +289,12 @@ __global__ __launch_bounds__(256) void cm_project_kernel(const float* __restrict
                                                          const int* __restrict__ index, int k, float scale, float offset,
                                                          float* __restrict__ out) {
     const int p = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= geo_count(vcounts, p, V)) return;
+    if (i >= clamped_count(vcounts, p, V)) return;
     const int64_t row = (int64_t)p * V + i;
     const float fx = verts[row * 3] * scale + offset, fy = verts[row * 3 + 1] * scale + offset, fz = verts[row * 3 + 2] * scale + offset;
     float ox = fx, oy = fy, oz = fz;
     if (index) {
-        const int n = geo_count(counts, p, N);
+        const int n = clamped_count(counts, p, N);
         const float* pts = points + (int64_t)p * N * 3;
         const int* idx = index + row * k;
         const double px = (double)fx, py = (double)fy, pz = (double)fz;

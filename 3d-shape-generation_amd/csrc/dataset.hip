@@ -51,7 +51,6 @@ __device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* wave_u) 
     return total;
 }
 
-struct SumOp { __device__ float operator()(float a, float b) const { return a + b; } };
 
 // what a slot's run is made of, uniform over the workgroup
 struct VoxSlot {

@@ -218,9 +218,21 @@ __device__ __forceinline__ half8 frag128(const char* img, int row, int hh, int j
 // ------------------------------------------------------------------------------------------------ block reductions
 struct MaxOp { __device__ float operator()(float a, float b) const { return fmaxf(a, b); } };
 struct MinOp { __device__ float operator()(float a, float b) const { return fminf(a, b); } };
+struct SumOp { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
 
+// butterfly over the wave: every lane ends with the same bits
 template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [blockDim/64] */) {
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+    return v;
+}
+
+// Fixed order: the butterfly, then the waves in order, ((w0 op w1) op w2) op ...; every thread gets the result.  The barrier in front lets a kernel
+// use one scratch array for reduction after reduction.  WAVES = 0 reads the wave count from blockDim; a kernel launched with 64 WAVES threads
+// may name it, which unrolls the last loop.
+template <int WAVES = 0, typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [waves] */) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -228,8 +240,14 @@ __device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [blockDim/64
     if (lane == 0) scratch[wave] = v;
     __syncthreads();
     T r = scratch[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = op(r, scratch[w]);
+    for (int w = 1; w < (WAVES > 0 ? WAVES : (int)(blockDim.x >> 6)); ++w) r = op(r, scratch[w]);
     return r;
+}
+
+// the count of ragged cloud p, clamped to its padded rows
+__device__ __forceinline__ int clamped_count(const int* n, int p, int cap) {
+    const int v = n[p];
+    return v < 0 ? 0 : (v > cap ? cap : v);
 }
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10

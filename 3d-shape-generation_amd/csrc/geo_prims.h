@@ -1,6 +1,5 @@
-// Device helpers shared by cloud_geometry.hip and cloud_mesh.hip: the clamped count of a ragged cloud, sums over a workgroup of 256 threads
-// in a fixed order, and the Jacobi eigen-solve of a symmetric 3 x 3 matrix in double.  Contraction is off in here, as in the files that
-// include it, and is switched back to the compiler's default at the end.
+// Device helpers shared by cloud_geometry.hip and cloud_mesh.hip: the Jacobi eigen-solve of a symmetric 3 x 3 matrix in double.  Contraction
+// is off in here, as in the files that include it, and is switched back to the compiler's default at the end.
 #pragma once
 #include <math.h>
 
@@ -9,30 +8,6 @@
 namespace pcd {
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ int geo_count(const int* n, int p, int cap) {
-    const int v = n[p];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-// sums over the 256 threads in a fixed order: butterfly over each wave (every lane ends with the same bits), then the four waves in order
-__device__ __forceinline__ double geo_block_sum(double v, double* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
-
-__device__ __forceinline__ int geo_block_sum(int v, int* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
-}
 
 // one Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix, r the third index: app, aqq, apq, arp, arq and the columns p, q of V
 __device__ __forceinline__ void geo_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v1p,

@@ -20,7 +20,6 @@ constexpr int MDT_CDF_LDS = 4096;                              // running sums o
 
 static int g_mesh_data_resident = 1;
 
-struct MdtSum { __device__ float operator()(float a, float b) const { return a + b; } };
 
 // the slot's mesh, uniform over the workgroup
 struct MdtMesh {
@@ -118,7 +117,7 @@ __device__ __forceinline__ void mdt_centroid_radius(Get get, int n, float* wave_
         get(i, p);
         acc[0] += p[0]; acc[1] += p[1]; acc[2] += p[2];
     }
-    for (int c = 0; c < 3; ++c) mean[c] = (block_reduce(acc[c], MdtSum(), wave_f)) / (float)n;
+    for (int c = 0; c < 3; ++c) mean[c] = (block_reduce(acc[c], SumOp(), wave_f)) / (float)n;
     float d2 = 0.f;
     for (int i = threadIdx.x; i < n; i += MDT_THREADS) {
         float p[3];

@@ -2,7 +2,7 @@
 // All HBM/latency-bound integer-and-compare work; no MFMA (reference metrics.py:7-47,
 // utils.py:488-539).  fp32 expressions keep the reference's operation order (contract off)
 // so normalisation, voxel indices and compacted coordinates are bit-exact.
-#include "common.h"
+#include "pair_scan.h"
 
 namespace pcd {
 
@@ -11,31 +11,7 @@ namespace pcd {
 // one block per cloud
 __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict__ pts, int n, float* __restrict__ out) {
     __shared__ float scratch[4];
-    const float* p = pts + (int64_t)blockIdx.x * n * 3;
-    float* o = out + (int64_t)blockIdx.x * n * 3;
-    float mx[3] = {-INFINITY, -INFINITY, -INFINITY}, mn[3] = {INFINITY, INFINITY, INFINITY};
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = p[i * 3 + a];
-            mx[a] = fmaxf(mx[a], v);
-            mn[a] = fminf(mn[a], v);
-        }
-    float c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float hi = block_reduce(mx[a], MaxOp(), scratch);
-        const float lo = block_reduce(mn[a], MinOp(), scratch);
-        c[a] = (hi + lo) / 2.f;   // metrics.py:17
-    }
-    float am = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) am = fmaxf(am, fabsf(p[i * 3 + a] - c[a]));
-    const float scale = block_reduce(am, MaxOp(), scratch);   // metrics.py:19
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) o[i * 3 + a] = (p[i * 3 + a] - c[a]) / scale;
+    normalize_cloud(pts + (int64_t)blockIdx.x * n * 3, n, out + (int64_t)blockIdx.x * n * 3, scratch);
 }
 
 // grid (B, 2): direction 0 = queries x against refs y, 1 = queries y against refs x.
@@ -90,13 +66,7 @@ __global__ __launch_bounds__(256) void voxelize_kernel(const float* __restrict__
     if (i >= total_pts) return;
     const int b = (int)(i / n);
     int idx[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float v = ((pts[i * 3 + a] + 1.f) * (float)(res - 1)) / 2.f;   // utils.py:501
-        long long t = (v == v) ? (long long)v : 0;                            // .long(): truncate toward zero
-        t = t < 0 ? 0 : (t > res - 1 ? res - 1 : t);
-        idx[a] = (int)t;
-    }
+    voxel_cell(pts + i * 3, res, idx);
     vox[(((int64_t)b * res + idx[0]) * res + idx[1]) * res + idx[2]] = 1.f;   // utils.py:507, index order [x][y][z]
 }
 

@@ -3,37 +3,15 @@
 // points (12 bytes per point from LDS), so a pass is VALU/exp-bound, not HBM-bound.
 //   alpha_i = eps * (log(mu + 1e-10) - logsumexp_j(-C_ij / eps + beta_j))     (and the mirror for beta)
 // One thread per row, the other cloud + its dual streamed through LDS tiles, online logsumexp.
-#include "common.h"
+#include "pair_scan.h"
 
 namespace pcd {
 
-constexpr int SK_TILE = 512;
-
 __global__ __launch_bounds__(256) void pair_max_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                         int n, int m, unsigned* __restrict__ out_bits) {
-    __shared__ float ty[SK_TILE * 3];
+    __shared__ float ty[SCAN_TILE * 3];
     const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float* xb = x + (int64_t)b * n * 3;
-    const float* yb = y + (int64_t)b * m * 3;
-    const bool live = i < n;
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (live) { px = xb[i * 3]; py = xb[i * 3 + 1]; pz = xb[i * 3 + 2]; }
-    float best = 0.f;
-    for (int j0 = 0; j0 < m; j0 += SK_TILE) {
-        const int cnt = min(SK_TILE, m - j0);
-        __syncthreads();
-        for (int t = threadIdx.x; t < cnt * 3; t += blockDim.x) ty[t] = yb[(int64_t)j0 * 3 + t];
-        __syncthreads();
-        if (live)
-            for (int j = 0; j < cnt; ++j) {
-                const float dx = px - ty[j * 3], dy = py - ty[j * 3 + 1], dz = pz - ty[j * 3 + 2];
-                best = fmaxf(best, dx * dx + dy * dy + dz * dz);
-            }
-    }
-    best = sqrtf(best);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
+    const float best = max_dist_row(x + (int64_t)b * n * 3, n, y + (int64_t)b * m * 3, m, ty);
     if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __float_as_uint(best));
 }
 
@@ -44,42 +22,10 @@ __global__ __launch_bounds__(256) void sinkhorn_dual_kernel(const float* __restr
                                                              float lambda, float eps, float logmarg,
                                                              const float* __restrict__ dq, float* __restrict__ dp,
                                                              unsigned* __restrict__ err_bits) {
-    __shared__ float tq[SK_TILE * 4];
+    __shared__ float tq[SCAN_TILE * 4];
     const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float* pb = p + (int64_t)b * np_ * 3;
-    const float* qb = q + (int64_t)b * nq * 3;
-    const float* dqb = dq + (int64_t)b * nq;
-    const bool live = i < np_;
-    const float scale = lambda / cmax[0];
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (live) { px = pb[i * 3]; py = pb[i * 3 + 1]; pz = pb[i * 3 + 2]; }
-    float mrun = -INFINITY, srun = 0.f;
-    for (int j0 = 0; j0 < nq; j0 += SK_TILE) {
-        const int cnt = min(SK_TILE, nq - j0);
-        __syncthreads();
-        for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-            tq[t * 4] = qb[(int64_t)(j0 + t) * 3]; tq[t * 4 + 1] = qb[(int64_t)(j0 + t) * 3 + 1];
-            tq[t * 4 + 2] = qb[(int64_t)(j0 + t) * 3 + 2]; tq[t * 4 + 3] = dqb[j0 + t];
-        }
-        __syncthreads();
-        if (live)
-            for (int j = 0; j < cnt; ++j) {
-                const float dx = px - tq[j * 4], dy = py - tq[j * 4 + 1], dz = pz - tq[j * 4 + 2];
-                const float v = tq[j * 4 + 3] - scale * sqrtf(dx * dx + dy * dy + dz * dz);
-                if (v > mrun) { srun = srun * __expf(mrun - v) + 1.f; mrun = v; }
-                else srun += __expf(v - mrun);
-            }
-    }
-    float e = 0.f;
-    if (live) {
-        const float nv = eps * (logmarg - (mrun + logf(srun)));
-        float* dst = dp + (int64_t)b * np_ + i;
-        e = fabsf(nv - *dst);
-        *dst = nv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) e = fmaxf(e, __shfl_xor(e, o));
+    const float e = sinkhorn_dual_row(p + (int64_t)b * np_ * 3, np_, q + (int64_t)b * nq * 3, nq, lambda / cmax[0], eps, logmarg,
+                                      dq + (int64_t)b * nq, dp + (int64_t)b * np_, tq);
     if ((threadIdx.x & 63) == 0) atomicMax(err_bits, __float_as_uint(e));
 }
 
@@ -89,32 +35,10 @@ __global__ __launch_bounds__(256) void sinkhorn_cost_kernel(const float* __restr
                                                              const float* __restrict__ alpha,
                                                              const float* __restrict__ beta,
                                                              float* __restrict__ row_cost) {
-    __shared__ float tq[SK_TILE * 4];
+    __shared__ float tq[SCAN_TILE * 4];
     const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float* xb = x + (int64_t)b * n * 3;
-    const float* yb = y + (int64_t)b * m * 3;
-    const bool live = i < n;
-    const float inv = 1.f / cmax[0];
-    float px = 0.f, py = 0.f, pz = 0.f, a = 0.f;
-    if (live) { px = xb[i * 3]; py = xb[i * 3 + 1]; pz = xb[i * 3 + 2]; a = alpha[(int64_t)b * n + i]; }
-    float acc = 0.f;
-    for (int j0 = 0; j0 < m; j0 += SK_TILE) {
-        const int cnt = min(SK_TILE, m - j0);
-        __syncthreads();
-        for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-            tq[t * 4] = yb[(int64_t)(j0 + t) * 3]; tq[t * 4 + 1] = yb[(int64_t)(j0 + t) * 3 + 1];
-            tq[t * 4 + 2] = yb[(int64_t)(j0 + t) * 3 + 2]; tq[t * 4 + 3] = beta[(int64_t)b * m + j0 + t];
-        }
-        __syncthreads();
-        if (live)
-            for (int j = 0; j < cnt; ++j) {
-                const float dx = px - tq[j * 4], dy = py - tq[j * 4 + 1], dz = pz - tq[j * 4 + 2];
-                const float c = sqrtf(dx * dx + dy * dy + dz * dz) * inv;
-                acc += __expf(-lambda * c + a + tq[j * 4 + 3]) * c;
-            }
-    }
-    if (live) row_cost[(int64_t)b * n + i] = acc;
+    sinkhorn_cost_row(x + (int64_t)b * n * 3, n, y + (int64_t)b * m * 3, m, 1.f / cmax[0], lambda, alpha + (int64_t)b * n,
+                      beta + (int64_t)b * m, row_cost + (int64_t)b * n, tq);
 }
 
 // out[b] = sum_i row_cost[b][i], fixed order (one block per batch entry)
@@ -122,11 +46,8 @@ __global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ 
     __shared__ double ws[4];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)v[(int64_t)blockIdx.x * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(ws[0] + ws[1] + ws[2] + ws[3]);
+    acc = block_reduce<4>(acc, SumOp(), ws);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)acc;
 }
 
 }  // namespace pcd

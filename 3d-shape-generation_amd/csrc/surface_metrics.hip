@@ -1,89 +1,37 @@
 // Surface evaluation of P ragged cloud pairs (DESIGN.md "Surface metrics"): the nearest neighbour of every point WITH its index, the
 // reductions behind accuracy / completeness / Chamfer-L1 / -L2 / F-score / Hausdorff / normal consistency, and the IoU of two
 // occupancy grids.  Pair p: a[p][0..na[p]) and b[p][0..nb[p]) inside padded [P][NA][3] / [P][NB][3] arrays, as in metrics_pairs.hip.
-//   * nearest neighbour: the loop of pair_chamfer_min_kernel (targets in LDS as float4, read as a wave-wide broadcast, SQ queries
-//     per thread in registers) with a running index: compare-and-select instead of fminf.  The target range is split over
+//   * nearest neighbour: nearest_scan of pair_scan.h in its form with a running index.  The target range is split over
 //     blockIdx.y; the partial results of a query meet in a 64-bit unsigned atomic min on (float bits of d^2) << 32 | j, which
 //     orders by d^2 (>= 0, so its bits order as the value) and then by j: the result does not depend on the order of arrival or on
 //     the number of splits, and equal minima go to the lowest j.
-//   * reduction: one workgroup per pair walks both directions; sums in double (per-thread strided partials, a butterfly over the
-//     wave, the four waves in order), counts in integers, one rounding to fp32 per mean.
+//   * reduction: one workgroup per pair walks both directions; sums in double (per-thread strided partials, then block_reduce),
+//     counts in integers, one rounding to fp32 per mean.
 //   * IoU: one workgroup per pair, integer counts, one fp32 division.
 #include <math.h>
 
-#include "common.h"
+#include "pair_scan.h"
 
 namespace pcd {
 
 #pragma clang fp contract(off)
 
-constexpr int ST = 512;     // targets per LDS tile
-constexpr int SQ = 4;       // queries per thread: one LDS read of a target serves SQ distances
-constexpr int SURF_QBLOCK = 256 * SQ;
 constexpr unsigned long long SURF_NONE = ~0ull;     // a key no candidate reaches: its d^2 bits would be a NaN's
 
 struct SurfTaus { float t[PCD_SURF_MAX_THRESHOLDS]; };
 
-__device__ __forceinline__ int surf_count(const int* n, int p, int cap) {
-    const int v = n[p];
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-// grid (query blocks of 256 * SQ, target splits, jobs); job z = pair z / dirs, direction z % dirs (0: a queries b, 1: b queries a).
+// grid (query blocks of SCAN_QBLOCK, target splits, jobs); job z = pair z / dirs, direction z % dirs (0: a queries b, 1: b queries a).
 // keys[z][q] (stride NQ, all ones before the launch) takes the least (d^2 bits, j) over the targets with a FINITE d^2 = (dx dx +
 // dy dy) + dz dz; a query without one keeps the all-ones key.  Rows at or past a cloud's count are never read.
 __global__ __launch_bounds__(256) void surf_nn_kernel(const float* __restrict__ a, const int* __restrict__ na, int NA,
                                                        const float* __restrict__ b, const int* __restrict__ nb, int NB, int dirs,
                                                        int NQ, unsigned long long* __restrict__ keys) {
-    __shared__ float4 tile[ST];
+    __shared__ float4 tile[SCAN_TILE];
     const int p = blockIdx.z / dirs, dir = blockIdx.z % dirs;
     const float* q = dir == 0 ? a + (int64_t)p * NA * 3 : b + (int64_t)p * NB * 3;
     const float* r = dir == 0 ? b + (int64_t)p * NB * 3 : a + (int64_t)p * NA * 3;
-    const int ca = surf_count(na, p, NA), cb = surf_count(nb, p, NB);
-    const int nq = dir == 0 ? ca : cb, nr = dir == 0 ? cb : ca;
-    const int q0 = blockIdx.x * SURF_QBLOCK;
-    if (q0 >= nq) return;
-    const int per = (nr + gridDim.y - 1) / gridDim.y;
-    const int r_lo = blockIdx.y * per, r_hi = min(nr, r_lo + per);
-    if (r_lo >= r_hi) return;
-    float qx[SQ], qy[SQ], qz[SQ], best[SQ];
-    int arg[SQ];
-#pragma unroll
-    for (int c = 0; c < SQ; ++c) {
-        int qi = q0 + c * 256 + threadIdx.x;
-        qi = qi < nq ? qi : nq - 1;                          // clamped duplicates are not stored
-        qx[c] = q[(int64_t)qi * 3]; qy[c] = q[(int64_t)qi * 3 + 1]; qz[c] = q[(int64_t)qi * 3 + 2];
-        best[c] = INFINITY;
-        arg[c] = -1;
-    }
-    for (int r0 = r_lo; r0 < r_hi; r0 += ST) {
-        const int cnt = min(ST, r_hi - r0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const float* t = r + (int64_t)(r0 + i) * 3;
-            tile[i] = make_float4(t[0], t[1], t[2], 0.f);
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < cnt; ++j) {
-            const float4 t = tile[j];
-            const int jj = r0 + j;
-#pragma unroll
-            for (int c = 0; c < SQ; ++c) {
-                const float dx = qx[c] - t.x, dy = qy[c] - t.y, dz = qz[c] - t.z;
-                const float d = dx * dx + dy * dy + dz * dz;
-                const bool closer = d < best[c];             // false for a NaN and for +inf: neither is ever a neighbour; ties keep the lower j
-                best[c] = closer ? d : best[c];
-                arg[c] = closer ? jj : arg[c];
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < SQ; ++c) {
-        const int qi = q0 + c * 256 + threadIdx.x;
-        if (qi < nq && arg[c] >= 0)
-            atomicMin(keys + (int64_t)blockIdx.z * NQ + qi, ((unsigned long long)__float_as_uint(best[c]) << 32) | (unsigned)arg[c]);
-    }
+    const int ca = clamped_count(na, p, NA), cb = clamped_count(nb, p, NB);
+    nearest_scan(q, dir == 0 ? ca : cb, r, dir == 0 ? cb : ca, keys + (int64_t)blockIdx.z * NQ, tile);
 }
 
 __device__ __forceinline__ void surf_decode(unsigned long long key, float& d2, int& index) {
@@ -98,35 +46,7 @@ __global__ __launch_bounds__(256) void surf_nn_decode_kernel(const unsigned long
     const int p = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NQ) return;
     const int64_t at = (int64_t)p * NQ + i;
-    surf_decode(i < surf_count(nq_, p, NQ) ? keys[at] : SURF_NONE, d2[at], index[at]);
-}
-
-// sums over the 256 threads in a fixed order: butterfly over each wave (every lane ends with the same bits), then the four waves in order
-__device__ __forceinline__ double surf_block_sum(double v, double* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-}
-
-__device__ __forceinline__ int surf_block_sum(int v, int* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
-}
-
-__device__ __forceinline__ float surf_block_max(float v, float* scratch) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
+    surf_decode(i < clamped_count(nq_, p, NQ) ? keys[at] : SURF_NONE, d2[at], index[at]);
 }
 
 // grid (P): rows[p][PCD_SURF_ROW_BASE + 3 K] from the keys of both directions ([2p] a queries b, [2p + 1] b queries a, stride NQ).
@@ -148,7 +68,7 @@ __global__ __launch_bounds__(256) void surf_rows_kernel(const unsigned long long
     float far2 = 0.f, frac[2][PCD_SURF_MAX_THRESHOLDS];
     int lost = 0;
     for (int dir = 0; dir < 2; ++dir) {
-        const int n = dir == 0 ? surf_count(na, p, NA) : surf_count(nb, p, NB), N = dir == 0 ? NA : NB;
+        const int n = dir == 0 ? clamped_count(na, p, NA) : clamped_count(nb, p, NB), N = dir == 0 ? NA : NB;
         const unsigned long long* kq = keys + (int64_t)(2 * p + dir) * NQ;
         const float* nq = (dir == 0 ? normals_a : normals_b) + (with_normals ? (int64_t)p * N * 3 : 0);
         const float* nt = (dir == 0 ? normals_b : normals_a) + (with_normals ? (int64_t)p * (dir == 0 ? NB : NA) * 3 : 0);
@@ -176,18 +96,18 @@ __global__ __launch_bounds__(256) void surf_rows_kernel(const unsigned long long
                 s_nc += (double)fabsf(u[0] * v[0] + u[1] * v[1] + u[2] * v[2]);
             }
         }
-        lost += surf_block_sum(none, si);
-        mean_d[dir] = surf_block_sum(s_d, sd) / (double)n;
-        mean_d2[dir] = surf_block_sum(s_d2, sd) / (double)n;
-        mean_nc[dir] = surf_block_sum(s_nc, sd) / (double)n;
-        far2 = fmaxf(far2, surf_block_max(far, sf));
-        for (int k = 0; k < K; ++k) frac[dir][k] = (float)surf_block_sum(within[k], si) / (float)n;
+        lost += block_reduce<4>(none, SumOp(), si);
+        mean_d[dir] = block_reduce<4>(s_d, SumOp(), sd) / (double)n;
+        mean_d2[dir] = block_reduce<4>(s_d2, SumOp(), sd) / (double)n;
+        mean_nc[dir] = block_reduce<4>(s_nc, SumOp(), sd) / (double)n;
+        far2 = fmaxf(far2, block_reduce<4>(far, MaxOp(), sf));
+        for (int k = 0; k < K; ++k) frac[dir][k] = (float)block_reduce<4>(within[k], SumOp(), si) / (float)n;
     }
     if (threadIdx.x != 0) return;
     float* row = rows + (int64_t)p * width;
     // a pair with an empty cloud, or with a point that has no finite distance to the other cloud (a coordinate that is not finite,
     // on either side), has no metrics
-    if (surf_count(na, p, NA) == 0 || surf_count(nb, p, NB) == 0 || lost > 0) {
+    if (clamped_count(na, p, NA) == 0 || clamped_count(nb, p, NB) == 0 || lost > 0) {
         for (int c = 0; c < width; ++c) row[c] = __builtin_nanf("");
         return;
     }
@@ -224,24 +144,14 @@ __global__ __launch_bounds__(256) void surf_voxel_iou_kernel(const float* __rest
         both += (oa && ob) ? 1 : 0;
         either += (oa || ob) ? 1 : 0;
     }
-    both = surf_block_sum(both, si);
-    either = surf_block_sum(either, si);
+    both = block_reduce<4>(both, SumOp(), si);
+    either = block_reduce<4>(either, SumOp(), si);
     if (threadIdx.x == 0) out[p] = either > 0 ? (float)both / (float)either : __builtin_nanf("");
 }
 
 #pragma clang fp contract(fast)
 
 constexpr int SURF_MAX_JOBS = 65535;      // gridDim.z
-
-// target splits so that ~1024 workgroups exist even for one pair, never below 128 targets a split
-static int surf_splits(int jobs, int NQ, int NT) {
-    const int64_t qblocks = ceil_div(NQ, SURF_QBLOCK);
-    int64_t s = ceil_div(1024, qblocks * jobs);
-    const int64_t max_split = ceil_div(NT, 128);
-    s = s > max_split ? max_split : s;
-    s = s > 65535 ? 65535 : s;
-    return s < 1 ? 1 : (int)s;
-}
 
 static size_t surf_key_bytes(int jobs, int NQ) { return align_up((size_t)jobs * NQ * sizeof(unsigned long long)); }
 
@@ -262,7 +172,7 @@ extern "C" int pcd_nearest_neighbors(const float* q, const int* nq, int nq_max, 
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)workspace;
     PCD_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)pairs * nq_max * sizeof(unsigned long long), s));
-    const dim3 grid((unsigned)ceil_div(nq_max, SURF_QBLOCK), surf_splits(pairs, nq_max, nt_max), pairs);
+    const dim3 grid((unsigned)ceil_div(nq_max, SCAN_QBLOCK), scan_splits(pairs, nq_max, nt_max), pairs);
     hipLaunchKernelGGL(surf_nn_kernel, grid, dim3(256), 0, s, q, nq, nq_max, t, nt, nt_max, 1, nq_max, keys);
     hipLaunchKernelGGL(surf_nn_decode_kernel, dim3((unsigned)ceil_div(nq_max, 256), pairs), dim3(256), 0, s, keys, nq, nq_max, d2, index);
     PCD_CHECK_LAUNCH();
@@ -290,7 +200,7 @@ extern "C" int pcd_surface_metrics(const float* a, const float* normals_a, const
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)workspace;
     PCD_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)2 * pairs * NQ * sizeof(unsigned long long), s));
-    const dim3 grid((unsigned)ceil_div(NQ, SURF_QBLOCK), surf_splits(2 * pairs, NQ, NQ), 2 * pairs);
+    const dim3 grid((unsigned)ceil_div(NQ, SCAN_QBLOCK), scan_splits(2 * pairs, NQ, NQ), 2 * pairs);
     hipLaunchKernelGGL(surf_nn_kernel, grid, dim3(256), 0, s, a, na, na_max, b, nb, nb_max, 2, NQ, keys);
     hipLaunchKernelGGL(surf_rows_kernel, dim3(pairs), dim3(256), 0, s, keys, NQ, na, na_max, nb, nb_max, normals_a, normals_b, taus,
                        n_thresholds, rows, d2_a, index_a, d2_b, index_b);

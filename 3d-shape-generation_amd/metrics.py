@@ -45,22 +45,28 @@ def chamfer_per_sample(x, y, scaling_factor=1e+3) -> torch.Tensor:
     return _pair_rows(x, y, False)[:, 0] * scaling_factor
 
 
-def _pair_rows(a: torch.Tensor, b: torch.Tensor, sinkhorn: bool, epsilon=1e-2, thresh=1e-5, max_iter=100) -> torch.Tensor:
-    """pcd_pair_metrics on dense (P, N, 3) / (P, M, 3) clouds: rows (P, 3) = (Chamfer x1, Sinkhorn EMD | 0, voxel BCE)."""
-    P, n, m = a.shape[0], a.shape[1], b.shape[1]
-    dev = a.device
-    na = torch.full((P,), n, dtype=torch.int32, device=dev)
-    nb = torch.full((P,), m, dtype=torch.int32, device=dev)
-    log_mu = torch.log(torch.ones(P) / n + 1e-10).to(dev)
-    log_nu = torch.log(torch.ones(P) / m + 1e-10).to(dev)
+def _pair_call(a, ca, b, cb, sinkhorn, epsilon, thresh, max_iter) -> torch.Tensor:
+    """pcd_pair_metrics on packed (P, NA, 3) / (P, NB, 3) clouds with the host counts ca / cb: rows (P, 3) = (Chamfer x1,
+    Sinkhorn EMD | 0, voxel BCE)."""
+    P, dev = len(ca), a.device
+    counts = torch.tensor([ca, cb], dtype=torch.int32)
+    # log(mu + 1e-10) with the reference's fp32 torch ops (metrics.py:133-134,141), one value per pair and side
+    logm = torch.log(torch.ones(2, P) / counts.to(torch.float32) + 1e-10)
+    na, nb, log_mu, log_nu = torch.cat([counts, logm.view(torch.int32)]).to(dev)       # one copy to the device for the four rows
     lib = _lib.load()
     out = torch.empty(P, 3, dtype=torch.float32, device=dev)
-    need = int(lib.pcd_pair_metrics_workspace_bytes(P, n, m))
+    need = int(lib.pcd_pair_metrics_workspace_bytes(P, a.shape[1], b.shape[1]))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _lib.check(lib.pcd_pair_metrics(a.data_ptr(), na.data_ptr(), n, b.data_ptr(), nb.data_ptr(), m, P, 1 if sinkhorn else 0,
-                                    float(epsilon), float(thresh), int(max_iter), log_mu.data_ptr(), log_nu.data_ptr(),
-                                    out.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()), "pair_metrics")
+    _lib.check(lib.pcd_pair_metrics(a.data_ptr(), na.data_ptr(), a.shape[1], b.data_ptr(), nb.data_ptr(), b.shape[1], P,
+                                    1 if sinkhorn else 0, float(epsilon), float(thresh), int(max_iter), log_mu.data_ptr(),
+                                    log_nu.data_ptr(), out.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr()), "pair_metrics")
     return out
+
+
+def _pair_rows(a: torch.Tensor, b: torch.Tensor, sinkhorn: bool, epsilon=1e-2, thresh=1e-5, max_iter=100) -> torch.Tensor:
+    """_pair_call on dense (P, N, 3) / (P, M, 3) clouds."""
+    P = a.shape[0]
+    return _pair_call(a, [a.shape[1]] * P, b, [b.shape[1]] * P, sinkhorn, epsilon, thresh, max_iter)
 
 
 def earth_mover_distance_cpu(x, y, scaling_factor=1):
@@ -117,29 +123,14 @@ def pair_metrics(a_clouds, b_clouds, use_approximate_gpu_emd=False, epsilon=1e-2
 
     def pack(clouds):
         counts = [int(clouds[i].shape[0]) for i in keep]
-        nmax = max(counts)
         if isinstance(clouds, torch.Tensor) and len(keep) == P:
-            return clouds.to(torch.float32).contiguous(), counts, nmax
-        buf = torch.zeros(len(keep), nmax, 3, dtype=torch.float32, device=dev)
+            return clouds.to(torch.float32).contiguous(), counts
+        buf = torch.zeros(len(keep), max(counts), 3, dtype=torch.float32, device=dev)
         for j, i in enumerate(keep):
             buf[j, :counts[j]] = clouds[i]
-        return buf, counts, nmax
+        return buf, counts
 
-    a, ca, na_max = pack(a_clouds)
-    b, cb, nb_max = pack(b_clouds)
-    na = torch.tensor(ca, dtype=torch.int32, device=dev)
-    nb = torch.tensor(cb, dtype=torch.int32, device=dev)
-    # log(mu + 1e-10) with the reference's fp32 torch ops (metrics.py:133-134,141), one value per pair
-    log_mu = torch.log(torch.ones(len(keep)) / torch.tensor(ca, dtype=torch.float32) + 1e-10).to(dev)
-    log_nu = torch.log(torch.ones(len(keep)) / torch.tensor(cb, dtype=torch.float32) + 1e-10).to(dev)
-    lib = _lib.load()
-    out = torch.empty(len(keep), 3, dtype=torch.float32, device=dev)
-    need = int(lib.pcd_pair_metrics_workspace_bytes(len(keep), na_max, nb_max))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _lib.check(lib.pcd_pair_metrics(a.data_ptr(), na.data_ptr(), na_max, b.data_ptr(), nb.data_ptr(), nb_max, len(keep),
-                                    1 if use_approximate_gpu_emd else 0, float(epsilon), float(thresh), int(max_iter),
-                                    log_mu.data_ptr(), log_nu.data_ptr(), out.data_ptr(), ws.data_ptr(), need,
-                                    _lib.stream_ptr()), "pair_metrics")
+    out = _pair_call(*pack(a_clouds), *pack(b_clouds), use_approximate_gpu_emd, epsilon, thresh, max_iter)
     out[:, 0] *= 1e3                                         # chamfer_distance's default scaling_factor
     if not use_approximate_gpu_emd:
         for j, i in enumerate(keep):
