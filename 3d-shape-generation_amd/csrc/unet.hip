@@ -60,6 +60,9 @@ struct UnetWs {
     size_t x1, x2, x3, x4, s0, s1, pooled, pooled16, gbias, total;      // pooled16: only above 256 shapes (the dense GEMM for the pooled product reads fp16)
 };
 
+// With the row-panel chains (csrc/panelchain.hip) on, enc4.conv1-2 and dec3.conv2 write no buffer at all: s0 and s1 are not touched between x3 and x4, and
+// dec3 goes s0 (dec3.conv1's output) -> s1 (dec3.conv3's, which the per-layer sequence leaves in s0), so dec2 / dec1.conv1 swap their buffers too.  The sizes
+// stay: the per-layer sequence (ragged m, hi / lo layers, chains switched off) still needs both.
 static UnetWs carve(int64_t batch, int64_t n) {
     const size_t m = (size_t)batch * (size_t)n;
     UnetWs w{};
@@ -90,10 +93,12 @@ static const int kLinC[PCD_UNET_NLIN] = {64, 128, 128, 128, 256, 256, 256, 512, 
                                          1024, 1024, 512, 512, 512, 256, 256, 256, 128, 128, 128, 64, 64};
 
 static int g_unet_chains = 3;        // tuning / testing hook (pcd_unet_config): bit 0 = the narrow chains (csrc/chain.hip), bit 1 = the
-                                     // 256-channel chains (csrc/widechain.hip): enc2 + enc3 and dec2 + dec1.conv1 on whole 256-point tiles; 0 = one GEMM launch per layer
+                                     // 256-channel chains (csrc/widechain.hip): enc2 + enc3 and dec2 + dec1.conv1 on whole 256-point tiles, and the row-panel
+                                     // chains (csrc/panelchain.hip): enc4 and dec3.conv2-3 on whole 128-point tiles; bit 2 = the row-panel chains OFF (3 stays
+                                     // "everything on"); 0 = one GEMM launch per layer
 
 extern "C" int pcd_unet_config(int use_chains) {
-    g_unet_chains = use_chains & 3;
+    g_unet_chains = use_chains & 7;
     return PCD_OK;
 }
 
@@ -273,9 +278,24 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
             PCD_RUN(run_lin(d, 7, m, s1, nullptr, 0, nullptr, 0, x3, s));
         }
     }
-    PCD_RUN(run_lin(d, 8, m, x3, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[8]));
-    PCD_RUN(run_lin(d, 9, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[9]));
-    PCD_RUN(run_lin(d, 10, m, s1, nullptr, 0, nullptr, 0, x4, s, h->lin_frag[10]));
+    // enc4 and dec3.conv2-3 as row-panel chains (whole 128-point tiles, fp16 weights with their fragment-order copies); bitwise the per-layer launches
+    const bool panel = (g_unet_chains & 6) == 2 && m % 128 == 0;
+    auto panel_chain = [&](int chain, int first, int nl, const void* in, void* out, int ld) {
+        const void* frag[3]; const float* bias[3];
+        for (int i = 0; i < nl; ++i) { frag[i] = h->lin_frag[first + i]; bias[i] = d.lin[first + i].b; }
+        return pcd_panel_chain(chain, in, m, frag, bias, 0, out, ld, 256, s);
+    };
+    auto has_frags = [&](int first, int nl) {
+        for (int i = first; i < first + nl; ++i) if (h->lin_frag[i] == nullptr || ((d.hilo_mask >> i) & 1u)) return false;
+        return true;
+    };
+    if (panel && has_frags(8, 3)) {
+        PCD_RUN(panel_chain(0, 8, 3, x3, x4, 1024));
+    } else {
+        PCD_RUN(run_lin(d, 8, m, x3, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[8]));
+        PCD_RUN(run_lin(d, 9, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[9]));
+        PCD_RUN(run_lin(d, 10, m, s1, nullptr, 0, nullptr, 0, x4, s, h->lin_frag[10]));
+    }
     PCD_RUN(run_lin(d, 11, m, x4, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[11]));
     {   // global_feat.3 + max over the N points of each shape
         if (!pooled_cleared) PCD_RUN(pcd_fill_zero(pooled, (size_t)batch * 4096 * sizeof(float), s));
@@ -320,8 +340,14 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
                                                                              hipMemcpyDeviceToDevice, s)); } while (0)
     TAP(0, s1, 512);
     PCD_RUN(run_lin(d, 16, m, s1, x3, 512, nullptr, 0, s0, s, h->lin_frag[16]));
-    PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
-    PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
+    if (panel && has_frags(17, 2)) {
+        // rows of another width than the input's: not in place, so dec3's output is in s1 and everything below has s0 and s1 swapped
+        PCD_RUN(panel_chain(1, 17, 2, s0, s1, 256));
+        void* t = s0; s0 = s1; s1 = t;
+    } else {
+        PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
+        PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
+    }
     TAP(1, s0, 256);
     void *ta = s0, *tb = s1;                              // dec1.conv1's output and the other ping-pong buffer
     if (d21) {

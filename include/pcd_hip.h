@@ -317,8 +317,16 @@ int pcd_pw_chain_tail_hilo(const void* in, int64_t m, const void* w_a, const flo
 int pcd_conv1x1_supported(int k, int c);
 int pcd_conv1x1_f16(const void* in, int64_t m, int k, const void* w, int64_t ldw, const float* bias, int relu, int c,
                     void* out, void* stream);
-/* testing / tuning hook for pcd_unet_forward: 0 = one GEMM launch per layer, 1 (default) = the chained kernels above */
+/* testing / tuning hook for pcd_unet_forward, a mask: bit 0 = the narrow chained kernels above, bit 1 = the 256-channel chains and the row-panel chains
+ * below, bit 2 = the row-panel chains OFF (so 3, the default, is everything on; 7 = everything but the row-panel chains; 1 and 0 = per-layer GEMMs there) */
 int pcd_unet_config(int use_chains);
+/* Row-panel chains (csrc/panelchain.hip): consecutive 512-channel-input store layers as one launch with the activations of a 128-row panel resident in
+ * LDS.  chain 0 (E4): enc4.conv1-3, x [M][512] -> out [M][ld >= 1024]; chain 1 (D3T): dec3.conv2-3, x [M][512] -> out [M][ld >= 256].  frag[l] =
+ * pcd_gemm_pack_wfrag's copy of layer l's [C][512] weights, bias[l] fp32 [C] (3 layers / 2 layers); every layer ends in ReLU.  hilo: bit l set = layer l
+ * has hi | lo weights.  cap = the most workgroups (1 .. 256).  Bitwise the per-layer pcd_gemm_f16 launches.  Refuses (PCD_ERR_ARG, nothing launched)
+ * M % 128 != 0, a null fragment copy, hilo != 0, out == x. */
+int pcd_panel_chain(int chain, const void* x, int64_t m, const void* const* frag, const float* const* bias, int hilo, void* out, int64_t ld, int cap,
+                    void* stream);
 /* The 256-channel chains of the same network as one launch each (csrc/widechain.hip): chain 0 = enc3.conv1-3 (x2 [M][256] -> x3 [M][512]),
  * chain 1 = dec2.conv1-3 ([in1 [M][256] | in2 [M][256]] -> [M][128]).  A wave carries 32 points through the chain with the activations
  * in registers (the layer-to-layer hand-over is a v_permlane32_swap per register); only the weights stream, as 32-KB stage images that
