@@ -184,6 +184,7 @@ _SIGS = {
     "pcd_pw_chain_tail": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pcd_unet_config": (i32, [i32]),
     "pcd_panel_chain": (i32, [i32, vp, i64, vp, vp, i32, vp, i64, i32, vp]),
+    "pcd_panel_chain_dec": (i32, [vp, vp, i64, vp, vp, i32, vp, i64, i32, vp]),
     "pcd_pw_wide_packed_bytes": (sz, [i32]),
     "pcd_pw_wide_pack": (i32, [i32, vp, vp, vp, vp]),
     "pcd_pw_wide_chain": (i32, [i32, vp, vp, i64, vp, vp, vp]),

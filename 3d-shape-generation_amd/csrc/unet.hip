@@ -60,9 +60,9 @@ struct UnetWs {
     size_t x1, x2, x3, x4, s0, s1, pooled, pooled16, gbias, total;      // pooled16: only above 256 shapes (the dense GEMM for the pooled product reads fp16)
 };
 
-// With the row-panel chains (csrc/panelchain.hip) on, enc4.conv1-2 and dec3.conv2 write no buffer at all: s0 and s1 are not touched between x3 and x4, and
-// dec3 goes s0 (dec3.conv1's output) -> s1 (dec3.conv3's, which the per-layer sequence leaves in s0), so dec2 / dec1.conv1 swap their buffers too.  The sizes
-// stay: the per-layer sequence (ragged m, hi / lo layers, chains switched off) still needs both.
+// With the row-panel chains (csrc/panelchain.hip) on, enc4.conv1-2, dec4.conv3 and dec3.conv1-2 write no buffer at all: s0 and s1 are not touched between x3
+// and x4, and dec4.conv2's output in s0 goes straight to dec3.conv3's in s1 (which the per-layer sequence leaves in s0), so dec2 / dec1.conv1 swap their
+// buffers too.  The sizes stay: the per-layer sequence (ragged m, hi / lo layers, chains switched off) still needs both.
 static UnetWs carve(int64_t batch, int64_t n) {
     const size_t m = (size_t)batch * (size_t)n;
     UnetWs w{};
@@ -94,11 +94,11 @@ static const int kLinC[PCD_UNET_NLIN] = {64, 128, 128, 128, 256, 256, 256, 512, 
 
 static int g_unet_chains = 3;        // tuning / testing hook (pcd_unet_config): bit 0 = the narrow chains (csrc/chain.hip), bit 1 = the
                                      // 256-channel chains (csrc/widechain.hip): enc2 + enc3 and dec2 + dec1.conv1 on whole 256-point tiles, and the row-panel
-                                     // chains (csrc/panelchain.hip): enc4 and dec3.conv2-3 on whole 128-point tiles; bit 2 = the row-panel chains OFF (3 stays
-                                     // "everything on"); 0 = one GEMM launch per layer
+                                     // chains (csrc/panelchain.hip): enc4 and dec4.conv3 + dec3 on whole 128-point tiles; bit 2 = the row-panel chains OFF (3 stays
+                                     // "everything on"); bit 3 = D43 OFF: dec4.conv3 and dec3.conv1 per layer, then D3T; 0 = one GEMM launch per layer
 
 extern "C" int pcd_unet_config(int use_chains) {
-    g_unet_chains = use_chains & 7;
+    g_unet_chains = use_chains & 15;
     return PCD_OK;
 }
 
@@ -335,18 +335,27 @@ extern "C" int pcd_unet_forward(pcd_unet_t* h, const float* x, int batch, int n_
     }
     PCD_RUN(run_lin(d, 13, m, x4, nullptr, 0, gbias, n_points, s1, s, h->lin_frag[13]));
     PCD_RUN(run_lin(d, 14, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[14]));
-    PCD_RUN(run_lin(d, 15, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[15]));
 #define TAP(i, buf, ch) do { if (h->dec_tap[i]) PCD_CHECK_HIP(hipMemcpyAsync(h->dec_tap[i], buf, (size_t)m * (ch) * 2, \
                                                                              hipMemcpyDeviceToDevice, s)); } while (0)
-    TAP(0, s1, 512);
-    PCD_RUN(run_lin(d, 16, m, s1, x3, 512, nullptr, 0, s0, s, h->lin_frag[16]));
-    if (panel && has_frags(17, 2)) {
-        // rows of another width than the input's: not in place, so dec3's output is in s1 and everything below has s0 and s1 swapped
-        PCD_RUN(panel_chain(1, 17, 2, s0, s1, 256));
+    if (panel && (g_unet_chains & 8) == 0 && h->dec_tap[0] == nullptr && has_frags(15, 4)) {
+        // dec4.conv3 and dec3 in one launch (D43): dec4's output exists only inside it, so a capture of it runs the sequence below.  Not in place: dec3's
+        // output is in s1 and everything below has s0 and s1 swapped
+        const void* frag[4]; const float* bias[4];
+        for (int i = 0; i < 4; ++i) { frag[i] = h->lin_frag[15 + i]; bias[i] = d.lin[15 + i].b; }
+        PCD_RUN(pcd_panel_chain_dec(s0, x3, m, frag, bias, 0, s1, 256, 256, s));
         void* t = s0; s0 = s1; s1 = t;
     } else {
-        PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
-        PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
+        PCD_RUN(run_lin(d, 15, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[15]));
+        TAP(0, s1, 512);
+        PCD_RUN(run_lin(d, 16, m, s1, x3, 512, nullptr, 0, s0, s, h->lin_frag[16]));
+        if (panel && has_frags(17, 2)) {
+            // rows of another width than the input's: not in place, so dec3's output is in s1 and everything below has s0 and s1 swapped
+            PCD_RUN(panel_chain(1, 17, 2, s0, s1, 256));
+            void* t = s0; s0 = s1; s1 = t;
+        } else {
+            PCD_RUN(run_lin(d, 17, m, s0, nullptr, 0, nullptr, 0, s1, s, h->lin_frag[17]));
+            PCD_RUN(run_lin(d, 18, m, s1, nullptr, 0, nullptr, 0, s0, s, h->lin_frag[18]));
+        }
     }
     TAP(1, s0, 256);
     void *ta = s0, *tb = s1;                              // dec1.conv1's output and the other ping-pong buffer

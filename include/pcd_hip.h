@@ -318,7 +318,8 @@ int pcd_conv1x1_supported(int k, int c);
 int pcd_conv1x1_f16(const void* in, int64_t m, int k, const void* w, int64_t ldw, const float* bias, int relu, int c,
                     void* out, void* stream);
 /* testing / tuning hook for pcd_unet_forward, a mask: bit 0 = the narrow chained kernels above, bit 1 = the 256-channel chains and the row-panel chains
- * below, bit 2 = the row-panel chains OFF (so 3, the default, is everything on; 7 = everything but the row-panel chains; 1 and 0 = per-layer GEMMs there) */
+ * below, bit 2 = the row-panel chains OFF (so 3, the default, is everything on; 7 = everything but the row-panel chains; 1 and 0 = per-layer GEMMs there),
+ * bit 3 = D43 OFF: dec4.conv3 and dec3.conv1 as per-layer launches in front of D3T (11 = everything but D43) */
 int pcd_unet_config(int use_chains);
 /* Row-panel chains (csrc/panelchain.hip): consecutive 512-channel-input store layers as one launch with the activations of a 128-row panel resident in
  * LDS.  chain 0 (E4): enc4.conv1-3, x [M][512] -> out [M][ld >= 1024]; chain 1 (D3T): dec3.conv2-3, x [M][512] -> out [M][ld >= 256].  frag[l] =
@@ -327,6 +328,13 @@ int pcd_unet_config(int use_chains);
  * M % 128 != 0, a null fragment copy, hilo != 0, out == x. */
 int pcd_panel_chain(int chain, const void* x, int64_t m, const void* const* frag, const float* const* bias, int hilo, void* out, int64_t ld, int cap,
                     void* stream);
+/* The same kernel over dec4.conv3, dec3.conv1-3 (D43: lin 15, 16, 17, 18): x [M][1024] and x3 [M][512] -> out [M][ld >= 256].  The two K = 1024 layers
+ * read their first K half from the resident panel while the second half (columns 512 .. 1023 of x; x3) rolls into the K-tile images already read.
+ * frag[0], frag[1] = pcd_gemm_pack_wfrag's copies of [512][1024] weights (lin 16's K is [lin 15's output | x3]), frag[2], frag[3] of [512][512] and
+ * [256][512]; bias[l] fp32 [C]; every layer ends in ReLU.  Bitwise the per-layer pcd_gemm_f16 launches.  Refuses (PCD_ERR_ARG, nothing launched)
+ * M % 128 != 0, a null fragment copy, hilo != 0, out == x or out == x3. */
+int pcd_panel_chain_dec(const void* x, const void* x3, int64_t m, const void* const* frag, const float* const* bias, int hilo, void* out, int64_t ld,
+                        int cap, void* stream);
 /* The 256-channel chains of the same network as one launch each (csrc/widechain.hip): chain 0 = enc3.conv1-3 (x2 [M][256] -> x3 [M][512]),
  * chain 1 = dec2.conv1-3 ([in1 [M][256] | in2 [M][256]] -> [M][128]).  A wave carries 32 points through the chain with the activations
  * in registers (the layer-to-layer hand-over is a v_permlane32_swap per register); only the weights stream, as 32-KB stage images that
