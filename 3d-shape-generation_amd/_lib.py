@@ -327,6 +327,19 @@ _SIGS = {
     "pcd_mesh_voxelize": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
     "pcd_mesh_sample_workspace_bytes": (sz, [i32, i64]),
     "pcd_mesh_sample_points": (i32, [vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]),
+    "pcd_mesh_adjacency_workspace_bytes": (sz, [i32, i64, i64]),
+    "pcd_mesh_adjacency": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pcd_mesh_smooth_workspace_bytes": (sz, [i64]),
+    "pcd_mesh_smooth": (i32, [vp, vp, i32, i64, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp]),
+    "pcd_mesh_vertex_normals": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp]),
+    "pcd_mesh_components_workspace_bytes": (sz, [i64]),
+    "pcd_mesh_components": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pcd_mesh_component_keep": (i32, [vp, i32, vp, vp, i32, i32, vp, vp]),
+    "pcd_mesh_compact_workspace_bytes": (sz, [i64]),
+    "pcd_mesh_compact_count": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "pcd_mesh_compact_emit": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "pcd_mesh_measures": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "pcd_mesh_ops_config": (i32, [i32]),
     "pcd_render_points": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, f32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
     "pcd_render_meshes": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
     "pcd_render_config": (i32, [i32]),

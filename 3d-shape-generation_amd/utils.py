@@ -91,30 +91,41 @@ def mesh_is_closed(mesh) -> bool:
     return bool(np.array_equal(np.sort(a * n + b), np.sort(b * n + a)))
 
 
-def save_mesh(path: str, mesh) -> None:
+def save_mesh(path: str, mesh, normals=None) -> None:
     """Write `mesh` = (vertices (V,3), faces (F,3)), CPU or device tensors, by the extension of `path`: `.obj` (text, `v x y z` lines with 9
     significant digits -- float32 round-trips -- and 1-based `f a b c` lines) or `.ply` (binary little-endian, `float x y z` and
-    `list uchar int vertex_indices`).  Host only."""
+    `list uchar int vertex_indices`).  With `normals` (V,3), one per vertex (`mesh_ops.vertex_normals`), the `.obj` also gets `vn` lines
+    and `f a//a b//b c//c`, the `.ply` `float nx ny nz` on the vertex element.  Host only."""
     ext = os.path.splitext(path)[1].lower()
     if ext not in (".obj", ".ply"):
         raise ValueError(f"save_mesh writes .obj or .ply, not {ext!r} ({path})")
     v, f = _mesh_arrays(mesh)
+    n = None
+    if normals is not None:
+        n = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4")
+        if n.shape != v.shape:
+            raise ValueError(f"save_mesh: normals must be one row per vertex, {v.shape}, got {n.shape}")
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     if ext == ".obj":
         with open(path, "w") as out:
             out.write(f"# {v.shape[0]} vertices, {f.shape[0]} triangles\n")
             out.writelines(f"v {float(x):.9g} {float(y):.9g} {float(z):.9g}\n" for x, y, z in v)
-            out.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in f.tolist())
+            if n is None:
+                out.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in f.tolist())
+            else:
+                out.writelines(f"vn {float(x):.9g} {float(y):.9g} {float(z):.9g}\n" for x, y, z in n)
+                out.writelines(f"f {a + 1}//{a + 1} {b + 1}//{b + 1} {c + 1}//{c + 1}\n" for a, b, c in f.tolist())
         return
     rows = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     rows["n"] = 3
     rows["idx"] = f
     header = ("ply\nformat binary_little_endian 1.0\n"
               f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              + ("" if n is None else "property float nx\nproperty float ny\nproperty float nz\n") +
               f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as out:
         out.write(header.encode("ascii"))
-        out.write(v.tobytes())
+        out.write((v if n is None else np.concatenate([v, n], axis=1)).tobytes())
         out.write(rows.tobytes())
 
 

@@ -3,6 +3,7 @@ triangle mesh per shape.
 
     python generate_mesh_ldm.py [--vae-ckpt FILE] [--ldm-ckpt FILE] [--num-samples 16] [--sampler ddim|dpm] [--steps N]
                                 [--threshold 0.4] [--format obj|ply] [--out DIR] [--png-dir DIR]
+                                [--smooth N] [--keep-largest] [--normals]
 
 `--sampler dpm` (default, 20 steps) is `LatentDiffusion.sample_dpm`, `ddim` (default 1000 steps) is `sample`; both run with
 `output="mesh"`, so the decoded grids go through the surface-nets kernel (`utils.voxel_tensor_to_meshes`) at `--threshold`, the
@@ -11,7 +12,8 @@ a trained VAE under a denoiser with synthetic weights.  Without checkpoints (non
 synthetic weights, so the plumbing is exercised end to end.  One file `mesh_<i>.<format>` per shape goes to `--out`; vertices are in
 the [-1, 1] cube of the point clouds (a surface that reaches the grid's border closes up to one voxel pitch outside it).  Per shape
 the log gives the vertex and triangle counts and whether the mesh is closed.  `--png-dir DIR` also writes `sample_<i>_3d.png` and
-`sample_<i>_2d.png`, the meshes rendered on the device.  One process, one GPU.
+`sample_<i>_2d.png`, the meshes rendered on the device.  `--keep-largest`, `--smooth N` and `--normals` apply the steps of
+`process_meshes.py`, in that order, to the decoded meshes before they are written; without them nothing changes.  One process, one GPU.
 """
 from __future__ import annotations
 
@@ -57,6 +59,9 @@ def main():
     ap.add_argument("--format", choices=("obj", "ply"), default="obj")
     ap.add_argument("--out", default=os.path.join("test", "outputs", "meshes"))
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write the reference's pictures (sample_{i}_3d.png, sample_{i}_2d.png) here")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="rounds of Taubin smoothing of the decoded meshes")
+    ap.add_argument("--keep-largest", action="store_true", help="keep only the connected component with the most faces")
+    ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals with the meshes")
     args = ap.parse_args()
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.sampler]
     torch.manual_seed(24)
@@ -74,10 +79,14 @@ def main():
     log.info(f"{name}: {len(meshes)} meshes, sampler {args.sampler}, {steps} steps, threshold {args.threshold}")
     if rank != 0:
         return
+    normals = None
+    if args.smooth or args.keep_largest or args.normals:             # components, then smoothing, then normals (process_meshes.py)
+        from shapegen_amd import mesh_ops
+        meshes, normals = mesh_ops.process_meshes(meshes, keep_largest=args.keep_largest, smooth=args.smooth, normals=args.normals)
     os.makedirs(args.out, exist_ok=True)
     for i, mesh in enumerate(meshes):
         path = os.path.join(args.out, f"mesh_{i}.{args.format}")
-        save_mesh(path, mesh)
+        save_mesh(path, mesh, normals=None if normals is None else normals[i])
         log.info(f"mesh {i}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles, closed {mesh_is_closed(mesh)} -> {path}")
         if args.png_dir:
             save_shape_pngs(args.png_dir, i, mesh)

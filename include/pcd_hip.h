@@ -939,6 +939,79 @@ int pcd_mesh_sample_points(const float* vertices, const int32_t* faces, const in
                            uint64_t philox_offset, const float* u, void* workspace, float* points, float* normals, int32_t* face_index,
                            void* stream);
 
+/* ---- Mesh processing: vertex rings, smoothing, normals, components, compaction, measures (csrc/mesh_ops.hip; DESIGN.md "Mesh processing") ----
+ * Meshes are packed as for pcd_mesh_voxelize: vertices fp32 [sum V][3], faces int32 [sum F][3] local to the mesh, offsets int64 [B + 1][2].
+ * total_vertices and total_faces are the last row of offsets, known to the caller on the host (rows past them are never read); max_vertices
+ * (pcd_mesh_components) is an upper bound of every mesh's V (total_vertices is one) and only decides which launches are made.  A face is VALID iff its three indices
+ * are rows of its mesh and pairwise different; every function skips the others.  No floating-point atomics, every sum in a fixed order, every
+ * device loop bounded by V, F or the iteration count: bitwise repeatable, a mesh gets in a batch what it gets alone, and empty meshes are legal.
+ * No host synchronisation except between pcd_mesh_compact_count and pcd_mesh_compact_emit.  PCD_ERR_ARG (before any device work) for a null
+ * pointer, batch outside 1 .. 65535, total_vertices >= 2^31 - 1, 6 total_faces >= 2^31 - 1024, or max_vertices > total_vertices.
+ *
+ * Adjacency.  Rows are indexed by packed vertex row g (nbr_start, inc_start int32 [sum V + 1], exclusive running sums by a device scan; the sizes
+ * are bounded by 6 and 3 entries per face, so nothing is sized from the data).  Row g of nbr_index (int32 [6 sum F]) holds the distinct
+ * neighbours u of the vertex (local indices, they share an edge of a valid face) in ascending u, and nbr_counts (int32 [6 sum F][2]) per entry
+ * (out, in) = the number of valid faces holding the directed edge a -> u and u -> a.  Row g of inc_faces (int32 [3 sum F]) holds its incident valid
+ * faces (local) in ascending order.  Entries past nbr_start[sum V] / inc_start[sum V] are not written.  flags int32 [sum V]:
+ * PCD_MESH_VERTEX_REFERENCED (in some valid face), _BOUNDARY (some entry has out + in == 1), _IRREGULAR (some entry has out != 1 or in != 1: a
+ * boundary, a non-manifold edge or an inconsistently oriented one).  Rows of any length (one wave sorts a row by rank). */
+#define PCD_MESH_VERTEX_REFERENCED 1
+#define PCD_MESH_VERTEX_BOUNDARY 2
+#define PCD_MESH_VERTEX_IRREGULAR 4
+size_t pcd_mesh_adjacency_workspace_bytes(int batch, int64_t total_vertices, int64_t total_faces);
+int pcd_mesh_adjacency(const int32_t* faces, const int64_t* offsets, int batch, int64_t total_vertices, int64_t total_faces, void* workspace,
+                       int32_t* nbr_start, int32_t* nbr_index, int32_t* nbr_counts, int32_t* inc_start, int32_t* inc_faces, int32_t* flags,
+                       void* stream);
+/* Taubin smoothing: `iterations` rounds of a lam step then (mu != 0) a mu step of the uniform umbrella operator, Jacobi style.  Per step and
+ * component, fp32 without contraction: s = +0; s = s + x[u] over the row in order; m = s / float(n); x' = x + f (m - x).  A vertex with an empty
+ * row keeps its position, with pin_boundary a BOUNDARY vertex does too, bitwise.  One launch per step over the whole batch, one thread per
+ * vertex, the positions alternating between `workspace` (pcd_mesh_smooth_workspace_bytes()) and out so that the last step lands in out.
+ * out fp32 [sum V][3], not `vertices`.  PCD_ERR_ARG also for iterations outside 0 .. 2^20, lam outside (0, 1], mu outside (-1, 0] or a factor
+ * that is not finite. */
+size_t pcd_mesh_smooth_workspace_bytes(int64_t total_vertices);
+int pcd_mesh_smooth(const float* vertices, const int64_t* offsets, int batch, int64_t total_vertices, const int32_t* nbr_start,
+                    const int32_t* nbr_index, const int32_t* flags, int iterations, float lam, float mu, int pin_boundary, void* workspace,
+                    float* out, void* stream);
+/* Area-weighted vertex normals, fp32 without contraction: per incident face in ascending order e1 = b - a, e2 = c - a (a, b, c in the face's
+ * order), n += (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x) from +0; len = sqrt((nx nx + ny ny) + nz nz); normals fp32 [sum V][3] =
+ * n / len, zeros where len is 0 or the vertex is unreferenced. */
+int pcd_mesh_vertex_normals(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, int64_t total_vertices,
+                            const int32_t* inc_start, const int32_t* inc_faces, float* normals, void* stream);
+/* Connected components by min-label propagation with pointer jumping, one workgroup per mesh, at most V sweeps.  labels int32 [sum V]: the
+ * least vertex index of the component, -1 for an unreferenced vertex; counts int32 [B]: components per mesh; component_faces int32 [sum V]: at a
+ * label root the valid faces of its component, 0 elsewhere.  Labels of a mesh of at most PCD_MESH_LABELS_LDS_MAX_V vertices live in LDS while
+ * they move, larger ones in `workspace` (pcd_mesh_components_workspace_bytes()). */
+#define PCD_MESH_LABELS_LDS_MAX_V 32768
+size_t pcd_mesh_components_workspace_bytes(int64_t total_vertices);
+int pcd_mesh_components(const int32_t* faces, const int64_t* offsets, int batch, int64_t total_vertices, int64_t max_vertices,
+                        const int32_t* nbr_start, const int32_t* nbr_index, const int32_t* flags, void* workspace, int32_t* labels,
+                        int32_t* counts, int32_t* component_faces, void* stream);
+/* keep int32 [sum V] = 1 for the vertices of the chosen components, 0 elsewhere (unreferenced vertices always 0).  PCD_MESH_KEEP_LARGEST: the
+ * component with the most faces, the smaller label on a tie; PCD_MESH_KEEP_MIN_FACES: every component with at least min_faces (>= 0) faces. */
+#define PCD_MESH_KEEP_LARGEST 0
+#define PCD_MESH_KEEP_MIN_FACES 1
+int pcd_mesh_component_keep(const int64_t* offsets, int batch, const int32_t* labels, const int32_t* component_faces, int rule, int min_faces,
+                            int32_t* keep, void* stream);
+/* Compaction under keep int32 [sum V] (nonzero = kept): the kept vertices in order, and in order the valid faces whose three vertices are all
+ * kept, renumbered.  The protocol of pcd_mesh_count / pcd_mesh_emit: pcd_mesh_compact_count leaves each vertex's new index or -1 in `workspace`
+ * (pcd_mesh_compact_workspace_bytes()) and counts int32 [B][2] = (vertices, faces); the caller sizes the outputs on the host and passes
+ * out_offsets int64 [B][2], the exclusive running sums of counts, to pcd_mesh_compact_emit with the same inputs and workspace. */
+size_t pcd_mesh_compact_workspace_bytes(int64_t total_vertices);
+int pcd_mesh_compact_count(const int32_t* faces, const int64_t* offsets, int batch, const int32_t* keep, void* workspace, int32_t* counts,
+                           void* stream);
+int pcd_mesh_compact_emit(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, const void* workspace,
+                          const int64_t* out_offsets, float* out_vertices, int32_t* out_faces, void* stream);
+/* Measures.  real float64 [B][5] = area sum |e1 x e2| / 2, signed volume sum a . (b x c) / 6, and the area-weighted centroid of the surface
+ * (zeros for area 0), formed per face in double from the fp32 vertices and added in a fixed tree (the butterfly of a wave, the 16 waves in order,
+ * then chunks of 1024 faces in order).  whole int32 [B][8] = referenced vertices, undirected edges (ring entries / 2), valid faces, boundary
+ * edges (out + in == 1), irregular edges (out != 1 or in != 1), components (the roots of `labels` from pcd_mesh_components), the Euler
+ * characteristic V - E + F of those three, and closed = 1 iff every entry has out == in. */
+int pcd_mesh_measures(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, const int32_t* nbr_start,
+                      const int32_t* nbr_index, const int32_t* nbr_counts, const int32_t* labels, double* real, int32_t* whole, void* stream);
+/* Where pcd_mesh_components keeps the moving labels.  TEST ONLY: process-global.  0 (default): in LDS for the meshes they fit; 1: always in
+ * the workspace, as for larger meshes.  Same bits either way.  PCD_ERR_ARG for any other code. */
+int pcd_mesh_ops_config(int code);
+
 /* ---- Images out: depth-buffered renderer for point clouds and triangle meshes (csrc/render.hip; DESIGN.md "Render") ----
  * View.  views fp32 [view_sets][V][12], a row-major 3 x 4 matrix [M | t] each; view_sets = 1 shares the V views among the shapes, view_sets = B
  * gives every shape its own.  A world point p maps to q = M p + t = (x, y, z), each component evaluated in fp32 without contraction as
