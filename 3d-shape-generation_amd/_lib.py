@@ -340,6 +340,9 @@ _SIGS = {
     "pcd_mesh_compact_emit": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "pcd_mesh_measures": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "pcd_mesh_ops_config": (i32, [i32]),
+    "pcd_mesh_simplify_workspace_bytes": (sz, [i32, i64, i64]),
+    "pcd_mesh_simplify_count": (i32, [vp, vp, vp, i32, i64, i64, i64, i32, vp, i32, vp, sz, vp, vp, vp, vp]),
+    "pcd_mesh_simplify_emit": (i32, [vp, vp, vp, i32, i64, i64, i64, i32, vp, sz, vp, vp, vp, vp]),
     "pcd_render_points": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, f32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
     "pcd_render_meshes": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, C.POINTER(RenderStyle), vp, vp, vp, vp]),
     "pcd_render_config": (i32, [i32]),

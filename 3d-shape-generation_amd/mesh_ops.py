@@ -1,5 +1,6 @@
 """Mesh processing on the device (csrc/mesh_ops.hip; DESIGN.md "Mesh processing"): vertex rings, Taubin smoothing, vertex normals,
-connected components, compaction and measures, on lists of `utils.Mesh` / (vertices, faces) pairs.  No CPU path."""
+connected components, compaction and measures, and (csrc/mesh_simplify.hip; DESIGN.md "Mesh simplification") simplification by vertex
+clustering, on lists of `utils.Mesh` / (vertices, faces) pairs.  No CPU path."""
 from __future__ import annotations
 
 import math
@@ -221,14 +222,118 @@ def remove_small_components(meshes, min_faces: Optional[int] = None, keep_larges
     return _compact(p, keep)
 
 
+SIMPLIFY_RESOLUTION, SIMPLIFY_CELL_SIZE, SIMPLIFY_TARGET_FACES = 0, 1, 2   # include/pcd_hip.h PCD_MESH_SIMPLIFY_*
+PLACEMENTS = {"quadric": 0, "mean": 1}
+SIMPLIFY_MAX_RESOLUTION, SIMPLIFY_MAX_VERTICES = 1024, 1 << 21
+
+
+def _per_mesh(value, batch: int, name: str) -> list:
+    values = list(value) if isinstance(value, (list, tuple)) or (torch.is_tensor(value) and value.dim() > 0) else [value] * batch
+    if len(values) != batch:
+        raise ValueError(f"{name} must be a scalar or one value per mesh ({batch}), got {len(values)}")
+    return [v.item() if torch.is_tensor(v) else v for v in values]
+
+
+def _check_simplify(batch: int, resolution, cell_size, target_faces, placement) -> Tuple[int, list, int]:
+    """-> (mode, one validated value per mesh, placement code)"""
+    given = [(m, v) for m, v in ((SIMPLIFY_RESOLUTION, resolution), (SIMPLIFY_CELL_SIZE, cell_size), (SIMPLIFY_TARGET_FACES, target_faces))
+             if v is not None]
+    if len(given) != 1:
+        raise ValueError("simplify_meshes: give exactly one of resolution, cell_size and target_faces")
+    if placement not in PLACEMENTS:
+        raise ValueError(f"placement must be 'quadric' or 'mean', got {placement!r}")
+    mode, value = given[0]
+    if mode == SIMPLIFY_CELL_SIZE:
+        values = [float(c) for c in _per_mesh(value, batch, "cell_size")]
+        for c in values:
+            if not (math.isfinite(c) and c > 0.0):
+                raise ValueError(f"cell_size must be finite and > 0, got {c!r}")
+        return mode, values, PLACEMENTS[placement]
+    name = "resolution" if mode == SIMPLIFY_RESOLUTION else "target_faces"
+    values = []
+    for x in _per_mesh(value, batch, name):
+        n = int(x)
+        if n != x:
+            raise ValueError(f"{name} must be an integer, got {x!r}")
+        if mode == SIMPLIFY_RESOLUTION and not 1 <= n <= SIMPLIFY_MAX_RESOLUTION:
+            raise ValueError(f"resolution must lie in 1 .. {SIMPLIFY_MAX_RESOLUTION}, got {x!r}")
+        if mode == SIMPLIFY_TARGET_FACES and not 0 <= n < 2 ** 31:
+            raise ValueError(f"target_faces must be an integer >= 0, got {x!r}")
+        values.append(n)
+    return mode, values, PLACEMENTS[placement]
+
+
+def simplify_meshes(meshes, resolution=None, cell_size=None, target_faces=None, placement: str = "quadric", deduplicate: bool = False,
+                    return_map: bool = False):
+    """Simplification by vertex clustering (DESIGN.md "Mesh simplification"): per mesh a grid of `resolution`^3 cubic cells over the box of
+    its referenced vertices (or cells of side `cell_size`, or the resolution a ten-round bisection on the device finds for a budget of
+    `target_faces`: the result has at most that many faces); the vertices of a cell become one vertex, at the minimiser of the cell's summed
+    face quadrics pulled towards the members' mean (`placement="quadric"`) or at the mean (`"mean"`), and the faces that keep three
+    different vertices survive, in order.  Exactly one of the first three must be given, a scalar or one value per mesh.  Unreferenced
+    vertices and invalid faces go; a cluster whose faces all collapse keeps its vertex.  A closed mesh (`mesh_measures(...)["closed"]`) stays closed; `deduplicate` keeps only the first of the
+    faces with the same oriented vertex triple and may break that.  -> list of Mesh; with `return_map` (meshes, maps, resolutions): per mesh
+    the (V,) int32 new index of every input vertex (-1 unreferenced) and the (B,) int32 device tensor of the resolutions used.  Bitwise
+    repeatable; one host read to size the result."""
+    meshes = list(meshes)
+    mode, values, place = _check_simplify(len(meshes), resolution, cell_size, target_faces, placement)
+    p, _ = _pack(meshes, "simplify_meshes")
+    if p.max_vertices >= SIMPLIFY_MAX_VERTICES:
+        raise ValueError(f"simplify_meshes: a mesh has {p.max_vertices} vertices, the limit is {SIMPLIFY_MAX_VERTICES - 1}")
+    lib = _lib.load()
+    b, (tv, tf), dev = p.batch, p.totals, p.verts.device
+    params = torch.tensor(values, dtype=torch.float32 if mode == SIMPLIFY_CELL_SIZE else torch.int32).to(dev)
+    nbytes = lib.pcd_mesh_simplify_workspace_bytes(b, tv, tf)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+    res, vmap, counts = _i32(b, dev), _i32(tv, dev), torch.empty(b, 2, dtype=torch.int32, device=dev)
+    sizes = (b, tv, tf, p.max_vertices)
+    _lib.check(lib.pcd_mesh_simplify_count(p.verts.data_ptr(), p.faces.data_ptr(), p.offsets.data_ptr(), *sizes, mode, params.data_ptr(),
+                                           int(bool(deduplicate)), ws.data_ptr(), nbytes, res.data_ptr(), vmap.data_ptr(), counts.data_ptr(),
+                                           _lib.stream_ptr()), "mesh_simplify_count")
+    offsets = (torch.cumsum(counts, dim=0, dtype=torch.int64) - counts).contiguous()
+    cnt = counts.cpu().tolist()          # the packed outputs are sized on the host: the one sync, as in _compact
+    nv, nf = [c[0] for c in cnt], [c[1] for c in cnt]
+    verts = torch.empty(max(sum(nv), 1), 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(max(sum(nf), 1), 3, dtype=torch.int32, device=dev)
+    _lib.check(lib.pcd_mesh_simplify_emit(p.verts.data_ptr(), p.faces.data_ptr(), p.offsets.data_ptr(), *sizes, place, ws.data_ptr(), nbytes,
+                                          offsets.data_ptr(), verts.data_ptr(), faces.data_ptr(), _lib.stream_ptr()), "mesh_simplify_emit")
+    out = [Mesh(v, f) for v, f in zip(torch.split(verts[:sum(nv)], nv), torch.split(faces[:sum(nf)], nf))]
+    return (out, p.split_vertices(vmap), res[:b]) if return_map else out
+
+
+def add_simplify_arguments(ap) -> None:
+    """The simplification flags of `process_meshes.py` and `generate_mesh_ldm.py` on an argparse parser"""
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--simplify-resolution", type=int, default=None, metavar="R", help="cluster the vertices in an R^3 grid over each mesh's box")
+    how.add_argument("--simplify-cell", type=float, default=None, metavar="H", help="cluster the vertices in cubic cells of side H")
+    how.add_argument("--target-faces", type=int, default=None, metavar="N", help="the finest grid a bisection finds that leaves at most N faces")
+    ap.add_argument("--placement", choices=tuple(PLACEMENTS), default="quadric", help="a cluster's vertex: quadric minimiser or mean")
+    ap.add_argument("--deduplicate", action="store_true", help="keep one of the faces that share an oriented vertex triple")
+
+
+def simplify_keywords(args) -> dict:
+    """`process_meshes`' keywords from the flags of `add_simplify_arguments`"""
+    return dict(simplify_resolution=args.simplify_resolution, simplify_cell_size=args.simplify_cell, target_faces=args.target_faces,
+                placement=args.placement, deduplicate=args.deduplicate)
+
+
 def process_meshes(meshes, keep_largest: bool = False, min_faces: Optional[int] = None, smooth: int = 0, lam: float = 0.5, mu: float = -0.53,
-                   pin_boundary: bool = False, normals: bool = False):
-    """The steps of `process_meshes.py` and `generate_mesh_ldm.py` in their fixed order -- components, then smoothing, then normals -- each
-    only where asked for.  -> (meshes, list of (V, 3) normals or None)."""
+                   pin_boundary: bool = False, normals: bool = False, simplify_resolution=None, simplify_cell_size=None, target_faces=None,
+                   placement: str = "quadric", deduplicate: bool = False, info: Optional[dict] = None):
+    """The steps of `process_meshes.py` and `generate_mesh_ldm.py` in their fixed order -- components, then simplification, then smoothing,
+    then normals -- each only where asked for.  -> (meshes, list of (V, 3) normals or None).  A dict passed as `info` gets
+    `resolutions`, the (B,) int32 device tensor of the grid resolutions used, where simplification ran."""
     _check_smooth(smooth, lam, mu)
     meshes = [Mesh(*m) for m in meshes]
+    simplify = any(x is not None for x in (simplify_resolution, simplify_cell_size, target_faces))
+    if simplify:
+        _check_simplify(len(meshes), simplify_resolution, simplify_cell_size, target_faces, placement)
     if keep_largest or min_faces is not None:
         meshes = remove_small_components(meshes, min_faces=min_faces, keep_largest=keep_largest)
+    if simplify:
+        meshes, _, resolutions = simplify_meshes(meshes, resolution=simplify_resolution, cell_size=simplify_cell_size,
+                                                 target_faces=target_faces, placement=placement, deduplicate=deduplicate, return_map=True)
+        if info is not None:
+            info["resolutions"] = resolutions
     adj = mesh_adjacency(meshes) if smooth > 0 or normals else None
     if smooth > 0:
         meshes = smooth_meshes(meshes, smooth, lam, mu, pin_boundary=pin_boundary, adjacency=adj)

@@ -4,6 +4,7 @@ triangle mesh per shape.
     python generate_mesh_ldm.py [--vae-ckpt FILE] [--ldm-ckpt FILE] [--num-samples 16] [--sampler ddim|dpm] [--steps N]
                                 [--threshold 0.4] [--format obj|ply] [--out DIR] [--png-dir DIR]
                                 [--smooth N] [--keep-largest] [--normals]
+                                [--simplify-resolution R | --simplify-cell H | --target-faces N] [--placement quadric|mean] [--deduplicate]
 
 `--sampler dpm` (default, 20 steps) is `LatentDiffusion.sample_dpm`, `ddim` (default 1000 steps) is `sample`; both run with
 `output="mesh"`, so the decoded grids go through the surface-nets kernel (`utils.voxel_tensor_to_meshes`) at `--threshold`, the
@@ -12,8 +13,9 @@ a trained VAE under a denoiser with synthetic weights.  Without checkpoints (non
 synthetic weights, so the plumbing is exercised end to end.  One file `mesh_<i>.<format>` per shape goes to `--out`; vertices are in
 the [-1, 1] cube of the point clouds (a surface that reaches the grid's border closes up to one voxel pitch outside it).  Per shape
 the log gives the vertex and triangle counts and whether the mesh is closed.  `--png-dir DIR` also writes `sample_<i>_3d.png` and
-`sample_<i>_2d.png`, the meshes rendered on the device.  `--keep-largest`, `--smooth N` and `--normals` apply the steps of
-`process_meshes.py`, in that order, to the decoded meshes before they are written; without them nothing changes.  One process, one GPU.
+`sample_<i>_2d.png`, the meshes rendered on the device.  `--keep-largest`, the simplification flags (`--target-faces N` and the others of
+`process_meshes.py`), `--smooth N` and `--normals` apply the steps of `process_meshes.py`, in that order, to the decoded meshes before they
+are written; without them nothing changes.  One process, one GPU.
 """
 from __future__ import annotations
 
@@ -62,6 +64,8 @@ def main():
     ap.add_argument("--smooth", type=int, default=0, metavar="N", help="rounds of Taubin smoothing of the decoded meshes")
     ap.add_argument("--keep-largest", action="store_true", help="keep only the connected component with the most faces")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals with the meshes")
+    from shapegen_amd import mesh_ops
+    mesh_ops.add_simplify_arguments(ap)
     args = ap.parse_args()
     steps = args.steps if args.steps is not None else DEFAULT_STEPS[args.sampler]
     torch.manual_seed(24)
@@ -80,9 +84,11 @@ def main():
     if rank != 0:
         return
     normals = None
-    if args.smooth or args.keep_largest or args.normals:             # components, then smoothing, then normals (process_meshes.py)
-        from shapegen_amd import mesh_ops
-        meshes, normals = mesh_ops.process_meshes(meshes, keep_largest=args.keep_largest, smooth=args.smooth, normals=args.normals)
+    simplify = mesh_ops.simplify_keywords(args)
+    if args.smooth or args.keep_largest or args.normals or any(simplify[k] is not None for k in ("simplify_resolution", "simplify_cell_size",
+                                                                                                   "target_faces")):
+        # components, then simplification, then smoothing, then normals (process_meshes.py)
+        meshes, normals = mesh_ops.process_meshes(meshes, keep_largest=args.keep_largest, smooth=args.smooth, normals=args.normals, **simplify)
     os.makedirs(args.out, exist_ok=True)
     for i, mesh in enumerate(meshes):
         path = os.path.join(args.out, f"mesh_{i}.{args.format}")

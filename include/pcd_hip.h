@@ -1012,6 +1012,39 @@ int pcd_mesh_measures(const float* vertices, const int32_t* faces, const int64_t
  * the workspace, as for larger meshes.  Same bits either way.  PCD_ERR_ARG for any other code. */
 int pcd_mesh_ops_config(int code);
 
+/* ---- Mesh simplification: vertex clustering with quadric-optimal representatives (csrc/mesh_simplify.hip; DESIGN.md "Mesh simplification") ----
+ * Packing, valid faces and the promises (integer atomics only, fixed-order sums, bounded loops, bitwise repeatable, a mesh gets in a batch what
+ * it gets alone, empty meshes legal) as in the block above.  Per mesh a cubic grid of R^3 cells of side h over the box of the referenced
+ * vertices; the referenced vertices of a cell form a cluster, numbered by their least vertex index; a valid face survives iff its three
+ * clusters differ (and, with `deduplicate`, iff it is the first with its oriented triple of clusters up to rotation); a cluster's vertex is
+ * the regularised minimiser of its summed face quadrics (PCD_MESH_SIMPLIFY_QUADRIC) or the mean of its members (_MEAN), in fp64, rounded to fp32.
+ *
+ * `params` is a device array of one entry per mesh, read by `mode`: _RESOLUTION int32 R (h = ext / R), _CELL_SIZE fp32 h (R follows from the
+ * box), _TARGET_FACES int32 face budget (ten rounds of bisection over R in 1 .. 1024 on the device, surviving faces <= budget).  The entries
+ * are the caller's to validate (shapegen_amd.mesh_ops does); the kernels clamp R to 1 .. PCD_MESH_SIMPLIFY_MAX_RESOLUTION, take R = 1 for a
+ * cell size that is not finite and positive, and a negative budget as 0, so no entry can index out of range.
+ *
+ * The protocol of pcd_mesh_compact_count / _emit: pcd_mesh_simplify_count writes resolutions int32 [B] (the R used), map int32 [sum V] (vertex ->
+ * cluster number of its mesh, -1 unreferenced) and counts int32 [B][2] = (clusters, surviving faces); the caller sizes the outputs on the host
+ * -- the one host read -- and passes out_offsets int64 [B][2], the exclusive running sums of counts, to pcd_mesh_simplify_emit with the same
+ * inputs and the workspace as _count left it.  max_vertices is an upper bound of every mesh's V.  PCD_ERR_ARG (nothing launched) for a null
+ * pointer, an unknown mode, placement or deduplicate flag, sizes the block above refuses, max_vertices > total_vertices or
+ * max_vertices >= PCD_MESH_SIMPLIFY_MAX_VERTICES; PCD_ERR_WORKSPACE for workspace_bytes below pcd_mesh_simplify_workspace_bytes() (0 = refused sizes). */
+#define PCD_MESH_SIMPLIFY_RESOLUTION 0
+#define PCD_MESH_SIMPLIFY_CELL_SIZE 1
+#define PCD_MESH_SIMPLIFY_TARGET_FACES 2
+#define PCD_MESH_SIMPLIFY_QUADRIC 0
+#define PCD_MESH_SIMPLIFY_MEAN 1
+#define PCD_MESH_SIMPLIFY_MAX_RESOLUTION 1024
+#define PCD_MESH_SIMPLIFY_MAX_VERTICES (1 << 21)
+size_t pcd_mesh_simplify_workspace_bytes(int batch, int64_t total_vertices, int64_t total_faces);
+int pcd_mesh_simplify_count(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, int64_t total_vertices,
+                            int64_t total_faces, int64_t max_vertices, int mode, const void* params, int deduplicate, void* workspace,
+                            size_t workspace_bytes, int32_t* resolutions, int32_t* map, int32_t* counts, void* stream);
+int pcd_mesh_simplify_emit(const float* vertices, const int32_t* faces, const int64_t* offsets, int batch, int64_t total_vertices,
+                           int64_t total_faces, int64_t max_vertices, int placement, void* workspace, size_t workspace_bytes,
+                           const int64_t* out_offsets, float* out_vertices, int32_t* out_faces, void* stream);
+
 /* ---- Images out: depth-buffered renderer for point clouds and triangle meshes (csrc/render.hip; DESIGN.md "Render") ----
  * View.  views fp32 [view_sets][V][12], a row-major 3 x 4 matrix [M | t] each; view_sets = 1 shares the V views among the shapes, view_sets = B
  * gives every shape its own.  A world point p maps to q = M p + t = (x, y, z), each component evaluated in fp32 without contraction as
