@@ -22,38 +22,16 @@ struct VoxShared {
     uint32_t pick[2];                           // radix select: the digit found and the rank left inside it
 };
 
-// exclusive scan of one value per lane in lane order; *total (if given) = the sum.  Safe to call back to back.
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* wave_u, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_u[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < VOX_WAVES; ++w) {
-        const uint32_t s = wave_u[w];
-        if (w < wave) before += s;
-        all += s;
-    }
-    if (total) *total = all;
-    return before + inc - v;
-}
-
+// the sum of one value per lane; safe to call back to back
 __device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* wave_u) {
     uint32_t total;
-    block_scan_excl(v, wave_u, &total);
+    block_scan_excl<VOX_WAVES>(v, wave_u, &total);
     return total;
 }
 
 
 // what a slot's run is made of, uniform over the workgroup
-struct VoxSlot {
+struct VoxSlot {                                // field for field mesh_data.hip's MdtSlot: the two chains are kept apart, see profiles/mesh_family_isa.md
     uint64_t seed, ctr0;                        // ctr0: first counter of the slot's span
     int flags;
     float sigma, clip;
@@ -131,7 +109,7 @@ __global__ __launch_bounds__(VOX_LANES) void voxel_batch_clouds_kernel(const uin
     const uint32_t cnt = (uint32_t)__builtin_popcount(word);
     const int z = t >> 5, y = t & 31;
     uint32_t M;
-    const uint32_t base = block_scan_excl(cnt, sh.wave_u, &M);
+    const uint32_t base = block_scan_excl<VOX_WAVES>(cnt, sh.wave_u, &M);
     sh.words[t] = word;
     sh.base[t] = base;
     if (t == 0) { sh.base[VOX_WORDS] = M; counts[b] = (int)M; }
@@ -231,7 +209,7 @@ __global__ __launch_bounds__(VOX_LANES) void voxel_batch_clouds_kernel(const uin
         }
         __syncthreads();
         const uint32_t h = t < 256 ? sh.hist[t] : 0u;
-        const uint32_t before = block_scan_excl(h, sh.wave_u, nullptr);
+        const uint32_t before = block_scan_excl<VOX_WAVES>(h, sh.wave_u);
         if (t < 256 && before < rank && rank <= before + h) { sh.pick[0] = (uint32_t)t; sh.pick[1] = rank - before; }
         __syncthreads();
         prefix = (prefix << 8) | sh.pick[0];
@@ -253,8 +231,8 @@ __global__ __launch_bounds__(VOX_LANES) void voxel_batch_clouds_kernel(const uin
         }
     }
     const uint32_t nb = (uint32_t)__builtin_popcount(below), ne = (uint32_t)__builtin_popcount(equal);
-    uint32_t b_before = block_scan_excl(nb, sh.wave_u, nullptr);
-    uint32_t e_before = block_scan_excl(ne, sh.wave_u, nullptr);
+    uint32_t b_before = block_scan_excl<VOX_WAVES>(nb, sh.wave_u);
+    uint32_t e_before = block_scan_excl<VOX_WAVES>(ne, sh.wave_u);
     uint32_t ord = base, i = 0;
     for (uint32_t w = word; w; w &= w - 1, ++ord, ++i) {
         const bool is_b = (below >> i) & 1u, is_e = (equal >> i) & 1u;

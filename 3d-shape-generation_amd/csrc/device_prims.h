@@ -1,5 +1,5 @@
 // Device primitives shared by the kernels of this library (included from common.h): the LDS-DMA instruction, counted waits, the weight-image ring
-// of the register-resident chains, LayerNorm and regrouping on MFMA fragments, the swizzled 32 x 128-byte image, block reductions, Philox.  One definition
+// of the register-resident chains, LayerNorm and regrouping on MFMA fragments, the swizzled 32 x 128-byte image, block reductions and scans, Philox.  One definition
 // of each: an invariant found in one kernel is kept for all of them here.
 #pragma once
 
@@ -242,6 +242,72 @@ __device__ __forceinline__ T block_reduce(T v, Op op, T* scratch /* [waves] */) 
     T r = scratch[0];
     for (int w = 1; w < (WAVES > 0 ? WAVES : (int)(blockDim.x >> 6)); ++w) r = op(r, scratch[w]);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------ block scans
+// Running sums of one value per thread over a workgroup of 64 WAVES threads, in thread order; wsum: WAVES values of LDS.  Two forms: their
+// barriers and their costs differ, and a caller relies on the one it has.
+//
+// Inclusive; total = the sum.  Wave 0 scans the wave sums.  Two barriers inside; the caller puts one more between the last use of `total` and
+// the next call.  A fixed tree: the lanes of a wave, then the waves, then (sum within this wave) + (wave sums before it).
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_scan_incl(T v, T* wsum, T& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    if (wave == 0) {
+        T t = lane < WAVES ? wsum[lane] : T(0);
+#pragma unroll
+        for (int o = 1; o < WAVES; o <<= 1) {
+            const T y = __shfl_up(t, o);
+            if (lane >= o) t += y;
+        }
+        if (lane < WAVES) wsum[lane] = t;
+    }
+    __syncthreads();
+    total = wsum[WAVES - 1];
+    return x + (wave ? wsum[wave - 1] : T(0));
+}
+
+// Exclusive; *total (if given) = the sum.  A barrier in front and every thread adds the wave sums itself: safe to call back to back.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_scan_excl(T v, T* wsum, T* total = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    __syncthreads();
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const T s = wsum[w];
+        if (w < wave) before += s;
+        all += s;
+    }
+    if (total) *total = all;
+    return before + incl - v;
+}
+
+// the least l in [0, last] with c[l] > target, `last` if there is none: the owner of `target` in the non-decreasing running sums c
+template <typename T>
+__device__ __forceinline__ int first_above(const T* c, int last, T target) {
+    int l = 0, h = last;
+    while (l < h) {
+        const int m = (l + h) >> 1;
+        if (c[m] > target) h = m; else l = m + 1;
+    }
+    return l;
 }
 
 // the count of ragged cloud p, clamped to its padded rows

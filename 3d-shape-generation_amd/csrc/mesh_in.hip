@@ -97,32 +97,6 @@ __device__ __forceinline__ int min_column_event(const MinTri& q, float x, float 
     return nz > 0.f ? 1 : -1;
 }
 
-// inclusive scan of one int per thread over the workgroup; wsum: MIN_WAVES ints of LDS.  Two barriers inside; the caller puts one more between the
-// last use of `total` and the next call.
-__device__ __forceinline__ int min_block_scan(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int t = lane < MIN_WAVES ? wsum[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < MIN_WAVES; o <<= 1) {
-            const int y = __shfl_up(t, o);
-            if (lane >= o) t += y;
-        }
-        if (lane < MIN_WAVES) wsum[lane] = t;
-    }
-    __syncthreads();
-    total = wsum[MIN_WAVES - 1];
-    return x + (wave ? wsum[wave - 1] : 0);
-}
-
 static inline size_t min_bit_words(int r) { return ((size_t)r * r * r + 31) / 32; }
 static inline size_t min_acc_bytes(int r) { return align_up((size_t)r * r * r * sizeof(int32_t) + min_bit_words(r) * sizeof(uint32_t)); }
 
@@ -135,11 +109,11 @@ __global__ __launch_bounds__(MIN_THREADS) void mesh_voxelize_kernel(const float*
     __shared__ int prefix[MIN_THREADS];
     __shared__ int wsum[MIN_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t v0 = offsets[b * 2], f0 = offsets[b * 2 + 1];
-    const int64_t nv = offsets[b * 2 + 2] - v0, nf64 = offsets[b * 2 + 3] - f0;
-    const int nf = nv > 0 && nf64 > 0 && nf64 <= 0x7fffffff ? (int)nf64 : 0;
-    const float* v = vertices + v0 * 3;
-    const int32_t* f = faces + f0 * 3;
+    const MeshRows m = mesh_rows(offsets, b);
+    const int64_t nv = m.nv;
+    const int nf = nv > 0 && m.nf > 0 && m.nf <= 0x7fffffff ? (int)m.nf : 0;
+    const float* v = vertices + m.v0 * 3;
+    const int32_t* f = faces + m.f0 * 3;
     const int n3 = r * r * r, nw = (n3 + 31) >> 5;
     int* ev;
     unsigned* bits;
@@ -165,14 +139,10 @@ __global__ __launch_bounds__(MIN_THREADS) void mesh_voxelize_kernel(const float*
             }
         }
         int total;
-        prefix[tid] = min_block_scan(mine, wsum, total);
+        prefix[tid] = block_scan_incl<MIN_WAVES>(mine, wsum, total);
         __syncthreads();
         for (int item = tid; item < total; item += MIN_THREADS) {
-            int l = 0, h = MIN_THREADS - 1;                                   // the first triangle whose inclusive sum exceeds the item
-            while (l < h) {
-                const int m = (l + h) >> 1;
-                if (prefix[m] > item) h = m; else l = m + 1;
-            }
+            const int l = first_above(prefix, MIN_THREADS - 1, item);         // the first triangle whose inclusive sum exceeds the item
             const MinTri q = min_load_tri(v, f, c0 + l, nv, lo, ip);          // l has items, so c0 + l < nf and q.ok
             int x0, xn, y0, yn, z0, zn;
             min_axis_range(q.ax, q.bx, q.cx, r, x0, xn);
@@ -223,7 +193,9 @@ __device__ __forceinline__ float min_tri_area(const float* __restrict__ v, const
     return a == a && a <= 3.0e38f ? a : 0.f;                                  // a face with a non-finite area is never drawn
 }
 
-// cdf[f0 + i] = area_0 + ... + area_i of mesh b, added in a fixed tree: lanes of a wave, the 16 waves, then the chunks of 1024 in order
+// cdf[f0 + i] = area_0 + ... + area_i of mesh b, added in a fixed tree: lanes of a wave, the 16 waves, then the chunks of 1024 in order.  The
+// scan is block_scan_incl<MIN_WAVES, float> of device_prims.h written out: through the template the same 304 instructions come out in another
+// order, and the launch measured 0.4 us slower than the parent's (profiles/mesh_family_isa.md).
 __global__ __launch_bounds__(MIN_THREADS) void mesh_area_scan_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                                       const int64_t* __restrict__ offsets, float* __restrict__ cdf) {
     __shared__ float wsum[MIN_WAVES];
@@ -268,8 +240,8 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float* __restric
     const int b = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_points) return;
-    const int64_t v0 = offsets[b * 2], f0 = offsets[b * 2 + 1];
-    const int64_t nv = offsets[b * 2 + 2] - v0, nf64 = offsets[b * 2 + 3] - f0;
+    const MeshRows mr = mesh_rows(offsets, b);
+    const int64_t v0 = mr.v0, f0 = mr.f0, nv = mr.nv, nf64 = mr.nf;
     const int64_t row = (int64_t)b * n_points + i;
     float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
     int face = 0;
@@ -292,8 +264,8 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float* __restric
         float s = 0.f, t = 0.f;                                                // total area 0: the first vertex of the first face
         if (total > 0.f) {
             const float target = u0 * total;
-            int l = 0, h = nf - 1;                                             // the first face whose running sum exceeds the target (the last at most)
-            while (l < h) {
+            int l = 0, h = nf - 1;                                             // the first face whose running sum exceeds the target (the last at most);
+            while (l < h) {                                                    // first_above written out, as in mesh_data.hip, which draws the same bits
                 const int m = (l + h) >> 1;
                 if (c[m] > target) h = m; else l = m + 1;
             }

@@ -8,6 +8,48 @@ namespace pcd {
 
 #pragma clang fp contract(off)
 
+// ---------------------------------------------------------------------------------------------------------------- device scan
+// out[i] = in[0] + ... + in[i - 1] for i < n, three launches: chunks of MO_WG, the chunk sums, the add.
+__global__ __launch_bounds__(MO_WG) void mo_scan_chunks_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t n,
+                                                               int32_t* __restrict__ partial) {
+    __shared__ int wsum[MO_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * MO_WG + threadIdx.x;
+    const int x = i < n ? in[i] : 0;
+    int total;
+    const int e = block_scan_excl<MO_WAVES>(x, wsum, &total);
+    if (i < n) out[i] = e;
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(MO_WG) void mo_scan_partials_kernel(int32_t* __restrict__ partial, int chunks) {
+    __shared__ int wsum[MO_WAVES];
+    int base = 0;
+    for (int c0 = 0; c0 < chunks; c0 += MO_WG) {
+        const int i = c0 + threadIdx.x;
+        const int x = i < chunks ? partial[i] : 0;
+        int total;
+        const int e = block_scan_excl<MO_WAVES>(x, wsum, &total);
+        if (i < chunks) partial[i] = base + e;
+        base += total;
+    }
+}
+
+__global__ __launch_bounds__(MO_WG) void mo_scan_add_kernel(int32_t* __restrict__ out, int64_t n, const int32_t* __restrict__ partial) {
+    const int64_t i = (int64_t)blockIdx.x * MO_WG + threadIdx.x;
+    if (i < n) out[i] += partial[blockIdx.x];
+}
+
+int mo_scan(const int32_t* in, int32_t* out, int64_t n, int32_t* partial, hipStream_t stream) {
+    const int chunks = (int)ceil_div(n, MO_WG);
+    hipLaunchKernelGGL(mo_scan_chunks_kernel, dim3(chunks), dim3(MO_WG), 0, stream, in, out, n, partial);
+    PCD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mo_scan_partials_kernel, dim3(1), dim3(MO_WG), 0, stream, partial, chunks);
+    PCD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mo_scan_add_kernel, dim3(chunks), dim3(MO_WG), 0, stream, out, n, partial);
+    PCD_CHECK_LAUNCH();
+    return PCD_OK;
+}
+
 namespace {
 
 constexpr int MO_FLAG_REFERENCED = 1, MO_FLAG_BOUNDARY = 2, MO_FLAG_IRREGULAR = 4;
@@ -314,7 +356,7 @@ __global__ __launch_bounds__(MO_WG) void mo_compact_count_kernel(const int32_t* 
         const int v = c0 + threadIdx.x;
         const int k = v < m.nv && keep[m.v0 + v] != 0;
         int total;
-        const int e = mo_block_scan(k, wsum, total);
+        const int e = block_scan_excl<MO_WAVES>(k, wsum, &total);
         if (v < m.nv) remap[m.v0 + v] = k ? base + e : -1;
         base += total;
     }
@@ -325,7 +367,7 @@ __global__ __launch_bounds__(MO_WG) void mo_compact_count_kernel(const int32_t* 
         const int t = c0 + threadIdx.x;
         int a, b, c, total;
         const int k = t < m.nf && mo_face_kept(fc, t, m.nv, remap + m.v0, a, b, c);
-        mo_block_scan(k, wsum, total);
+        block_scan_excl<MO_WAVES>(k, wsum, &total);
         nf += total;
     }
     if (threadIdx.x == 0) {
@@ -353,7 +395,7 @@ __global__ __launch_bounds__(MO_WG) void mo_compact_emit_kernel(const float* __r
         const int t = c0 + threadIdx.x;
         int a = 0, b = 0, c = 0, total;
         const int k = t < m.nf && mo_face_kept(fc, t, m.nv, remap + m.v0, a, b, c);
-        const int e = mo_block_scan(k, wsum, total);
+        const int e = block_scan_excl<MO_WAVES>(k, wsum, &total);
         if (k) {
             int32_t* o = out_faces + (of + base + e) * 3;
             o[0] = a; o[1] = b; o[2] = c;

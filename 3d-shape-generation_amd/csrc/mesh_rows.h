@@ -1,9 +1,13 @@
-// Packed mesh batches on the device, shared by mesh_ops.hip and mesh_simplify.hip: the rows of a mesh in `offsets`, the valid-face test, the
-// workgroup scan and the three-launch device scan.  Everything sits in the unnamed namespace: each including file gets its own copy.
+// Packed mesh batches on the device, shared by mesh_ops.hip and mesh_simplify.hip: the rows of a mesh in `offsets` clamped to int, the
+// valid-face test and the three-launch device scan (defined once, in mesh_ops.hip).  The rest sits in the unnamed namespace: each including
+// file gets its own copy.  The workgroup scan is device_prims.h's block_scan_excl<MO_WAVES>.
 #pragma once
-#include "common.h"
+#include "mesh_tri.h"
 
 namespace pcd {
+
+// out[i] = in[0] + ... + in[i - 1] for i < n, three launches: chunks of 1024, the chunk sums, the add.  partial: ceil(n / 1024) ints.
+int mo_scan(const int32_t* in, int32_t* out, int64_t n, int32_t* partial, hipStream_t stream);
 
 #pragma clang fp contract(off)
 
@@ -19,12 +23,12 @@ struct MoMesh {
 };
 
 __device__ __forceinline__ MoMesh mo_mesh(const int64_t* __restrict__ offsets, int b) {
+    const MeshRows r = mesh_rows(offsets, b);
     MoMesh m;
-    m.v0 = offsets[b * 2];
-    m.f0 = offsets[b * 2 + 1];
-    const int64_t nv = offsets[b * 2 + 2] - m.v0, nf = offsets[b * 2 + 3] - m.f0;
-    m.nv = nv > 0 && nv <= 0x7fffffff ? (int)nv : 0;
-    m.nf = nf > 0 && nf <= 0x7fffffff ? (int)nf : 0;
+    m.v0 = r.v0;
+    m.f0 = r.f0;
+    m.nv = r.nv > 0 && r.nv <= 0x7fffffff ? (int)r.nv : 0;
+    m.nf = r.nf > 0 && r.nf <= 0x7fffffff ? (int)r.nf : 0;
     return m;
 }
 
@@ -44,71 +48,6 @@ __device__ __forceinline__ bool mo_face(const int32_t* __restrict__ f, int t, in
     b = f[(int64_t)t * 3 + 1];
     c = f[(int64_t)t * 3 + 2];
     return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv && a != b && b != c && a != c;
-}
-
-// exclusive running sum of one int per thread over the workgroup's MO_WG threads, in thread order; total = the sum.  Barriers inside.
-__device__ __forceinline__ int mo_block_scan(int x, int* wsum /* [MO_WAVES] */, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < MO_WAVES; ++w) {
-        const int s = wsum[w];
-        if (w < wave) before += s;
-        all += s;
-    }
-    total = all;
-    return before + incl - x;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- device scan
-// out[i] = in[0] + ... + in[i - 1] for i < n, three launches: chunks of MO_WG, the chunk sums, the add.
-__global__ __launch_bounds__(MO_WG) void mo_scan_chunks_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t n,
-                                                               int32_t* __restrict__ partial) {
-    __shared__ int wsum[MO_WAVES];
-    const int64_t i = (int64_t)blockIdx.x * MO_WG + threadIdx.x;
-    const int x = i < n ? in[i] : 0;
-    int total;
-    const int e = mo_block_scan(x, wsum, total);
-    if (i < n) out[i] = e;
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(MO_WG) void mo_scan_partials_kernel(int32_t* __restrict__ partial, int chunks) {
-    __shared__ int wsum[MO_WAVES];
-    int base = 0;
-    for (int c0 = 0; c0 < chunks; c0 += MO_WG) {
-        const int i = c0 + threadIdx.x;
-        const int x = i < chunks ? partial[i] : 0;
-        int total;
-        const int e = mo_block_scan(x, wsum, total);
-        if (i < chunks) partial[i] = base + e;
-        base += total;
-    }
-}
-
-__global__ __launch_bounds__(MO_WG) void mo_scan_add_kernel(int32_t* __restrict__ out, int64_t n, const int32_t* __restrict__ partial) {
-    const int64_t i = (int64_t)blockIdx.x * MO_WG + threadIdx.x;
-    if (i < n) out[i] += partial[blockIdx.x];
-}
-
-int mo_scan(const int32_t* in, int32_t* out, int64_t n, int32_t* partial, hipStream_t stream) {
-    const int chunks = (int)ceil_div(n, MO_WG);
-    hipLaunchKernelGGL(mo_scan_chunks_kernel, dim3(chunks), dim3(MO_WG), 0, stream, in, out, n, partial);
-    PCD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mo_scan_partials_kernel, dim3(1), dim3(MO_WG), 0, stream, partial, chunks);
-    PCD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mo_scan_add_kernel, dim3(chunks), dim3(MO_WG), 0, stream, out, n, partial);
-    PCD_CHECK_LAUNCH();
-    return PCD_OK;
 }
 
 bool mo_sizes_ok(int batch, int64_t total_vertices, int64_t total_faces) {

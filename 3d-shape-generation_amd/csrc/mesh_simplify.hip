@@ -290,7 +290,7 @@ __global__ __launch_bounds__(MO_WG) void ms_count_kernel(const int64_t* __restri
             if (k && dedup) k = dmin[m.f0 * 2 + fslot[m.f0 + t]] == (uint32_t)t;
             keepf[m.f0 + t] = k;
         }
-        mo_block_scan(k, wsum, total);
+        block_scan_excl<MO_WAVES>(k, wsum, &total);
         nf += total;
     }
     if (threadIdx.x == 0) {
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(MO_WG) void ms_emit_faces_kernel(const int32_t* __r
         const int t = f0 + threadIdx.x;
         int a = 0, b = 0, c = 0, total;
         const int k = t < m.nf && keepf[m.f0 + t] != 0 && mo_face(fc, t, m.nv, a, b, c);
-        const int e = mo_block_scan(k, wsum, total);
+        const int e = block_scan_excl<MO_WAVES>(k, wsum, &total);
         if (k) {
             int32_t* o = out_faces + (of + base + e) * 3;
             o[0] = cscan[m.v0 + root[m.v0 + a]] - c0;

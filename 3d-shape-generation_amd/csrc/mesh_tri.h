@@ -1,8 +1,23 @@
-// Triangles of a packed mesh batch, shared by the mesh kernels (mesh_in.hip: voxelizer and sampler; mesh_data.hip: the resident mesh dataset).
+// Packed mesh batches, shared by the mesh kernels (mesh_in.hip, mesh_data.hip, render.hip, and mesh_rows.h for mesh_ops.hip and
+// mesh_simplify.hip): the rows of a mesh in `offsets` and its triangles.
 #pragma once
 #include "common.h"
 
 namespace pcd {
+
+// mesh b of a packed batch as offsets[b * 2 .. b * 2 + 3] give it: first vertex row, first face row and the two row counts, unchecked.  What
+// counts as an empty mesh differs from kernel to kernel and stays with the caller.
+struct MeshRows { int64_t v0, f0, nv, nf; };
+
+template <typename Index>                                      // int, or int64_t where b * 2 + 3 may pass 2^31
+__device__ __forceinline__ MeshRows mesh_rows(const int64_t* __restrict__ offsets, Index b) {
+    MeshRows m;
+    m.v0 = offsets[b * 2];
+    m.f0 = offsets[b * 2 + 1];
+    m.nv = offsets[b * 2 + 2] - m.v0;
+    m.nf = offsets[b * 2 + 3] - m.f0;
+    return m;
+}
 
 #pragma clang fp contract(off)
 struct MinTri {

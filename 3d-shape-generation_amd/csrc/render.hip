@@ -11,7 +11,7 @@
 // Coverage, depth and shading are functions of (primitive, pixel) alone, fp32 without contraction and without a division in any coverage
 // decision: the same bits for either tile shape, for a shape alone or in a batch, and -- where every intermediate value is exactly
 // representable -- the decisions of the float64 statement (tests/render_statement.py).
-#include "common.h"
+#include "mesh_tri.h"
 #include <cmath>
 
 namespace pcd {
@@ -148,32 +148,6 @@ __device__ __forceinline__ void ren_tri_box(const RenTri& q, int tx0, int tx1, i
     if (xn <= 0 || yn <= 0) xn = yn = 0;
 }
 
-// inclusive scan of one int per thread over the workgroup (the scan of mesh_in.hip); wsum: REN_WAVES ints of LDS.  Two barriers inside; the
-// caller puts one more between the last use of `total` and the next call.
-__device__ __forceinline__ int ren_block_scan(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int t = lane < REN_WAVES ? wsum[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < REN_WAVES; o <<= 1) {
-            const int y = __shfl_up(t, o);
-            if (lane >= o) t += y;
-        }
-        if (lane < REN_WAVES) wsum[lane] = t;
-    }
-    __syncthreads();
-    total = wsum[REN_WAVES - 1];
-    return x + (wave ? wsum[wave - 1] : 0);
-}
-
 template <bool MESH, int TH>
 __global__ __launch_bounds__(REN_THREADS) void render_kernel(const RenArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long ren_keys[];   // [TH][REN_TW]
@@ -194,12 +168,11 @@ __global__ __launch_bounds__(REN_THREADS) void render_kernel(const RenArgs a) {
     int64_t nv;
     int np;                                                    // primitives of this shape
     if (MESH) {
-        const int64_t v0 = a.offsets[b * 2], f0 = a.offsets[b * 2 + 1];
-        const int64_t nf64 = a.offsets[b * 2 + 3] - f0;
-        nv = a.offsets[b * 2 + 2] - v0;
-        np = nv > 0 && nf64 > 0 && nf64 <= 0x7fffffff ? (int)nf64 : 0;
-        pv = a.prims + v0 * 3;
-        f = a.faces + f0 * 3;
+        const MeshRows m = mesh_rows(a.offsets, b);
+        nv = m.nv;
+        np = nv > 0 && m.nf > 0 && m.nf <= 0x7fffffff ? (int)m.nf : 0;
+        pv = a.prims + m.v0 * 3;
+        f = a.faces + m.f0 * 3;
     } else {
         const int64_t p0 = a.offsets[b];
         nv = a.offsets[b + 1] - p0;
@@ -220,14 +193,10 @@ __global__ __launch_bounds__(REN_THREADS) void render_kernel(const RenArgs a) {
             mine = yn;
         }
         int total;
-        prefix[tid] = ren_block_scan(mine, wsum, total);
+        prefix[tid] = block_scan_incl<REN_WAVES>(mine, wsum, total);
         __syncthreads();
         for (int item = tid; item < total; item += REN_THREADS) {
-            int l = 0, h = REN_THREADS - 1;                                       // the first primitive whose inclusive sum exceeds the item
-            while (l < h) {
-                const int m = (l + h) >> 1;
-                if (prefix[m] > item) h = m; else l = m + 1;
-            }
+            const int l = first_above(prefix, REN_THREADS - 1, item);             // the first primitive whose inclusive sum exceeds the item
             const int local = item - (l ? prefix[l - 1] : 0);
             const unsigned index = (unsigned)(c0 + l);                            // l has items, so c0 + l < np and the primitive is ok
             int x0, xn, y0, yn;

@@ -72,6 +72,29 @@ def test_lattice_meshes_equal_the_statement_voxel_for_voxel(lattice_reference, f
     assert int(lattice_reference[5]["surface"].sum()) > 100
 
 
+def chunked_lattice_mesh():
+    """1025 small triangles on the lattice of halves: one more than a chunk of 1024.  The first 1024 stay below index 6; the last one lies alone
+    at z = 6.5 over the nodes (6, 6), so surface and interior both change if the chunk that holds only this triangle is lost."""
+    g = np.random.default_rng(7)
+    v = g.integers(0, 10, size=(1024, 1, 3)) / 2.0 + g.integers(-1, 3, size=(1024, 3, 3)) / 2.0
+    v = np.concatenate([v, np.asarray([[(5.5, 5.5, 6.5), (7.0, 5.5, 6.5), (5.5, 7.0, 6.5)]])]).reshape(-1, 3)
+    return v, np.arange(3 * 1025, dtype=np.int32).reshape(-1, 3)
+
+
+def test_a_lattice_mesh_of_1025_triangles_equals_the_statement():
+    v, f = chunked_lattice_mesh()
+    assert np.array_equal(np.round(v * 2.0), v * 2.0) and v.min() >= -1.0 and v.max() <= 8.0
+    want = {"surface": S.voxelize_surface_vec(v, f, 8)[0], "interior": S.voxelize_interior_vec(v, f, 8)[0]}
+    want["solid"] = want["surface"] | want["interior"]
+    assert v[:-3].max() <= 5.5 and np.argwhere(want["surface"]).max() == 7         # index 7 is reached by the last triangle alone
+    assert (want["interior"] != S.voxelize_interior_vec(v, f[:1024], 8)[0]).sum() >= 4
+    for fill in FILLS:
+        got = voxelize([(v, f)], 8, fill, bounds=(0.0, 7.0))[0]
+        print(f"{fill}: device {int(got.sum())} statement {int(want[fill].sum())} differ {int((got != want[fill]).sum())}")
+        assert np.array_equal(got, want[fill]), (fill, np.argwhere(got != want[fill])[:8].tolist())
+    assert 0 < int(want["solid"].sum()) < 512
+
+
 # ------------------------------------------------------------------ 2. round trip with the surface-nets kernel
 def r5_grids():
     """Small shapes in 5^3 whose meshes have at most 256 faces (the sampler's inputs too)."""

@@ -188,6 +188,16 @@ def test_general_position_against_the_statement(general_reference, name):
     compare(gpu_case(case, view), want, want32, name)
 
 
+def test_a_mesh_of_1025_triangles_against_the_statement():
+    """One more triangle than a chunk of 1024: the last chunk holds triangle 1024 alone, and the statement sees it (the seed was chosen for that
+    from the statement alone).  Margins and tolerances as for the other general-position cases."""
+    case = ("mesh", S.random_triangles(1025, 29, 0.12), 48, 64, None)
+    view = views_of(48, 64)[0][0]
+    want, want32 = S.render_case(case, view.numpy()), S.render_case(case, view.numpy(), dtype=np.float32)
+    assert (S.comparable(want, MARGIN)[0] & (want["ids"] == 1024)).sum() >= 5
+    compare(gpu_case(case, view), want, want32, "tri1025")
+
+
 @pytest.mark.parametrize("own_views", [False, True])
 def test_ragged_batch_and_several_views(own_views):
     meshes, clouds, radius = S.ragged_batch()
