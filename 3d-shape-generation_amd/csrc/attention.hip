@@ -12,6 +12,7 @@
 // the hardware transpose read ds_read_b64_tr_b16, so there is no transpose pass and no workspace.
 #include <type_traits>
 #include "common.h"
+#include "layernorm_rows.h"
 
 namespace pcd {
 
@@ -38,47 +39,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
     for (int i = lane; i < c; i += 64) orow[i] = to_half_sat(((float)xr[i] - mean) * rstd * gamma[i] + beta[i]);
 }
 
-// C = 8 * LPR (64 / 128 / 256, the widths of the attention U-Net): a row is LPR lanes x 16 bytes, read once and kept in
-// registers through both statistics passes and the output (the kernel above reads every element three times, two bytes
-// per lane and access: 3x off the HBM time of this purely bandwidth-bound step); 64 / LPR rows per wave.
-template <int LPR>
-__global__ __launch_bounds__(256) void layernorm_vec_kernel(const half_t* __restrict__ x, int64_t rows,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             half_t* __restrict__ out) {
-    constexpr int C = LPR * 8, RPW = 64 / LPR;
-    const int lane = threadIdx.x & 63, l = lane % LPR;
-    const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    const int64_t rr = row < rows ? row : rows - 1;                    // whole groups stay active for the shuffles
-    const half8 v = *(const half8*)(x + rr * C + l * 8);
-    float f[8];
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { f[e] = (float)v[e]; s += f[e]; }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] -= mean;
-    float q = f[1] * f[1];                           // f1^2 rounded, the others fused: the form `q += f[e] * f[e]` had been contracted to
-    q = __builtin_fmaf(f[0], f[0], q);
-#pragma unroll
-    for (int e = 2; e < 8; ++e) q = __builtin_fmaf(f[e], f[e], q);
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + 1e-5f);
-    const f32x4 g0 = *(const f32x4*)(gamma + l * 8), g1 = *(const f32x4*)(gamma + l * 8 + 4);
-    const f32x4 b0 = *(const f32x4*)(beta + l * 8), b1 = *(const f32x4*)(beta + l * 8 + 4);
-    half8 o8;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        o8[e] = to_half_sat(__builtin_fmaf(f[e] * rstd, g0[e], b0[e]));
-        o8[4 + e] = to_half_sat(__builtin_fmaf(f[4 + e] * rstd, g1[e], b1[e]));
-    }
-    if (row < rows) *(half8*)(out + row * C + l * 8) = o8;
-}
+// C = 64 / 128 / 256, the widths of the attention U-Net, take layernorm_rows_kernel<C / 8, false> of layernorm_rows.h instead
 
 // ------------------------------------------------------------ flash attention
-// block = 4 waves, each wave owns QT x 32 queries of one (shape, head); K [64][D] and Vt [D][64]
+// block = 4 waves, each wave owns 32 (generic kernel) or 2 x 32 (pipelined kernels) queries of one (shape, head); K [64][D] and Vt [D][64]
 // tiles arrive by LDS-DMA (global_load_lds 16 B/lane) into a 2-deep ring, XOR-swizzled through the
 // source address so the ds_read_b128 fragment reads are bank-conflict free.
 constexpr int KT = 64;              // keys per K/V tile (128 measured neutral: fewer barriers, but 2 workgroups/CU)
@@ -135,9 +99,101 @@ __device__ __forceinline__ void stage_tile(const half_t* __restrict__ src, int64
     }
 }
 
-template <int D, int QT>
-__global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __restrict__ qkv, int n, int c, int heads,
-                                                             float scale_log2e, half_t* __restrict__ out) {
+// ------------------------------------------------------------ pieces every kernel of the family is built from
+#define SP_SB() __builtin_amdgcn_sched_barrier(0)
+#define SP_MF(a, b, cacc) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, cacc, 0, 0, 0)
+constexpr unsigned SP_BIG_BITS = 0x70007000u;          // both halves hold the same fp16 sum T: T > 8192 (0x7000), inf, NaN
+
+__device__ __forceinline__ half2_ sp_pk(float a, float b) { half2_ r; r.x = (half_t)a; r.y = (half_t)b; return r; }
+
+// row max of a 32 x 32 score tile (7 v_max3 + one half-wave exchange)
+__device__ __forceinline__ float sp_rowmax(const f32x16& s) {
+    float mx = max3(s[0], s[1], s[2]);
+#pragma unroll
+    for (int r = 3; r < 15; r += 2) mx = max3(mx, s[r], s[r + 1]);
+    return xhalf_max(fmaxf(mx, s[15]));
+}
+
+// lane-partial row sum of the fp16 P of one tile, both halves of the result hold the total
+__device__ __forceinline__ half2_ sp_tile_sum(const half8& p0, const half8& p1) {
+    const half8 a = p0 + p1;
+    const half4 b4 = a.lo + a.hi;
+    const half2_ c2 = b4.lo + b4.hi;
+    return c2 + c2.yx;
+}
+
+// Q fragments (B operand) of one 32-query block from its row qp: lane (query qr, half hh) holds Q[query][16*s + 8*hh + j],
+// pre-scaled by log2(e)/sqrt(d) (one fp16 rounding) so the MFMA output is already in the exp2 domain
+template <int KSTEPS>
+__device__ __forceinline__ void attn_load_q(const half_t* qp, int hh, float scale_log2e, half8 (&qf)[KSTEPS]) {
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) {
+        const half8 raw = *(const half8*)(qp + 16 * s + 8 * hh);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[s][e] = (half_t)((float)raw[e] * scale_log2e);
+    }
+}
+
+// the same for the two blocks A and B of a wave of the pipelined kernels, load by load
+template <int KSTEPS>
+__device__ __forceinline__ void attn_load_q2(const half_t* qpA, const half_t* qpB, int hh, float scale_log2e, half8 (&qA)[KSTEPS],
+                                             half8 (&qB)[KSTEPS]) {
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) {
+        const half8 ra = *(const half8*)(qpA + 16 * s + 8 * hh), rb = *(const half8*)(qpB + 16 * s + 8 * hh);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            qA[s][e] = (half_t)((float)ra[e] * scale_log2e);
+            qB[s][e] = (half_t)((float)rb[e] * scale_log2e);
+        }
+    }
+}
+
+// one LDS-DMA instruction (1 KiB per wave): wave-uniform source base and LDS address (through m0), lane-constant 32-bit offset
+__device__ __forceinline__ void sp_dma(const char* sbase, unsigned voff, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr)
+                 : "memory", "m0");
+}
+
+// Tail of a phase of the pipelined kernels (c0 .. c7: the tile's fp16 P in pairs, b1: the sum tree so far).  On gfx950 a
+// packed (VOP3P) result needs one wait state before any VALU reads it, so the compiler puts an s_nop behind each of the three
+// dependent v_pk_add_f16 of this tail.  Written out by hand, the OTHER block's pending row sum (its tile was checked a phase
+// ago) is folded into its fp32 l in those slots instead:
+//   a3 = c3 + c7 | lo = f32(t_other) | t = b1 + a3 | l_other += lo | tt = t + swap(t)   (the compiler adds the one
+//   wait state between the asm block and its own compare of tt)
+// Packs P into the two MFMA operands and returns the tile's lane-partial row sum (fp16, in both halves).
+__device__ __forceinline__ half2_ sp_phase_tail(half2_ c0, half2_ c1, half2_ c2, half2_ c3, half2_ c4, half2_ c5, half2_ c6,
+                                                half2_ c7, half2_ b1, half2_ t_other, float& l_other, half8& p0, half8& p1) {
+    half2_ a3, t, tt;
+    float lo;
+    asm volatile("v_pk_add_f16 %0, %5, %6\n\t"
+                 "v_cvt_f32_f16_e32 %3, %8\n\t"
+                 "v_pk_add_f16 %1, %7, %0\n\t"
+                 "v_add_f32_e32 %4, %4, %3\n\t"
+                 "v_pk_add_f16 %2, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]"
+                 : "=&v"(a3), "=&v"(t), "=&v"(tt), "=&v"(lo), "+v"(l_other)
+                 : "v"(c3), "v"(c7), "v"(b1), "v"(t_other));
+    p0 = __builtin_shufflevector(__builtin_shufflevector(c0, c1, 0, 1, 2, 3), __builtin_shufflevector(c2, c3, 0, 1, 2, 3),
+                                 0, 1, 2, 3, 4, 5, 6, 7);
+    p1 = __builtin_shufflevector(__builtin_shufflevector(c4, c5, 0, 1, 2, 3), __builtin_shufflevector(c6, c7, 0, 1, 2, 3),
+                                 0, 1, 2, 3, 4, 5, 6, 7);
+    return tt;
+}
+
+// ------------------------------------------------------------ generic kernel (d = 16 / 32 / 64, any n)
+// One 32-query block per wave, 2-deep K/V ring, masked last tile.  The frame is written once; the softmax between the score
+// MFMAs and the PV MFMAs comes in two forms:
+//   RunningMax  the round-1 form, a running row max with a deferred rescale: the tests' comparator and pcd_set_attention_config(1)
+//   MaxFree     the softmax of set_attention_sp_kernel: every shape the pipelined kernels do not take
+enum class AttnSoftmax { RunningMax, MaxFree };
+
+__device__ __forceinline__ float lane_row_sum(float l) { return l; }
+__device__ __forceinline__ float lane_row_sum(f32x2 l) { return l[0] + l[1]; }
+
+template <int D, AttnSoftmax SOFTMAX>
+__global__ __launch_bounds__(256, SOFTMAX == AttnSoftmax::MaxFree ? 2 : 1) void set_attention_generic_kernel(
+    const half_t* __restrict__ qkv, int n, int c, int heads, float scale_log2e, half_t* __restrict__ out) {
+    constexpr bool MAX_FREE = SOFTMAX == AttnSoftmax::MaxFree;
     constexpr int DP = (D < 32) ? 32 : D;        // O^T rows padded to the 32-row MFMA tile
     constexpr int KSTEPS = D / 16;               // MFMA k-steps of the S^T product
     constexpr int OT = DP / 32;                  // 32-row O^T tiles
@@ -150,41 +206,28 @@ __global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __rest
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qr = lane & 31, hh = lane >> 5;
     const int bh = blockIdx.y, b = bh / heads, head = bh - b * heads;
-    const int q0 = blockIdx.x * (128 * QT) + wave * (32 * QT);
+    const int q0 = blockIdx.x * 128 + wave * 32;
     const int64_t row_base = (int64_t)b * n;
     const int ld = 3 * c;
 
-    // Q fragments (B operand): lane (query qr, half hh) holds Q[query][16*s + 8*hh + j]
-    half8 qf[QT][KSTEPS];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        int qi = q0 + t * 32 + qr;
-        qi = qi < n ? qi : n - 1;
-        const half_t* qp = qkv + (row_base + qi) * ld + head * D;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            // pre-scaled by log2(e)/sqrt(d) (one fp16 rounding) so the MFMA output is already in the exp2 domain
-            const half8 raw = *(const half8*)(qp + 16 * s + 8 * hh);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[t][s][e] = (half_t)((float)raw[e] * scale_log2e);
-        }
+    half8 qf[KSTEPS];
+    {
+        int qi = q0 + qr;
+        qi = qi < n ? qi : n - 1;                // rows past n compute a copy of the last one and store nothing
+        attn_load_q(qkv + (row_base + qi) * ld + head * D, hh, scale_log2e, qf);
     }
-
-    // negm[t]: 16 registers all holding -m (running row max of query qr, exp2 domain).  It is the C input of
-    // the first S^T MFMA of every tile (D != C), so the accumulator comes out as s*c - m with no VALU work.
-    f32x16 oacc[QT][OT], negm[QT];
-    f32x2 l_acc[QT];
+    // negm: 16 registers all holding -m (running row max of query qr, exp2 domain).  It is the C input of the first S^T MFMA
+    // of every tile (D != C), so the accumulator comes out as s*c - m with no VALU work.  (For d <= 32 the compiler rebuilds it
+    // with 15 v_mov per tile; carrying -m through an extra MFMA k-step instead -- constant K fragment [1, 1, 0..], Q fragment
+    // [-m_hi, -m_lo, 0..] -- removes the moves and measured SLOWER: 696 v. 734 TFLOP/s at d = 32, 388 v. 410 at d = 16.)
+    f32x16 oacc[OT], negm;
+    std::conditional_t<MAX_FREE, float, f32x2> l = {};       // lane-partial row sum (RunningMax: two at a time, v_pk_add_f32)
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        l_acc[t] = (f32x2){0.f, 0.f};
+    for (int r = 0; r < 16; ++r) negm[r] = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) negm[t][r] = 0.f;
+    for (int o = 0; o < OT; ++o)
 #pragma unroll
-        for (int o = 0; o < OT; ++o)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[t][o][r] = 0.f;
-    }
-
+        for (int r = 0; r < 16; ++r) oacc[o][r] = 0.f;
     if (tid < 16) *(float*)(smem + ZERO_OFF + tid * 4) = 0.f;
 
     const half_t* kbase = qkv + row_base * ld + c + head * D;
@@ -242,54 +285,88 @@ __global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __rest
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { vf[s2][o][e] = (half_t)lo[e]; vf[s2][o][4 + e] = (half_t)hi[e]; }
                 }
+            // S'^T tile: 32 keys x 32 queries, already relative to the running max
+            f32x16 sacc = SP_MF(kf[0], qf[0], negm);
 #pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                // S'^T tile: 32 keys x 32 queries, already relative to the running max
-                f32x16 sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0], qf[t][0], negm[t], 0, 0, 0);
+            for (int s = 1; s < KSTEPS; ++s) sacc = SP_MF(kf[s], qf[s], sacc);
+            if constexpr (MASK) {   // register r of lane (qr, hh) is key (r&3) + 8*(r>>2) + 4*hh of this sub-tile
 #pragma unroll
-                for (int s = 1; s < KSTEPS; ++s)
-                    sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[s], qf[t][s], sacc, 0, 0, 0);
-                if constexpr (MASK) {   // register r of lane (qr, hh) is key (r&3) + 8*(r>>2) + 4*hh of this sub-tile
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = kt * KT + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                        if (key >= n) sacc[r] = -INFINITY;
-                    }
+                for (int r = 0; r < 16; ++r) {
+                    const int key = kt * KT + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    if (key >= n) sacc[r] = -INFINITY;
                 }
-                // row max of s' (7 v_max3 + one half-wave exchange)
-                float mx = max3(sacc[0], sacc[1], sacc[2]);
+            }
+            const bool first = (kt == 0) && (sub == 0);
+            half8 p0, p1;                        // P^T of this tile, the B operands of the two PV k-steps
+            if constexpr (MAX_FREE) {
+                // The running-max form below spends 66 VALU instructions per 32 x 32 score tile, 50 of them around the 16 v_exp_f32
+                // (row max chain, half-wave exchange, compare, fp32 row sums); at d = 32 / 16 a tile is only 4 / 3 MFMAs (128 / 96
+                // matrix cycles), so it is VALU bound at 25.6 % / 14.2 % of the MFMA peak.  This form: m is fixed exactly by the first
+                // 32 keys (every row then has a P = 1 term); afterwards a tile is exponentiated against the old m, its lane-partial
+                // row sum is formed from the fp16 P by a packed-fp16 tree and only a sum >= 2^13 (or inf) sends the wave down the rare
+                // path (exact maxima, rescale O / l, redo the tile).  Softmax is invariant to m: the same function as the
+                // reference's.  ~36 VALU instructions per tile.  The bound that remains is the exponentials themselves: 16 v_exp_f32
+                // (8 cycles each) + 8 packs + 8 packed adds = ~200 issue cycles per tile and wave against 128 / 96 cycles of MFMA,
+                // i.e. <= ~42 % / ~21 % of the MFMA peak for d = 32 / 16 however the rest is arranged.  Measured (B = 64, N = 2048):
+                // d = 32 734 v. 641 TFLOP/s, d = 16 410 v. 367.
+                if (first) {                     // the first 32 keys fix the running max exactly
+                    const float mx = sp_rowmax(sacc);
 #pragma unroll
-                for (int r = 3; r < 15; r += 2) mx = max3(mx, sacc[r], sacc[r + 1]);
-                mx = xhalf_max(fmaxf(mx, sacc[15]));
-                // Deferred max: move m only when some row's scores exceed it by more than RESCALE_THR (then
-                // P <= 2^THR, exact in fp16's exponent range; row sums and O are fp32).  The very first tile
-                // always sets m to its true row max (which may be negative).
-                const bool first = (kt == 0) && (sub == 0);
-                if (first || __any(mx > RESCALE_THR)) {          // wave-uniform, rare after the first tiles
-                    const float delta = first ? mx : fmaxf(mx, 0.f);
+                    for (int r = 0; r < 16; ++r) { negm[r] = -mx; sacc[r] -= mx; }
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    p0[j] = (half_t)__builtin_amdgcn_exp2f(sacc[j]);
+                    p1[j] = (half_t)__builtin_amdgcn_exp2f(sacc[8 + j]);
+                }
+                half2_ tt = sp_tile_sum(p0, p1);
+                if (__builtin_expect(__any(__builtin_bit_cast(unsigned, tt) > SP_BIG_BITS), 0)) {
+                    // rare: some score is ~9 or more above the running max (or P overflowed fp16): exact maxima, rescale, redo the tile
+                    const float delta = fmaxf(sp_rowmax(sacc), 0.f);
                     const float alpha = __builtin_amdgcn_exp2f(-delta);
-                    l_acc[t] *= (f32x2){alpha, alpha};
+                    l *= alpha;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) { negm[t][r] -= delta; sacc[r] -= delta; }
+                    for (int r = 0; r < 16; ++r) { negm[r] -= delta; sacc[r] -= delta; }
 #pragma unroll
                     for (int o = 0; o < OT; ++o)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) oacc[t][o][r] *= alpha;
+                        for (int r = 0; r < 16; ++r) oacc[o][r] *= alpha;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        p0[j] = (half_t)__builtin_amdgcn_exp2f(sacc[j]);
+                        p1[j] = (half_t)__builtin_amdgcn_exp2f(sacc[8 + j]);
+                    }
+                    tt = sp_tile_sum(p0, p1);
+                }
+                l += (float)tt.x;
+            } else {
+                // Deferred max: move m only when some row's scores exceed it by more than RESCALE_THR (then
+                // P <= 2^THR, exact in fp16's exponent range; row sums and O are fp32).  The very first tile
+                // always sets m to its true row max (which may be negative).
+                const float mx = sp_rowmax(sacc);
+                if (first || __any(mx > RESCALE_THR)) {          // wave-uniform, rare after the first tiles
+                    const float delta = first ? mx : fmaxf(mx, 0.f);
+                    const float alpha = __builtin_amdgcn_exp2f(-delta);
+                    l *= (f32x2){alpha, alpha};
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { negm[r] -= delta; sacc[r] -= delta; }
+#pragma unroll
+                    for (int o = 0; o < OT; ++o)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) oacc[o][r] *= alpha;
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sacc[r] = __builtin_amdgcn_exp2f(sacc[r]);
                 // per-lane partial row sums, two at a time (v_pk_add_f32); halves combined in the epilogue
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) l_acc[t] += (f32x2){sacc[r], sacc[r + 1]};
+                for (int r = 0; r < 16; r += 2) l += (f32x2){sacc[r], sacc[r + 1]};
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    half8 pf;
+                for (int j = 0; j < 8; ++j) { p0[j] = (half_t)sacc[j]; p1[j] = (half_t)sacc[8 + j]; }
+            }
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (half_t)sacc[8 * s2 + j];
-#pragma unroll
-                    for (int o = 0; o < OT; ++o)
-                        oacc[t][o] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s2][o], pf, oacc[t][o], 0, 0, 0);
-                }
+            for (int o = 0; o < OT; ++o) {
+                oacc[o] = SP_MF(vf[0][o], p0, oacc[o]);
+                oacc[o] = SP_MF(vf[1][o], p1, oacc[o]);
             }
         }
     };
@@ -308,35 +385,31 @@ __global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __rest
         tile_body(full_tiles, std::true_type{});
     }
 
-    // epilogue: lane (query qr, half hh) holds O^T rows dd = o*32 + (r&3) + 8*(r>>2) + 4*hh
+    const int qi = q0 + qr;
+    const float l_lane = lane_row_sum(l);
+    const float l_tot = l_lane + __shfl_xor(l_lane, 32);     // the other half of the row sum sits in lane ^ 32
+    if (qi < n) {
+        // lane (query qr, half hh) holds O^T rows dd = o*32 + (r&3) + 8*(r>>2) + 4*hh
+        const float inv = 1.f / l_tot;
+        half_t* orow = out + (row_base + qi) * c + head * D;
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        const int qi = q0 + t * 32 + qr;
-        const float l_half = l_acc[t][0] + l_acc[t][1];
-        const float l_tot = l_half + __shfl_xor(l_half, 32);
-        if (qi < n) {
-            const float inv = 1.f / l_tot;
-            half_t* orow = out + (row_base + qi) * c + head * D;
+        for (int o = 0; o < OT; ++o)
 #pragma unroll
-            for (int o = 0; o < OT; ++o)
+            for (int g = 0; g < 4; ++g) {
+                const int dd = o * 32 + 8 * g + 4 * hh;
+                if (dd < D) {
+                    half4 ov;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int dd = o * 32 + 8 * g + 4 * hh;
-                    if (dd < D) {
-                        half4 ov;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) ov[e] = to_half_sat(oacc[t][o][4 * g + e] * inv);
-                        *(half4*)(orow + dd) = ov;
-                    }
+                    for (int e = 0; e < 4; ++e) ov[e] = to_half_sat(oacc[o][4 * g + e] * inv);
+                    *(half4*)(orow + dd) = ov;
                 }
-        }
+            }
     }
 }
 
 
-
 // ------------------------------------------------------------ software-pipelined kernel (d = 64, n % 256 == 0)
-// The kernel above keeps one 32-query block per wave and leaves the MFMA / softmax overlap to whichever waves share
+// The generic kernel (figures of its running-max form) keeps one 32-query block per wave and leaves the MFMA / softmax overlap to whichever waves share
 // a SIMD; measured, the two add up (583 cycles per 32 x 32 score tile for 256 cycles of MFMA, 66 VALU instructions per
 // tile).  Here a wave owns TWO 32-query blocks A and B and interleaves them by hand, half a step apart:
 //
@@ -356,26 +429,6 @@ __global__ __launch_bounds__(256) void set_attention_kernel(const half_t* __rest
 // per SIMD, which hide each other's LDS / branch / dependency stalls.  K/V tiles (64 keys) arrive by LDS-DMA into a
 // 4-slot ring, two tiles ahead; the tile loop is unrolled by the ring so every LDS address is a lane-constant base
 // plus an immediate: no address arithmetic in the loop.
-#define SP_SB() __builtin_amdgcn_sched_barrier(0)
-#define SP_MF(a, b, cacc) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, cacc, 0, 0, 0)
-constexpr unsigned SP_BIG_BITS = 0x70007000u;          // both halves hold the same fp16 sum T: T > 8192 (0x7000), inf, NaN
-
-__device__ __forceinline__ half2_ sp_pk(float a, float b) { half2_ r; r.x = (half_t)a; r.y = (half_t)b; return r; }
-
-__device__ __forceinline__ float sp_rowmax(const f32x16& s) {
-    float mx = max3(s[0], s[1], s[2]);
-#pragma unroll
-    for (int r = 3; r < 15; r += 2) mx = max3(mx, s[r], s[r + 1]);
-    return xhalf_max(fmaxf(mx, s[15]));
-}
-
-// lane-partial row sum of the fp16 P of one tile, both halves of the result hold the total
-__device__ __forceinline__ half2_ sp_tile_sum(const half8& p0, const half8& p1) {
-    const half8 a = p0 + p1;
-    const half4 b4 = a.lo + a.hi;
-    const half2_ c2 = b4.lo + b4.hi;
-    return c2 + c2.yx;
-}
 
 // rare path: raise the running max of the rows that need it, rescale everything that was formed against the old one
 // (O, l, the -m accumulator seed, the pending next score tile) and redo this tile's exponentials
@@ -454,26 +507,7 @@ __device__ __forceinline__ half2_ sp_phase(const f32x16& s, half8& p0, half8& p1
     const half2_ b1 = b0 + a2;
     SP_SB();
 #undef SP_M
-    // tail: on gfx950 a packed (VOP3P) result needs one wait state before any VALU reads it, so the compiler puts an
-    // s_nop behind each of the three dependent v_pk_add_f16 of this tail.  Written out by hand, the OTHER block's pending
-    // row sum (its tile was checked a phase ago) is folded into its fp32 l in those slots instead:
-    //   a3 = c3 + c7 | lo = f32(t_other) | t = b1 + a3 | l_other += lo | tt = t + swap(t)   (the compiler adds the one
-    //   wait state between the asm block and its own compare of tt)
-    const half2_ c7 = sp_pk(e14, e15);
-    half2_ a3, t, tt;
-    float lo;
-    asm volatile("v_pk_add_f16 %0, %5, %6\n\t"
-                 "v_cvt_f32_f16_e32 %3, %8\n\t"
-                 "v_pk_add_f16 %1, %7, %0\n\t"
-                 "v_add_f32_e32 %4, %4, %3\n\t"
-                 "v_pk_add_f16 %2, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]"
-                 : "=&v"(a3), "=&v"(t), "=&v"(tt), "=&v"(lo), "+v"(l_other)
-                 : "v"(c3), "v"(c7), "v"(b1), "v"(t_other));
-    p0 = __builtin_shufflevector(__builtin_shufflevector(c0, c1, 0, 1, 2, 3), __builtin_shufflevector(c2, c3, 0, 1, 2, 3),
-                                 0, 1, 2, 3, 4, 5, 6, 7);
-    p1 = __builtin_shufflevector(__builtin_shufflevector(c4, c5, 0, 1, 2, 3), __builtin_shufflevector(c6, c7, 0, 1, 2, 3),
-                                 0, 1, 2, 3, 4, 5, 6, 7);
-    return tt;
+    return sp_phase_tail(c0, c1, c2, c3, c4, c5, c6, sp_pk(e14, e15), b1, t_other, l_other, p0, p1);
 }
 
 // ABL: timing ablations (pcd_set_attention_config(16 + bits), outputs wrong while set): 1 = no K/V restaging in the loop, 2 = no rare-path test
@@ -524,20 +558,16 @@ __global__ __launch_bounds__(64 * NW, 2) void set_attention_sp_kernel(const half
     const size_t tile_bytes = (size_t)KT * ld * 2, half_bytes = (size_t)32 * ld * 2;
     const char* kwave = (const char*)kbase + (size_t)(8 * wave) * ld * 2;     // this wave's first piece of tile 0
     const char* vwave = (const char*)vbase + (size_t)(8 * wave) * ld * 2;
-    auto dma = [&](const char* sbase, unsigned voff, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr)
-                     : "memory", "m0");
-    };
     // piece j (0..3) of tile kt into ring slot `slot`: K rows 8w.., K rows 8w+32.., V rows 8w.., V rows 8w+32..
     auto stage_piece = [&](int kt, int slot, int j) __attribute__((always_inline)) {
         if constexpr (NW == 4) {
             const char* src = ((j & 2) ? vwave : kwave) + (size_t)kt * tile_bytes + ((j & 1) ? half_bytes : 0);
             const unsigned dst = lds0 + slot * STAGE + ((j & 2) ? KBYTES : 0) + (wave + 4 * (j & 1)) * 1024;
-            dma(src, (j & 2) ? voff32 : koff32, dst);
+            sp_dma(src, (j & 2) ? voff32 : koff32, dst);
         } else {                                               // eight waves: piece 0 = K rows 8 w .., piece 2 = V rows 8 w .. (one in front of each sub-tile)
             if (j == 0 || j == 2) {
                 const char* src = (j ? vwave : kwave) + (size_t)kt * tile_bytes;
-                dma(src, j ? voff32 : koff32, lds0 + slot * STAGE + (j ? KBYTES : 0) + wave * 1024);
+                sp_dma(src, j ? voff32 : koff32, lds0 + slot * STAGE + (j ? KBYTES : 0) + wave * 1024);
             }
         }
     };
@@ -550,17 +580,7 @@ __global__ __launch_bounds__(64 * NW, 2) void set_attention_sp_kernel(const half
     half8 qA[KSTEPS], qB[KSTEPS];
     {
         const half_t* qpA = qkv + (row_base + q0 + qr) * ld + head * D;
-        const half_t* qpB = qpA + (int64_t)32 * ld;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            // pre-scaled by log2(e)/sqrt(d) (one fp16 rounding) so the MFMA output is already in the exp2 domain
-            const half8 ra = *(const half8*)(qpA + 16 * s + 8 * hh), rb = *(const half8*)(qpB + 16 * s + 8 * hh);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                qA[s][e] = (half_t)((float)ra[e] * scale_log2e);
-                qB[s][e] = (half_t)((float)rb[e] * scale_log2e);
-            }
-        }
+        attn_load_q2(qpA, qpA + (int64_t)32 * ld, hh, scale_log2e, qA, qB);
     }
 
     // lane-constant LDS addresses (slot 0, key sub-tile 0); every read adds a compile-time offset.
@@ -689,7 +709,7 @@ __global__ __launch_bounds__(64 * NW, 2) void set_attention_sp_kernel(const half
 
 
 // ------------------------------------------------------------ software-pipelined kernel for d = 32 / 16 (n % 256 == 0)
-// set_attention_om_kernel below keeps ONE 32-query block per wave: the score MFMAs, the 16 v_exp_f32, the packs, the row sum, the any() branch and the
+// The max-free form of the generic kernel keeps ONE 32-query block per wave: the score MFMAs, the 16 v_exp_f32, the packs, the row sum, the any() branch and the
 // PV MFMAs of a 32 x 32 score tile are one dependent chain, and two waves per SIMD do not hide it -- 441 cycles per tile and SIMD at d = 32 for 128 cycles of
 // MFMA and ~200 of VALU issue (profiles/r05_b: the matrix pipe and the VALU overlap, so the floor is the LARGER of the two, not their sum).  Here a wave
 // owns TWO 32-query blocks half a step apart, exactly as in set_attention_sp_kernel: while block A's scores are exponentiated the matrix pipe holds block
@@ -773,22 +793,7 @@ __device__ __forceinline__ half2_ spn_phase(f32x16& s, half8& p0, half8& p1, con
     SP_SB();
 #undef SPN_SLOT
 #undef SPN_PV
-    // tail as in sp_phase: the other block's pending row sum goes into its fp32 l in the wait states of the three dependent packed adds
-    const half2_ c7 = sp_pk(e14, e15);
-    half2_ a3, t, tt;
-    float lo;
-    asm volatile("v_pk_add_f16 %0, %5, %6\n\t"
-                 "v_cvt_f32_f16_e32 %3, %8\n\t"
-                 "v_pk_add_f16 %1, %7, %0\n\t"
-                 "v_add_f32_e32 %4, %4, %3\n\t"
-                 "v_pk_add_f16 %2, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]"
-                 : "=&v"(a3), "=&v"(t), "=&v"(tt), "=&v"(lo), "+v"(l_other)
-                 : "v"(c3), "v"(c7), "v"(b1), "v"(t_other));
-    p0 = __builtin_shufflevector(__builtin_shufflevector(c0, c1, 0, 1, 2, 3), __builtin_shufflevector(c2, c3, 0, 1, 2, 3),
-                                 0, 1, 2, 3, 4, 5, 6, 7);
-    p1 = __builtin_shufflevector(__builtin_shufflevector(c4, c5, 0, 1, 2, 3), __builtin_shufflevector(c6, c7, 0, 1, 2, 3),
-                                 0, 1, 2, 3, 4, 5, 6, 7);
-    return tt;
+    return sp_phase_tail(c0, c1, c2, c3, c4, c5, c6, sp_pk(e14, e15), b1, t_other, l_other, p0, p1);
 }
 
 // ABL: timing ablations for tools/bench_attn_small_d.py (pcd_set_attention_config(16 + bits); outputs are wrong while set): 1 = no K/V restaging in the loop,
@@ -844,20 +849,16 @@ __global__ __launch_bounds__(256, 3) void set_attention_spn_kernel(const half_t*
     const int prow = D == 32 ? 16 * wave : 32 * (wave & 1);
     const char* kwave = (const char*)kbase + (size_t)prow * ld * 2;
     const char* vwave = (const char*)vbase + (size_t)prow * ld * 2;
-    auto dma = [&](const char* sbase, unsigned voff, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr)
-                     : "memory", "m0");
-    };
     // piece j of this wave's PPW pieces of tile kt into ring slot `slot`
     auto stage_piece = [&](int kt, int slot, int j) __attribute__((always_inline)) {
         if constexpr (D == 32) {
             const char* src = (j ? vwave : kwave) + (size_t)kt * tile_bytes;
-            dma(src, j ? voff32 : koff32, lds0 + slot * STAGE + (j ? KBYTES : 0) + wave * 1024);
+            sp_dma(src, j ? voff32 : koff32, lds0 + slot * STAGE + (j ? KBYTES : 0) + wave * 1024);
         } else {
             if (j == 0) {
                 const bool is_v = wave >= 2;
                 const char* src = (is_v ? vwave : kwave) + (size_t)kt * tile_bytes;
-                dma(src, is_v ? voff32 : koff32, lds0 + slot * STAGE + (is_v ? KBYTES : 0) + (wave & 1) * 1024);
+                sp_dma(src, is_v ? voff32 : koff32, lds0 + slot * STAGE + (is_v ? KBYTES : 0) + (wave & 1) * 1024);
             }
         }
     };
@@ -869,16 +870,7 @@ __global__ __launch_bounds__(256, 3) void set_attention_spn_kernel(const half_t*
     half8 qA[KSTEPS], qB[KSTEPS];
     {
         const half_t* qpA = qkv + (row_base + q0 + qr) * ld + head * D;
-        const half_t* qpB = qpA + (int64_t)32 * ld;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const half8 ra = *(const half8*)(qpA + 16 * s + 8 * hh), rb = *(const half8*)(qpB + 16 * s + 8 * hh);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                qA[s][e] = (half_t)((float)ra[e] * scale_log2e);
-                qB[s][e] = (half_t)((float)rb[e] * scale_log2e);
-            }
-        }
+        attn_load_q2(qpA, qpA + (int64_t)32 * ld, hh, scale_log2e, qA, qB);
     }
 
     // lane-constant LDS addresses (slot 0, key sub-tile 0); every read adds a compile-time offset (the K swizzle of row qr + 32 i is that of row qr)
@@ -992,189 +984,6 @@ __global__ __launch_bounds__(256, 3) void set_attention_spn_kernel(const half_t*
 }
 
 
-// ------------------------------------------------------------ generic kernel without the running max (d = 16 / 32 / 64, any n)
-// set_attention_kernel above spends 66 VALU instructions per 32 x 32 score tile, 50 of them around the 16 v_exp_f32 (row max chain,
-// half-wave exchange, compare, fp32 row sums); at d = 32 / 16 a tile is only 4 / 3 MFMAs (128 / 96 matrix cycles), so the kernel is VALU
-// bound at 25.6 % / 14.2 % of the MFMA peak.  This kernel keeps its structure (one 32-query block per wave, 2-deep K/V ring, masked last
-// tile: any n) and takes the softmax of set_attention_sp_kernel: m is fixed exactly by the first 32 keys (every row then has a P = 1 term);
-// afterwards a tile is exponentiated against the old m, its lane-partial row sum is formed from the fp16 P by a packed-fp16 tree and only a
-// sum >= 2^13 (or inf) sends the wave down the rare path (exact maxima, rescale O / l, redo the tile).  Softmax is invariant to m: the same
-// function as the reference's.  ~36 VALU instructions per tile.  The bound that remains is the exponentials themselves: 16 v_exp_f32
-// (8 cycles each) + 8 packs + 8 packed adds = ~200 issue cycles per tile and wave against 128 / 96 cycles of MFMA, i.e. <= ~42 % / ~21 % of
-// the MFMA peak for d = 32 / 16 however the rest is arranged.  Measured (B = 64, N = 2048): d = 32 734 v. 641 TFLOP/s, d = 16 410 v. 367.
-template <int D>
-__global__ __launch_bounds__(256, 2) void set_attention_om_kernel(const half_t* __restrict__ qkv, int n, int c, int heads,
-                                                                   float scale_log2e, half_t* __restrict__ out) {
-    constexpr int DP = (D < 32) ? 32 : D;
-    constexpr int KSTEPS = D / 16;
-    constexpr int OT = DP / 32;
-    constexpr int KRB = D * 2;
-    constexpr int KBYTES = KT * KRB, STAGE = 2 * KBYTES;
-    constexpr int ZERO_OFF = 2 * STAGE;
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + 64];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int qr = lane & 31, hh = lane >> 5;
-    const int bh = blockIdx.y, b = bh / heads, head = bh - b * heads;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const int64_t row_base = (int64_t)b * n;
-    const int ld = 3 * c;
-
-    half8 qf[KSTEPS];
-    {
-        int qi = q0 + qr;
-        qi = qi < n ? qi : n - 1;
-        const half_t* qp = qkv + (row_base + qi) * ld + head * D;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const half8 raw = *(const half8*)(qp + 16 * s + 8 * hh);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[s][e] = (half_t)((float)raw[e] * scale_log2e);
-        }
-    }
-    // negm: 16 registers of -m, the C operand of the first S^T MFMA of every tile.  (For d <= 32 the compiler rebuilds it with 15 v_mov per
-    // tile; carrying -m through an extra MFMA k-step instead -- constant K fragment [1, 1, 0..], Q fragment [-m_hi, -m_lo, 0..] -- removes the
-    // moves and measured SLOWER: 696 v. 734 TFLOP/s at d = 32, 388 v. 410 at d = 16.)
-    f32x16 oacc[OT], negm;
-    float l = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) negm[r] = 0.f;
-#pragma unroll
-    for (int o = 0; o < OT; ++o)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[o][r] = 0.f;
-    if (tid < 16) *(float*)(smem + ZERO_OFF + tid * 4) = 0.f;
-
-    const half_t* kbase = qkv + row_base * ld + c + head * D;
-    const half_t* vbase = qkv + row_base * ld + 2 * c + head * D;
-    const int ntiles = (n + KT - 1) / KT;
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = lane >> 4;
-    const int tr_dd0 = 16 * (tg & 1);
-
-    auto stage = [&](int kt, int buf) {
-        char* base = smem + buf * STAGE;
-        stage_tile<KT, KRB, false, 4, true>(kbase, ld, kt * KT, n, base, wave, lane);
-        stage_tile<KT, KRB, true, 4, true>(vbase, ld, kt * KT, n, base + KBYTES, wave, lane);
-    };
-
-    auto tile_body = [&](int kt, auto mask_tag) {
-        constexpr bool MASK = decltype(mask_tag)::value;
-        const char* kb = smem + (kt & 1) * STAGE;
-        const char* vb = kb + KBYTES;
-#pragma unroll
-        for (int sub = 0; sub < KT / 32; ++sub) {
-            half8 kf[KSTEPS];
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                const int row = sub * 32 + qr;
-                kf[s] = *(const half8*)(kb + row * KRB + (k_swz<KRB>(row, 2 * s + hh) << 4));
-            }
-            half8 vf[2][OT];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int o = 0; o < OT; ++o) {
-                    const int dd0 = o * 32 + tr_dd0;
-                    fp16x4 lo, hi;
-                    if (D >= 32 || dd0 < D) {
-                        const int key = sub * 32 + 16 * s2 + 4 * (tg >> 1) + tq;
-                        const int ch = (dd0 >> 3) + (tp >> 1);
-                        const char* a0 = vb + key * KRB + (v_swz<KRB>(key, ch) << 4) + (tp & 1) * 8;
-                        const char* a1 = vb + (key + 8) * KRB + (v_swz<KRB>(key + 8, ch) << 4) + (tp & 1) * 8;
-                        lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4*)a0);
-                        hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4*)a1);
-                    } else {
-                        const char* z = smem + ZERO_OFF + (tp & 1) * 8;
-                        lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp16x4*)z);
-                        hi = lo;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { vf[s2][o][e] = (half_t)lo[e]; vf[s2][o][4 + e] = (half_t)hi[e]; }
-                }
-            f32x16 sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0], qf[0], negm, 0, 0, 0);
-#pragma unroll
-            for (int s = 1; s < KSTEPS; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[s], qf[s], sacc, 0, 0, 0);
-            if constexpr (MASK) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KT + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    if (key >= n) sacc[r] = -INFINITY;
-                }
-            }
-            if (kt == 0 && sub == 0) {                       // the first 32 keys fix the running max exactly
-                const float mx = sp_rowmax(sacc);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { negm[r] = -mx; sacc[r] -= mx; }
-            }
-            half8 p0, p1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                p0[j] = (half_t)__builtin_amdgcn_exp2f(sacc[j]);
-                p1[j] = (half_t)__builtin_amdgcn_exp2f(sacc[8 + j]);
-            }
-            half2_ tt = sp_tile_sum(p0, p1);
-            if (__builtin_expect(__any(__builtin_bit_cast(unsigned, tt) > SP_BIG_BITS), 0)) {
-                // rare: some score is ~9 or more above the running max (or P overflowed fp16): exact maxima, rescale, redo the tile
-                const float delta = fmaxf(sp_rowmax(sacc), 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
-                l *= alpha;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { negm[r] -= delta; sacc[r] -= delta; }
-#pragma unroll
-                for (int o = 0; o < OT; ++o)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[o][r] *= alpha;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    p0[j] = (half_t)__builtin_amdgcn_exp2f(sacc[j]);
-                    p1[j] = (half_t)__builtin_amdgcn_exp2f(sacc[8 + j]);
-                }
-                tt = sp_tile_sum(p0, p1);
-            }
-            l += (float)tt.x;
-#pragma unroll
-            for (int o = 0; o < OT; ++o) {
-                oacc[o] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[0][o], p0, oacc[o], 0, 0, 0);
-                oacc[o] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[1][o], p1, oacc[o], 0, 0, 0);
-            }
-        }
-    };
-
-    const int full_tiles = n / KT;
-    stage(0, 0);
-    for (int kt = 0; kt < full_tiles; ++kt) {
-        wait_vmcnt<0>();
-        __syncthreads();
-        if (kt + 1 < ntiles) stage(kt + 1, (kt + 1) & 1);
-        tile_body(kt, std::false_type{});
-    }
-    if (full_tiles < ntiles) {
-        wait_vmcnt<0>();
-        __syncthreads();
-        tile_body(full_tiles, std::true_type{});
-    }
-
-    const int qi = q0 + qr;
-    const float l_tot = l + __shfl_xor(l, 32);
-    if (qi < n) {
-        const float inv = 1.f / l_tot;
-        half_t* orow = out + (row_base + qi) * c + head * D;
-#pragma unroll
-        for (int o = 0; o < OT; ++o)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int dd = o * 32 + 8 * g + 4 * hh;
-                if (dd < D) {
-                    half4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = to_half_sat(oacc[o][4 * g + e] * inv);
-                    *(half4*)(orow + dd) = ov;
-                }
-            }
-    }
-}
-
 }  // namespace pcd
 
 using namespace pcd;
@@ -1184,10 +993,11 @@ extern "C" int pcd_layernorm_f16(const void* x, int64_t rows, int c, const float
     PCD_CHECK_ARG(x && gamma && beta && out && rows > 0 && c > 0);
     hipStream_t s = (hipStream_t)stream;
     const half_t* x16 = (const half_t*)x; half_t* o16 = (half_t*)out;
-    if (c == 64) hipLaunchKernelGGL((layernorm_vec_kernel<8>), dim3((unsigned)ceil_div(rows, 32)), dim3(256), 0, s, x16, rows, gamma, beta, o16);
-    else if (c == 128) hipLaunchKernelGGL((layernorm_vec_kernel<16>), dim3((unsigned)ceil_div(rows, 16)), dim3(256), 0, s, x16, rows, gamma, beta, o16);
-    else if (c == 256) hipLaunchKernelGGL((layernorm_vec_kernel<32>), dim3((unsigned)ceil_div(rows, 8)), dim3(256), 0, s, x16, rows, gamma, beta, o16);
-    else hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, s, x16, rows, c, gamma, beta, o16);
+    const bool vec = ln_launch(c, [&](auto lpr) {
+        hipLaunchKernelGGL((layernorm_rows_kernel<decltype(lpr)::value, false>), dim3(ln_row_blocks(rows, c)), dim3(256), 0, s, x16, rows, gamma, beta, o16,
+                           (float*)nullptr, (float*)nullptr);
+    });
+    if (!vec) hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, s, x16, rows, c, gamma, beta, o16);
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
@@ -1197,22 +1007,67 @@ extern "C" size_t pcd_set_attention_workspace_bytes(int batch, int n_points, int
     return 0;   // V is transposed on the fly by ds_read_b64_tr_b16: no workspace needed any more
 }
 
-static int g_attn_force_generic = 0;   // tuning/testing hook: 1 = always the round-1 generic kernel, 2 = always the max-free generic kernel
-static int g_attn_spn_abl = 0;         // timing ablations of set_attention_spn_kernel (pcd_set_attention_config(16 + bits)); outputs are wrong while set
-static int g_attn_sp_waves = 4;        // tuning hook (pcd_set_attention_config(5) / (6)): set_attention_sp_kernel with 4 / 8 waves per workgroup
-static int g_attn_spn = 1;             // tuning/testing hook (pcd_set_attention_config(3) / (4)): d = 32 / 16 on the software-pipelined kernel: off / on (default)
+// tuning / testing hooks, set through pcd_set_attention_config
+struct AttnConfig {
+    int force_generic = 0;   // 1 = always the round-1 generic kernel (running max), 2 = always the max-free generic kernel
+    int abl = 0;             // timing ablations of the pipelined kernels (code 16 + bits); outputs are wrong while set
+    int sp_waves = 4;        // codes 5 / 6: set_attention_sp_kernel with 4 / 8 waves per workgroup
+    int spn = 1;             // codes 3 / 4: d = 32 / 16 on the software-pipelined kernel: off / on (default)
+};
+static AttnConfig g_attn_config;
 
 extern "C" int pcd_set_attention_config(int force_generic) {
-    if (force_generic == 3 || force_generic == 4) { g_attn_spn = force_generic == 4; return PCD_OK; }
-    if (force_generic == 5 || force_generic == 6) { g_attn_sp_waves = force_generic == 6 ? 8 : 4; return PCD_OK; }
-    if (force_generic >= 16 && force_generic < 32) { g_attn_spn_abl = force_generic - 16; return PCD_OK; }
-    g_attn_force_generic = force_generic < 0 ? 0 : (force_generic > 2 ? 2 : force_generic);
+    AttnConfig& cfg = g_attn_config;
+    if (force_generic == 3 || force_generic == 4) { cfg.spn = force_generic == 4; return PCD_OK; }
+    if (force_generic == 5 || force_generic == 6) { cfg.sp_waves = force_generic == 6 ? 8 : 4; return PCD_OK; }
+    if (force_generic >= 16 && force_generic < 32) { cfg.abl = force_generic - 16; return PCD_OK; }
+    cfg.force_generic = force_generic < 0 ? 0 : (force_generic > 2 ? 2 : force_generic);
     return PCD_OK;
 }
 
 static const char* g_attn_last_kernel = "";   // which kernel the last pcd_set_attention_f16 call launched (bench.py reports it)
 
 extern "C" const char* pcd_set_attention_last_kernel(void) { return g_attn_last_kernel; }
+
+// Every kernel of the family takes (qkv, n, c, heads, scale_log2e, out): which one runs, on what grid and under which name
+// is a function of the shape and the hooks alone.
+typedef void (*AttnKernel)(const half_t*, int, int, int, float, half_t*);
+struct AttnPlan { AttnKernel kernel; dim3 grid, block; const char* name; };
+
+// the timing-ablation instantiations of the pipelined kernels; a (d, code) without an entry runs the default kernel
+struct AttnAblation { int d, code; AttnKernel kernel; };
+static const AttnAblation kAttnAblations[] = {
+    {64, 1, set_attention_sp_kernel<1>}, {64, 2, set_attention_sp_kernel<2>}, {64, 3, set_attention_sp_kernel<3>}, {64, 8, set_attention_sp_kernel<8>},
+    {32, 1, set_attention_spn_kernel<32, 1>}, {32, 2, set_attention_spn_kernel<32, 2>}, {32, 3, set_attention_spn_kernel<32, 3>},
+    {32, 7, set_attention_spn_kernel<32, 7>}, {32, 8, set_attention_spn_kernel<32, 8>},
+    {16, 1, set_attention_spn_kernel<16, 1>}, {16, 2, set_attention_spn_kernel<16, 2>}, {16, 3, set_attention_spn_kernel<16, 3>},
+    {16, 7, set_attention_spn_kernel<16, 7>}, {16, 8, set_attention_spn_kernel<16, 8>},
+};
+
+static AttnPlan attn_plan(int batch, int n, int d, int heads, const AttnConfig& cfg) {
+    const int di = d == 16 ? 0 : d == 32 ? 1 : 2;
+    if (cfg.force_generic == 0 && n % 256 == 0 && (d == 64 || cfg.spn)) {
+        // software-pipelined kernels: 64 queries per wave, 256 per workgroup of four waves
+        static const AttnKernel kernels[3] = {set_attention_spn_kernel<16>, set_attention_spn_kernel<32>, set_attention_sp_kernel<0, 4>};
+        static const char* const names[3] = {"set_attention_spn_kernel<16>", "set_attention_spn_kernel<32>", "set_attention_sp_kernel"};
+        const dim3 grid((unsigned)((n / 256) * batch * heads));
+        for (const AttnAblation& a : kAttnAblations)
+            if (a.d == d && a.code == cfg.abl) return {a.kernel, grid, dim3(256), d == 64 ? names[2] : "set_attention_spn_kernel (timing ablation)"};
+        if (d == 64 && cfg.sp_waves == 8 && n % 512 == 0) return {set_attention_sp_kernel<0, 8>, dim3(grid.x / 2), dim3(512), names[2]};
+        return {kernels[di], grid, dim3(256), names[di]};
+    }
+    // every other shape (n not a multiple of 256, or the pipelined kernels switched off): one 32-query block per wave, 128 per workgroup.
+    // (Two blocks per wave measured slower here, 764 v. 836 TFLOP/s at d = 64: 256 VGPRs, and the shared K/V fragments do not pay for the lost occupancy.)
+    static const AttnKernel kernels[2][3] = {
+        {set_attention_generic_kernel<16, AttnSoftmax::MaxFree>, set_attention_generic_kernel<32, AttnSoftmax::MaxFree>,
+         set_attention_generic_kernel<64, AttnSoftmax::MaxFree>},
+        {set_attention_generic_kernel<16, AttnSoftmax::RunningMax>, set_attention_generic_kernel<32, AttnSoftmax::RunningMax>,
+         set_attention_generic_kernel<64, AttnSoftmax::RunningMax>}};
+    static const char* const names[2][3] = {{"set_attention_om_kernel<16>", "set_attention_om_kernel<32>", "set_attention_om_kernel<64>"},
+                                            {"set_attention_kernel<16>", "set_attention_kernel<32>", "set_attention_kernel<64>"}};
+    const int round1 = cfg.force_generic == 1;
+    return {kernels[round1][di], dim3((unsigned)ceil_div(n, 128), (unsigned)(batch * heads)), dim3(256), names[round1][di]};
+}
 
 extern "C" int pcd_set_attention_f16(const void* qkv, int batch, int n_points, int c, int heads, void* out,
                                      void* workspace, size_t workspace_bytes, void* stream) {
@@ -1221,64 +1076,10 @@ extern "C" int pcd_set_attention_f16(const void* qkv, int batch, int n_points, i
     const int d = c / heads;
     PCD_CHECK_ARG(d == 16 || d == 32 || d == 64);
     PCD_CHECK_ARG(c % 8 == 0);
-    hipStream_t s = (hipStream_t)stream;
     const float scale_log2e = 1.4426950408889634f / sqrtf((float)d);
-    // 32*QT queries per wave.  QT = 1 measured fastest (836 vs 764 TFLOP/s at d = 64): at QT = 2 the kernel
-    // sits at 256 VGPRs (2 waves/SIMD) and the shared K/V fragments do not pay for the lost occupancy.
-    constexpr int QT = 1;
-    if (d == 64 && n_points % 256 == 0 && g_attn_force_generic == 0) {   // software-pipelined kernel: 64 queries per wave, 256 per workgroup
-        dim3 sgrid((unsigned)((n_points / 256) * batch * heads));
-        if (g_attn_spn_abl == 1) hipLaunchKernelGGL(set_attention_sp_kernel<1>, sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else if (g_attn_spn_abl == 2) hipLaunchKernelGGL(set_attention_sp_kernel<2>, sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else if (g_attn_spn_abl == 8) hipLaunchKernelGGL(set_attention_sp_kernel<8>, sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else if (g_attn_spn_abl == 3) hipLaunchKernelGGL(set_attention_sp_kernel<3>, sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else if (g_attn_sp_waves == 8 && n_points % 512 == 0)
-            hipLaunchKernelGGL((set_attention_sp_kernel<0, 8>), dim3(sgrid.x / 2), dim3(512), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else
-        hipLaunchKernelGGL((set_attention_sp_kernel<0, 4>), sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads,
-                           scale_log2e, (half_t*)out);
-        g_attn_last_kernel = "set_attention_sp_kernel";
-        PCD_CHECK_LAUNCH();
-        return PCD_OK;
-    }
-    if ((d == 32 || d == 16) && n_points % 256 == 0 && g_attn_force_generic == 0 && g_attn_spn) {   // the same pipeline at d <= 32
-        dim3 sgrid((unsigned)((n_points / 256) * batch * heads));
-#define PCD_SPN_ABL(A)                                                                                                                                   \
-        if (g_attn_spn_abl == A) {                                                                                                                           \
-            if (d == 32) hipLaunchKernelGGL((set_attention_spn_kernel<32, A>), sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out); \
-            else hipLaunchKernelGGL((set_attention_spn_kernel<16, A>), sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);          \
-            g_attn_last_kernel = "set_attention_spn_kernel (timing ablation)";                                                                               \
-            PCD_CHECK_LAUNCH();                                                                                                                              \
-            return PCD_OK;                                                                                                                                   \
-        }
-        PCD_SPN_ABL(1) PCD_SPN_ABL(2) PCD_SPN_ABL(3) PCD_SPN_ABL(7) PCD_SPN_ABL(8)
-#undef PCD_SPN_ABL
-        if (d == 32) hipLaunchKernelGGL((set_attention_spn_kernel<32>), sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else hipLaunchKernelGGL((set_attention_spn_kernel<16>), sgrid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        g_attn_last_kernel = d == 32 ? "set_attention_spn_kernel<32>" : "set_attention_spn_kernel<16>";
-        PCD_CHECK_LAUNCH();
-        return PCD_OK;
-    }
-    dim3 grid((unsigned)ceil_div(n_points, 128 * QT), (unsigned)(batch * heads));
-    if (g_attn_force_generic != 1) {
-        // every other shape (d = 16 / 32, or n not a multiple of 256): the generic structure with the max-free softmax
-        if (d == 16) hipLaunchKernelGGL((set_attention_om_kernel<16>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else if (d == 32) hipLaunchKernelGGL((set_attention_om_kernel<32>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        else hipLaunchKernelGGL((set_attention_om_kernel<64>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
-        g_attn_last_kernel = d == 16 ? "set_attention_om_kernel<16>" : d == 32 ? "set_attention_om_kernel<32>" : "set_attention_om_kernel<64>";
-        PCD_CHECK_LAUNCH();
-        return PCD_OK;
-    }
-    if (d == 16)
-        hipLaunchKernelGGL((set_attention_kernel<16, QT>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads,
-                           scale_log2e, (half_t*)out);
-    else if (d == 32)
-        hipLaunchKernelGGL((set_attention_kernel<32, QT>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads,
-                           scale_log2e, (half_t*)out);
-    else
-        hipLaunchKernelGGL((set_attention_kernel<64, QT>), grid, dim3(256), 0, s, (const half_t*)qkv, n_points, c, heads,
-                           scale_log2e, (half_t*)out);
-    g_attn_last_kernel = d == 16 ? "set_attention_kernel<16>" : d == 32 ? "set_attention_kernel<32>" : "set_attention_kernel<64>";
+    const AttnPlan plan = attn_plan(batch, n_points, d, heads, g_attn_config);
+    hipLaunchKernelGGL(plan.kernel, plan.grid, plan.block, 0, (hipStream_t)stream, (const half_t*)qkv, n_points, c, heads, scale_log2e, (half_t*)out);
+    g_attn_last_kernel = plan.name;
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }

@@ -13,6 +13,7 @@
 // reduction index permuted as k(g, i) = i < 4 ? 4g + i : 16 + 4g + (i - 4); the other operand is read from a transposed
 // LDS copy in the same order.
 #include "common.h"
+#include "layernorm_rows.h"
 
 namespace pcd {
 
@@ -277,50 +278,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const half_t* __restri
         for (int r = 0; r < 4; ++r) dqkv[(row0 + r) * ld + h * D + t * 16 + l16] = to_half_sat(dq[t][r] * rs);
 }
 
-// ---------------------------------------------------------------- LayerNorm with saved statistics
-// C = 8 * LPR; the arithmetic of pcd_layernorm_f16's vector kernel (same bits), plus mean / rstd per row.  The fused multiply-adds are spelled out in
-// both: left to contraction, the same source came out as a chain of v_fmac in one file and as v_pk_mul + v_add (every square rounded) in the other, rstd
-// differed in its last bit and a few outputs by an fp16 ulp (tests/test_gpu_layernorm_rows.py compares the two bit for bit).
-template <int LPR>
-__global__ __launch_bounds__(256) void layernorm_train_kernel(const half_t* __restrict__ x, int64_t rows,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              half_t* __restrict__ out, float* __restrict__ mean_out,
-                                                              float* __restrict__ rstd_out) {
-    constexpr int C = LPR * 8, RPW = 64 / LPR;
-    const int lane = threadIdx.x & 63, l = lane % LPR;
-    const int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    const int64_t rr = row < rows ? row : rows - 1;
-    const half8 v = *(const half8*)(x + rr * C + l * 8);
-    float f[8];
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { f[e] = (float)v[e]; s += f[e]; }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] -= mean;
-    float q = f[1] * f[1];                           // f1^2 rounded, the others fused: the form `q += f[e] * f[e]` had been contracted to
-    q = __builtin_fmaf(f[0], f[0], q);
-#pragma unroll
-    for (int e = 2; e < 8; ++e) q = __builtin_fmaf(f[e], f[e], q);
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + 1e-5f);
-    const f32x4 g0 = *(const f32x4*)(gamma + l * 8), g1 = *(const f32x4*)(gamma + l * 8 + 4);
-    const f32x4 b0 = *(const f32x4*)(beta + l * 8), b1 = *(const f32x4*)(beta + l * 8 + 4);
-    half8 o8;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        o8[e] = to_half_sat(__builtin_fmaf(f[e] * rstd, g0[e], b0[e]));
-        o8[4 + e] = to_half_sat(__builtin_fmaf(f[4 + e] * rstd, g1[e], b1[e]));
-    }
-    if (row < rows) {
-        *(half8*)(out + row * C + l * 8) = o8;
-        if (l == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
-    }
-}
-
+// ---------------------------------------------------------------- LayerNorm backward
+// (the forward with saved statistics is layernorm_rows_kernel<LPR, true> of layernorm_rows.h)
 // dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) [+ dx]; per-workgroup partial sums of dy xhat and dy into
 // slab[blockIdx.x] = [dgamma C | dbeta C] (summed in a fixed order by ln_sum_slabs_kernel).  x - mean in fp32.
 template <int LPR>
@@ -465,9 +424,9 @@ extern "C" int pcd_layernorm_train_f16(const void* x, int64_t rows, int c, const
     hipStream_t s = (hipStream_t)stream;
     const half_t* x16 = (const half_t*)x;
     half_t* o16 = (half_t*)out;
-    if (c == 64) hipLaunchKernelGGL(layernorm_train_kernel<8>, dim3((unsigned)ceil_div(rows, 32)), dim3(256), 0, s, x16, rows, gamma, beta, o16, mean, rstd);
-    else if (c == 128) hipLaunchKernelGGL(layernorm_train_kernel<16>, dim3((unsigned)ceil_div(rows, 16)), dim3(256), 0, s, x16, rows, gamma, beta, o16, mean, rstd);
-    else hipLaunchKernelGGL(layernorm_train_kernel<32>, dim3((unsigned)ceil_div(rows, 8)), dim3(256), 0, s, x16, rows, gamma, beta, o16, mean, rstd);
+    ln_launch(c, [&](auto lpr) {
+        hipLaunchKernelGGL((layernorm_rows_kernel<decltype(lpr)::value, true>), dim3(ln_row_blocks(rows, c)), dim3(256), 0, s, x16, rows, gamma, beta, o16, mean, rstd);
+    });
     PCD_CHECK_LAUNCH();
     return PCD_OK;
 }
@@ -492,9 +451,9 @@ extern "C" int pcd_layernorm_backward_f16(const void* dy, const void* x, int64_t
     float* slabs = (float*)workspace;
     const half_t *g16 = (const half_t*)dy, *x16 = (const half_t*)x;
     half_t* d16 = (half_t*)dx;
-    if (c == 64) hipLaunchKernelGGL(layernorm_backward_kernel<8>, dim3(nb), dim3(256), 0, s, g16, x16, rows, mean, rstd, gamma, accumulate, d16, slabs);
-    else if (c == 128) hipLaunchKernelGGL(layernorm_backward_kernel<16>, dim3(nb), dim3(256), 0, s, g16, x16, rows, mean, rstd, gamma, accumulate, d16, slabs);
-    else hipLaunchKernelGGL(layernorm_backward_kernel<32>, dim3(nb), dim3(256), 0, s, g16, x16, rows, mean, rstd, gamma, accumulate, d16, slabs);
+    ln_launch(c, [&](auto lpr) {
+        hipLaunchKernelGGL(layernorm_backward_kernel<decltype(lpr)::value>, dim3(nb), dim3(256), 0, s, g16, x16, rows, mean, rstd, gamma, accumulate, d16, slabs);
+    });
     hipLaunchKernelGGL(ln_sum_slabs_kernel, dim3((unsigned)ceil_div(2 * c, 256)), dim3(256), 0, s, slabs, nb, c, dgamma, dbeta);
     PCD_CHECK_LAUNCH();
     return PCD_OK;

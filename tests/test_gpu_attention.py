@@ -137,6 +137,80 @@ def test_attention_max_free_generic_kernel(pattern, C, N):
         assert torch.equal(ops.set_attention_f16(qkv16.cuda(), B, N, C, H).float().cpu(), outs[2])
 
 
+@pytest.mark.parametrize("d", [16, 32, 64])
+@pytest.mark.parametrize("N", [1, 31, 32, 33, 64, 65, 129])
+def test_attention_generic_frame_at_its_edges(N, d):
+    """The one generic frame (set_attention_generic_kernel: staging, K / V fragment reads, masked last tile, ring loop, epilogue) under both of its
+    softmax forms, at the lengths where the frame can go wrong: the first 32-key sub-tile partly masked (N = 1, 31), a whole sub-tile masked (32, 33),
+    exactly one full tile (64), one key into the second and third tile (65, 129); Q rows past N are clamped at every one of them.  Against fp64, whole
+    tensor and row by row; the default dispatch at these lengths is the max-free form, bit for bit."""
+    from shapegen_amd import _lib, ops
+    B, H = 2, 4
+    C = H * d
+    g = torch.Generator().manual_seed(1000 * d + N)
+    qkv16 = torch.randn(B * N, 3 * C, generator=g).half()
+    want = _attention_fp64(qkv16, B, N, C, H)
+    lib = _lib.load()
+    outs = {}
+    for mode, name in ((2, f"set_attention_om_kernel<{d}>"), (1, f"set_attention_kernel<{d}>")):
+        _lib.check(lib.pcd_set_attention_config(mode))
+        try:
+            outs[mode] = ops.set_attention_f16(qkv16.cuda(), B, N, C, H).float().cpu()
+            assert lib.pcd_set_attention_last_kernel().decode() == name
+        finally:
+            _lib.check(lib.pcd_set_attention_config(0))
+        got = outs[mode]
+        assert got.shape == want.shape and torch.isfinite(got).all(), (mode, N, d)
+        rows = ((got - want).norm(dim=1) / want.norm(dim=1).clamp_min(1e-3))
+        print(f"generic frame, config({mode}), N = {N}, d = {d}: rel-L2 {rel_l2(got, want):.2e}, worst row {float(rows.max()):.2e}")
+        assert rel_l2(got, want) < 2e-3, (mode, N, d)
+        assert float(rows.max()) < 2e-2, (mode, N, d, int(rows.argmax()))
+    default = ops.set_attention_f16(qkv16.cuda(), B, N, C, H).float().cpu()      # N % 256 != 0 at every one of these lengths
+    assert lib.pcd_set_attention_last_kernel().decode() == f"set_attention_om_kernel<{d}>"
+    assert torch.equal(default, outs[2])
+
+
+# what pcd_set_attention_last_kernel reports per (config code, d, N): the dispatch ladder of the library before it became one plan, written out
+_SP, _ABL = "set_attention_sp_kernel", "set_attention_spn_kernel (timing ablation)"
+_DISPATCH = {
+    # code: {(d, N): name}
+    0: {(16, 256): "set_attention_spn_kernel<16>", (32, 256): "set_attention_spn_kernel<32>", (64, 256): _SP,
+        (16, 333): "set_attention_om_kernel<16>", (32, 333): "set_attention_om_kernel<32>", (64, 333): "set_attention_om_kernel<64>"},
+    1: {(16, 256): "set_attention_kernel<16>", (32, 256): "set_attention_kernel<32>", (64, 256): "set_attention_kernel<64>",
+        (16, 333): "set_attention_kernel<16>", (32, 333): "set_attention_kernel<32>", (64, 333): "set_attention_kernel<64>"},
+    2: {(16, 256): "set_attention_om_kernel<16>", (32, 256): "set_attention_om_kernel<32>", (64, 256): "set_attention_om_kernel<64>",
+        (16, 333): "set_attention_om_kernel<16>", (32, 333): "set_attention_om_kernel<32>", (64, 333): "set_attention_om_kernel<64>"},
+    3: {(16, 256): "set_attention_om_kernel<16>", (32, 256): "set_attention_om_kernel<32>", (64, 256): _SP,                    # d <= 32 off the pipeline
+        (16, 333): "set_attention_om_kernel<16>", (32, 333): "set_attention_om_kernel<32>", (64, 333): "set_attention_om_kernel<64>"},
+    6: {(16, 256): "set_attention_spn_kernel<16>", (32, 256): "set_attention_spn_kernel<32>", (64, 256): _SP,                  # eight waves need N % 512 == 0: four
+        (16, 333): "set_attention_om_kernel<16>", (32, 333): "set_attention_om_kernel<32>", (64, 333): "set_attention_om_kernel<64>"},
+}
+_RESTORE = {0: 0, 1: 0, 2: 0, 3: 4, 6: 5}
+
+
+@pytest.mark.parametrize("code", [0, 1, 2, 3, 6])
+@pytest.mark.parametrize("d,N", [(16, 256), (32, 256), (64, 256), (16, 333), (32, 333), (64, 333)])
+def test_attention_dispatch_table(d, N, code):
+    """The plan is the ladder: for every (d, N) on either side of N % 256 == 0 and every pcd_set_attention_config code that selects a kernel (0 default,
+    1 round-1 generic, 2 max-free generic, 3 d <= 32 off the pipelined kernel [4 restores], 6 eight-wave workgroups [5 restores]) the name reported
+    for the launch is the one written out above, and the launch computes attention."""
+    from shapegen_amd import _lib, ops
+    B, H = 1, 4
+    C = H * d
+    qkv16 = torch.randn(B * N, 3 * C, generator=torch.Generator().manual_seed(d + N)).half()
+    lib = _lib.load()
+    _lib.check(lib.pcd_set_attention_config(code))
+    try:
+        got = ops.set_attention_f16(qkv16.cuda(), B, N, C, H).float().cpu()
+        name = lib.pcd_set_attention_last_kernel().decode()
+    finally:
+        _lib.check(lib.pcd_set_attention_config(_RESTORE[code]))
+    assert name == _DISPATCH[code][(d, N)], (code, d, N)
+    assert rel_l2(got, _attention_fp64(qkv16, B, N, C, H)) < 2e-3
+    ops.set_attention_f16(qkv16.cuda(), B, N, C, H)                               # and the hook is back at its default
+    assert lib.pcd_set_attention_last_kernel().decode() == _DISPATCH[0][(d, N)]
+
+
 @pytest.mark.parametrize("pattern", ["plain", "late_spike", "rising", "falling", "huge_first"])
 @pytest.mark.parametrize("C,N", [(64, 256), (64, 512), (128, 512), (128, 768), (64, 2048)])
 def test_attention_pipelined_kernel_d32_d16(pattern, C, N):
@@ -223,6 +297,37 @@ def test_layernorm_rows(rows, c):
     got = ops.layernorm_f16(x.cuda(), gamma.cuda(), beta.cuda()).cpu()
     assert got.shape == x.shape and got.dtype == torch.float16
     assert float((got.double() - want).abs().max()) <= 2e-3 * max(1.0, float(want.abs().max()))      # one fp16 rounding
+
+
+@pytest.mark.parametrize("c", [64, 128, 256])
+@pytest.mark.parametrize("which", ["one_row", "block_plus_one"])
+def test_layernorm_forward_forms_bitwise_at_launch_edges(which, c):
+    """pcd_layernorm_f16 and pcd_layernorm_train_f16 are one row kernel behind one launcher (2048 / c rows per block): a single row (every other
+    row group of the block clamped) and one full block plus one row (a second block with one live row), the two forms bit for bit, against fp64,
+    and nothing written past the last row."""
+    from shapegen_amd import _lib
+    lib, st = _lib.load(), _lib.stream_ptr()
+    rows = 1 if which == "one_row" else 2048 // c + 1
+    g = torch.Generator().manual_seed(7 * c + rows)
+    x = (torch.randn(rows, c, generator=g) * 2 + 0.5).half()
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    want = torch.nn.functional.layer_norm(x.double(), (c,), gamma.double(), beta.double(), 1e-5)
+    xd, gd, bd = x.cuda(), gamma.cuda(), beta.cuda()
+    guard = 8                                                    # rows behind the last one that must stay as they are
+    y0 = torch.full((rows + guard, c), float("nan"), dtype=torch.float16, device="cuda")
+    y1 = torch.full_like(y0, float("nan"))
+    mu, rs = torch.full((rows + guard,), float("nan"), device="cuda"), torch.full((rows + guard,), float("nan"), device="cuda")
+    _lib.check(lib.pcd_layernorm_f16(xd.data_ptr(), rows, c, gd.data_ptr(), bd.data_ptr(), y0.data_ptr(), st), "ln")
+    _lib.check(lib.pcd_layernorm_train_f16(xd.data_ptr(), rows, c, gd.data_ptr(), bd.data_ptr(), y1.data_ptr(), mu.data_ptr(), rs.data_ptr(), st), "ln_train")
+    torch.cuda.synchronize()
+    y0, y1, mu, rs = y0.cpu(), y1.cpu(), mu.cpu(), rs.cpu()
+    assert torch.isnan(y0[rows:]).all() and torch.isnan(y1[rows:]).all() and torch.isnan(mu[rows:]).all() and torch.isnan(rs[rows:]).all()
+    assert torch.isfinite(y0[:rows]).all() and torch.equal(y0[:rows], y1[:rows])
+    assert float((y0[:rows].double() - want).abs().max()) <= 2e-3 * max(1.0, float(want.abs().max()))      # one fp16 rounding, as test_layernorm_rows
+    m64 = x.double().mean(dim=1)
+    r64 = (x.double().var(dim=1, unbiased=False) + 1e-5).rsqrt()
+    assert float((mu[:rows].double() - m64).abs().max()) <= 1e-6 * float(x.double().abs().max())          # the bounds of test_gpu_layernorm_rows.py
+    assert float((rs[:rows].double() / r64 - 1).abs().max()) <= 1e-6
 
 
 def test_unet_attention_golden(golden):

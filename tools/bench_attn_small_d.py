@@ -1,4 +1,4 @@
-"""Dev tool: the set-attention kernel at d = 32 / 16 (B = 64, N = 2048, 4 heads): the one-block kernel (set_attention_om_kernel), the two-block software pipeline
+"""Dev tool: the set-attention kernel at d = 32 / 16 (B = 64, N = 2048, 4 heads): the one-block kernel (set_attention_generic_kernel's max-free form, reported as set_attention_om_kernel), the two-block software pipeline
 (set_attention_spn_kernel) and the pipeline's timing ablations (outputs wrong while set), min of 3 x 10 launches after a 20-launch ramp, one process."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -14,6 +14,12 @@ matched by mangled name ACROSS files, so a kernel may move from one file to anot
     python tools/kernel_identity.py OLD_TREE NEW_TREE --old-files conv3d.hip --new-files conv3d_igemm.hip conv3d_halo.hip
     python tools/kernel_identity.py OLD_TREE NEW_TREE --files vae.hip unet.hip          # the same names in both trees
 
+A kernel that was renamed is matched with --map OLD=NEW: OLD and NEW are substrings of the mangled name, and every old
+kernel whose name contains OLD is compared under the name with NEW in its place (the template arguments and the signature
+are part of the mangled name, so a rename that changes them needs them inside OLD and NEW):
+
+    python tools/kernel_identity.py OLD_TREE NEW_TREE --files attention.hip --map 23set_attention_om_kernelILi32EE=28set_attention_generic_kernelILi32ELNS_11AttnSoftmaxE1EE
+
 File names are relative to <tree>/3d-shape-generation_amd/csrc.  Exit status 0: the two sets of kernels are equal and
 every kernel is identical; 1 otherwise.  --markdown prints the outcome as a table row per file.
 """
@@ -114,9 +120,25 @@ def main():
     ap.add_argument("--new-files", nargs="+", default=[], help="files compiled in the new tree only")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW",
+                    help="a renamed kernel: the substring OLD of an old tree's mangled name reads NEW (may be given several times)")
     a = ap.parse_args()
     old = tree_kernels(a.old_tree, a.files + a.old_files, a.jobs)
     new = tree_kernels(a.new_tree, a.files + a.new_files, a.jobs)
+    for rule in a.map:
+        frm, sep, to = rule.partition("=")
+        if not sep or not frm:
+            ap.error(f"--map {rule}: expected OLD=NEW")
+        hits = [k for k in old if frm in k]
+        if not hits:
+            ap.error(f"--map {rule}: no kernel of the old tree has {frm} in its name")
+        for k in hits:
+            renamed = k.replace(frm, to)
+            if renamed in old:
+                ap.error(f"--map {rule}: {k} would become {renamed}, which the old tree already has")
+            print(f"MAPPED {k} -> {renamed}")
+            old[renamed] = old.pop(k)
+            old[renamed]["body"] = [line.replace(k, renamed) for line in old[renamed]["body"]]   # (its own name in its directives)
     bad = 0
     for k in sorted(set(old) - set(new)):
         print(f"LOST   {k} ({old[k]['file']})")
