@@ -234,6 +234,8 @@ _SIGS = {
     "pcd_latent_persist_trace": (i32, [vp, vp, i32]),
     "pcd_latent_persist_forward": (i32, [vp, vp, i32, vp, vp, vp, sz, vp]),
     "pcd_latent_persist_ddim": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, sz, vp]),
+    "pcd_latent_persist_ddim_guided": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp, sz, vp]),
+    "pcd_latent_persist_forward_guided": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
     "pcd_latent_persist_status": (i32, [vp, C.POINTER(C.c_uint), vp]),
     "pcd_latent_persist_inject_fault": (i32, [vp, i32, i32]),
     "pcd_latent_persist_plan_check": (i32, []),

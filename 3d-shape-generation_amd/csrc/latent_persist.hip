@@ -31,9 +31,16 @@
 //     thread) and apply the DDIM update to them in the tile's epilogue (same fp32 operation order as pcd_ddim_update, FMA
 //     contraction off): what they publish is the NEXT step's enc1 operand, z rounded to fp16 in fragment order (poison = fp16 NaN,
 //     the state is signed), so the update is 4 divisions per thread instead of a separate 32-per-thread stage between two layers.
+//   * class-conditional runs (template parameter MODE; 0 = none, the code above): MODE 1 adds class_bias[label] of the row's shape to the
+//     step's time row in enc1's head threads (loaded once before the step loop); MODE 2 (classifier-free guidance) also pairs rows: a
+//     32-row tile carries up to 16 shapes, local row r < 16 with the shape's label and row r + 16 with the null class, both holding the same
+//     state.  After output.2's cross-wave reduction the whole 32 x 32 tile is in the LDS scratch, so each thread forms its own row's eps and
+//     row ^ 16's by the same expression, combines them (pcd_cfg_combine's operation order) and applies the update: the two threads of a pair
+//     execute the same operations on the same numbers and publish bitwise the same state.  No new buffers, units, schedule or barriers;
+//     17 .. 32 guided shapes are the two interleaved streams of 16.
 // Every wait is bounded (s_memrealtime) and reports through a status word; the grid is exactly the number of CUs and
 // the host refuses to launch on a device with fewer (pcd_latent_persist_supported).  Timeline tool:
-// tools/trace_latent_persist.py (instrumented build).  Measured, B = 32: 47 us / step against 74 us for the per-layer launches.
+// tools/trace_latent_persist.py (instrumented build).  Measured, B = 32: 35 us / step against 74 us for the per-layer launches.
 #include <new>
 #include <vector>
 #include <algorithm>
@@ -103,6 +110,16 @@ struct LpArgs {
     unsigned* trace;                   // diagnostic build only: [wg][step][unit][8] s_memrealtime stamps (enter, operands in, stored, epilogue computed, operands in of waves 0..3)
     int trace_steps;
 };
+
+// the kernel's argument of a class-conditional run (MODE != 0); the unlabelled kernels keep LpArgs
+struct LpArgsCfg : LpArgs {
+    const float* class_bias;           // fp32 [class_rows][128], the class table through enc1's time columns
+    int class_rows, null_row;
+    const int* labels;                 // [batch]; a value outside [0, class_rows) reads null_row
+    const float* w; int w_stride;      // MODE 2: guidance scale per shape (stride 1) or shared (0)
+};
+template <int MODE> struct LpArgsOf { typedef LpArgsCfg type; };
+template <> struct LpArgsOf<0> { typedef LpArgs type; };
 
 // ------------------------------------------------------------------------------------------------ device helpers
 __device__ __forceinline__ bool lp_poison16(u32x4 v) { return ((v.x | v.y | v.z | v.w) & 0x80008000u) != 0u; }
@@ -259,6 +276,12 @@ __device__ __forceinline__ void lp_ddim(float z, float e, float n, float s, floa
     const float b = n2 * e;
     zn = a + b;
 }
+// classifier-free guidance of one element, the operation order of pcd_cfg_combine (cfg_elem)
+__device__ __forceinline__ float lp_cfg(float ec, float eu, float w) {
+    const float d = ec - eu;
+    const float wd = w * d;
+    return eu + wd;
+}
 #pragma clang fp contract(fast)
 
 struct LpStep {
@@ -301,10 +324,10 @@ __device__ __forceinline__ void lp_gemm_store(const LpCtx& c, const LpLayer& L, 
 
 __device__ __forceinline__ void lp_poison_all(const LpCtx& c, const LpArgs& A, const LpUnit* units, int other_off);
 
-template <int CT, int MAXCH>
+template <int CT, int MAXCH, int MODE>
 __device__ __forceinline__ bool lp_run_gemm(const LpCtx& c, const LpLayer& L, const LpUnit& U, const LpStep& S, const LpArgs& A,
                                             bool& poisoned, const LpUnit* units, const float (&tbv)[4], float (&zs)[4], const float (&rates)[4],
-                                            bool last_step) {
+                                            bool last_step, float gw) {
     f32x16 acc[CT];
 #pragma unroll
     for (int t = 0; t < CT; ++t)
@@ -393,21 +416,53 @@ __device__ __forceinline__ bool lp_run_gemm(const LpCtx& c, const LpLayer& L, co
     if (L.slabs == 0 && L.mode == 2) {
         // output.2: v = eps of this thread's 4 columns.  Forward mode hands eps back; the sampler applies the DDIM update to the
         // thread's piece of the state and publishes the new state as the next step's enc1 operand
-        if (A.forward_only) {
-            if (row < S.nb) *(float4*)(A.eps_out + (int64_t)(S.r0 + row) * L.c + U.col0 + 4 * q) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
-            return true;
-        }
-        float x0v[4];
+        // (MODE 2 is a branch of its own, not the code below with `row & 15` masks: written once, the shared form gave the MODE 0 kernels
+        // another register allocation, and those must stay the parent's instruction streams, profiles/latent_cfg_isa.md)
+        if constexpr (MODE == 2) {
+            // paired rows: row r < 16 is the shape with its label, row r + 16 the same state with the null class.  The tile is still in
+            // the reduction scratch (the next write to it is behind the next unit's first barrier): the partner row's eps by the same
+            // expression as this row's, then the guided eps and the update, the same bits in both threads of the pair
+            const float* pst = (const float*)(c.smem + U.lds_p);
+            const int prow = row ^ 16, srow = row & 15;          // the partner; the row's shape inside the stream
+            float x0v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float zn;
-            lp_ddim(zs[i], v[0][i], rates[0], rates[1], rates[2], rates[3], x0v[i], zn);
-            zs[i] = row < S.nb ? zn : 0.f;
-            v[0][i] = zs[i];
-        }
-        if (last_step && row < S.nb) {
-            *(float4*)(A.z + (int64_t)(S.r0 + row) * 256 + U.col0 + 4 * q) = make_float4(zs[0], zs[1], zs[2], zs[3]);
-            if (A.x0 != nullptr) *(float4*)(A.x0 + (int64_t)(S.r0 + row) * 256 + U.col0 + 4 * q) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+            for (int i = 0; i < 4; ++i) {
+                float pv = (red[0][prow][4 * q + i] + red[1][prow][4 * q + i]) + (red[2][prow][4 * q + i] + red[3][prow][4 * q + i]);
+                pv += pst[4 * q + i];
+                v[0][i] = row < 16 ? lp_cfg(v[0][i], pv, gw) : lp_cfg(pv, v[0][i], gw);
+                if (!A.forward_only) {
+                    float zn;
+                    lp_ddim(zs[i], v[0][i], rates[0], rates[1], rates[2], rates[3], x0v[i], zn);
+                    zs[i] = srow < S.nb ? zn : 0.f;
+                    v[0][i] = zs[i];
+                }
+            }
+            // eps, z and x0 leave from the conditional row of a pair
+            if (A.forward_only) {
+                if (row < 16 && srow < S.nb) *(float4*)(A.eps_out + (int64_t)(S.r0 + srow) * L.c + U.col0 + 4 * q) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
+                return true;
+            }
+            if (last_step && row < 16 && srow < S.nb) {
+                *(float4*)(A.z + (int64_t)(S.r0 + srow) * 256 + U.col0 + 4 * q) = make_float4(zs[0], zs[1], zs[2], zs[3]);
+                if (A.x0 != nullptr) *(float4*)(A.x0 + (int64_t)(S.r0 + srow) * 256 + U.col0 + 4 * q) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+            }
+        } else {
+            if (A.forward_only) {
+                if (row < S.nb) *(float4*)(A.eps_out + (int64_t)(S.r0 + row) * L.c + U.col0 + 4 * q) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
+                return true;
+            }
+            float x0v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float zn;
+                lp_ddim(zs[i], v[0][i], rates[0], rates[1], rates[2], rates[3], x0v[i], zn);
+                zs[i] = row < S.nb ? zn : 0.f;
+                v[0][i] = zs[i];
+            }
+            if (last_step && row < S.nb) {
+                *(float4*)(A.z + (int64_t)(S.r0 + row) * 256 + U.col0 + 4 * q) = make_float4(zs[0], zs[1], zs[2], zs[3]);
+                if (A.x0 != nullptr) *(float4*)(A.x0 + (int64_t)(S.r0 + row) * 256 + U.col0 + 4 * q) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+            }
         }
     }
     wait_vmcnt<0>();        // this wave's poison stores are complete before its data stores leave
@@ -584,8 +639,9 @@ __device__ __forceinline__ void lp_poison_all(const LpCtx& c, const LpArgs& A, c
 // per-wave spin of the single-stream loop.  51-53 us per step of the pair (26 per 32 rows) against 2 x 35 for one stream after the other.
 // (Trying both streams' next units in turn, or one probe load per stream in flight, were both slower than running the streams one after
 // the other: a poll that involves the whole workgroup delays the other stream's detection by its round trip: 71 and 103 us per step.)
-template <bool TRACE, int NS>
-__global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A) {
+// MODE: 0 unlabelled, 1 labelled (a class bias per row), 2 guided (paired rows, <= 16 shapes per stream): the header comment.
+template <bool TRACE, int NS, int MODE = 0>
+__global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(typename LpArgsOf<MODE>::type A) {
     extern __shared__ __attribute__((aligned(16))) char lp_smem[];
     __shared__ int lp_flag[4];
     __shared__ unsigned lp_hist[(LP_MAX_UNITS + 1) * 4];
@@ -667,13 +723,33 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
     const int k_base = A.counter != nullptr ? A.counter[0] : 0;
     // rows of the batch per stream: stream s carries global rows sr0[s] .. sr0[s] + snb[s] - 1 as its local rows 0 ..
     int sr0[NS], snb[NS];
-    sr0[0] = 0; snb[0] = NS == 1 ? A.batch : 32;
-    if constexpr (NS == 2) { sr0[1] = 32; snb[1] = A.batch - 32; }
+    constexpr int SROWS = MODE == 2 ? 16 : 32;              // shapes a stream carries
+    sr0[0] = 0; snb[0] = NS == 1 ? A.batch : SROWS;
+    if constexpr (NS == 2) { sr0[1] = SROWS; snb[1] = A.batch - SROWS; }
     // the latent state: the thread (row = tid >> 3, q = tid & 7) of an output.2 unit keeps columns col0 + 4 q .. + 3 of its row (rows past
     // the stream's are zero) and publishes the initial state the way every later step's epilogue does: fp16, fragment order, into the set
     // "before" step 0 (the stream's set 2; the host poisoned all the sets)
     float zs[NS][4];
-    const int zrow = c.tid >> 3;
+    const int zrow = MODE == 2 ? ((c.tid >> 3) & 15) : (c.tid >> 3);       // (guided: both rows of a pair hold their shape's state)
+    // class-conditional runs: the class bias of this head thread's row and the guidance scale of this state thread's shape, once per call
+    float cbv[NS][4] = {}, gw[NS] = {};
+    if constexpr (MODE != 0) {
+#pragma unroll
+        for (int st = 0; st < NS; ++st) {
+            gw[st] = 1.f;
+            if (is_head) {
+                int cls = A.null_row;
+                const bool conditional = MODE == 2 ? (c.tid >> 3) < 16 : true;
+                if (conditional && zrow < snb[st]) {
+                    const int l = A.labels[sr0[st] + zrow];
+                    if (l >= 0 && l < A.class_rows) cls = l;
+                }
+                const float4 b4 = *(const float4*)(A.class_bias + (int64_t)cls * 128 + units[0].col0 + 4 * (c.tid & 7));
+                cbv[st][0] = b4.x; cbv[st][1] = b4.y; cbv[st][2] = b4.z; cbv[st][3] = b4.w;
+            }
+            if (MODE == 2 && zu >= 0 && zrow < snb[st]) gw[st] = A.w[(sr0[st] + zrow) * A.w_stride];
+        }
+    }
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
         zs[st][0] = zs[st][1] = zs[st][2] = zs[st][3] = 0.f;
@@ -705,11 +781,15 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
     };
     // per-step constants, requested at the start of a step and used behind the waits: enc1's bias is the hoisted time row of the step;
     // the update's four rates of this thread's row
-    auto step_consts = [&](const LpStep& S, float (&tbv)[4], float (&rates)[4]) __attribute__((always_inline)) {
+    auto step_consts = [&](const LpStep& S, const float (&cb)[4], float (&tbv)[4], float (&rates)[4]) __attribute__((always_inline)) {
         tbv[0] = tbv[1] = tbv[2] = tbv[3] = 0.f;
         if (is_head) {
             const float4 t4 = *(const float4*)(A.tb_table + (int64_t)S.k * A.tb_elems + units[0].col0 + 4 * (c.tid & 7));
             tbv[0] = t4.x; tbv[1] = t4.y; tbv[2] = t4.z; tbv[3] = t4.w;
+            if constexpr (MODE != 0) {                       // pcd_step_select_labels' fp32 add
+#pragma unroll
+                for (int i = 0; i < 4; ++i) tbv[i] += cb[i];
+            }
         }
         rates[0] = 0.f; rates[1] = 1.f; rates[2] = 0.f; rates[3] = 0.f;
         if (zu >= 0 && !A.forward_only && zrow < S.nb) {
@@ -720,7 +800,7 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
     };
     bool poisoned = false;
     // one unit of (stream, step), blocking
-    auto run_unit = [&](const LpStep& S, int u, int step, bool traced, const float (&tbv)[4], float (&zst)[4], const float (&rates)[4]) __attribute__((always_inline)) {
+    auto run_unit = [&](const LpStep& S, int u, int step, bool traced, const float (&tbv)[4], float (&zst)[4], const float (&rates)[4], float gws) __attribute__((always_inline)) {
         const LpUnit U = units[u];
         const LpLayer& L = A.layers[U.layer];
         if (TRACE && traced && step < A.trace_steps) {
@@ -729,8 +809,8 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
         } else c.tr = nullptr;
         bool ok;
         if (U.kind == LP_GEMM) {
-            if (U.ct == 2) ok = lp_run_gemm<2, 1>(c, L, U, S, A, poisoned, units, tbv, zst, rates, step == total - 1);
-            else ok = lp_run_gemm<1, 4>(c, L, U, S, A, poisoned, units, tbv, zst, rates, step == total - 1);
+            if (U.ct == 2) ok = lp_run_gemm<2, 1, MODE>(c, L, U, S, A, poisoned, units, tbv, zst, rates, step == total - 1, gws);
+            else ok = lp_run_gemm<1, 4, MODE>(c, L, U, S, A, poisoned, units, tbv, zst, rates, step == total - 1, gws);
         } else {
             ok = lp_dispatch_finish(c, L, U, S, A, poisoned, units);
         }
@@ -742,11 +822,11 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
             if (step == A.fault_step && vwg == A.fault_wg) return;      // injected fault: this workgroup's publishes of the step never happen
             const LpStep S = step_of(0, step);
             float tbv[4], rates[4];
-            step_consts(S, tbv, rates);
+            step_consts(S, cbv[0], tbv, rates);
             for (int u = 0; u < LP_MAX_UNITS; ++u) {
                 if (units[u].kind == LP_END) break;
                 c.hist = lp_hist + u * 4 + c.wave;
-                if (!run_unit(S, u, step, true, tbv, zs[0], rates)) return;
+                if (!run_unit(S, u, step, true, tbv, zs[0], rates, gw[0])) return;
             }
             // End of this workgroup's step s.  Its units consumed step-s data, so every reader of the previous step's set is done (step
             // s's first layer needed the complete state published by step s - 1): re-poison this workgroup's regions of that set, which step s + 2
@@ -773,11 +853,11 @@ __global__ __launch_bounds__(LP_THREADS, 1) void latent_persist_kernel(LpArgs A)
                 const LpStep S = step_of(st, step);
                 bool ok;
                 if (st == 0) {
-                    if (u == 0) step_consts(S, tbv_[0], rates_[0]);
-                    ok = run_unit(S, u, step, true, tbv_[0], zs[0], rates_[0]);
+                    if (u == 0) step_consts(S, cbv[0], tbv_[0], rates_[0]);
+                    ok = run_unit(S, u, step, true, tbv_[0], zs[0], rates_[0], gw[0]);
                 } else {
-                    if (u == 0) step_consts(S, tbv_[NS - 1], rates_[NS - 1]);
-                    ok = run_unit(S, u, step, false, tbv_[NS - 1], zs[NS - 1], rates_[NS - 1]);
+                    if (u == 0) step_consts(S, cbv[NS - 1], tbv_[NS - 1], rates_[NS - 1]);
+                    ok = run_unit(S, u, step, false, tbv_[NS - 1], zs[NS - 1], rates_[NS - 1], gw[NS - 1]);
                 }
                 if (!ok) return;
                 // end of a stream's step on this workgroup: the ordering argument of the single-stream loop holds inside a stream
@@ -1101,6 +1181,10 @@ extern "C" int pcd_latent_persist_create(const pcd_latent_desc_t* desc, pcd_late
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<false, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)latent_persist_kernel<false, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LP_DYN_LDS);
     if (e != hipSuccess) {
         set_error("pcd_latent_persist_create: %s", hipGetErrorString(e));
         if (h->d_layers) (void)hipFree(h->d_layers);
@@ -1148,7 +1232,8 @@ extern "C" int pcd_latent_persist_inject_fault(pcd_latent_persist_t* h, int work
     return PCD_OK;
 }
 
-static int lp_launch(pcd_latent_persist_t* h, LpArgs& a, void* workspace, size_t workspace_bytes, void* stream) {
+// mode: the kernel's MODE (0 unlabelled, 1 labelled, 2 guided: 16 shapes per stream)
+static int lp_launch(pcd_latent_persist_t* h, LpArgsCfg& a, void* workspace, size_t workspace_bytes, void* stream, int mode = 0) {
     const size_t need = pcd_latent_persist_workspace_bytes(h);
     if (workspace_bytes < need) {
         set_error("pcd_latent_persist: workspace %zu < required %zu", workspace_bytes, need);
@@ -1171,18 +1256,23 @@ static int lp_launch(pcd_latent_persist_t* h, LpArgs& a, void* workspace, size_t
     a.fault_wg = h->fault_wg;
     a.fault_step = h->fault_step;
     // a batch of more than 32 rows: two interleaved streams (rows 0 .. 31 | the rest)
-    const int ns = a.batch > 32 ? 2 : 1;
+    const int ns = a.batch > (mode == 2 ? 16 : 32) ? 2 : 1;
     a.sched = ns == 2 ? h->d_sched : nullptr;
     // status word cleared, every set poisoned (a stream's set 2 receives its initial state before step 0 and is re-poisoned at the end of step 0)
     PCD_CHECK_HIP(hipMemsetAsync(workspace, 0, LP_CTRL_BYTES, s));
     PCD_CHECK_HIP(hipMemsetAsync((char*)workspace + LP_CTRL_BYTES, 0xff, (size_t)ns * 3 * (size_t)h->plan.set_bytes, s));
     // dynamic LDS = everything but the static flag words (rounded)
-    if (ns == 2) {
-        if (a.trace != nullptr) hipLaunchKernelGGL((latent_persist_kernel<true, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
-        else hipLaunchKernelGGL((latent_persist_kernel<false, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+    if (mode != 0) {                      // the entries refuse a trace buffer: the class-conditional modes exist for the plain kernel only
+        if (mode == 1 && ns == 1) hipLaunchKernelGGL((latent_persist_kernel<false, 1, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+        else if (mode == 1) hipLaunchKernelGGL((latent_persist_kernel<false, 2, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+        else if (ns == 1) hipLaunchKernelGGL((latent_persist_kernel<false, 1, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+        else hipLaunchKernelGGL((latent_persist_kernel<false, 2, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+    } else if (ns == 2) {
+        if (a.trace != nullptr) hipLaunchKernelGGL((latent_persist_kernel<true, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, (const LpArgs&)a);
+        else hipLaunchKernelGGL((latent_persist_kernel<false, 2>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, (const LpArgs&)a);
     } else {
-        if (a.trace != nullptr) hipLaunchKernelGGL((latent_persist_kernel<true, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
-        else hipLaunchKernelGGL((latent_persist_kernel<false, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, a);
+        if (a.trace != nullptr) hipLaunchKernelGGL((latent_persist_kernel<true, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, (const LpArgs&)a);
+        else hipLaunchKernelGGL((latent_persist_kernel<false, 1>), dim3(LP_WGS), dim3(LP_THREADS), LP_DYN_LDS, s, (const LpArgs&)a);
     }
     PCD_CHECK_LAUNCH();
     return PCD_OK;
@@ -1191,7 +1281,7 @@ static int lp_launch(pcd_latent_persist_t* h, LpArgs& a, void* workspace, size_t
 extern "C" int pcd_latent_persist_forward(pcd_latent_persist_t* h, const float* z, int batch, const float* tbias, float* eps,
                                           void* workspace, size_t workspace_bytes, void* stream) {
     PCD_CHECK_ARG(h && z && tbias && eps && workspace && batch > 0);
-    LpArgs a{};
+    LpArgsCfg a{};
     a.z = (float*)z; a.x0 = nullptr; a.eps_out = eps; a.batch = batch;
     a.tb_table = tbias; a.tb_elems = 128;
     a.rates = nullptr; a.rate_width = 1; a.rate_stride = 0; a.T = 1;
@@ -1204,12 +1294,51 @@ extern "C" int pcd_latent_persist_ddim(pcd_latent_persist_t* h, float* z, float*
                                        void* workspace, size_t workspace_bytes, void* stream) {
     PCD_CHECK_ARG(h && z && tb_table && rate_tables && counter && workspace && batch > 0 && nsteps > 0 && n_steps_table > 0);
     PCD_CHECK_ARG(tb_elems == 128 && (rate_width == 1 || rate_width == batch));
-    LpArgs a{};
+    LpArgsCfg a{};
     a.z = z; a.x0 = x0; a.eps_out = nullptr; a.batch = batch;
     a.tb_table = tb_table; a.tb_elems = tb_elems;
     a.rates = rate_tables; a.rate_width = rate_width; a.rate_stride = rate_width == 1 ? 0 : 1; a.T = n_steps_table;
     a.counter = counter; a.nsteps = nsteps; a.forward_only = 0;
     return lp_launch(h, a, workspace, workspace_bytes, stream);
+}
+
+// the class-conditional arguments of the two guided entries, checked before any device call
+static int lp_guided_args(pcd_latent_persist_t* h, LpArgsCfg& a, int batch, const float* class_bias, int class_rows, int null_row, const int* labels,
+                          const float* w, int w_stride) {
+    PCD_CHECK_ARG(class_bias && labels && class_rows > 0 && null_row >= 0 && null_row < class_rows);
+    PCD_CHECK_ARG(w_stride == 0 || w_stride == 1);
+    PCD_CHECK_ARG(batch <= (w != nullptr ? 32 : 64));
+    PCD_CHECK_ARG(h->trace == nullptr);
+    a.class_bias = class_bias; a.class_rows = class_rows; a.null_row = null_row; a.labels = labels; a.w = w; a.w_stride = w_stride;
+    return PCD_OK;
+}
+
+extern "C" int pcd_latent_persist_forward_guided(pcd_latent_persist_t* h, const float* z, int batch, const float* tbias_row,
+                                                 const float* class_bias, int class_rows, int null_row, const int* labels, const float* w,
+                                                 int w_stride, float* eps, void* workspace, size_t workspace_bytes, void* stream) {
+    PCD_CHECK_ARG(h && z && tbias_row && eps && workspace && batch > 0);
+    LpArgsCfg a{};
+    if (const int rc = lp_guided_args(h, a, batch, class_bias, class_rows, null_row, labels, w, w_stride); rc != PCD_OK) return rc;
+    a.z = (float*)z; a.x0 = nullptr; a.eps_out = eps; a.batch = batch;
+    a.tb_table = tbias_row; a.tb_elems = 128;
+    a.rates = nullptr; a.rate_width = 1; a.rate_stride = 0; a.T = 1;
+    a.counter = nullptr; a.nsteps = 1; a.forward_only = 1;
+    return lp_launch(h, a, workspace, workspace_bytes, stream, w != nullptr ? 2 : 1);
+}
+
+extern "C" int pcd_latent_persist_ddim_guided(pcd_latent_persist_t* h, float* z, float* x0, int batch, const float* tb_table, int tb_elems,
+                                              const float* class_bias, int class_rows, int null_row, const int* labels, const float* w,
+                                              int w_stride, const float* rate_tables, int rate_width, int n_steps_table, int* counter,
+                                              int nsteps, void* workspace, size_t workspace_bytes, void* stream) {
+    PCD_CHECK_ARG(h && z && tb_table && rate_tables && counter && workspace && batch > 0 && nsteps > 0 && n_steps_table > 0);
+    PCD_CHECK_ARG(tb_elems == 128 && (rate_width == 1 || rate_width == batch));
+    LpArgsCfg a{};
+    if (const int rc = lp_guided_args(h, a, batch, class_bias, class_rows, null_row, labels, w, w_stride); rc != PCD_OK) return rc;
+    a.z = z; a.x0 = x0; a.eps_out = nullptr; a.batch = batch;
+    a.tb_table = tb_table; a.tb_elems = tb_elems;
+    a.rates = rate_tables; a.rate_width = rate_width; a.rate_stride = rate_width == 1 ? 0 : 1; a.T = n_steps_table;
+    a.counter = counter; a.nsteps = nsteps; a.forward_only = 0;
+    return lp_launch(h, a, workspace, workspace_bytes, stream, w != nullptr ? 2 : 1);
 }
 
 extern "C" int pcd_latent_persist_status(const void* workspace, unsigned* status_host, void* stream) {

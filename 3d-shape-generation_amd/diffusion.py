@@ -331,6 +331,48 @@ class _DiffusionBase(nn.Module):
         c, q = (torch.tensor(v, dtype=torch.float64).to(torch.float32) for v in (c, q))
         return DpmTable(t, n, s, n2, s2, c, q, self.device, skip_last_update=updates < K)
 
+    # ------------------------------------------------------------------ class conditioning
+    def _guide(self, labels, guidance_scale, batch: int):
+        """Validate `labels` / `guidance_scale` on the host.  None for a model without classes (labels or a scale other
+        than 1 raise), else the Stepper's (class_bias, labels (B,) int32, w): w is None when every scale is exactly 1 (the
+        unconditional forward is skipped), a (1,) fp32 tensor for one scale, (B,) for one per shape."""
+        w = torch.as_tensor(guidance_scale).detach().to("cpu")
+        if w.is_complex() or w.dtype == torch.bool or w.dim() > 1 or (w.dim() == 1 and w.shape[0] != batch):
+            raise ValueError(f"guidance_scale must be a number or a ({batch},) tensor, got {tuple(w.shape)} {w.dtype}")
+        w = w.to(torch.float32)
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("guidance_scale must be finite")
+        off = bool((w == 1.0).all())
+        if not getattr(self, "num_classes", 0):
+            if labels is not None:
+                raise ValueError("labels were given to a model without classes (num_classes=0)")
+            if not off:
+                raise ValueError("guidance_scale other than 1 needs a class-conditional model (num_classes > 0)")
+            return None
+        lab = self.model.check_labels(labels, batch)
+        return self.model.class_bias(), lab, None if off else w.reshape(-1).to(self.device).contiguous()
+
+    def _split_batch(self, batch):
+        """(shapes, labels or None) of a training batch: a tensor, or a (shapes, labels) pair."""
+        if isinstance(batch, (tuple, list)):
+            if len(batch) != 2:
+                raise ValueError(f"a labelled batch is (shapes, labels), got {len(batch)} entries")
+            return batch[0], batch[1]
+        return batch, None
+
+    def _training_labels(self, labels, batch: int, drop: bool):
+        """Device labels of a training (drop: each replaced by the null class with probability p_uncond, one torch.rand draw
+        after t's) or validation batch.  A model without classes draws nothing and returns None."""
+        if not getattr(self, "num_classes", 0):
+            if labels is not None:
+                raise ValueError("a labelled batch was given to a model without classes (num_classes=0)")
+            return None
+        lab = self.model.check_labels(labels, batch)
+        if drop:
+            null = torch.full_like(lab, self.num_classes)
+            lab = torch.where(torch.rand(batch, device=self.device) < self.p_uncond, null, lab)
+        return lab
+
     # ------------------------------------------------------------------ stepping
     GRAPH_MIN_STEPS = 8
     GRAPH_STEPS = 8            # timesteps captured per HIP graph (one graph launch costs ~10 us of host time: the
@@ -364,7 +406,7 @@ class _DiffusionBase(nn.Module):
     def _run_table(self, x, tab: "StepTable", kind: str, **kw):
         return self._run(x, tab, self.model.time_bias(tab.t), self._forward_fn(), kind, **kw)
 
-    def _run_from_state(self, num_samples, fresh, x, start_t, num_steps):
+    def _run_from_state(self, num_samples, fresh, x, start_t, num_steps, **kw):
         """`sample3` (diffusion.py:306-337): DDIM from the given state and time, or (x None) from `fresh()` at t = 1."""
         self.eval()
         if x is None:
@@ -373,7 +415,7 @@ class _DiffusionBase(nn.Module):
             x = x.to(self.device, torch.float32).contiguous().clone()
         if start_t is None:
             start_t = torch.ones(num_samples)
-        return self._run_table(x, self.from_state_table(start_t.reshape(-1)[0], num_steps), "ddim")
+        return self._run_table(x, self.from_state_table(start_t.reshape(-1)[0], num_steps), "ddim", **kw)
 
     def _l1_loss(self, pred, noise):
         """mean |pred - noise| of an eval-mode `diffusion_loss`."""
@@ -595,48 +637,6 @@ class PointCloudDiffusion(_DiffusionBase):
     def _forward_fn(self):
         return lambda x, tb_cur, eps, stride=0: self.model.forward_with_bias(x, tb_cur, stride, out=eps)
 
-    # ------------------------------------------------------------------ class conditioning
-    def _guide(self, labels, guidance_scale, batch: int):
-        """Validate `labels` / `guidance_scale` on the host.  None for a model without classes (labels or a scale other
-        than 1 raise), else the Stepper's (class_bias, labels (B,) int32, w): w is None when every scale is exactly 1 (the
-        unconditional forward is skipped), a (1,) fp32 tensor for one scale, (B,) for one per shape."""
-        w = torch.as_tensor(guidance_scale).detach().to("cpu")
-        if w.is_complex() or w.dtype == torch.bool or w.dim() > 1 or (w.dim() == 1 and w.shape[0] != batch):
-            raise ValueError(f"guidance_scale must be a number or a ({batch},) tensor, got {tuple(w.shape)} {w.dtype}")
-        w = w.to(torch.float32)
-        if not bool(torch.isfinite(w).all()):
-            raise ValueError("guidance_scale must be finite")
-        off = bool((w == 1.0).all())
-        if not self.num_classes:
-            if labels is not None:
-                raise ValueError("labels were given to a model without classes (num_classes=0)")
-            if not off:
-                raise ValueError("guidance_scale other than 1 needs a class-conditional model (num_classes > 0)")
-            return None
-        lab = self.model.check_labels(labels, batch)
-        return self.model.class_bias(), lab, None if off else w.reshape(-1).to(self.device).contiguous()
-
-    def _split_batch(self, batch):
-        """(clouds, labels or None) of a training batch: a tensor, or a (clouds, labels) pair."""
-        if isinstance(batch, (tuple, list)):
-            if len(batch) != 2:
-                raise ValueError(f"a labelled batch is (clouds, labels), got {len(batch)} entries")
-            return batch[0], batch[1]
-        return batch, None
-
-    def _training_labels(self, labels, batch: int, drop: bool):
-        """Device labels of a training (drop: each replaced by the null class with probability p_uncond, one torch.rand draw
-        after t's) or validation batch.  A model without classes draws nothing and returns None."""
-        if not self.num_classes:
-            if labels is not None:
-                raise ValueError("a labelled batch was given to a model without classes (num_classes=0)")
-            return None
-        lab = self.model.check_labels(labels, batch)
-        if drop:
-            null = torch.full_like(lab, self.num_classes)
-            lab = torch.where(torch.rand(batch, device=self.device) < self.p_uncond, null, lab)
-        return lab
-
     # ------------------------------------------------------------------ training surface (diffusion.py:56-86, 170-186)
     def configure_optimizers(self):
         """AdamW(lr, weight_decay=1e-5) + ReduceLROnPlateau(min, factor 0.5, patience 5) on `val_loss`
@@ -770,20 +770,24 @@ class PointCloudDiffusion(_DiffusionBase):
 class LatentDiffusion(_DiffusionBase):
     """Drop-in for reference diffusion.py:361-734 (sampling surface) over the latents of a frozen VAE."""
     _sample_dims = 1   # one sample is (latent_dim,)
+    _class_conditional = False                 # `ConditionalLatentDiffusion` is the class with classes
+    _HP_KEYS = ("latent_dim", "dim", "time_dim", "lr", "noise_schedule", "is_voxel_based")
 
     def __init__(self, vae, latent_dim=256, dim=512, time_dim=256, lr=1e-4, noise_schedule="cosine",
                  is_voxel_based=True, num_classes=0):
         super().__init__()
-        if num_classes:
-            raise ValueError("class conditioning is available for PointCloudDiffusion(backbone='pointnet') only: the persistent latent "
-                             "launch carries one time-bias row per step")
+        # `num_classes` is for the subclass alone: ConditionalLatentDiffusion.__init__ is the only sanctioned caller that passes it
+        if num_classes and not self._class_conditional:
+            raise ValueError("LatentDiffusion has no classes: class conditioning in latent space is ConditionalLatentDiffusion(vae, "
+                             "num_classes=...)")
         from .networks import SimpleLatentUNetPointNet
         self.hparams = _HParams(latent_dim=latent_dim, dim=dim, time_dim=time_dim, lr=lr,
                                 noise_schedule=noise_schedule, is_voxel_based=is_voxel_based)
         self.vae = vae
         for p in self.vae.parameters():
             p.requires_grad = False
-        self.model = SimpleLatentUNetPointNet(latent_dim, dim, time_dim)
+        self.num_classes = int(num_classes)
+        self.model = SimpleLatentUNetPointNet(latent_dim, dim, time_dim, num_classes=self.num_classes)
         self.lr = lr
         self._init_schedule(noise_schedule)
         self.init_weights()
@@ -810,24 +814,26 @@ class LatentDiffusion(_DiffusionBase):
         """`vae=` is required: the reference saves hyper-parameters with ignore=['vae'] (diffusion.py:375)."""
         from .checkpoint import load_lightning_checkpoint
         if vae is None:
-            raise TypeError("LatentDiffusion.load_from_checkpoint needs vae=")
+            raise TypeError(f"{cls.__name__}.load_from_checkpoint needs vae=")
         hp, sd = load_lightning_checkpoint(path, map_location, weights)
         hp.update(kwargs)
-        keys = ("latent_dim", "dim", "time_dim", "lr", "noise_schedule", "is_voxel_based")
-        obj = cls(vae, **{k: hp[k] for k in keys if k in hp})
+        obj = cls(vae, **{k: hp[k] for k in cls._HP_KEYS if k in hp})
         obj.load_state_dict(sd, strict=True)
         return obj
 
     def _forward_fn(self):
-        return lambda x, tb_cur, eps: self.model.forward_with_bias(x, tb_cur, 0, out=eps)
+        return lambda x, tb_cur, eps, stride=0: self.model.forward_with_bias(x, tb_cur, stride, out=eps)
 
     # The DDIM loops (`sample`, `sample3`) of a batch <= 64 run as ONE persistent launch for all their steps
     # (csrc/latent_persist.hip) when this process can have the whole GPU: 256 workgroups, one per CU, each with the whole LDS,
     # must be co-resident.  Otherwise -- larger batches, DDPM (`sample2`), PCD_LATENT_PERSISTENT=0 / use_persistent = False, a CU
     # mask, several ranks of this job on one device -- the per-layer launches run.  A persistent launch that still cannot
     # complete (a foreign process holding CUs: every wait inside is bounded) is not an error: the loop is re-run from the saved
-    # start state on the per-layer launches, with one warning, and the module stays on them.
+    # start state on the per-layer launches, with one warning, and the module stays on them.  A class-conditional run
+    # (`guide`) takes the same launch: labelled only up to 64 shapes, guided up to 32 (a shape's conditional and null-class rows
+    # share a tile and are combined inside the launch).
     use_persistent = os.environ.get("PCD_LATENT_PERSISTENT", "1") != "0"
+    GUIDED_PERSIST_MAX = 32
 
     def _persistent_allowed(self, x) -> bool:
         if not self.use_persistent or x.dim() != 2:
@@ -846,8 +852,9 @@ class LatentDiffusion(_DiffusionBase):
                 return False
         return self.model.persist_supported(x.shape[0])
 
-    def _run(self, x, tab, bias_table, forward, kind, noises=None, **kw):
-        if kind == "ddim" and noises is None and self._persistent_allowed(x):
+    def _run(self, x, tab, bias_table, forward, kind, noises=None, guide=None, **kw):
+        guided = guide is not None and guide[2] is not None
+        if kind == "ddim" and noises is None and not (guided and x.shape[0] > self.GUIDED_PERSIST_MAX) and self._persistent_allowed(x):
             # A non-finite start state cannot go through the kernel's exchange (a value IS its own ready flag: NaN / set sign bits
             # mean "not written yet"), so such a call takes the per-layer launches, where GroupNorm keeps the damage inside its row.
             if bool(torch.isfinite(x).all()):
@@ -856,7 +863,10 @@ class LatentDiffusion(_DiffusionBase):
                 counter = torch.zeros(2, dtype=torch.int32, device=x.device)
                 x0 = torch.empty_like(x)
                 # the last step's update of z is computed and discarded when `tab.skip_last_update` (sample3): x0 is the result
-                self.model.ddim_steps_persist(x, x0, bias_table.contiguous(), rates, counter, tab.steps)
+                if guide is None:
+                    self.model.ddim_steps_persist(x, x0, bias_table.contiguous(), rates, counter, tab.steps)
+                else:
+                    self.model.ddim_steps_persist_guided(x, x0, bias_table.contiguous(), rates, counter, tab.steps, *guide)
                 status = self.model.persist_status()
                 if status == 0:
                     return x0
@@ -868,7 +878,7 @@ class LatentDiffusion(_DiffusionBase):
                               RuntimeWarning, stacklevel=3)
                 self.use_persistent = False
                 x.copy_(start)
-        return super()._run(x, tab, bias_table, forward, kind, noises, **kw)
+        return super()._run(x, tab, bias_table, forward, kind, noises, guide=guide, **kw)
 
     # ------------------------------------------------------------------ training surface (diffusion.py:410-443, 522-537)
     def configure_optimizers(self, max_epochs: int = 100):
@@ -880,22 +890,30 @@ class LatentDiffusion(_DiffusionBase):
             self._scheduler = CosineAnnealingLR(self._trainer, T_max=max_epochs, eta_min=1e-6)
         return {"optimizer": self._trainer, "lr_scheduler": self._scheduler}
 
-    def diffusion_loss(self, z_0, t, noise=None, dropout_mask=None):
-        """diffusion.py:522-537.  train(): the denoiser runs with Dropout active and the gradients are left in the trainer."""
+    def diffusion_loss(self, z_0, t, noise=None, dropout_mask=None, labels=None):
+        """diffusion.py:522-537.  train(): the denoiser runs with Dropout active and the gradients are left in the trainer.
+        `labels`: the classes of a class-conditional model's batch (None = the null class)."""
         z_t, noise, _, _ = self.add_noise(z_0, t, noise)
+        cond = {"labels": labels} if self.num_classes or labels is not None else {}
         if self.training:
             tr = self.configure_optimizers()["optimizer"]
-            tr.forward(z_t, t.to(self.device, torch.float32), dropout_mask)
+            tr.forward(z_t, t.to(self.device, torch.float32), dropout_mask, **cond)
             return tr.backward(noise)
-        return self._l1_loss(self.model(z_t, t.to(self.device, torch.float32)), noise)
+        return self._l1_loss(self.model(z_t, t.to(self.device, torch.float32), **cond), noise)
 
-    def training_step(self, batch, batch_idx=0):
-        """diffusion.py:424-443: z = reparameterize(encode(x)) through the frozen VAE, t ~ U(0,1), L1 loss."""
-        x = batch.to(self.device)
+    def _latent_step(self, batch, drop: bool):
+        x, labels = self._split_batch(batch)
+        x = x.to(self.device)
         mu, logvar = self.vae.encode(x)
         z = self.vae.reparameterize(mu, logvar)
         t = torch.rand(z.shape[0], device=self.device)
-        return self.diffusion_loss(z, t)
+        return self.diffusion_loss(z, t, labels=self._training_labels(labels, z.shape[0], drop))
+
+    def training_step(self, batch, batch_idx=0):
+        """diffusion.py:424-443: z = reparameterize(encode(x)) through the frozen VAE, t ~ U(0,1), L1 loss.  A class-conditional
+        model takes (grids, labels) and replaces each label by the null class with probability p_uncond (one torch.rand draw after
+        t's)."""
+        return self._latent_step(batch, True)
 
     validation_step = training_step        # diffusion.py:445-467: same computation under eval() (figures not reproduced)
 
@@ -923,35 +941,68 @@ class LatentDiffusion(_DiffusionBase):
                                 "(is_voxel_based=False is not supported by the reference's samplers either)")
 
     @torch.no_grad()
-    def sample(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, return_latent=False, output="points"):
+    def sample(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, return_latent=False, output="points", labels=None,
+               guidance_scale=1.0):
         """DDIM in latent space, VAE decode, voxel -> points (diffusion.py:619-653).  `output="mesh"` (here and in `sample2`, `sample3`,
-        `sample_dpm`): the decoded grids leave as `utils.Mesh` surfaces of the same threshold (`utils.voxel_tensor_to_meshes`) instead."""
+        `sample_dpm`): the decoded grids leave as `utils.Mesh` surfaces of the same threshold (`utils.voxel_tensor_to_meshes`) instead.
+        `labels`, `guidance_scale` (here and in the other samplers; `ConditionalLatentDiffusion` only): as in
+        `PointCloudDiffusion.sample`; the arithmetic is tests/latent_cfg_statement.py."""
         self._check_output(output)
+        guide = self._guide(labels, guidance_scale, num_samples)
         z = self._start(num_samples, z_T)
-        return self._finish(self._run_table(z, self.ddim_table(num_steps, num_samples), "ddim"), threshold, return_latent, output)
+        return self._finish(self._run_table(z, self.ddim_table(num_steps, num_samples), "ddim", guide=guide), threshold, return_latent,
+                            output)
 
     @torch.no_grad()
     def sample_dpm(self, num_samples, num_steps=20, order=2, spacing="logsnr", t_last=1e-3, threshold=0.4, z_T=None,
-                   return_latent=False, output="points"):
+                   return_latent=False, output="points", labels=None, guidance_scale=1.0):
         """`PointCloudDiffusion.sample_dpm` in latent space, then VAE decode and voxel -> points like `sample`.  Runs on the per-layer
         launches (the persistent kernel implements the DDIM update only)."""
         self._check_output(output)
         if z_T is not None and tuple(z_T.shape) != (num_samples, self.hparams.latent_dim):
             raise ValueError(f"z_T must be {(num_samples, self.hparams.latent_dim)}, got {tuple(z_T.shape)}")
+        guide = self._guide(labels, guidance_scale, num_samples)
         tab = self.dpm_table(num_steps, order, spacing, t_last)
-        return self._finish(self._run_table(self._start(num_samples, z_T), tab, "dpm"), threshold, return_latent, output)
+        return self._finish(self._run_table(self._start(num_samples, z_T), tab, "dpm", guide=guide), threshold, return_latent, output)
 
     @torch.no_grad()
-    def sample2(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, noises=None, return_latent=False, output="points"):
+    def sample2(self, num_samples, num_steps=1000, threshold=0.4, z_T=None, noises=None, return_latent=False, output="points",
+                labels=None, guidance_scale=1.0):
         """DDPM in latent space (diffusion.py:575-616)."""
         self._check_output(output)
+        guide = self._guide(labels, guidance_scale, num_samples)
         z = self._start(num_samples, z_T)
-        return self._finish(self._run_table(z, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises), threshold, return_latent,
-                            output)
+        return self._finish(self._run_table(z, self.ddpm_table(num_steps, num_samples), "ddpm", noises=noises, guide=guide), threshold,
+                            return_latent, output)
 
     @torch.no_grad()
-    def sample3(self, num_samples, z=None, start_t=None, num_steps=1000, threshold=0.4, return_latent=False, output="points"):
+    def sample3(self, num_samples, z=None, start_t=None, num_steps=1000, threshold=0.4, return_latent=False, output="points",
+                labels=None, guidance_scale=1.0):
         """DDIM from a given latent/time (diffusion.py:655-707)."""
         self._check_output(output)
-        z0 = self._run_from_state(num_samples, lambda: self._start(num_samples, None), z, start_t, num_steps)
+        guide = self._guide(labels, guidance_scale, num_samples)
+        z0 = self._run_from_state(num_samples, lambda: self._start(num_samples, None), z, start_t, num_steps, guide=guide)
         return self._finish(z0, threshold, return_latent, output)
+
+
+class ConditionalLatentDiffusion(LatentDiffusion):
+    """`LatentDiffusion` over a class-conditional denoiser (not in the reference): `SimpleLatentUNetPointNet(num_classes=K)` owns
+    `class_emb` (K + 1 rows, the last the null class).  The samplers take `labels` (B,) in [0, K] (K, or None, = unconditional)
+    and `guidance_scale` w, a number or a (B,) tensor: eps = eps_u + w (eps_c - eps_u), one forward per step when every scale is
+    exactly 1.  `sample` / `sample3` of up to 32 guided (64 labelled) shapes stay ONE persistent launch for all their steps;
+    `sample2`, `sample_dpm`, larger batches and the fp32 mode run the per-layer launches, two forwards per guided step.
+    Training takes (grids, labels) batches and replaces each label by the null class with probability `p_uncond`."""
+    _class_conditional = True
+    _HP_KEYS = LatentDiffusion._HP_KEYS + ("num_classes", "p_uncond")
+
+    def __init__(self, vae, num_classes, p_uncond=0.1, **latent_kwargs):
+        num_classes = int(num_classes)
+        if num_classes < 1 or not 0.0 <= float(p_uncond) <= 1.0:
+            raise ValueError(f"num_classes must be >= 1 and p_uncond in [0, 1], got {num_classes} and {p_uncond}")
+        super().__init__(vae, num_classes=num_classes, **latent_kwargs)
+        self.p_uncond = float(p_uncond)
+        self.hparams["num_classes"], self.hparams["p_uncond"] = num_classes, self.p_uncond
+
+    def validation_step(self, batch, batch_idx=0):
+        """`training_step` under eval() with the labels as given (no drop to the null class, no draw)."""
+        return self._latent_step(batch, False)

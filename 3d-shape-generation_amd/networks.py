@@ -184,6 +184,25 @@ class _HandleDenoiser(_Denoiser):
                            _lib.stream_ptr()), forward.__name__)
         return out
 
+    def check_labels(self, labels, batch: int) -> Optional[torch.Tensor]:
+        """Host-side validation of a label argument: None on a model without classes, else (batch,) int32 on the device with
+        values in [0, num_classes] (`None` = the null class `num_classes` for every shape)."""
+        if not getattr(self, "num_classes", 0):
+            if labels is not None:
+                raise ValueError("labels were given to a model without classes (num_classes=0)")
+            return None
+        if labels is None:
+            return torch.full((batch,), self.num_classes, dtype=torch.int32, device=self.device)
+        lab = torch.as_tensor(labels)
+        if lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f"labels must be integers, got {lab.dtype}")
+        if lab.dim() != 1 or lab.shape[0] != batch:
+            raise ValueError(f"labels must be ({batch},), got {tuple(lab.shape)}")
+        if batch and (int(lab.min()) < 0 or int(lab.max()) > self.num_classes):
+            raise ValueError(f"labels must lie in [0, {self.num_classes}] ({self.num_classes} = unconditional), got "
+                             f"[{int(lab.min())}, {int(lab.max())}]")
+        return lab.to(self.device, torch.int32).contiguous()
+
     def _tap(self, name: str, batch: int, n_points: int, ws: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         handle, _, _, tap = self._entry
         _lib.check(tap(handle, name.encode(), batch, n_points, ws.data_ptr(), dst.data_ptr(), dst.numel() * dst.element_size(),
@@ -300,25 +319,6 @@ class UNetPointNetLarge(_HandleDenoiser):
                                                   _lib.stream_ptr()), "linear_f32")
             pk["class_bias"] = out
         return pk["class_bias"]
-
-    def check_labels(self, labels, batch: int) -> Optional[torch.Tensor]:
-        """Host-side validation of a label argument: None on a model without classes, else (batch,) int32 on the device with
-        values in [0, num_classes] (`None` = the null class `num_classes` for every shape)."""
-        if not self.num_classes:
-            if labels is not None:
-                raise ValueError("labels were given to a model without classes (num_classes=0)")
-            return None
-        if labels is None:
-            return torch.full((batch,), self.num_classes, dtype=torch.int32, device=self.device)
-        lab = torch.as_tensor(labels)
-        if lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f"labels must be integers, got {lab.dtype}")
-        if lab.dim() != 1 or lab.shape[0] != batch:
-            raise ValueError(f"labels must be ({batch},), got {tuple(lab.shape)}")
-        if batch and (int(lab.min()) < 0 or int(lab.max()) > self.num_classes):
-            raise ValueError(f"labels must lie in [0, {self.num_classes}] ({self.num_classes} = unconditional), got "
-                             f"[{int(lab.min())}, {int(lab.max())}]")
-        return lab.to(self.device, torch.int32).contiguous()
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, labels=None) -> torch.Tensor:
         self._need_cuda(x, t)
@@ -563,12 +563,20 @@ class UNetAttentionPointExperimental(_HandleDenoiser):
 class SimpleLatentUNetPointNet(_HandleDenoiser):
     """Drop-in for reference networks.py:962-1106: eps = model(z (B, latent), t (B,)).
     Eval-mode only (Dropout(0.1) in dec1 is the identity, as in every sampler).  fp16 mode: the per-layer launches or the
-    persistent kernel; fp32 mode: one launch per layer, csrc/latent_f32.hip (see `_Denoiser`)."""
+    persistent kernel; fp32 mode: one launch per layer, csrc/latent_f32.hip (see `_Denoiser`).  `num_classes` (not in the
+    reference) > 0: the module owns `class_emb`, an nn.Embedding(num_classes + 1, time_dim) registered after the reference's
+    modules (row `num_classes` is the null class), and te_b = time_mlp(sinusoid(t_b)) + class_emb[label_b].  Time enters only
+    through enc1's time columns and that product is linear, so the class term is one more hoisted bias (`class_bias`)."""
 
-    def __init__(self, latent_dim, dim=512, time_dim=256, dropout_rate=0.1):
+    def __init__(self, latent_dim, dim=512, time_dim=256, dropout_rate=0.1, num_classes=0):
         super().__init__()
         self.latent_dim, self.dim, self.time_dim = latent_dim, dim, time_dim
+        self.num_classes = int(num_classes)
+        if self.num_classes < 0:
+            raise ValueError(f"num_classes must be >= 0, got {num_classes}")
         self._build_from_spec(specs.latent_unet_spec(latent_dim, dim, time_dim))
+        if self.num_classes:
+            self.class_emb = nn.Embedding(self.num_classes + 1, time_dim)
 
     # ------------------------------------------------------------------ the whole step as one persistent launch
     def persist_supported(self, batch: int) -> bool:
@@ -616,6 +624,31 @@ class SimpleLatentUNetPointNet(_HandleDenoiser):
                                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "latent_persist_forward")
         return out
 
+    def forward_persist_guided(self, z, tbias_row, labels, w=None, out=None):
+        """One launch: eps_u + w (eps_c - eps_u) per shape for ONE t shared by the batch (batch <= 32: a shape's conditional and
+        null-class rows share a tile), or with w None the conditional eps (batch <= 64).  labels (B,) int32 on the device (a
+        value outside the table reads the null row), w (1,) or (B,) fp32 on the device."""
+        h, ws = self._persist_handle()
+        cb = self.class_bias()
+        if out is None:
+            out = torch.empty_like(z)
+        _lib.check(_lib.load().pcd_latent_persist_forward_guided(
+            h, z.data_ptr(), z.shape[0], tbias_row.data_ptr(), cb.data_ptr(), cb.shape[0], cb.shape[0] - 1, labels.data_ptr(),
+            0 if w is None else w.data_ptr(), 0 if w is None else int(w.numel() > 1), out.data_ptr(), ws.data_ptr(), ws.numel(),
+            _lib.stream_ptr()), "latent_persist_forward_guided")
+        return out
+
+    def ddim_steps_persist_guided(self, z, x0, bias_table, rates, counter, nsteps, class_bias, labels, w):
+        """`ddim_steps_persist` of a class-conditional run, still ONE launch: every step's bias row is bias_table[k] +
+        class_bias[label] per shape, and with w (guided, batch <= 32) each shape's conditional and null-class rows share a tile
+        and are combined in output.2's epilogue before the update."""
+        h, ws = self._persist_handle()
+        _lib.check(_lib.load().pcd_latent_persist_ddim_guided(
+            h, z.data_ptr(), x0.data_ptr(), z.shape[0], bias_table.data_ptr(), bias_table.shape[1], class_bias.data_ptr(),
+            class_bias.shape[0], class_bias.shape[0] - 1, labels.data_ptr(), 0 if w is None else w.data_ptr(),
+            0 if w is None else int(w.numel() > 1), rates.data_ptr(), rates.shape[2], rates.shape[1], counter.data_ptr(), int(nsteps),
+            ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "latent_persist_ddim_guided")
+
     def ddim_steps_persist(self, z, x0, bias_table, rates, counter, nsteps):
         """`nsteps` DDIM steps from table row counter[0] in ONE launch: z updated in place, x0 = the last step's x_0.
         rates (4, T, R) fp32 = (n, s, n_next, s_next)."""
@@ -660,12 +693,33 @@ class SimpleLatentUNetPointNet(_HandleDenoiser):
         """Hoisted time half of enc1 for each value of t: (len(t), 128) fp32."""
         return _time_embed(self, t, self.time_dim, 128)
 
-    def forward(self, z: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    def class_bias(self) -> torch.Tensor:
+        """Hoisted class half of enc1: the time columns applied to every row of `class_emb`, without the bias term
+        (`time_bias` carries it), (num_classes + 1, 128) fp32.  Kept with the packed weights `time_bias` uses, so it is
+        rebuilt whenever they are."""
+        if not self.num_classes:
+            raise RuntimeError("class_bias needs a class-conditional model (num_classes > 0)")
+        pk = self._ensure_packed()
+        if "class_bias" not in pk:
+            emb = self.class_emb.weight.detach().to(torch.float32).contiguous()
+            out = torch.empty(emb.shape[0], 128, dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().pcd_linear_f32(emb.data_ptr(), emb.shape[0], self.time_dim, pk["e1w_t"].data_ptr(), None, 128,
+                                                  out.data_ptr(), _lib.stream_ptr()), "linear_f32")
+            pk["class_bias"] = out
+        return pk["class_bias"]
+
+    def forward(self, z: torch.Tensor, t: torch.Tensor, labels=None) -> torch.Tensor:
         self._need_cuda(z, t)
         if z.dim() != 2 or z.shape[1] != self.latent_dim:
             raise ValueError(f"z must be (B, {self.latent_dim}), got {tuple(z.shape)}")
         z = z.to(torch.float32).contiguous()
-        return self.forward_with_bias(z, self.time_bias(t), 1)
+        tb = self.time_bias(t)
+        if self.num_classes or labels is not None:
+            lab = self.check_labels(labels, z.shape[0])
+            cb = self.class_bias()
+            _lib.check(_lib.load().pcd_embed_add_rows(tb.data_ptr(), cb.data_ptr(), lab.data_ptr(), z.shape[0], 128, cb.shape[0],
+                                                      _lib.stream_ptr()), "embed_add_rows")
+        return self.forward_with_bias(z, tb, 1)
 
 
 def __getattr__(name):   # VAE3DLarge lives in vae.py; keep `networks.VAE3DLarge` importable like the reference

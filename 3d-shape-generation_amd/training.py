@@ -757,7 +757,9 @@ class LatentTrainer(_Trainer):
     `LatentDiffusion.training_step` (diffusion.py:424-443; the VAE stays frozen).  The batch is 16-32 latent vectors,
     so every product is a few-row fp32 product (`pcd_matmul_f32`: weights read once) and everything stays fp32 (no loss
     scale) - GroupNorm is per sample, so unlike the point denoiser nothing here couples the batch.  Dropout(0.1) after
-    `dec1` (networks.py:1035) takes its keep mask from torch's generator, or from the caller (parity tests)."""
+    `dec1` (networks.py:1035) takes its keep mask from torch's generator, or from the caller (parity tests).  A class-conditional
+    model (`num_classes` > 0) adds class_emb[label_b] to the time embedding, as `PointTrainer` does; `class_emb.weight` is the
+    last entry of the flat parameter layout."""
 
     GROUPS = 8
     DROPOUT = 0.1
@@ -788,11 +790,22 @@ class LatentTrainer(_Trainer):
         return dx
 
     # ------------------------------------------------------------------ forward / backward
-    def forward(self, z_t: torch.Tensor, t: torch.Tensor, dropout_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, z_t: torch.Tensor, t: torch.Tensor, dropout_mask: Optional[torch.Tensor] = None, labels=None) -> torch.Tensor:
+        """eps_hat (B, 256) fp32 in train() mode; keeps what backward needs.  `labels`: the classes of a class-conditional
+        model's shapes (None = the null class)."""
         lib, st = self.lib, self._st()
         b = z_t.shape[0]
         self.z = z_t.to(torch.float32).contiguous()
         te = self._time_embedding(t)
+        self.labels = None
+        if getattr(self.model, "num_classes", 0):
+            # te_b += class_emb[label_b]: in place on the buffer enc1.0's weight gradient reads (time_mlp.2's backward reads its input)
+            self.labels = self.model.check_labels(labels, b)
+            table = self.p["class_emb.weight"]
+            self._chk(lib.pcd_embed_add_rows(te.data_ptr(), table.data_ptr(), self.labels.data_ptr(), b, te.shape[1], table.shape[0], st),
+                      "embed_add_rows")
+        elif labels is not None:
+            raise ValueError("labels were given to a model without classes (num_classes=0)")
         z1 = self._gn("enc1.1", self._lin("enc1.0", [(self.z, 256), (te, 256)]))
         z2 = self._gn("enc2.1", self._lin("enc2.0", [(z1, 128)]))
         z3 = self._gn("enc3.1", self._lin("enc3.0", [(z2, 256)]))
@@ -855,11 +868,15 @@ class LatentTrainer(_Trainer):
         dx = self._gn_backward("enc1.1", dz[128])
         d_te = new("te", 256)
         self._lin_backward("enc1.0", dx, [None, ("set", d_te)])
+        if self.labels is not None:            # class_emb: the ordered sum of d_te's rows per class
+            gt = self.g["class_emb.weight"]
+            self._chk(lib.pcd_embed_rows_backward(d_te.data_ptr(), self.labels.data_ptr(), b, gt.shape[1], gt.shape[0], gt.data_ptr(), st),
+                      "embed_rows_backward")
         self._time_mlp_backward(d_te)
         return loss_sum[0] / float(n)
 
-    def train_step(self, z_t, t, noise, dropout_mask=None) -> torch.Tensor:
-        self.forward(z_t, t, dropout_mask)
+    def train_step(self, z_t, t, noise, dropout_mask=None, labels=None) -> torch.Tensor:
+        self.forward(z_t, t, dropout_mask, **({} if labels is None else {"labels": labels}))
         loss = self.backward(noise)
         self.micro_step()
         return loss

@@ -508,6 +508,23 @@ int pcd_latent_persist_forward(pcd_latent_persist_t* h, const float* z, int batc
 int pcd_latent_persist_ddim(pcd_latent_persist_t* h, float* z, float* x0, int batch, const float* tb_table, int tb_elems,
                             const float* rate_tables, int rate_width, int n_steps_table, int* counter, int nsteps,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Class-conditional forms of the two launches above (classifier-free guidance; the arithmetic is tests/latent_cfg_statement.py).
+ * A row's enc1 bias is the step's time row + class_bias[c], class_bias (class_rows, 128) fp32 = the class table through enc1's
+ * time columns, c = labels[shape] (a value outside [0, class_rows) reads null_row, as pcd_step_select_labels does).
+ *  - w == NULL: labelled only.  Rows map as in the unlabelled launches (batch <= 64).
+ *  - w != NULL (batch <= 32): a 32-row tile carries up to 16 shapes, local row r < 16 the shape with its label and row r + 16 the
+ *    same state with the null class; output.2's epilogue forms eps = eps_u + w (eps_c - eps_u) (pcd_cfg_combine's operation order;
+ *    w[shape * w_stride], w_stride 0 or 1) before the update, so both rows publish the same next state.  17 .. 32 shapes run as
+ *    the two interleaved streams.
+ * No new buffers or workspace bytes.  With a trace buffer set (pcd_latent_persist_trace) both return PCD_ERR_ARG.
+ *  - pcd_latent_persist_forward_guided: eps (batch, 256) = the guided eps, or the conditional eps when w == NULL. */
+int pcd_latent_persist_ddim_guided(pcd_latent_persist_t* h, float* z, float* x0, int batch, const float* tb_table, int tb_elems,
+                                   const float* class_bias, int class_rows, int null_row, const int* labels, const float* w,
+                                   int w_stride, const float* rate_tables, int rate_width, int n_steps_table, int* counter,
+                                   int nsteps, void* workspace, size_t workspace_bytes, void* stream);
+int pcd_latent_persist_forward_guided(pcd_latent_persist_t* h, const float* z, int batch, const float* tbias_row,
+                                      const float* class_bias, int class_rows, int null_row, const int* labels, const float* w,
+                                      int w_stride, float* eps, void* workspace, size_t workspace_bytes, void* stream);
 /* waits for `stream` (the stream the launch was enqueued on; nothing else is synchronised), then reads the status word of the last launch:
  * 0 = every wait was met; else (wait kind << 16) | workgroup.
  * A non-zero status means the launch was ABANDONED (its outputs are undefined): the caller re-runs from its saved input on
