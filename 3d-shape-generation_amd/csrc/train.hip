@@ -85,8 +85,11 @@ __device__ __forceinline__ bool cr_range(int64_t rows_per_group, int rows_per_bl
     return row0 < row1;
 }
 
+// 8 columns [col, col + 8) of one row of a [rows][c] tensor, col a multiple of 8.  The 16-byte path needs the row pitch to keep
+// p + col 16-byte aligned, i.e. c % 8 == 0 (one uniform compare per call, like transpose_kernel's vec); any other c goes
+// element by element, columns >= c read as 0 and are not written.
 __device__ __forceinline__ half8 ld8(const half_t* p, int col, int c) {
-    if (col + 8 <= c) return *(const half8*)(p + col);
+    if (c % 8 == 0 && col + 8 <= c) return *(const half8*)(p + col);
     half8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = col + e < c ? p[col + e] : (half_t)0.f;
@@ -100,9 +103,9 @@ __device__ __forceinline__ f8 ldf8(const half_t* p, int col, int c) {
     for (int e = 0; e < 8; ++e) r.v[e] = (float)h[e];
     return r;
 }
-__device__ __forceinline__ f8 ldf8(const float* p, int col, int c) {   // col is a multiple of 8: 32-byte aligned rows of c % 8 == 0
+__device__ __forceinline__ f8 ldf8(const float* p, int col, int c) {   // col is a multiple of 8: 32-byte aligned rows if c % 8 == 0
     f8 r;
-    if (col + 8 <= c) {
+    if (c % 8 == 0 && col + 8 <= c) {
         const f32x4 a = *(const f32x4*)(p + col), b = *(const f32x4*)(p + col + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { r.v[e] = a[e]; r.v[4 + e] = b[e]; }
@@ -113,7 +116,7 @@ __device__ __forceinline__ f8 ldf8(const float* p, int col, int c) {   // col is
     return r;
 }
 __device__ __forceinline__ void st8(half_t* p, int col, int c, const half8& v) {
-    if (col + 8 <= c) { *(half8*)(p + col) = v; return; }
+    if (c % 8 == 0 && col + 8 <= c) { *(half8*)(p + col) = v; return; }
 #pragma unroll
     for (int e = 0; e < 8; ++e) if (col + e < c) p[col + e] = v[e];
 }

@@ -1277,7 +1277,11 @@ int pcd_project_to_cloud(const float* vertices, const int* vertex_counts, int v_
  * are the BatchNorm1d-with-batch-statistics forward/backward (networks.py:31-48), the max-pool with its
  * argmax (networks.py:807), the K=3 / C=3 edge layers, reductions, transposes, loss and optimizer.
  * Activations / activation gradients fp16 [M][C]; statistics, parameter gradients, optimizer state fp32.
- * Gradients carry the caller's loss scale; pcd_adamw_step divides it out. */
+ * Gradients carry the caller's loss scale; pcd_adamw_step divides it out.
+ * Column widths: pcd_colsum_f16, pcd_bn_apply_f16, pcd_bn_backward_f16 and pcd_vec3_outer (its k) serve any c > 0.  With
+ * c % 8 == 0 (16-byte aligned base pointers: every row then starts 16-byte aligned) they read and write 8 columns in
+ * 16-byte accesses; with any other c, c = 1 included, every element is accessed on its own.  pcd_bn_batch_stats
+ * requires c % 8 == 0 and rejects other widths with PCD_ERR_ARG. */
 /* out[g][c] = sum over the rows_per_group rows of group g of x[row][c]   (bias gradients, per-shape sums) */
 int pcd_colsum_f16(const void* x, int64_t rows_per_group, int groups, int c, float* out, void* stream);
 /* BatchNorm1d training statistics over the M rows of the fp32 conv output z [M][c] (c % 8 == 0): mean[c], biased
